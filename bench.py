@@ -12,12 +12,22 @@ filter tables once, before the timed region.
 processes, one per GPU, rendezvous on 127.0.0.1) before anything touches the GPU; under
 `torch.distributed.run` the ranks already exist and it just joins them.
 
-Prints ONE JSON line (rank 0).  The timed loop of K steps is repeated `--reps` times; `value` and
-`ms_per_step` are the median repetition, `repetitions` lists them all.  `roofline` is timed with HIP
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up (`--warmup` steps, then at least SETTLE_S
+seconds of steps), times `--steps` K steps once, writes the last step's output if `--dump-outputs DIR` is
+given, and prints the line.  `roofline` is timed with HIP
 events on the launch stream inside the timed region: around the FIR launch when that kernel is the
-whole step, around every kernel of the step otherwise (`roofline.scope`).  `cpu_baseline` is the repo's
-own CPU restatement (oracle/, "port" -- the reference's Rust core is absent from the checkout and cannot
-be built here) on a bounded sample; `pcie_inclusive` is the same batch from pinned host memory.
+whole step, around every kernel of the step otherwise (`roofline.scope`).
+
+`--full` adds the rest: the timed loop of K steps is repeated `--reps` times (default 5; `value` and
+`ms_per_step` are the median repetition, `repetitions` lists them all), a `--sustain` stretch of
+back-to-back steps, `cpu_baseline` -- the repo's own CPU restatement (oracle/, "port" -- the reference's
+Rust core is absent from the checkout and cannot be built here) on a bounded sample -- and
+`pcie_inclusive`, the same batch from pinned host memory.
+
+`--dump-outputs DIR` writes DIR/pcm.npy (float32 [files, frames, channels]: the decoded PCM samples of a
+fixed, seeded set of frames of every file of rank 0's batch, the same frames in every file) and
+DIR/pcm_frame_index.npy (float64: those frames' indices), at most DUMP_MAX_BYTES in all.  The inputs are
+seeded, so the same arguments give the same inputs in every run.
 """
 import argparse
 import ctypes as C
@@ -38,6 +48,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: 8 TB/s spec
 DSD64 = 2822400
+DUMP_MAX_BYTES = 48 << 20
+SETTLE_S = 0.5            # a plain run's warm-up lasts at least this long (its one timed loop must not meet the clock ramp)
+DUMP_SEED = 206
 
 WORKLOADS = {
     # name: (dsd_rate, out_rate, bit_depth, dither, channels, algorithmic bytes per output sample)
@@ -247,11 +260,27 @@ def cpu_baseline(kw, files, threads, budget_s):
     return sum(counts) / dt / 1e6, sum(counts), dt
 
 
+def dump_outputs(out_dir, d_out, frames, fb, channels, bits, dev):
+    """the last step's PCM as a caller of the batch call receives it, decoded to float32: a seeded sample of frames
+    (the same in every file) when the whole batch exceeds DUMP_MAX_BYTES"""
+    import torch
+    from helpers import decode_pcm
+    n_files = d_out.shape[0]
+    n = max(1, min(frames, DUMP_MAX_BYTES // (4 * channels * n_files)))
+    idx = np.arange(frames) if n == frames else np.sort(np.random.default_rng(DUMP_SEED).choice(frames, n, replace=False))
+    pos = (torch.from_numpy(idx).to(dev)[:, None] * fb + torch.arange(fb, device=dev)[None, :]).reshape(-1)
+    raw = d_out.index_select(1, pos).cpu().numpy()
+    pcm = np.stack([decode_pcm(raw[f], bits, channels) for f in range(n_files)]).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pcm.npy"), pcm)
+    np.save(os.path.join(out_dir, "pcm_frame_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--warmup", type=int, default=2, help="warm-up steps; a plain run then goes on warming up for at least SETTLE_S seconds")
     ap.add_argument("--files", type=int, default=64, help="files per GPU")
     ap.add_argument("--seconds", type=float, default=60.0, help="audio seconds per file")
     ap.add_argument("--distinct", type=int, default=0, help="distinct synthetic files generated per rank (0 = all of them distinct; fewer are tiled to --files)")
@@ -264,10 +293,14 @@ def main():
                     help="--shard files only.  weak (default): --files files on EVERY rank.  strong: --files-total files split over the ranks "
                          "(SURVEY.md 8d S3: the 512-file batch on 1/2/4/8 GPUs with the same total)")
     ap.add_argument("--files-total", type=int, default=512, help="--scaling strong: files of the whole job")
-    ap.add_argument("--sustain", type=float, default=2.0, help="seconds of back-to-back steps timed once more after the repetitions (0 = skip)")
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the timed K-step loop (median reported)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the host-resident batch (pinned host in/out, upload/convert/download overlapped) that is reported as the extra pcie_inclusive object, never as value")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: repetitions of the timed loop, the sustained stretch, the PCIe-inclusive batch and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's output (rank 0's batch, decoded PCM, a seeded sample of frames) as DIR/*.npy")
+    ap.add_argument("--sustain", type=float, default=None, help="seconds of back-to-back steps timed once more after the repetitions (0 = skip; default 2 with --full, else 0)")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed K-step loop (median reported; default 5 with --full, else 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-pcie", action="store_true", help="--full without the host-resident batch (pinned host in/out, upload/convert/download overlapped) that is reported as the extra pcie_inclusive object, never as value")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU-baseline work")
     ap.add_argument("--dither", default="", help="override the workload's dither (T, R, X, F, N)")
     ap.add_argument("--level", type=float, default=0.0, help="volume in dB (the reference's -l; its own test scripts use +-4)")
@@ -277,6 +310,12 @@ def main():
     ap.add_argument("--debug", type=lambda v: int(v, 0), default=0, help="d2d_params.debug_flags (include/dsd2dxd_amd.h: D2D_DBG_*), e.g. 2 = the older kernels for levels other than 0 dB; the line then names the flags and cites no counter traffic")
     ap.add_argument("--pcie-slice", type=int, default=0, help="bytes per channel per slice of the host-resident batch (0 = the library's default)")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
+    if args.sustain is None:
+        args.sustain = 2.0 if args.full else 0.0
+    if not args.full:
+        args.no_cpu_baseline = args.no_pcie = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -408,6 +447,17 @@ def main():
     torch.cuda.synchronize()
     eng.profile_read_all()
     eng.profile_enable(True)
+    if not args.full:
+        # one timed loop only: settle the clocks first, and let the roofline's event pool grow to at least --steps launches
+        # (--full's repetitions do this across repetitions; its median is the reported one)
+        t0 = time.perf_counter()
+        while True:
+            for _ in range(max(1, args.steps)):
+                step()
+            torch.cuda.synchronize()
+            if time.perf_counter() - t0 >= SETTLE_S:
+                break
+        eng.profile_read_all()
     dts = []
     for _ in range(max(1, args.reps)):
         if dist_on:
@@ -427,6 +477,9 @@ def main():
         dts.append(dt)
     fir_ms, step_ms, launches = eng.profile_read_all()
     eng.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        # d_out holds the last timed step's output (nothing has run on the engine since); frames_out is what that call wrote
+        dump_outputs(args.dump_outputs, d_out, min(ios[f].frames_out for f in range(args.files)), fb, ch_count, bits, dev)
     # does the rate hold for seconds (the chip sets its clock by the load)?  One more timed stretch of back-to-back steps
     sustained = None
     if args.sustain > 0:

@@ -53,6 +53,48 @@ def pack_layout(chans, fmt, block_size):
     return out
 
 
+_FIX_DIR = os.path.join(ROOT, "tests", "golden", "reference_fixtures")
+_FIX = None
+
+
+def ref_fixture_meta():
+    """tests/golden/reference_fixtures.json: what is stored of the reference project's fixture files"""
+    global _FIX
+    if _FIX is None:
+        import json
+        with open(os.path.join(ROOT, "tests", "golden", "reference_fixtures.json")) as f:
+            _FIX = json.load(f)
+    return _FIX
+
+
+def ref_fixture(name, start=0, stop=None):
+    """bytes [start, stop) of a reference fixture file (e.g. 'test/1kHz_mono_p.dsd') as uint8; the range must lie inside
+    one stored slice"""
+    import hashlib
+    import lzma
+    m = ref_fixture_meta()[name]
+    stop = m["size"] if stop is None else min(stop, m["size"])
+    for r0, r1, fn, digest in m["stored"]:
+        if r0 <= start and stop <= r1:
+            with open(os.path.join(_FIX_DIR, fn), "rb") as f:
+                b = lzma.decompress(f.read())
+            assert len(b) == r1 - r0 and hashlib.sha256(b).hexdigest() == digest, fn
+            return np.frombuffer(b, dtype=np.uint8)[start - r0:stop - r0].copy()
+    raise KeyError(f"{name}[{start}:{stop}] is not stored under tests/golden/reference_fixtures")
+
+
+def ref_fixture_file(name, dirpath):
+    """a reference fixture rebuilt at its full size in dirpath: every stored slice in place (a container's header and
+    trailer always are), zeros where nothing is stored (audio payload no test reads).  Returns the path."""
+    m = ref_fixture_meta()[name]
+    buf = np.zeros(m["size"], dtype=np.uint8)
+    for r0, r1, _, _ in m["stored"]:
+        buf[r0:r1] = ref_fixture(name, r0, r1)
+    path = os.path.join(str(dirpath), os.path.basename(name))
+    buf.tofile(path)
+    return path
+
+
 BITREV = np.array([int(f"{i:08b}"[::-1], 2) for i in range(256)], dtype=np.uint8)
 
 

@@ -1,8 +1,8 @@
 """Committed golden vectors (tests/golden, made by tests/golden/make_golden.py from this repo's
 oracle -- parity with the reference itself is unpinned, see that script's header).
 
-CPU: the oracle still reproduces them byte for byte (and the fixture-derived digests when the
-reference's fixtures are present).  GPU (-m gpu): both kernels reproduce them through the C ABI with
+CPU: the oracle still reproduces them byte for byte, and the fixture-derived digests from the slices
+of the reference's fixtures stored under tests/golden/reference_fixtures.  GPU (-m gpu): both kernels reproduce them through the C ABI with
 no oracle in the loop.
 """
 import hashlib
@@ -11,6 +11,8 @@ import os
 
 import numpy as np
 import pytest
+
+from helpers import ref_fixture
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 META = json.load(open(os.path.join(HERE, "golden_meta.json")))
@@ -29,10 +31,9 @@ def test_oracle_reproduces_golden(oracle_mod, name):
     assert [o.peak(c) for c in range(m["kw"]["channels"])] == m["peaks"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/test"), reason="reference fixtures not present")
 def test_oracle_reproduces_fixture_digests(oracle_mod):
     for fname, m in META["_fixtures"].items():
-        raw = np.fromfile(os.path.join("/root/reference/test", fname), dtype=np.uint8)[m["skip"]:][:m["nbytes"]]
+        raw = ref_fixture("test/" + fname, m["skip"], m["skip"] + m["nbytes"])
         o = oracle_mod.Oracle(**m["kw"])
         pcm, fr = o.translate(raw)
         pcm = pcm[:fr * o.frame_bytes]

@@ -10,11 +10,10 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import decode_pcm, pack_layout, random_bytes, synth, write_dff, write_dsf
+from helpers import decode_pcm, pack_layout, random_bytes, ref_fixture_file, ref_fixture_meta, synth, write_dff, write_dsf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "dsd2dxd_amd", "dsd2dxd_amd_cli")
-REF = "/root/reference"
 
 
 @pytest.fixture(scope="module")
@@ -100,22 +99,22 @@ def test_tags_are_read_decoded_and_album_marked(cli, tmp_path):
     assert a["error"] == "" and a["tag_bytes"] == 0 and "damaged" in a["warning"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/id3_test"), reason="reference fixtures not present")
-def test_tags_of_reference_fixtures(cli):
-    good, bad_dff, bad_dsf = tags(cli, "-a", "176400", REF + "/id3_test/dff/1kHz_stereo_i.dff",
-                                  REF + "/id3_test/dff/1kHz_stereo_i_brokenid3.dff", REF + "/id3_test/1kHz_mono_brokenid3.dsf")
+def test_tags_of_reference_fixtures(cli, tmp_path):
+    """the reference's id3_test files, rebuilt from their stored headers and tags (tests/golden/reference_fixtures)"""
+    good, bad_dff, bad_dsf = tags(cli, "-a", "176400", *[ref_fixture_file(n, tmp_path) for n in (
+        "id3_test/dff/1kHz_stereo_i.dff", "id3_test/dff/1kHz_stereo_i_brokenid3.dff", "id3_test/1kHz_mono_brokenid3.dsf")])
     assert good["fields"] == {"TITLE": "1kHz Test Tone DSD64", "ARTIST": "clone206",
                               "ALBUM": "clone206's Greatest Test Tone Hits [176.4K]"} and good["album_edited"]
     for t in (bad_dff, bad_dsf):
         assert t["error"] == "" and t["tag_bytes"] == 0 and "damaged" in t["warning"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/test"), reason="reference fixtures not present")
-def test_probe_reference_fixtures(cli):
-    """the facts SURVEY.md 4.3 measured from the fixture files, including the damaged-ID3 ones"""
-    r = {os.path.basename(d["path"]): d for d in probe(
-        cli, REF + "/test/1kHz_mono_p.dsf", REF + "/test/1kHz_stereo_128.dsf", REF + "/test/pinknoise_mono_128.dsf",
-        REF + "/id3_test/1kHz_mono_brokenid3.dsf", REF + "/id3_test/dff/1kHz_stereo_i.dff", REF + "/id3_test/dff/1kHz_stereo_i_brokenid3.dff")}
+def test_probe_reference_fixtures(cli, tmp_path):
+    """the facts SURVEY.md 4.3 measured from the fixture files, including the damaged-ID3 ones (rebuilt at full size from
+    their stored headers and trailers, tests/golden/reference_fixtures)"""
+    r = {os.path.basename(d["path"]): d for d in probe(cli, *[ref_fixture_file(n, tmp_path) for n in (
+        "test/1kHz_mono_p.dsf", "test/1kHz_stereo_128.dsf", "test/pinknoise_mono_128.dsf",
+        "id3_test/1kHz_mono_brokenid3.dsf", "id3_test/dff/1kHz_stereo_i.dff", "id3_test/dff/1kHz_stereo_i_brokenid3.dff")])}
     m = r["1kHz_mono_p.dsf"]
     assert (m["channels"], m["dsd_rate"], m["msb_first"], m["block_size"], m["sample_count"], m["data_offset"], m["data_bytes"]) == (1, 1, False, 4096, 14112000, 92, 1765376)
     s = r["1kHz_stereo_128.dsf"]
@@ -124,12 +123,13 @@ def test_probe_reference_fixtures(cli):
     d = r["1kHz_stereo_i.dff"]
     assert (d["channels"], d["dsd_rate"], d["planar"], d["msb_first"], d["data_offset"], d["bytes_per_channel"]) == (2, 1, False, True, 130, 1058400)
     assert r["1kHz_stereo_i_brokenid3.dff"]["error"] == "" and r["1kHz_stereo_i_brokenid3.dff"]["metadata_truncated"]
-    # payload identities the README states (README.md:205): the .dsd files are the containers' payloads
-    raw = np.fromfile(REF + "/test/1kHz_mono_p.dsd", dtype=np.uint8)
-    dsf = np.fromfile(REF + "/test/1kHz_mono_p.dsf", dtype=np.uint8)
-    assert np.array_equal(raw, dsf[92:92 + 1765376])
-    dff = np.fromfile(REF + "/id3_test/dff/1kHz_stereo_i.dff", dtype=np.uint8)
-    assert np.array_equal(np.fromfile(REF + "/test/1kHz_stereo_i.dsd", dtype=np.uint8), dff[130:130 + 2116800])
+    # payload identities the README states (README.md:205): the .dsd files are the containers' payloads (by the digests
+    # recorded from the whole files; the probe found each payload where the record puts it)
+    fx = ref_fixture_meta()
+    dsf, raw = fx["test/1kHz_mono_p.dsf"], fx["test/1kHz_mono_p.dsd"]
+    assert dsf["payload"] == [92, 1765376] == [m["data_offset"], raw["size"]] and dsf["payload_sha256"] == raw["sha256"]
+    dff, raw = fx["id3_test/dff/1kHz_stereo_i.dff"], fx["test/1kHz_stereo_i.dsd"]
+    assert dff["payload"] == [130, 2116800] == [d["data_offset"], raw["size"]] and dff["payload_sha256"] == raw["sha256"]
 
 
 # ---- GPU: whole-file conversions through the CLI --------------------------------------------------

@@ -3,18 +3,13 @@
 The reference holds no golden vectors for this path (parity unpinned), so the oracle
 is pinned by what can be derived without it: the fixtures' measured properties (bit order, tone
 level), the impulse response against the committed tap tables, exact invariances of the arithmetic,
-and the statistics of the dither.  Tests that read /root/reference/test/* skip when that directory
-is absent (it never travels to the GPU box).
+and the statistics of the dither.  The reference's fixture files are read from the slices stored under
+tests/golden/reference_fixtures.
 """
-import os
-
 import numpy as np
 import pytest
 
-from helpers import BITREV, decode_pcm, pack_layout, random_bytes, synth
-
-REF = "/root/reference/test"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference fixtures not present")
+from helpers import BITREV, decode_pcm, pack_layout, random_bytes, ref_fixture, synth
 
 
 def band_residual_db(y, fs, f0=1000.0, lo=2000.0, hi=20000.0):
@@ -36,10 +31,9 @@ def tone_fit(y, fs, f0=1000.0):
     return float(np.hypot(c[0], c[1])), float(c[2])
 
 
-@needs_ref
 def test_bit_order_discriminator_lsb_fixture(oracle_mod):
     """1kHz_mono_p.dsd is LSB-first (DSF payload): right order -> clean 2-20 kHz band, wrong -> ~-36 dB"""
-    raw = np.fromfile(os.path.join(REF, "1kHz_mono_p.dsd"), dtype=np.uint8)[:4096 * 200]
+    raw = ref_fixture("test/1kHz_mono_p.dsd", 0, 4096 * 200)
     res = {}
     for e in "LM":
         o = oracle_mod.Oracle(dsd_rate=1, output_rate=88200, channels=1, fmt="P", endianness=e, bit_depth=32, dither="X")
@@ -49,10 +43,9 @@ def test_bit_order_discriminator_lsb_fixture(oracle_mod):
     assert res["M"] > -45.0
 
 
-@needs_ref
 def test_bit_order_discriminator_msb_fixture(oracle_mod):
     """1kHz_stereo_i.dsd is byte-interleaved, MSB-first (DFF payload); L == R bit-identically"""
-    raw = np.fromfile(os.path.join(REF, "1kHz_stereo_i.dsd"), dtype=np.uint8)[:2 * 4096 * 100]
+    raw = ref_fixture("test/1kHz_stereo_i.dsd", 0, 2 * 4096 * 100)
     res = {}
     for e in "LM":
         o = oracle_mod.Oracle(dsd_rate=1, output_rate=88200, channels=2, fmt="I", endianness=e, bit_depth=32, dither="X")
@@ -63,15 +56,12 @@ def test_bit_order_discriminator_msb_fixture(oracle_mod):
     assert res["L"] > -45.0
 
 
-@needs_ref
 @pytest.mark.parametrize("name,dsd_rate,channels,amp_db", [
     ("1kHz_mono_p.dsd", 1, 1, -9.23), ("1kHz_mono_128.dsf", 2, 1, -9.07), ("1kHz_stereo_128.dsf", 2, 2, -9.07)])
 def test_tone_level_matches_fixture_measurement(oracle_mod, name, dsd_rate, channels, amp_db):
     """unity DC gain: the 1 kHz tone comes out at the level measured in the DSD stream"""
-    raw = np.fromfile(os.path.join(REF, name), dtype=np.uint8)
-    if name.endswith(".dsf"):
-        raw = raw[92:]                                   # DSF: data chunk payload starts at byte 92
-    raw = raw[:channels * 4096 * 120]
+    skip = 92 if name.endswith(".dsf") else 0            # DSF: data chunk payload starts at byte 92
+    raw = ref_fixture("test/" + name, skip, skip + channels * 4096 * 120)
     o = oracle_mod.Oracle(dsd_rate=dsd_rate, output_rate=88200, channels=channels, fmt="P", endianness="L",
                           block_size=4096, bit_depth=32, dither="X")
     _, fr, f = o.translate(raw, want_f64=True)

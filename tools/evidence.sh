@@ -23,5 +23,6 @@ case $PART in
   workloads)
     bash tools/workloads.sh ${R}_workloads > gpurun_out/$R/workloads.txt 2>&1; tail -40 gpurun_out/$R/workloads.txt ;;
   default)
-    timeout -k 10 500 python bench.py > gpurun_out/$R/bench_default.json 2> gpurun_out/$R/bench_default.err; echo "default rc=$?"; tail -c 1500 gpurun_out/$R/bench_default.json ;;
+    D=bench_out/$R; mkdir -p $D
+    timeout -k 10 500 python bench.py --full > $D/bench_default.json 2> $D/bench_default.err; echo "default rc=$?"; tail -c 1500 $D/bench_default.json ;;
 esac
