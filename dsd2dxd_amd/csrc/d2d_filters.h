@@ -20,7 +20,7 @@ namespace d2d {
 struct FilterChoice {
     const d2d_filter_def* fir = nullptr;     // integer decimator (the only stage for 44.1k multiples)
     const d2d_resamp_def* resamp = nullptr;  // stage B for 48k multiples, else null
-    // DSD64 / DSD128 -> 48k multiples: the two stages composed into ONE polyphase filter on the bits (d2d_kernels_px.hip).  `fir` and
+    // DSD64 / DSD128 -> 48k multiples and DSD256 -> 192 / 384 kHz: the two stages composed into ONE polyphase filter on the bits (d2d_kernels_px.hip).  `fir` and
     // `resamp` then only say how many frames a call yields (an output exists as soon as the two-stage form would have produced it).
     const d2d_poly_def* poly = nullptr;
 };

@@ -57,7 +57,34 @@ __host__ __device__ constexpr int mx_slot(int MB, int NT, int G, int u, int g, i
 // M = 128: one group (the fragments of a second one would be held for twelve steps: 84 registers)
 __host__ __device__ constexpr int mx_g(int MB) { return MB == 4 ? D2D_MX_G4 : MB == 16 ? 1 : D2D_MX_G8; }
 
+// ---- the compiled kernels: ONE row per object --------------------------------------------------------------------------------
+// X(unit, MB, NT, flavour, NPR).  Unit n is d2d_mx_unit.hip compiled with -DD2D_MX_UNIT=n (unit 0 rides in d2d_kernels_mx.hip, next to the
+// dispatcher) and holds every sample format of its row: launch_mx_formats in d2d_mx_kernel.h.  The dispatcher's table, launch_fir_mx and
+// the mx_*_supported functions all read this list and nothing else.  Adding a shape is one row here plus MX_UNITS in the Makefile
+// (the dispatcher's static_assert says so when the two disagree).
+//   MX_INT   unit gain, all-integer requantiser (KIND 0-2: 24-bit, 16-bit, float frames); NPR = 1 also holds the exact integers for the scratch,
+//            NPR > 1 converts that many channel pairs per wave (planar multichannel frames: 2 quad, 3 a 5.1 stream, 4 a 7.1 / eight-channel stream)
+//   MX_GAIN  the f64 requantiser (KIND 4-7: other levels, 20-bit, the float dither) of the shapes that serve frames (not the cascade's A filters)
+//   MX_WIDE  the one-pass form of the 32-bit tap grid (ND = 7, KIND 4-7; stereo frames)
+// (MB, NT) are the filters X_M32, C_M32, E_M32, A_M32, A_M64, C_M64, E_M64, E_M128.
+enum MxFlavour { MX_INT, MX_GAIN, MX_WIDE };
+#define D2D_MX_UNIT_LIST(X)                                                                                              \
+    X(0, 4, 560, MX_INT, 1)   X(1, 4, 352, MX_INT, 1)   X(2, 4, 384, MX_INT, 1)    X(3, 4, 512, MX_INT, 1)                  \
+    X(4, 8, 688, MX_INT, 1)   X(5, 8, 1024, MX_INT, 1)  X(6, 8, 1104, MX_INT, 1)   X(7, 16, 2192, MX_INT, 1)                \
+    X(8, 4, 560, MX_GAIN, 1)  X(9, 4, 384, MX_GAIN, 1)  X(10, 4, 512, MX_GAIN, 1)  X(11, 8, 1024, MX_GAIN, 1)               \
+    X(12, 8, 1104, MX_GAIN, 1) X(13, 16, 2192, MX_GAIN, 1)                                                               \
+    X(14, 4, 560, MX_INT, 3)  X(15, 8, 1104, MX_INT, 3) X(16, 16, 2192, MX_INT, 3) X(17, 4, 560, MX_INT, 2)                 \
+    X(18, 4, 560, MX_INT, 4)  X(19, 8, 1104, MX_INT, 2) X(20, 8, 1104, MX_INT, 4)                                           \
+    X(21, 4, 560, MX_WIDE, 1) X(22, 8, 1104, MX_WIDE, 1)
+// -DD2D_MX_DEV (A/B builds, tools/ab_build.sh): only the rows of the E_M32 shape are in the table, so only their units need compiling
+#ifdef D2D_MX_DEV
+constexpr bool mx_unit_kept(int MB, int NT) { return MB == 4 && NT == 560; }
+#else
+constexpr bool mx_unit_kept(int, int) { return true; }
+#endif
+
 struct Mfma2Args;
+template <int UNIT> hipError_t launch_mx_unit(Mfma2Args& m, uint32_t max_nout, uint32_t nrows, hipStream_t s);   // d2d_mx_kernel.h; one explicit instantiation per object
 bool mx_supported(int MB, int NT);                 // is a kernel compiled for this shape?
 bool mx_pairs_supported(int MB, int NT, int npairs);   // ... for `npairs` channel pairs per wave (planar multichannel frames)?
 bool mx_gain_supported(int MB, int NT);            // ... and its gain flavours (frames at another level than 0 dB)?

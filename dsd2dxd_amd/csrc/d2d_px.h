@@ -1,6 +1,6 @@
 // d2d_px.h -- geometry of the direct polyphase kernels (d2d_kernels_px.hip), shared by host and device.
 //
-// DSD64 / DSD128 -> 96 / 192 / 384 kHz: the 48k cascade composed into ONE polyphase filter on the bits (filters/filter_tables.inc: D2D_POLYS)
+// DSD64 / DSD128 -> 96 / 192 / 384 kHz and DSD256 -> 192 / 384 kHz: the 48k cascade composed into ONE polyphase filter on the bits (filters/filter_tables.inc: D2D_POLYS)
 //
 //     y[m] = sum_j c[rho][j] s[q + D - j],   Mp m = Lp q + rho,   c = Q 2^-S (24-bit Q, every phase sums to 2^S)
 //
@@ -91,6 +91,17 @@ struct PxArgs {
     uint32_t qsh;              // 4: 20-bit samples in a 24-bit container
     Epilogue epi;
 };
+
+// ---- the compiled matrix-core kernels: ONE row per object ------------------------------------------------------------------------
+// X(unit, LP, MP, NP, G): the (Lp, Mp, NP) of a generated table (filters/filter_tables.inc: D2D_POLYS; tests/test_poly48k.py fails when a table
+// has no row here) and the groups per column it is compiled with.  Unit n is d2d_px_unit.hip compiled with -DD2D_PX_UNIT=n (unit 0 rides in
+// d2d_kernels_px.hip, next to the plain kernel and the dispatcher) and holds every KIND of its row.  launch_fir_px, px_supported and px_groups
+// read this list and nothing else.  Adding a shape is one row here plus PX_UNITS in the Makefile (the dispatcher's static_assert says so
+// when the two disagree).
+#define D2D_PX_UNIT_LIST(X)                                                                  \
+    X(0, 5, 147, 751, 3)  X(1, 10, 147, 375, 4) X(2, 20, 147, 269, 4) X(3, 5, 294, 1501, 2)  \
+    X(4, 5, 147, 771, 3)  X(5, 10, 147, 539, 4) X(6, 5, 294, 1541, 2) X(7, 5, 147, 1079, 3)
+template <int UNIT> hipError_t launch_px_unit(PxArgs& a, uint32_t max_nout, uint32_t nfiles, hipStream_t s);   // d2d_px_kernel.h; one explicit instantiation per object
 
 bool px_supported(const d2d_poly_def& p);                                   // is a matrix-core kernel compiled for this table?
 bool px_exact(const d2d_poly_def& p);                                       // do the table's base-32 digit sums recombine exactly in f32?

@@ -39,6 +39,25 @@ def _digits32(v):
     return out
 
 
+def test_every_table_has_a_compiled_shape():
+    """every row of D2D_POLYS (filters/filter_tables.inc) meets a row of D2D_PX_UNIT_LIST (dsd2dxd_amd/csrc/d2d_px.h) with its (Lp, Mp, NP):
+    a regenerated table whose length moved would otherwise fall to the plain kernel without a word"""
+    import re
+    with open(os.path.join(ROOT, "filters", "filter_tables.inc")) as f:
+        inc = f.read()
+    body = re.search(r"D2D_POLYS\[(\d+)\] = \{(.*?)\n\};", inc, re.S)
+    tables = re.findall(r'\{ "(\w+)", \d+, \d+, (\d+), (\d+), (\d+),', body.group(2))
+    assert len(tables) == int(body.group(1)) == len(RATES)
+    with open(os.path.join(ROOT, "dsd2dxd_amd", "csrc", "d2d_px.h")) as f:
+        hdr = f.read()
+    lst = re.search(r"#define D2D_PX_UNIT_LIST\(X\)(.*?)\n[^ ]", hdr, re.S).group(1)
+    rows = [tuple(int(x) for x in r) for r in re.findall(r"X\((\d+), (\d+), (\d+), (\d+), (\d+)\)", lst)]
+    assert [r[0] for r in rows] == list(range(len(rows))) and rows     # units are numbered as the build numbers them
+    shapes = {r[1:4] for r in rows}
+    for name, lp, mp, np_ in tables:
+        assert (int(lp), int(mp), int(np_)) in shapes, f"{name}: no compiled d2d_fir_px_kernel for (Lp, Mp, NP) = ({lp}, {mp}, {np_})"
+
+
 @pytest.mark.parametrize("dsd_rate,out_rate", RATES)
 def test_table_invariants(dsd_rate, out_rate):
     """what the kernels rely on: unity DC gain per phase on the dyadic grid, 24-bit taps in five balanced base-32 digits whose sums
