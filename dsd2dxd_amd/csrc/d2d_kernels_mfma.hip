@@ -654,17 +654,6 @@ MfmaLayout mfma_layout(int M, int N) {
     return g;
 }
 
-static inline int8_t limb_of(int64_t v, int l) {
-    // balanced base-256 digits: v = d0 + d1*2^8 + d2*2^16 + d3*2^24, every d in [-128, 127]
-    int8_t dgt = 0;
-    for (int i = 0; i <= l; ++i) {
-        int64_t dd = ((v + 128) & 255) - 128;
-        dgt = (int8_t)dd;
-        v = (v - dd) / 256;
-    }
-    return dgt;
-}
-
 // Tap fragments [4 byte shifts][ksteps + 6][64 lanes][16 bytes].  Lane l supplies matrix row (l & 31) = 4*phase + limb
 // for the K slots (l >> 5)*16 + j; slot (ks, h, j) reads bit `wb` of the row window (see the
 // kernel's A00/A01), which sits at bit position p = wb & 7 of its stream byte and therefore arrives
@@ -689,7 +678,7 @@ std::vector<int8_t> build_mfma_tables(const d2d_filter_def& f, const MfmaLayout&
                     if (tau >= 0 && tap >= 0 && tap < f.ntaps) {
                         int64_t q = tap_q(f, tap);
                         q = p == 7 ? -q : q * (int64_t)(1 << (7 - p));
-                        v = limb_of(q, limb);
+                        v = limb256(q, limb);
                     }
                     t[sh * per + ((size_t)ks * 64 + l) * 16 + j] = v;
                 }
@@ -754,26 +743,10 @@ static hipError_t launch_mfma_t(const MfmaArgs& m, size_t smem, uint32_t nwt_max
     int dev = 0;
     hipError_t e = prep.max_dynamic_lds(reinterpret_cast<const void*>(&d2d_fir_mfma_kernel<MB>), 160 * 1024, &dev);
     if (e != hipSuccess) return e;
-    int blocks_per_cu, ncu;
-    {
-        std::lock_guard<std::mutex> g(prep.mu);
-        if (prep.blocks_per_cu[dev] == 0 || smem != prep.smem_seen[dev] || m.nwaves != prep.nwaves_seen[dev]) {
-            hipDeviceProp_t prop;
-            if ((e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return e;
-            int nb = 0;
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, d2d_fir_mfma_kernel<MB>, (int)(64 * m.nwaves), smem);
-            if (e != hipSuccess) return e;
-            prep.ncu[dev] = prop.multiProcessorCount;
-            prep.blocks_per_cu[dev] = nb < 1 ? 1 : nb;
-            prep.smem_seen[dev] = smem; prep.nwaves_seen[dev] = m.nwaves;
-        }
-        blocks_per_cu = prep.blocks_per_cu[dev]; ncu = prep.ncu[dev];
-    }
     // every wave loops over its share of the wave-tiles: launch what is resident at once
-    uint32_t gx = (uint32_t)(ncu * blocks_per_cu) / nfiles;
-    if (gx < 1) gx = 1;
-    const uint32_t need = (nwt_max + m.nwaves - 1) / m.nwaves;
-    if (gx > need) gx = need;
+    uint32_t gx;
+    e = persistent_grid_x(&d2d_fir_mfma_kernel<MB>, prep, dev, m.nwaves, smem, nfiles, (nwt_max + m.nwaves - 1) / m.nwaves, &gx);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL((d2d_fir_mfma_kernel<MB>), dim3(gx, nfiles), dim3(64 * m.nwaves), smem, s, m);
     d2d_last_launched_kernel = launched_name<MB>("d2d_fir_mfma_kernel");
     return hipGetLastError();

@@ -25,6 +25,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include "d2d_m3.h"
 #include "d2d_mfma2_dev.h"
 #include "d2d_mx.h"
 
@@ -622,17 +623,6 @@ __global__ __launch_bounds__(D2D_M2_THREADS) void d2d_fir_mfma2_kernel(Mfma2Args
 
 int mfma2_pairs(int M, int N) { return (N + 7 * M + 24 + 63) / 64; }
 
-static inline int8_t limb_of2(int64_t v, int l) {
-    // balanced base-256 digits: v = d0 + d1*2^8 + d2*2^16 + d3*2^24, every d in [-128, 127]
-    int8_t dgt = 0;
-    for (int i = 0; i <= l; ++i) {
-        int64_t dd = ((v + 128) & 255) - 128;
-        dgt = (int8_t)dd;
-        v = (v - dd) / 256;
-    }
-    return dgt;
-}
-
 // Tap fragments [4 byte shifts][2*NPG][64 lanes][16 bytes].  Fragment 2*pp + n serves pair step pp of a
 // group's window, bit positions 4n .. 4n+3 of every byte.  Lane l supplies matrix row (l & 31) =
 // 4*slot + limb for the K slots of lane half hh = l >> 5, i.e. the staged dword 2*pp + hh of the window;
@@ -653,35 +643,27 @@ std::vector<int8_t> build_mfma2_tables(const d2d_filter_def& f, bool msb_first, 
                 const int ph = 4 * ((row >> 2) & 1) + (row >> 3);
                 for (int j = 0; j < 16; ++j) {
                     const int p = 4 * n + (j >> 2);
-                    const int wb = 32 * (2 * pp + hh) + 8 * (j & 3) + p;                     // bit of the staged window
-                    const int tau = (msb_first ? (wb & ~7) + 7 - (wb & 7) : wb) - 8 * sh;   // its time index in the window
-                    const int tap = tau - ph * f.M;
                     auto entry = [&](int pp_) -> int64_t {                                   // q * 2^(7-p) (p = 7: -q) of bit position pp_ of this byte
-                        const int wb_ = 32 * (2 * pp + hh) + 8 * (j & 3) + pp_;
-                        const int tau_ = (msb_first ? (wb_ & ~7) + 7 - (wb_ & 7) : wb_) - 8 * sh;
+                        const int wb_ = 32 * (2 * pp + hh) + 8 * (j & 3) + pp_;                    // bit of the staged window
+                        const int tau_ = (msb_first ? (wb_ & ~7) + 7 - (wb_ & 7) : wb_) - 8 * sh;  // its time index in the window
                         const int tap_ = tau_ - ph * f.M;
                         if (tau_ < 0 || tap_ < 0 || tap_ >= f.ntaps) return 0;
                         const int64_t q = tap_q(f, tap_);
                         return pp_ == 7 ? -q : q * (int64_t)(1 << (7 - pp_));
                     };
-                    (void)tau; (void)tap;
                     int64_t T = entry(p);
                     if (unmask0 && p != 0) T -= entry(0);                                 // plane 0 arrives unmasked (see the kernel)
-                    t[sh * per + ((size_t)fr * 64 + l) * 16 + j] = limb_of2(T, limb);
+                    t[sh * per + ((size_t)fr * 64 + l) * 16 + j] = limb256(T, limb);
                 }
             }
     return t;
 }
 
 // (MB, NPG) pairs with a compiled kernel
-#ifdef D2D_M2_DEV
-#define D2D_M2_SHAPES(X) X(4, 13)
-#else
 // M = 32 and 64 only: with 1 or 2 bytes per output a 512-output tile holds so little stream that the per-tile work
 // (staging, waits, the epilogue) outweighs the shorter chain and the one-group kernel is faster (measured: DSD64 -> 352.8 kHz
 // float 451 against 514 Gsamples/s, the M = 8 stage A of the 48k cascade 4.7 against 3.8 ms)
 #define D2D_M2_SHAPES(X) X(4, 10) X(4, 12) X(4, 13) X(8, 19) X(8, 24) X(8, 25)
-#endif
 
 bool mfma2_supported(int M, int N) {
     const int MB = M / 8, NPG = mfma2_pairs(M, N);
@@ -824,6 +806,8 @@ static hipError_t launch_mfma2_t(Mfma2Args& m, size_t smem, uint32_t nwt_max, ui
     const void* fn = reinterpret_cast<const void*>(&d2d_fir_mfma2_kernel<MB, NPG, CH, EPI>);
     hipError_t e = prep.max_dynamic_lds(fn, 160 * 1024, &dev);
     if (e != hipSuccess) return e;
+    // (not persistent_grid_x of d2d_launch.h: the shrink loop below changes the block inside the occupancy query, and the cache keeps both what
+    // was asked for and what was admitted)
     int blocks_per_cu, ncu;
     {
         std::lock_guard<std::mutex> g(prep.mu);
@@ -879,8 +863,7 @@ hipError_t launch_fir_mfma2(const FirArgs& a, int M, int N, uint32_t max_nout, u
     const int epi = mfma2_epilogue(a, m);
     // stereo 24-bit at 0 dB: the software-pipelined kernel (d2d_kernels_mfma3.hip), same results; the engine chose it (and its
     // table variant) when it was created
-    if (a.pipelined == 5) return launch_fir_mx(m, MB, N, max_nout, nrows, s);
-    if (a.pipelined) return launch_fir_mfma3(m, (int)a.pipelined, MB, NPG, N, nwt, nrows, s);
+    if (a.pipelined) return launch_fir_mfma3(m, MB, NPG, N, nwt, nrows, s);
 #define X(mb, npg)                                                                                  \
     if (MB == mb && NPG == npg) {                                                                   \
         if (C == 1) return epi == 2 ? launch_mfma2_t<mb, npg, 1, 2>(m, smem, nwt, nrows, s) : launch_mfma2_t<mb, npg, 1, 0>(m, smem, nwt, nrows, s); \

@@ -23,8 +23,8 @@ struct KernelPrep {
     // occupancy cache of the persistent MFMA launch
     int blocks_per_cu[MAX_DEV] = {}, ncu[MAX_DEV] = {};
     size_t smem_seen[MAX_DEV] = {};
-    size_t smem_used[MAX_DEV] = {};
     uint32_t nwaves_seen[MAX_DEV] = {};
+    size_t smem_used[MAX_DEV] = {};          // (the two-group kernel: what its shrink loop settled on)
     uint32_t nwaves_used[MAX_DEV] = {};
 
     hipError_t max_dynamic_lds(const void* fn, int bytes, int* dev_out = nullptr) {
@@ -40,6 +40,35 @@ struct KernelPrep {
         return e;
     }
 };
+
+// The grid of a persistent launch of the matrix-core FIR kernels: every wave loops over its share of the wave-tiles, so gx = what is resident
+// at once (blocks per CU from the occupancy query, cached per device in the kernel's own `prep`, under its lock) spread over the `nrows`
+// block rows, and no more than the `need` blocks that have a tile to start on.  (launch_mfma2_t keeps its own copy: it shrinks the block
+// inside the query and caches what the register file admitted.)
+template <class Args>
+inline hipError_t persistent_grid_x(void (*kernel)(Args), KernelPrep& prep, int dev, uint32_t nwaves, size_t smem, uint32_t nrows, uint32_t need,
+                                    uint32_t* gx_out) {
+    int blocks_per_cu, ncu;
+    {
+        std::lock_guard<std::mutex> g(prep.mu);
+        if (prep.blocks_per_cu[dev] == 0 || smem != prep.smem_seen[dev] || nwaves != prep.nwaves_seen[dev]) {
+            hipDeviceProp_t prop;
+            hipError_t e = hipGetDeviceProperties(&prop, dev);
+            if (e != hipSuccess) return e;
+            int nb = 0;
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, (int)(64 * nwaves), smem);
+            if (e != hipSuccess) return e;
+            prep.ncu[dev] = prop.multiProcessorCount;
+            prep.blocks_per_cu[dev] = nb < 1 ? 1 : nb;
+            prep.smem_seen[dev] = smem; prep.nwaves_seen[dev] = nwaves;
+        }
+        blocks_per_cu = prep.blocks_per_cu[dev]; ncu = prep.ncu[dev];
+    }
+    uint32_t gx = (uint32_t)(ncu * blocks_per_cu) / nrows;
+    if (gx < 1) gx = 1;
+    *gx_out = gx > need ? need : gx;
+    return hipSuccess;
+}
 
 // The FIR kernel a launcher has just enqueued, spelled the way rocprofv3 prints it: set by every launch_fir_* at the point of the launch
 // (per thread: engines are driven from one thread each), copied into the engine by d2d_translate_batch_device, so that

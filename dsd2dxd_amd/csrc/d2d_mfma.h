@@ -18,6 +18,17 @@ struct MfmaLayout {
     int limbs = 4;        // int8 limbs per 32-bit tap
 };
 
+// balanced base-256 digit l of v (the int8 limbs of a tap): v = d0 + d1*2^8 + d2*2^16 + d3*2^24, every d in [-128, 127]
+inline int8_t limb256(int64_t v, int l) {
+    int8_t dgt = 0;
+    for (int i = 0; i <= l; ++i) {
+        int64_t dd = ((v + 128) & 255) - 128;
+        dgt = (int8_t)dd;
+        v = (v - dd) / 256;
+    }
+    return dgt;
+}
+
 bool mfma_supported(int M, int N);
 MfmaLayout mfma_layout(int M, int N);
 size_t mfma_smem_bytes(const MfmaLayout& g, uint32_t channels, uint32_t sample_bytes, uint32_t* waves_per_block);

@@ -86,11 +86,4 @@ static __device__ __noinline__ u32x4 gather_chunk(const StreamJob* job, uint32_t
     return u32x4{w[0], w[1], w[2], w[3]};
 }
 
-
-// defined in d2d_kernels_mfma2.hip / d2d_kernels_mfma3.hip
-hipError_t launch_fir_mfma3(Mfma2Args& m, int variant, int MB, int NPG, int NT, uint32_t nwt_max, uint32_t nrows, hipStream_t s);
-bool mfma3_supported(int MB, int NPG, int NT);
-bool mfma3_sparse_compiled(int MB, int NT);
-bool mfma3_scr_supported(int MB, int NPG);
-
 }  // namespace d2d

@@ -1061,27 +1061,11 @@ static hipError_t launch_mx_t(Mfma2Args& m, uint32_t max_nout, uint32_t nrows, h
     m.nwaves = nwaves;
     const size_t smem = (size_t)m.off_waves + (size_t)m.nwaves * m.wave_lds;
     if (smem > 160 * 1024) return hipErrorInvalidValue;
-    int blocks_per_cu, ncu;
-    {
-        std::lock_guard<std::mutex> g(prep.mu);
-        if (prep.blocks_per_cu[dev] == 0 || smem != prep.smem_seen[dev] || m.nwaves != prep.nwaves_seen[dev]) {
-            hipDeviceProp_t prop;
-            if ((e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return e;
-            int nb = 0;
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, d2d_fir_mx_kernel<MB, NT, G, KIND, SBY, NPR, ND>, (int)(64 * m.nwaves), smem);
-            if (e != hipSuccess) return e;
-            prep.ncu[dev] = prop.multiProcessorCount;
-            prep.blocks_per_cu[dev] = nb < 1 ? 1 : nb;
-            prep.smem_seen[dev] = smem; prep.nwaves_seen[dev] = m.nwaves;
-        }
-        blocks_per_cu = prep.blocks_per_cu[dev]; ncu = prep.ncu[dev];
-    }
     // every wave loops over its share of the wave-tiles: launch what is resident at once
     const uint32_t nwt_max = (max_nout + TILE - 1) / TILE;
-    uint32_t gx = (uint32_t)(ncu * blocks_per_cu) / nrows;
-    if (gx < 1) gx = 1;
-    const uint32_t need = coop ? nwt_max : (nwt_max + m.nwaves - 1) / m.nwaves;
-    if (gx > need) gx = need;
+    uint32_t gx;
+    e = persistent_grid_x(&d2d_fir_mx_kernel<MB, NT, G, KIND, SBY, NPR, ND>, prep, dev, m.nwaves, smem, nrows, coop ? nwt_max : (nwt_max + m.nwaves - 1) / m.nwaves, &gx);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL((d2d_fir_mx_kernel<MB, NT, G, KIND, SBY, NPR, ND>), dim3(gx, nrows), dim3(64 * m.nwaves), smem, s, m);
     d2d_last_launched_kernel = launched_name<MB, NT, G, KIND, SBY, NPR, ND>("d2d_fir_mx_kernel");     // (all seven arguments: the way rocprofv3 prints the instantiation)
     return hipGetLastError();
