@@ -61,7 +61,8 @@ EXPORTS = ["d2d_create", "d2d_create_error", "d2d_destroy", "d2d_reset", "d2d_la
            "d2d_translate_batch_host",
            "d2d_peak", "d2d_peak_dbfs", "d2d_convert_stream", "d2d_tables_bytes",
            "d2d_tables_export_device", "d2d_tables_import_device", "d2d_get_info", "d2d_kernel_name",
-           "d2d_profile_enable", "d2d_profile_read", "d2d_profile_read_all"]
+           "d2d_profile_enable", "d2d_profile_read", "d2d_profile_read_all",
+           "d2d_seek", "d2d_tell", "d2d_preroll_bytes", "d2d_slice_align_bytes", "d2d_prime", "d2d_prime_batch_device"]
 
 _lib = None
 
@@ -113,6 +114,14 @@ def lib():
     L.d2d_profile_enable.argtypes = [C.c_void_p, C.c_int]
     L.d2d_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.d2d_profile_read_all.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    L.d2d_seek.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
+    L.d2d_tell.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.d2d_preroll_bytes.argtypes = [C.c_void_p]
+    L.d2d_preroll_bytes.restype = C.c_size_t
+    L.d2d_slice_align_bytes.argtypes = [C.c_void_p]
+    L.d2d_slice_align_bytes.restype = C.c_size_t
+    L.d2d_prime.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.d2d_prime_batch_device.argtypes = [C.c_void_p, C.POINTER(FileIO), C.c_uint32, C.c_void_p]
     _lib = L
     return L
 
@@ -206,6 +215,37 @@ class Engine:
     def translate_batch_host(self, ios, slice_bytes_per_channel=0):
         """ios: ctypes array of FileIO with HOST pointers (pinned for overlap); synchronous."""
         self._check(lib().d2d_translate_batch_host(self._h, ios, len(ios), slice_bytes_per_channel))
+
+    def seek(self, pos, file=0):
+        """Put `file` into a fresh engine's state standing at `pos` bytes per channel (d2d_seek); synchronises."""
+        self._check(lib().d2d_seek(self._h, file, pos))
+
+    def tell(self, file=0):
+        """(bytes per channel consumed, index of the next frame) of `file`"""
+        pos, frame = C.c_uint64(), C.c_uint64()
+        rc = lib().d2d_tell(self._h, file, C.byref(pos), C.byref(frame))
+        if rc:
+            raise D2DError(rc, "file out of range")
+        return pos.value, frame.value
+
+    def preroll_bytes(self):
+        """bytes per channel of halo to prime with before a slice's first byte (d2d_preroll_bytes)"""
+        return lib().d2d_preroll_bytes(self._h)
+
+    def slice_align_bytes(self):
+        """positions at which a slice may begin are multiples of this (1 unless the dither is noise-shaped)"""
+        return lib().d2d_slice_align_bytes(self._h)
+
+    def prime(self, dsd):
+        """Host buffer like translate()'s: consumes the bytes, carries the history, produces no frames (d2d_prime)."""
+        import numpy as np
+        buf = np.ascontiguousarray(np.frombuffer(dsd, dtype=np.uint8) if not isinstance(dsd, np.ndarray) else dsd)
+        assert buf.size % self.channels == 0
+        self._check(lib().d2d_prime(self._h, buf.ctypes.data, buf.size // self.channels))
+
+    def prime_batch_device(self, ios, stream=None):
+        """ios as for translate_batch_device (pcm fields ignored); asynchronous on `stream`."""
+        self._check(lib().d2d_prime_batch_device(self._h, ios, len(ios), C.c_void_p(stream or 0)))
 
     def peak(self, channel, file=0):
         v = C.c_double()

@@ -34,6 +34,8 @@ struct FileState {
     uint64_t pos = 0;    // bytes per channel consumed
     uint64_t nfir = 0;   // FIR outputs produced
     uint64_t nres = 0;   // stage-B outputs produced (48k family)
+    bool ns_unknown = false;   // 'N' dither: the shaper's state is not the uninterrupted conversion's (after d2d_seek past 0 / a prime) until a
+                               // translate call starts on a multiple of 8192, where the state is zero by definition
 };
 
 constexpr int JOB_SLOTS = 8;
@@ -196,6 +198,18 @@ static int reset_state(d2d_engine* e) {
     for (int i = 0; i < 2; ++i) if (e->d_ns[i]) HIPCHK(e, hipMemset(e->d_ns[i], 0, sizeof(double) * 2 * e->nstreams));
     for (auto& f : e->files) f = FileState{};
     e->hist_cur = 0;
+    return D2D_OK;
+}
+
+// one file back to the device state of a fresh engine, in both ping-pong buffers; the other files' rows stay
+static int clear_file_state(d2d_engine* e, uint32_t file) {
+    const size_t s0 = (size_t)file * e->C;
+    const uint8_t idle = e->p.endianness == D2D_MSB_FIRST ? IDLE_BYTE : (uint8_t)0x96;
+    for (int b = 0; b < 2; ++b) HIPCHK(e, hipMemset(e->d_hist[b] + s0 * e->keep, idle, (size_t)e->C * e->keep));
+    HIPCHK(e, hipMemset(e->d_peak + s0, 0, sizeof(double) * e->C));
+    if (e->d_scratch && e->xs_hist)     // the stage-A history in front of each of the file's scratch lines
+        HIPCHK(e, hipMemset2D(e->d_scratch + s0 * e->scratch_stride, e->scratch_stride * sizeof(int32_t), 0, (size_t)e->xs_hist * sizeof(int32_t), e->C));
+    for (int i = 0; i < 2; ++i) if (e->d_ns[i]) HIPCHK(e, hipMemset(e->d_ns[i] + 2 * s0, 0, sizeof(double) * 2 * e->C));
     return D2D_OK;
 }
 
@@ -484,16 +498,66 @@ static int grow_scratch(d2d_engine* e, size_t need_stride, hipStream_t s) {
     return D2D_OK;
 }
 
-int d2d_translate_batch_device(d2d_engine* e, d2d_file_io* io, uint32_t n_files, void* hip_stream) {
+int d2d_seek(d2d_engine* e, uint32_t file, uint64_t pos) {
     if (!e) return D2D_ERR_PARAM;
+    if (file >= e->n_files) return e->fail(D2D_ERR_PARAM, "file out of range");
+    HIPCHK(e, hipSetDevice(e->p.device));
+    HIPCHK(e, hipDeviceSynchronize());
+    int rc = clear_file_state(e, file);
+    if (rc) return rc;
+    HIPCHK(e, hipDeviceSynchronize());      // (the fills are ordered before whatever stream the next call uses)
+    FileState& st = e->files[file];
+    st.pos = pos;
+    st.nfir = pos / (uint64_t)e->Mb;
+    st.nres = res_outputs_after(e, st.nfir);
+    st.ns_unknown = e->noise_shape && pos > 0;
+    return D2D_OK;
+}
+
+int d2d_tell(const d2d_engine* e, uint32_t file, uint64_t* pos, uint64_t* next_frame) {
+    if (!e || file >= e->n_files) return D2D_ERR_PARAM;
+    const FileState& st = e->files[file];
+    if (pos) *pos = st.pos;
+    if (next_frame) *next_frame = e->fc.resamp ? st.nres : st.nfir;
+    return D2D_OK;
+}
+
+// The oldest byte the first frame after position p can depend on, as a distance back from p (include/dsd2dxd_amd.h: the guarantee).
+//   single filter: output n = p / Mb ends at byte (n + 1) Mb > p - Mb + Mb, its window reaches Wb further back: Wb + Mb;
+//   composed polyphase: the carried history is sized for exactly this (d2d_create: keep);
+//   cascade: frame F(p) reads stage-A outputs no older than p / Mb - P - 1; the oldest of them ends no earlier than
+//   p - Mb - P Mb and its window reaches Wb further back: Wb + (P + 1) Mb.
+size_t d2d_preroll_bytes(const d2d_engine* e) {
+    if (!e) return 0;
+    if (e->poly) return e->keep;
+    if (e->cascade()) return (size_t)e->Wb + ((size_t)e->fc.resamp->P + 1) * (size_t)e->Mb;
+    return (size_t)e->Wb + (size_t)e->Mb;
+}
+
+size_t d2d_slice_align_bytes(const d2d_engine* e) {
+    if (!e) return 0;
+    if (!e->noise_shape) return 1;
+    if (!e->fc.resamp) return (size_t)e->Mb * 8192u;
+    // F(k A) = k (A / Mb) L / Mdn: whole for A / Mb a multiple of Mdn (L and Mdn are coprime), a multiple of 8192 once L's own powers of two are counted
+    const uint64_t L = (uint64_t)e->fc.resamp->L, Mdn = (uint64_t)e->fc.resamp->Mdn;
+    uint64_t g = 8192; while (L % g) g >>= 1;
+    return (size_t)((uint64_t)e->Mb * Mdn * (8192 / g));
+}
+
+// One call of every file: the plan, the job table and the launches that d2d_translate_batch_device and d2d_prime_batch_device share.
+// prime: the bytes are consumed and everything that carries over to the next call is updated (the planar copy the history is read from,
+// stage A of the cascade with its carried outputs, the bit history), but no frames are produced and the peaks stay.
+static int batch_call(d2d_engine* e, d2d_file_io* io, uint32_t n_files, hipStream_t s, const bool prime) {
     if (!io || n_files != e->n_files) return e->fail(D2D_ERR_PARAM, "file count does not match the engine");
-    hipStream_t s = (hipStream_t)hip_stream;
     HIPCHK(e, hipSetDevice(e->p.device));
     const size_t fb = d2d_frame_bytes(e);
     const uint32_t C = e->C;
     // plan
     uint32_t max_nx = 0, max_frames = 0;
-    std::vector<uint64_t> nfir1(n_files), nres1(n_files);
+    // a prime runs a FIR only where its outputs carry over: stage A of the cascade.  Every other engine's prime plans no outputs at all (max_nx,
+    // max_frames = 0), which is what keeps the FIR passes, the mono pair and the combining pass below out of it.
+    const bool run_fir = !prime || e->cascade();
+    std::vector<uint64_t> nfir1(n_files), nres1(n_files), nframes(n_files);
     for (uint32_t f = 0; f < n_files; ++f) {
         const FileState& st = e->files[f];
         const size_t L = io[f].bytes_per_channel;
@@ -501,19 +565,23 @@ int d2d_translate_batch_device(d2d_engine* e, d2d_file_io* io, uint32_t n_files,
         if (L && (!io[f].dsd || ((uintptr_t)io[f].dsd & 15))) return e->fail(D2D_ERR_PARAM, "dsd device pointer must be non-null and 16-byte aligned");
         nfir1[f] = (st.pos + L) / (uint64_t)e->Mb;
         nres1[f] = res_outputs_after(e, nfir1[f]);
-        const uint64_t nx = nfir1[f] - st.nfir;
-        const uint64_t frames = e->fc.resamp ? nres1[f] - st.nres : nx;
+        const uint64_t nx = run_fir ? nfir1[f] - st.nfir : 0;
+        const uint64_t frames = prime ? 0 : e->fc.resamp ? nres1[f] - st.nres : nx;
+        nframes[f] = frames;
         if (frames * fb > io[f].pcm_capacity_bytes) return e->fail(D2D_ERR_CAPACITY, "pcm buffer too small");
         if (frames && (!io[f].pcm || ((uintptr_t)io[f].pcm & 15))) return e->fail(D2D_ERR_PARAM, "pcm device pointer must be non-null and 16-byte aligned");
+        if (frames && st.ns_unknown && ((e->fc.resamp ? st.nres : st.nfir) & 8191u))
+            return e->fail(D2D_ERR_STATE, "noise-shaped dither after d2d_seek / d2d_prime: frames can only start at an index that is a multiple of 8192 "
+                                          "(cut the stream at multiples of d2d_slice_align_bytes)");
         max_nx = std::max<uint32_t>(max_nx, (uint32_t)nx);
         max_frames = std::max<uint32_t>(max_frames, (uint32_t)frames);
-        io[f].frames_out = (size_t)frames;
     }
+    for (uint32_t f = 0; f < n_files; ++f) io[f].frames_out = (size_t)nframes[f];       // (written once every file has passed its checks)
     if (e->cascade() || e->noise_shape || e->fine) {
         int rc = grow_scratch(e, (size_t)e->xs_hist + (e->poly ? max_frames : max_nx), s);
         if (rc) return rc;
     }
-    if (e->noise_shape && e->cascade() && (size_t)max_frames + 8 > e->ys_stride) {
+    if (!prime && e->noise_shape && e->cascade() && (size_t)max_frames + 8 > e->ys_stride) {
         HIPCHK(e, hipStreamSynchronize(s));
         if (e->d_ys) HIPCHK(e, hipFree(e->d_ys));
         e->d_ys = nullptr; e->ys_stride = 0;
@@ -549,7 +617,7 @@ int d2d_translate_batch_device(d2d_engine* e, d2d_file_io* io, uint32_t n_files,
             j.in_raw = e->deinterleave ? (const uint8_t*)io[f].dsd : nullptr;
             j.hist = e->d_hist[cur] + (size_t)sidx * e->keep;
             j.hist_next = e->d_hist[cur ^ 1] + (size_t)sidx * e->keep;
-            j.out = io[f].pcm;
+            j.out = prime ? nullptr : io[f].pcm;
             j.xs = e->d_scratch ? e->d_scratch + (size_t)sidx * e->scratch_stride + e->xs_hist : nullptr;
             j.peak = e->d_peak + sidx;
             j.L = io[f].bytes_per_channel;
@@ -560,7 +628,7 @@ int d2d_translate_batch_device(d2d_engine* e, d2d_file_io* io, uint32_t n_files,
             j.ch = e->c0 + c;
             j.och = c;
             j.m0 = st.nres;
-            j.nres = e->fc.resamp ? (uint32_t)(nres1[f] - st.nres) : 0;
+            j.nres = e->fc.resamp && !prime ? (uint32_t)(nres1[f] - st.nres) : 0;
             const uint64_t i0 = e->fc.resamp ? st.nres : st.nfir;     // index the dither counter runs on
             const uint64_t k = rng_key64(e->p.seed, e->c0 + c);
             j.rng_kstep = (uint32_t)k | 1u;
@@ -595,7 +663,7 @@ int d2d_translate_batch_device(d2d_engine* e, d2d_file_io* io, uint32_t n_files,
     e->job_ev_used[slot] = true;
 
     std::pair<hipEvent_t, hipEvent_t>* ps = nullptr;
-    if (e->profiling && max_nx) {
+    if (e->profiling && (max_nx || (prime && max_L))) {
         if (e->step_used == e->step_pool.size()) {
             std::pair<hipEvent_t, hipEvent_t> n{};
             HIPCHK(e, hipEventCreate(&n.first));
@@ -666,14 +734,16 @@ int d2d_translate_batch_device(d2d_engine* e, d2d_file_io* io, uint32_t n_files,
         HIPCHK(e, launch_fine_combine(e->d_jobs, e->nstreams, max_nx, (size_t)e->nstreams * e->scratch_stride, lo_bias, e->S + 8, e->epi, s));
     }
     if (e->cascade()) {
-        Rs2Args r{};
-        r.jobs = e->d_jobs; r.tables = reinterpret_cast<const uint8_t*>(e->d_resamp);
-        r.S = e->S; r.epi = e->epi;
-        if (e->noise_shape) { r.ys = e->d_ys; r.ys_stride = (uint32_t)e->ys_stride; }
-        HIPCHK(e, launch_resample2(r, *e->fc.resamp, max_frames, n_files, s));
+        if (!prime) {
+            Rs2Args r{};
+            r.jobs = e->d_jobs; r.tables = reinterpret_cast<const uint8_t*>(e->d_resamp);
+            r.S = e->S; r.epi = e->epi;
+            if (e->noise_shape) { r.ys = e->d_ys; r.ys_stride = (uint32_t)e->ys_stride; }
+            HIPCHK(e, launch_resample2(r, *e->fc.resamp, max_frames, n_files, s));
+        }
         HIPCHK(e, launch_xhist(e->d_jobs, e->nstreams, (uint32_t)e->fc.resamp->P, s));
     }
-    if (e->noise_shape) {
+    if (e->noise_shape && !prime) {
         NoiseShapeArgs ns{};
         ns.jobs = e->d_jobs; ns.state = e->d_ns[e->ns_cur]; ns.state_next = e->d_ns[e->ns_cur ^ 1]; ns.dump = e->d_ns_dump;
         ns.scale_bits = e->poly ? e->poly->S : e->S; ns.nstreams = e->nstreams; ns.max_nout = e->fc.resamp ? max_frames : max_nx; ns.epi = e->epi;
@@ -701,12 +771,27 @@ int d2d_translate_batch_device(d2d_engine* e, d2d_file_io* io, uint32_t n_files,
     e->hist_cur = cur ^ 1;
     for (uint32_t f = 0; f < n_files; ++f) {
         FileState& st = e->files[f];
+        if (e->noise_shape) {
+            // frames began on a segment boundary: the shaper's state is the uninterrupted conversion's from here on; a prime leaves it unknown
+            if (prime) { if (io[f].bytes_per_channel) st.ns_unknown = true; }
+            else if (io[f].frames_out) st.ns_unknown = false;
+        }
         st.pos += io[f].bytes_per_channel;
         st.nfir = nfir1[f];
         st.nres = nres1[f];
     }
     e->last_stream = s;
     return D2D_OK;
+}
+
+int d2d_translate_batch_device(d2d_engine* e, d2d_file_io* io, uint32_t n_files, void* hip_stream) {
+    if (!e) return D2D_ERR_PARAM;
+    return batch_call(e, io, n_files, (hipStream_t)hip_stream, false);
+}
+
+int d2d_prime_batch_device(d2d_engine* e, d2d_file_io* io, uint32_t n_files, void* hip_stream) {
+    if (!e) return D2D_ERR_PARAM;
+    return batch_call(e, io, n_files, (hipStream_t)hip_stream, true);
 }
 
 static int ensure_cap(d2d_engine* e, uint8_t** buf, size_t* cap, size_t need) {
@@ -772,6 +857,32 @@ int d2d_translate(d2d_engine* e, const uint8_t* dsd, size_t L, void* pcm, size_t
     if (out_bytes) HIPCHK(e, hipMemcpyAsync(pcm, e->d_out, out_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     if (frames_out) *frames_out = io.frames_out;
+    return D2D_OK;
+}
+
+int d2d_prime(d2d_engine* e, const uint8_t* dsd, size_t L) {
+    if (!e) return D2D_ERR_PARAM;
+    if (e->n_files != 1) return e->fail(D2D_ERR_STATE, "d2d_prime needs a single-file engine");
+    if (L && !dsd) return e->fail(D2D_ERR_PARAM, "null dsd pointer");
+    if (L >= (1ull << 31)) return e->fail(D2D_ERR_PARAM, "bytes_per_channel must be below 2 GiB per call");
+    if (!L) return D2D_OK;
+    HIPCHK(e, hipSetDevice(e->p.device));
+    hipStream_t s = e->own_stream;
+    d2d_file_io io{};
+    io.bytes_per_channel = L;
+    void* vin = nullptr;
+    if (!host_staged_forced(e) && device_view(dsd, &vin)) {
+        io.dsd = vin;
+    } else {
+        const size_t in_bytes = L * e->Cin;
+        int rc = ensure_cap(e, &e->d_in, &e->d_in_cap, std::max<size_t>(in_bytes, 16));
+        if (rc) return rc;
+        HIPCHK(e, hipMemcpyAsync(e->d_in, dsd, in_bytes, hipMemcpyHostToDevice, s));
+        io.dsd = e->d_in;
+    }
+    int rc = batch_call(e, &io, 1, s, true);
+    if (rc) { hipStreamSynchronize(s); return rc; }
+    HIPCHK(e, hipStreamSynchronize(s));
     return D2D_OK;
 }
 

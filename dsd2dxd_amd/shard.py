@@ -42,6 +42,28 @@ def shard_channels(channels, world, rank):
     return begin, end - begin
 
 
+def shard_time(total, world, rank, align=1, preroll=0):
+    """(halo_begin, begin, end) in bytes per channel of ONE stream of `total` bytes per channel cut along TIME for `rank` of
+    `world`: the rank seeks to halo_begin, primes with [halo_begin, begin) and converts [begin, end); the ranks' frames,
+    concatenated in rank order, are the uninterrupted conversion's (include/dsd2dxd_amd.h: d2d_seek).  Every rank reads
+    1/world of the bytes plus the halo and keeps the whole stream's engine parameters, hence its kernels.
+
+    Boundaries are shard_range's rounded down to a multiple of `align`; the last slice ends at `total`.  `align` is the
+    caller's file layout -- a DSF file is cut at multiples of its 4096-byte channel blocks -- times
+    Engine.slice_align_bytes() when the dither is noise-shaped ('N'), whose frames can only start at a multiple of 8192.
+    `preroll` is Engine.preroll_bytes(); halo_begin = max(0, begin - preroll) rounded down to `align` too.  A slice that
+    comes out empty (total too small for the alignment) is (begin, begin, begin): that rank sits out."""
+    if align < 1 or preroll < 0:
+        raise ValueError("bad align/preroll")
+    b, e = shard_range(total, world, rank)
+    begin = b // align * align
+    end = total if rank == world - 1 else e // align * align
+    if end <= begin:
+        return begin, begin, begin
+    halo = max(0, begin - preroll) // align * align
+    return halo, begin, end
+
+
 def merge_channel_frames(parts, sample_bytes):
     """Interleave per-rank PCM back into full-width frames.  `parts`: (channel_first, channel_count,
     uint8 array of frames * channel_count * sample_bytes bytes) per rank; the channel ranges must tile

@@ -20,7 +20,8 @@
 extern "C" {
 #endif
 
-#define D2D_ABI_VERSION 5   /* 3: the table blob header names the table variant; 4: d2d_params.tap_bits; 5: d2d_params.debug_flags (was reserved0) */
+#define D2D_ABI_VERSION 6   /* 3: the table blob header names the table variant; 4: d2d_params.tap_bits; 5: d2d_params.debug_flags (was reserved0);
+                             * 6: d2d_seek / d2d_tell / d2d_prime* and the two size queries (d2d_params unchanged) */
 
 /* status codes */
 enum {
@@ -172,6 +173,46 @@ int d2d_translate_batch_host(d2d_engine* e, d2d_file_io* io, uint32_t n_files, s
  * seen so far.  Synchronises with the engine's pending work. */
 int d2d_peak(d2d_engine* e, uint32_t file, uint32_t channel, double* peak_out);
 int d2d_peak_dbfs(d2d_engine* e, uint32_t file, float* dbfs_out);
+
+/* ---- time slices: start anywhere in a stream (ABI 6) -------------------------------------- */
+
+/* A FIR output depends only on its own bit history, the dither generator is keyed by (seed, channel, absolute output
+ * index) and the noise shaper restarts at every output index that is a multiple of 8192: an engine that knows its absolute
+ * position and has seen a short halo produces the same bytes as one that converted the stream from its first byte.
+ *
+ * Below, F(p) is the number of frames an uninterrupted conversion has produced after p bytes per channel (no alignment
+ * of p is needed).  THE GUARANTEE: for every p and every q <= max(0, p - d2d_preroll_bytes(e)), the sequence
+ * d2d_seek(q), prime with the bytes [q, p), translate calls from p on yields byte for byte the frames F(p), F(p) + 1, ...
+ * of the uninterrupted conversion, and the peak then read is the peak of exactly those frames.  N ranks can therefore cut
+ * ONE stream along time (dsd2dxd_amd/shard.py: shard_time), each reading 1/N of the bytes plus the
+ * halo, and a caller can convert an excerpt or resume an interrupted conversion without re-reading the file. */
+
+/* Put `file` into the state of a fresh engine that stands at `bytes_per_channel`: idle bit history, zero stage-A
+ * history, zero shaper errors, zero peaks; position, FIR and frame counters as after that many bytes.  Other files are
+ * untouched; d2d_seek(e, f, 0) is d2d_reset for one file.  Synchronises with the engine's pending work, as d2d_reset. */
+int d2d_seek(d2d_engine* e, uint32_t file, uint64_t bytes_per_channel);
+/* Where `file` stands: bytes per channel consumed, and F of that = the index of the next frame.  Host state only; does
+ * not synchronise.  Either pointer may be NULL. */
+int d2d_tell(const d2d_engine* e, uint32_t file, uint64_t* bytes_per_channel, uint64_t* next_frame);
+/* The halo of the guarantee above, in bytes per channel, from the engine's tables: window plus one decimation step for a
+ * single filter; the carried history of a composed polyphase filter; stage A's window plus P + 1 stage-A outputs for the
+ * 48k cascade.  Below 1 KiB for every shipped table. */
+size_t d2d_preroll_bytes(const d2d_engine* e);
+/* Noise-shaped dither ('N', integer depths) can only start where the shaper's state is known: at a frame index that is a
+ * multiple of 8192.  This is the smallest A with F(k A) a multiple of 8192 for every k -- cut such streams at multiples
+ * of it; 1 for every other engine.  After d2d_seek to a position > 0 or a prime, a translate call on that file whose
+ * first frame index is not a multiple of 8192 fails with D2D_ERR_STATE and changes nothing (a call that produces no
+ * frames for the file passes); one that starts on a multiple clears the condition. */
+size_t d2d_slice_align_bytes(const d2d_engine* e);
+/* d2d_translate's twin (host pointer, file 0): consumes the bytes exactly as d2d_translate would -- same layout rules --
+ * and leaves position, bit history and stage-A history as it would, but produces NO frames and leaves the peaks
+ * unchanged: only the kernels whose results carry over run (de-interleave pre-pass, stage A of the cascade, history
+ * carry).  With profiling enabled its kernels are timed like a translate call's (d2d_profile_read_all: step time). */
+int d2d_prime(d2d_engine* e, const uint8_t* dsd, size_t bytes_per_channel);
+/* d2d_translate_batch_device's twin: same checks on `dsd` (16-byte aligned device pointer, below 2 GiB per call); `pcm`
+ * and `pcm_capacity_bytes` are ignored and may be NULL / 0; frames_out is set to 0.  A file with bytes_per_channel = 0
+ * is left as it is.  Asynchronous on `hip_stream`. */
+int d2d_prime_batch_device(d2d_engine* e, d2d_file_io* io, uint32_t n_files, void* hip_stream);
 
 /* ---- whole-stream driver ------------------------------------------------------------------ */
 
