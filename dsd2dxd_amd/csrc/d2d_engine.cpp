@@ -1,11 +1,15 @@
 // d2d_engine.cpp -- host side of the engine and the C ABI of include/dsd2dxd_amd.h.
 //
-// One Engine is what the reference calls an Rdsd2Pcm (one per file, /root/reference/src/main.rs:
-// 325-342,361-394), widened to `n_files` files so that the Rayon par_iter over files
-// (src/main.rs:280-300) becomes a grid dimension of one launch.  The engine owns, in HBM:
+// One Engine is what the reference calls an Rdsd2Pcm (one per file, src/main.rs:325-342,361-394 there), widened to `n_files` files so
+// that the Rayon par_iter over files (src/main.rs:280-300) becomes a grid dimension of one launch.  The engine owns, in HBM:
 //   * the filter tables (nibble LUTs or int8 MFMA fragments; stage-B coefficients)
 //   * per (file, channel): `keep` history bytes (ping-pong), the running peak, and for the 48k
 //     cascade an f64 scratch line [P carried | stage-A outputs of this call]
+// Every one of them is a Buf: it knows its size and frees itself, so the engine has no list of things to free and a buffer that failed to
+// grow is empty, never stale.  Streams and events go in ~d2d_engine.
+// What a launch needs and no call changes (the FIR, polyphase, resampler and noise-shaper arguments, the job count) is built once, at the end
+// of d2d_create, into d2d_engine::launch.  A call (batch_call) is five steps joined by a CallPlan: plan (checks and counts, no HIP call),
+// buffers, job table, launches, commit.
 // No CPU fallback exists: without a HIP device d2d_create fails with D2D_ERR_DEVICE.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -13,6 +17,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -40,6 +45,93 @@ struct FileState {
 
 constexpr int JOB_SLOTS = 8;
 
+// what a growing buffer waits for before its old memory goes (Buf::reserve)
+inline auto wait_stream(hipStream_t s) { return [s] { return hipStreamSynchronize(s); }; }
+inline auto wait_device() { return [] { return hipDeviceSynchronize(); }; }
+
+// Device memory (Pinned: hipHostMalloc memory) that knows its byte size and frees itself.  Move-only.
+template <class T, bool Pinned = false>
+struct Buf {
+    T* p = nullptr;
+    size_t bytes = 0;
+
+    Buf() = default;
+    Buf& operator=(Buf&& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }     // (no copies: this declares them away)
+    ~Buf() { release(); }
+    operator T*() const { return p; }
+    size_t count() const { return bytes / sizeof(T); }
+
+    void release() {
+        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr; bytes = 0;
+    }
+    hipError_t alloc(size_t n) {
+        release();
+        const hipError_t r = Pinned ? hipHostMalloc((void**)&p, n, hipHostMallocDefault) : hipMalloc((void**)&p, n);
+        if (r == hipSuccess) bytes = n; else p = nullptr;
+        return r;
+    }
+    // Nothing when the buffer holds n bytes already.  Otherwise: sync() (whatever may still use the old memory), free, allocate n; the old
+    // contents are gone, and so is the buffer when the allocation fails.
+    template <class Sync>
+    hipError_t reserve(size_t n, Sync sync) {
+        if (n <= bytes) return hipSuccess;
+        const hipError_t r = sync();
+        return r != hipSuccess ? r : alloc(n);
+    }
+    // a create-time table
+    hipError_t upload(const void* src, size_t n) {
+        const hipError_t r = alloc(n);
+        return r != hipSuccess ? r : hipMemcpy(p, src, n, hipMemcpyHostToDevice);
+    }
+};
+
+// Timing brackets of the measurement entry points: pairs of events, handed out one per bracket and summed by elapsed_ms.
+struct EventPairs {
+    typedef std::pair<hipEvent_t, hipEvent_t> Pair;
+    std::vector<Pair> pool;
+    size_t used = 0;
+
+    ~EventPairs() { for (auto& pr : pool) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); } }
+    // the next pair, its first event recorded on s; the caller records the second
+    hipError_t open(hipStream_t s, Pair** out) {
+        if (used == pool.size()) {
+            Pair n{};
+            hipError_t r = hipEventCreate(&n.first);
+            if (r == hipSuccess) r = hipEventCreate(&n.second);
+            if (r != hipSuccess) return r;
+            pool.push_back(n);
+        }
+        *out = &pool[used++];
+        return hipEventRecord((*out)->first, s);
+    }
+    // waits for every bracket handed out, sums them and hands them back
+    hipError_t elapsed_ms(double* total) {
+        *total = 0.0;
+        for (size_t i = 0; i < used; ++i) {
+            hipError_t r = hipEventSynchronize(pool[i].second);
+            float ms = 0.f;
+            if (r == hipSuccess) r = hipEventElapsedTime(&ms, pool[i].first, pool[i].second);
+            if (r != hipSuccess) return r;
+            *total += ms;
+        }
+        used = 0;
+        return hipSuccess;
+    }
+};
+
+// Everything a call's launches need that is fixed once d2d_create has made its choices.  batch_call copies what a launcher writes into and
+// fills in what belongs to the call (the shaper's ping-pong state and grid, the cascade's f64 line).
+struct LaunchState {
+    FirArgs fir{};             // the main table
+    FirArgs fir_lo{};          // 32-bit taps in two passes: the residual table, on the second half of the job table and of the scratch
+    FirArgs fir_m2{};          // MONO2: the pair kernel, on the half-call jobs behind the ordinary ones
+    PxArgs px{};
+    Rs2Args rs{};
+    NoiseShapeArgs ns{};
+    size_t njobs = 0;          // job rows per slot (32-bit taps: the second pass's jobs behind the first's; MONO2: the half-call jobs)
+};
+
 }  // namespace
 
 struct d2d_engine {
@@ -54,42 +146,41 @@ struct d2d_engine {
     LutLayout lut{};
     MfmaLayout mfma{};
     bool mfma_v2 = false;      // the two-group matrix-core kernel (d2d_kernels_mfma2.hip) serves this shape
-    int mfma_pipe = 0;         // ... through its software-pipelined variant (d2d_kernels_mfma3.hip; stereo 24-bit at 0 dB): 3 dense chain, 4 sparse chain
-    std::string kname;
+    int mfma_pipe = PIPE_NONE; // ... through a software-pipelined variant: PIPE_INT8 (d2d_kernels_mfma3.hip) or PIPE_FP6 (d2d_kernels_mx.hip)
+    mutable std::string kname; // d2d_kernel_name's answer before the first call
     std::string launched;      // the FIR kernel the last call really enqueued (d2d_last_launched_kernel)
     Epilogue epi{};
     std::string err;
     std::vector<FileState> files;
 
     // device
-    void* d_fir_tables = nullptr; size_t fir_table_bytes = 0;
-    double* d_resamp = nullptr;   size_t resamp_bytes = 0;
-    uint8_t* d_hist[2] = {nullptr, nullptr}; int hist_cur = 0;
-    double* d_peak = nullptr;
-    int32_t* d_scratch = nullptr; size_t scratch_stride = 0;  // stage-A integers per stream (multiple of 4)
+    Buf<uint8_t> d_fir_tables;
+    Buf<uint8_t> d_resamp;
+    Buf<uint8_t> d_hist[2]; int hist_cur = 0;
+    Buf<double> d_peak;
+    Buf<int32_t> d_scratch;               // stage-A integers, one line per stream (a multiple of 4 long), twice that with two-pass 32-bit taps
     bool noise_shape = false;             // 'N' dither: the FIR writes integers, a sequential pass requantises
-    double* d_ns[2] = {nullptr, nullptr}; int ns_cur = 0;   // its state: two errors per stream, ping-pong between calls
-    uint8_t* d_ns_dump = nullptr;                            // NoiseShapeArgs::dump
-    double* d_ys = nullptr; size_t ys_stride = 0;            // 'N' on the 48k family: stage B's outputs as f64, one line per stream
+    Buf<double> d_ns[2]; int ns_cur = 0;  // its state: two errors per stream, ping-pong between calls
+    Buf<uint8_t> d_ns_dump;               // NoiseShapeArgs::dump
+    Buf<double> d_ys;                     // 'N' on the 48k family: stage B's outputs as f64, one line per stream
     uint32_t xs_hist = 0;                 // samples carried in front of each scratch line (P of the resampler, else 0)
-    StreamJob* d_jobs = nullptr;
-    StreamJob* h_jobs = nullptr;          // pinned, JOB_SLOTS x nstreams
+    Buf<StreamJob> d_jobs;
+    Buf<StreamJob, true> h_jobs;          // pinned, JOB_SLOTS x launch.njobs
     hipEvent_t job_ev[JOB_SLOTS]{}; bool job_ev_used[JOB_SLOTS]{}; int job_slot = 0;
     hipStream_t own_stream = nullptr;     // used by the host-pointer entry points
     // d2d_translate_batch_host: upload / convert / download streams, their events, double-buffered staging
     hipStream_t hb_stream[3] = {nullptr, nullptr, nullptr};
     hipEvent_t hb_ev[6] = {};
-    uint8_t* hb_in[2] = {nullptr, nullptr}; uint8_t* hb_out[2] = {nullptr, nullptr};
-    size_t hb_in_stride = 0, hb_out_stride = 0;
+    Buf<uint8_t> hb_in[2], hb_out[2];
     hipStream_t last_stream = nullptr;
     // measurement
     bool profiling = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pool; size_t prof_used = 0;     // around the FIR launch
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> step_pool; size_t step_used = 0;     // around every kernel of a batch call
+    EventPairs prof;                      // around the FIR launch
+    EventPairs step;                      // around every kernel of a batch call
     // staging for d2d_translate (host pointers)
-    uint8_t* d_in = nullptr; size_t d_in_cap = 0;
+    Buf<uint8_t> d_in, d_out;
     // planar copies of byte-interleaved inputs (one slice per file), see d2d_deinterleave_kernel
-    uint8_t* d_planar = nullptr; size_t planar_stride = 0;
+    Buf<uint8_t> d_planar;
     bool deinterleave = false;
     bool coop = false;                    // byte-interleaved 4/8-channel input de-interleaved inside the fp6 kernel's staging (FirArgs::coop)
     // tap_bits = 32: the FIR runs twice into the scratch (the 24-bit table, then the residual table q32 - 256 q) and d2d_fine_combine_kernel
@@ -98,8 +189,8 @@ struct d2d_engine {
     bool taps32 = false;                  // tap_bits = 32 in ONE pass (round 4): stereo at M = 32 on the fp6 kernel's seven-digit flavour -- one table, no scratch, no combining pass
     std::vector<int32_t> lo_half;
     d2d_filter_def lo_def{};
-    void* d_fir_tables_lo = nullptr;
-    int mfma_pipe_lo = 0;
+    Buf<uint8_t> d_fir_tables_lo;
+    int mfma_pipe_lo = PIPE_NONE;
     // DSD64 / DSD128 -> 48k multiples: one polyphase pass over the bits (d2d_kernels_px.hip); fc.fir / fc.resamp only count frames then
     const d2d_poly_def* poly = nullptr;
     bool poly_plain = false;              // ... through the bit-by-bit kernel (D2D_KERNEL_LUT engines)
@@ -107,10 +198,22 @@ struct d2d_engine {
     // MONO2 (round 4): a mono stream on the fp6 pipelined kernel as a planar PAIR -- the two halves of a call converted side by side (FirArgs::mono2);
     // calls it does not fit (odd sizes, very short ones) take the engine's ordinary mono kernel: same bytes either way
     bool mono2_ok = false;
-    int mono2_pipe = 0;                   // 5: the fp6 kernel (M = 32, 64, 128), 3: the int8 pipelined kernel (M = 8, 16)
-    void* d_fir_tables_m2 = nullptr;
+    int mono2_pipe = PIPE_NONE;           // PIPE_FP6: the fp6 kernel (M = 32, 64, 128), PIPE_INT8: the int8 pipelined kernel (M = 8, 16)
+    Buf<uint8_t> d_fir_tables_m2;
     bool il2 = false;                     // byte-interleaved stereo input de-interleaved inside the pipelined frame kernels' staging (FirArgs::il2)
-    uint8_t* d_out = nullptr; size_t d_out_cap = 0;
+    LaunchState launch;
+
+    // strides of the per-stream / per-file buffers, in elements: what the buffers hold, never a second record of it
+    size_t scratch_stride() const { return d_scratch.count() / ((size_t)nstreams * (fine ? 2u : 1u)); }
+    size_t ys_stride() const { return d_ys.count() / nstreams; }
+    size_t planar_stride() const { return d_planar.bytes / n_files; }
+
+    ~d2d_engine() {
+        for (hipEvent_t ev : job_ev) if (ev) hipEventDestroy(ev);
+        for (hipEvent_t ev : hb_ev) if (ev) hipEventDestroy(ev);
+        for (hipStream_t st : hb_stream) if (st) hipStreamDestroy(st);
+        if (own_stream) hipStreamDestroy(own_stream);
+    }
 
     int fail(int code, const std::string& m) { err = m; return code; }
     int hip_fail(hipError_t e, const char* what) {
@@ -160,42 +263,15 @@ static int validate(const d2d_params& p, std::string& err) {
     return D2D_OK;
 }
 
-static void free_device(d2d_engine* e) {
-    if (e->d_fir_tables) hipFree(e->d_fir_tables);
-    if (e->d_resamp) hipFree(e->d_resamp);
-    if (e->d_hist[0]) hipFree(e->d_hist[0]);
-    if (e->d_hist[1]) hipFree(e->d_hist[1]);
-    if (e->d_peak) hipFree(e->d_peak);
-    if (e->d_scratch) hipFree(e->d_scratch);
-    if (e->d_fir_tables_lo) hipFree(e->d_fir_tables_lo);
-    if (e->d_fir_tables_m2) hipFree(e->d_fir_tables_m2);
-    for (int i = 0; i < 2; ++i) if (e->d_ns[i]) hipFree(e->d_ns[i]);
-    if (e->d_ns_dump) hipFree(e->d_ns_dump);
-    if (e->d_ys) hipFree(e->d_ys);
-    if (e->d_jobs) hipFree(e->d_jobs);
-    if (e->h_jobs) hipHostFree(e->h_jobs);
-    if (e->d_in) hipFree(e->d_in);
-    if (e->d_planar) hipFree(e->d_planar);
-    if (e->d_out) hipFree(e->d_out);
-    for (int i = 0; i < JOB_SLOTS; ++i)
-        if (e->job_ev[i]) hipEventDestroy(e->job_ev[i]);
-    if (e->own_stream) hipStreamDestroy(e->own_stream);
-    for (int i = 0; i < 3; ++i) if (e->hb_stream[i]) hipStreamDestroy(e->hb_stream[i]);
-    for (int i = 0; i < 6; ++i) if (e->hb_ev[i]) hipEventDestroy(e->hb_ev[i]);
-    for (int b = 0; b < 2; ++b) { if (e->hb_in[b]) hipFree(e->hb_in[b]); if (e->hb_out[b]) hipFree(e->hb_out[b]); }
-    for (auto& pr : e->prof_pool) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
-    for (auto& pr : e->step_pool) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
-}
+// what a stream that has not started yet holds as history
+static uint8_t idle_byte(const d2d_engine* e) { return e->p.endianness == D2D_MSB_FIRST ? IDLE_BYTE : (uint8_t)0x96; }  // 0x69 bit-reversed
 
 static int reset_state(d2d_engine* e) {
     HIPCHK(e, hipSetDevice(e->p.device));
-    const size_t hbytes = (size_t)e->nstreams * e->keep;
-    const uint8_t idle = e->p.endianness == D2D_MSB_FIRST ? IDLE_BYTE : (uint8_t)0x96;  // 0x69 bit-reversed
-    HIPCHK(e, hipMemset(e->d_hist[0], idle, hbytes));
-    HIPCHK(e, hipMemset(e->d_hist[1], idle, hbytes));
-    HIPCHK(e, hipMemset(e->d_peak, 0, sizeof(double) * e->nstreams));
-    if (e->d_scratch) HIPCHK(e, hipMemset(e->d_scratch, 0, sizeof(int32_t) * e->scratch_stride * e->nstreams * (e->fine ? 2u : 1u)));
-    for (int i = 0; i < 2; ++i) if (e->d_ns[i]) HIPCHK(e, hipMemset(e->d_ns[i], 0, sizeof(double) * 2 * e->nstreams));
+    for (int b = 0; b < 2; ++b) HIPCHK(e, hipMemset(e->d_hist[b], idle_byte(e), e->d_hist[b].bytes));
+    HIPCHK(e, hipMemset(e->d_peak, 0, e->d_peak.bytes));
+    if (e->d_scratch) HIPCHK(e, hipMemset(e->d_scratch, 0, e->d_scratch.bytes));
+    for (int i = 0; i < 2; ++i) if (e->d_ns[i]) HIPCHK(e, hipMemset(e->d_ns[i], 0, e->d_ns[i].bytes));
     for (auto& f : e->files) f = FileState{};
     e->hist_cur = 0;
     return D2D_OK;
@@ -204,16 +280,16 @@ static int reset_state(d2d_engine* e) {
 // one file back to the device state of a fresh engine, in both ping-pong buffers; the other files' rows stay
 static int clear_file_state(d2d_engine* e, uint32_t file) {
     const size_t s0 = (size_t)file * e->C;
-    const uint8_t idle = e->p.endianness == D2D_MSB_FIRST ? IDLE_BYTE : (uint8_t)0x96;
-    for (int b = 0; b < 2; ++b) HIPCHK(e, hipMemset(e->d_hist[b] + s0 * e->keep, idle, (size_t)e->C * e->keep));
+    for (int b = 0; b < 2; ++b) HIPCHK(e, hipMemset(e->d_hist[b] + s0 * e->keep, idle_byte(e), (size_t)e->C * e->keep));
     HIPCHK(e, hipMemset(e->d_peak + s0, 0, sizeof(double) * e->C));
     if (e->d_scratch && e->xs_hist)     // the stage-A history in front of each of the file's scratch lines
-        HIPCHK(e, hipMemset2D(e->d_scratch + s0 * e->scratch_stride, e->scratch_stride * sizeof(int32_t), 0, (size_t)e->xs_hist * sizeof(int32_t), e->C));
+        HIPCHK(e, hipMemset2D(e->d_scratch + s0 * e->scratch_stride(), e->scratch_stride() * sizeof(int32_t), 0, (size_t)e->xs_hist * sizeof(int32_t), e->C));
     for (int i = 0; i < 2; ++i) if (e->d_ns[i]) HIPCHK(e, hipMemset(e->d_ns[i] + 2 * s0, 0, sizeof(double) * 2 * e->C));
     return D2D_OK;
 }
 
-// the part of a FIR launch's arguments that is fixed when the engine is created
+// The part of a FIR launch's arguments that is fixed when the engine is created.  d2d_create also calls it on the half-built engine, to ask
+// mfma2_pipelined what would serve a format.
 static void fir_args_static(const d2d_engine* e, FirArgs& a, bool lo_pass = false) {
     const d2d_filter_def& fd = lo_pass ? e->lo_def : *e->fc.fir;
     a.tables = lo_pass ? e->d_fir_tables_lo : e->d_fir_tables;
@@ -236,29 +312,52 @@ static void fir_args_static(const d2d_engine* e, FirArgs& a, bool lo_pass = fals
     a.dbg_flags = e->p.debug_flags;
 }
 
-namespace d2d { thread_local const char* d2d_last_launched_kernel = nullptr; }
-
-extern "C" {
-
-const char* d2d_create_error(void) { return g_create_error.c_str(); }
-
-int d2d_create(const d2d_params* params, uint32_t n_files, d2d_engine** out) {
-    if (out) *out = nullptr;
-    if (!params || !out) { g_create_error = "null argument"; return D2D_ERR_PARAM; }
-    constexpr size_t legacy_size = offsetof(d2d_params, channel_first);           // ABI 1: no channel subset
-    constexpr size_t abi3_size = offsetof(d2d_params, tap_bits);                  // ABI 2, 3: no tap grid (ABI 4 and 5 have today's size: reserved0 became debug_flags)
-    if (params->struct_size != sizeof(d2d_params) && params->struct_size != legacy_size && params->struct_size != abi3_size) {
-        g_create_error = "d2d_params.struct_size mismatch"; return D2D_ERR_PARAM;
+// d2d_engine::launch, once il2, coop, taps32, mfma_pipe, mfma_pipe_lo and mono2_pipe are final and every table and the job table exist
+static void build_launch_state(d2d_engine* e) {
+    LaunchState& l = e->launch;
+    l.fir.jobs = e->d_jobs;
+    fir_args_static(e, l.fir);
+    if (e->fine) {
+        l.fir_lo.jobs = e->d_jobs + e->nstreams;
+        fir_args_static(e, l.fir_lo, true);
     }
-    if (n_files < 1 || n_files > 65535) { g_create_error = "Invalid file count"; return D2D_ERR_PARAM; }
-    d2d_engine* e = new d2d_engine();
-    memset(&e->p, 0, sizeof(e->p));
-    memcpy(&e->p, params, params->struct_size);
-    e->p.struct_size = sizeof(d2d_params);
-    e->n_files = n_files;
-    int rc = validate(e->p, g_create_error);
-    if (rc == D2D_OK) rc = choose_filters(e->p, e->fc, g_create_error);
-    if (rc != D2D_OK) { delete e; return rc; }
+    if (e->mono2_ok) {
+        l.fir_m2 = l.fir;
+        l.fir_m2.jobs = e->d_jobs + e->nstreams; l.fir_m2.tables = e->d_fir_tables_m2;
+        l.fir_m2.epi.channels = 2; l.fir_m2.in_channels = 2;
+        l.fir_m2.B = 0x40000000u;     // (one "block" per half: the gather path's layout rule then reads half c at c * half)
+        l.fir_m2.pipelined = (uint32_t)e->mono2_pipe; l.fir_m2.mono2 = 1;
+    }
+    l.px.jobs = e->d_jobs; l.px.tables = e->d_fir_tables;
+    l.px.in_channels = e->Cin; l.px.B = e->B; l.px.keep = e->keep; l.px.msb = e->p.endianness == D2D_MSB_FIRST ? 1u : 0u;
+    l.px.to_scratch = e->noise_shape ? 1u : 0u;
+    l.px.il2 = e->il2 ? 1u : 0u;
+    l.px.epi = e->epi;
+    l.rs.jobs = e->d_jobs; l.rs.tables = e->d_resamp;
+    l.rs.S = e->S; l.rs.epi = e->epi;
+    NoiseShapeArgs& ns = l.ns;
+    ns.jobs = e->d_jobs; ns.dump = e->d_ns_dump;
+    ns.scale_bits = e->poly ? e->poly->S : e->S; ns.nstreams = e->nstreams; ns.epi = e->epi;
+    ns.res = e->cascade() ? 1u : 0u;
+    // the all-integer loop: the largest |y * 2^S| any output can reach (composed polyphase: its heaviest phase) leaves room for a few LSB
+    uint64_t sa = l.fir.sum_abs_q;
+    if (e->poly) {
+        sa = 0;
+        for (int ph = 0; ph < e->poly->Lp; ++ph) {
+            uint64_t sp = 0;
+            for (int j = 0; j < e->poly->NP; ++j) { const int64_t q = e->poly->q[(size_t)ph * e->poly->NP + j]; sp += (uint64_t)(q < 0 ? -q : q); }
+            sa = std::max(sa, sp);
+        }
+    }
+    ns.intq = (!(e->p.debug_flags & D2D_DBG_NO_INTQ) && sa + (1ull << 24) < (1ull << 31)) ? 1u : 0u;
+    ns.general = (e->p.debug_flags & D2D_DBG_NS_GENERAL) ? 1u : 0u;
+}
+
+// d2d_create after the parameters are copied: every choice, table and buffer.  Errors go to e->err.
+static int init_engine(d2d_engine* e) {
+    int rc = validate(e->p, e->err);
+    if (rc == D2D_OK) rc = choose_filters(e->p, e->fc, e->err);
+    if (rc != D2D_OK) return rc;
     const d2d_filter_def& f = *e->fc.fir;
     e->M = f.M; e->Mb = f.M / 8; e->N = f.ntaps; e->Wb = f.ntaps / 8; e->S = f.S;
     e->Cin = e->p.channels;
@@ -269,8 +368,8 @@ int d2d_create(const d2d_params* params, uint32_t n_files, d2d_engine** out) {
         e->deinterleave = e->Cin > 1;
         e->B = 4096;
     }
-    e->nstreams = n_files * e->C;
-    e->files.resize(n_files);
+    e->nstreams = e->n_files * e->C;
+    e->files.resize(e->n_files);
     e->epi.gain = pow(10.0, e->p.level_db / 20.0);
     e->epi.scale = e->p.bit_depth == 32 ? e->epi.gain : ldexp(e->epi.gain, (int)e->p.bit_depth - 1);
     e->epi.seed = e->p.seed;
@@ -280,9 +379,9 @@ int d2d_create(const d2d_params* params, uint32_t n_files, d2d_engine** out) {
         if (e->p.bit_depth == 32) e->epi.dither = 'X';                     // float output: nothing to shape
         else e->noise_shape = true;
     }
-    if (e->p.tap_bits != 0 && e->p.tap_bits != 24 && e->p.tap_bits != 32) { g_create_error = "Invalid tap grid; must be 24 or 32 bits"; delete e; return D2D_ERR_PARAM; }
+    if (e->p.tap_bits != 0 && e->p.tap_bits != 24 && e->p.tap_bits != 32) return e->fail(D2D_ERR_PARAM, "Invalid tap grid; must be 24 or 32 bits");
     if (e->p.tap_bits == 32) {
-        if (e->fc.resamp || e->noise_shape) { g_create_error = "32-bit taps serve the 44.1k-family rates with dither T, R, F or X"; delete e; return D2D_ERR_PARAM; }
+        if (e->fc.resamp || e->noise_shape) return e->fail(D2D_ERR_PARAM, "32-bit taps serve the 44.1k-family rates with dither T, R, F or X");
         e->fine = true;
         e->lo_half.resize((size_t)f.ntaps / 2);
         for (int k = 0; k < f.ntaps / 2; ++k) e->lo_half[(size_t)k] = (int32_t)((int64_t)f.half32[k] - ((int64_t)f.half[k] << 8));
@@ -321,9 +420,8 @@ int d2d_create(const d2d_params* params, uint32_t n_files, d2d_engine** out) {
         e->poly_plain = e->kernel == D2D_KERNEL_LUT;
         e->mfma_v2 = false;
     }
-    if (e->kernel == D2D_KERNEL_MFMA && !mfma_ok) {
-        g_create_error = "MFMA kernel does not support this configuration (decimation or LDS budget)"; delete e; return D2D_ERR_PARAM;
-    }
+    if (e->kernel == D2D_KERNEL_MFMA && !mfma_ok)
+        return e->fail(D2D_ERR_PARAM, "MFMA kernel does not support this configuration (decimation or LDS budget)");
     e->keep = (uint32_t)(e->Wb + e->Mb);
     // (direct polyphase: the oldest bit an output of the next call can need lies NP - D + M bits before the call's first byte)
     if (e->poly) e->keep = std::max<uint32_t>(e->keep, (uint32_t)((e->poly->NP - e->poly->D + e->M + 7) / 8 + 2));
@@ -332,38 +430,29 @@ int d2d_create(const d2d_params* params, uint32_t n_files, d2d_engine** out) {
     // ---- device side: fail loudly when there is no GPU ----
     int ndev = 0;
     hipError_t he = hipGetDeviceCount(&ndev);
-    if (he != hipSuccess || ndev <= 0) {
-        g_create_error = std::string("no HIP device available (") + (he != hipSuccess ? hipGetErrorString(he) : "device count 0") +
-                         "); this engine has no CPU path";
-        delete e; return D2D_ERR_DEVICE;
-    }
-    if (e->p.device < 0 || e->p.device >= ndev) { g_create_error = "Invalid device ordinal"; delete e; return D2D_ERR_DEVICE; }
-    auto bail = [&](hipError_t r, const char* what) {
-        g_create_error = std::string(what) + ": " + hipGetErrorString(r);
-        free_device(e); delete e; return D2D_ERR_DEVICE;
-    };
-#define CK(call) do { hipError_t _r = (call); if (_r != hipSuccess) return bail(_r, #call); } while (0)
-    CK(hipSetDevice(e->p.device));
-    CK(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
+    if (he != hipSuccess || ndev <= 0)
+        return e->fail(D2D_ERR_DEVICE, std::string("no HIP device available (") + (he != hipSuccess ? hipGetErrorString(he) : "device count 0") +
+                                           "); this engine has no CPU path");
+    if (e->p.device < 0 || e->p.device >= ndev) return e->fail(D2D_ERR_DEVICE, "Invalid device ordinal");
+    HIPCHK(e, hipSetDevice(e->p.device));
+    HIPCHK(e, hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
     const bool msb = e->p.endianness == D2D_MSB_FIRST;
     if (e->poly) {
         if (e->poly_plain) {
-            e->fir_table_bytes = (size_t)e->poly->Lp * e->poly->NP * sizeof(int32_t);
-            CK(hipMalloc(&e->d_fir_tables, e->fir_table_bytes));
-            CK(hipMemcpy(e->d_fir_tables, e->poly->q, e->fir_table_bytes, hipMemcpyHostToDevice));
+            HIPCHK(e, e->d_fir_tables.upload(e->poly->q, (size_t)e->poly->Lp * e->poly->NP * sizeof(int32_t)));
         } else {
             // byte-interleaved stereo (DFF files, the CLI's default -f I): de-interleaved inside the kernel's staging, no planar copy (D2D_NO_COOP=1: the pre-pass)
             if (e->deinterleave && e->Cin == 2 && e->C == 2 && !(e->p.debug_flags & D2D_DBG_NO_COOP)) { e->il2 = true; e->deinterleave = false; e->B = 1; }
             const std::vector<int8_t> t = build_px_tables(*e->poly);
-            e->fir_table_bytes = t.size();
-            CK(hipMalloc(&e->d_fir_tables, e->fir_table_bytes));
-            CK(hipMemcpy(e->d_fir_tables, t.data(), e->fir_table_bytes, hipMemcpyHostToDevice));
+            HIPCHK(e, e->d_fir_tables.upload(t.data(), t.size()));
         }
     } else if (e->kernel == D2D_KERNEL_LUT) {
-        std::vector<double> t = build_lut_tables(f, e->Mb, msb);
-        e->fir_table_bytes = t.size() * sizeof(double);
-        CK(hipMalloc(&e->d_fir_tables, e->fir_table_bytes));
-        CK(hipMemcpy(e->d_fir_tables, t.data(), e->fir_table_bytes, hipMemcpyHostToDevice));
+        const std::vector<double> t = build_lut_tables(f, e->Mb, msb);
+        HIPCHK(e, e->d_fir_tables.upload(t.data(), t.size() * sizeof(double)));
+        if (e->fine) {
+            const std::vector<double> tl = build_lut_tables(e->lo_def, e->Mb, msb);
+            HIPCHK(e, e->d_fir_tables_lo.upload(tl.data(), tl.size() * sizeof(double)));
+        }
     } else {
         // 32-bit taps in ONE pass (round 4) where the fp6 kernel's seven-digit flavour is compiled for the table and its digit sums are exact: stereo frames,
         // any depth, dither and level (D2D_DBG_TAPS32_2PASS: the two scratch passes and the combining pass, which serve everything else)
@@ -376,31 +465,28 @@ int d2d_create(const d2d_params* params, uint32_t n_files, d2d_engine** out) {
         // kernel's staging de-interleaves (D2D_DBG_NO_COOP: the pre-pass)
         {
             const bool nocoop = (e->p.debug_flags & D2D_DBG_NO_COOP) != 0;
-            if (e->deinterleave && e->mfma_pipe == 5 && (e->fc.resamp || e->noise_shape) && !e->fine && e->C == e->Cin && (e->Cin == 8 || e->Cin == 4) &&
+            if (e->deinterleave && e->mfma_pipe == PIPE_FP6 && (e->fc.resamp || e->noise_shape) && !e->fine && e->C == e->Cin && (e->Cin == 8 || e->Cin == 4) &&
                 !nocoop) {
                 e->coop = true; e->deinterleave = false; e->B = 1;
             }
             // byte-interleaved stereo (DFF files, the CLI's default -f I) into frames through a pipelined kernel (fp6: M = 32, 64; int8: M = 8, 16):
             // the same, inside one wave
             // (the scratch flavours too: stereo DFF input into the 48k cascade and the noise shaper; not the two passes of 32-bit taps)
-            if (e->deinterleave && ((e->mfma_pipe == 5 || (e->mfma_pipe == 3 && e->M < 64)) && !e->fine) && e->Cin == 2 && e->C == 2 &&
+            if (e->deinterleave && ((e->mfma_pipe == PIPE_FP6 || (e->mfma_pipe == PIPE_INT8 && e->M < 64)) && !e->fine) && e->Cin == 2 && e->C == 2 &&
                 !nocoop) {
                 e->il2 = true; e->deinterleave = false; e->B = 1;
             }
         }
-        std::vector<int8_t> t = e->mfma_pipe == 5 ? build_mx_tables(f, msb, e->taps32)
-                              : e->mfma_v2 ? build_mfma2_tables(f, msb, !e->mfma_pipe) : build_mfma_tables(f, e->mfma, msb);
-        e->fir_table_bytes = t.size();
-        CK(hipMalloc(&e->d_fir_tables, e->fir_table_bytes));
-        CK(hipMemcpy(e->d_fir_tables, t.data(), e->fir_table_bytes, hipMemcpyHostToDevice));
+        const std::vector<int8_t> t = e->mfma_pipe == PIPE_FP6 ? build_mx_tables(f, msb, e->taps32)
+                                    : e->mfma_v2 ? build_mfma2_tables(f, msb, !e->mfma_pipe) : build_mfma_tables(f, e->mfma, msb);
+        HIPCHK(e, e->d_fir_tables.upload(t.data(), t.size()));
         if (e->fine) {
             // the residual table goes through the same builders; which pipelined kernel serves it is decided on ITS digits
             if (e->mfma_v2) { FirArgs a{}; fir_args_static(e, a, true); e->mfma_pipe_lo = mfma2_pipelined(a, e->M, e->N); }
             const d2d_filter_def& fl = e->lo_def;
-            std::vector<int8_t> tl = e->mfma_pipe_lo == 5 ? build_mx_tables(fl, msb)
-                                   : e->mfma_v2 ? build_mfma2_tables(fl, msb, !e->mfma_pipe_lo) : build_mfma_tables(fl, e->mfma, msb);
-            CK(hipMalloc(&e->d_fir_tables_lo, tl.size()));
-            CK(hipMemcpy(e->d_fir_tables_lo, tl.data(), tl.size(), hipMemcpyHostToDevice));
+            const std::vector<int8_t> tl = e->mfma_pipe_lo == PIPE_FP6 ? build_mx_tables(fl, msb)
+                                         : e->mfma_v2 ? build_mfma2_tables(fl, msb, !e->mfma_pipe_lo) : build_mfma_tables(fl, e->mfma, msb);
+            HIPCHK(e, e->d_fir_tables_lo.upload(tl.data(), tl.size()));
         }
     }
     if (!e->poly && e->kernel == D2D_KERNEL_MFMA && e->Cin == 1 && e->C == 1 && !e->fine && !e->noise_shape && !e->fc.resamp &&
@@ -409,52 +495,58 @@ int d2d_create(const d2d_params* params, uint32_t n_files, d2d_engine** out) {
         FirArgs a2{}; fir_args_static(e, a2);
         a2.epi.channels = 2; a2.in_channels = 2;
         const int p2 = mfma2_pipelined(a2, e->M, e->N);
-        if (p2 == 5 || p2 == 3) {
-            const std::vector<int8_t> t2 = p2 == 5 ? build_mx_tables(f, msb) : build_mfma2_tables(f, msb, false);
+        if (p2 == PIPE_FP6 || p2 == PIPE_INT8) {
+            const std::vector<int8_t> t2 = p2 == PIPE_FP6 ? build_mx_tables(f, msb) : build_mfma2_tables(f, msb, false);
             e->mono2_pipe = p2;
-            CK(hipMalloc(&e->d_fir_tables_m2, t2.size()));
-            CK(hipMemcpy(e->d_fir_tables_m2, t2.data(), t2.size(), hipMemcpyHostToDevice));
+            HIPCHK(e, e->d_fir_tables_m2.upload(t2.data(), t2.size()));
             e->mono2_ok = true;
         }
     }
-    if (e->fine) {
-        if (e->kernel == D2D_KERNEL_LUT) {
-            std::vector<double> tl = build_lut_tables(e->lo_def, e->Mb, msb);
-            CK(hipMalloc(&e->d_fir_tables_lo, tl.size() * sizeof(double)));
-            CK(hipMemcpy(e->d_fir_tables_lo, tl.data(), tl.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-        e->scratch_stride = 4096;
-        CK(hipMalloc((void**)&e->d_scratch, sizeof(int32_t) * e->scratch_stride * e->nstreams * 2));
-    }
+    // the scratch: a line of 4096 stage-A integers per stream (the cascade: behind the P carried ones; two-pass 32-bit taps: one line per pass)
     if (e->cascade()) {
         const std::vector<int8_t> rt = build_resamp2_table(*e->fc.resamp);
-        e->resamp_bytes = rt.size();
-        CK(hipMalloc((void**)&e->d_resamp, e->resamp_bytes));
-        CK(hipMemcpy(e->d_resamp, rt.data(), e->resamp_bytes, hipMemcpyHostToDevice));
+        HIPCHK(e, e->d_resamp.upload(rt.data(), rt.size()));
         e->xs_hist = (uint32_t)e->fc.resamp->P;
-        e->scratch_stride = (size_t)e->fc.resamp->P + 4096;
-        CK(hipMalloc((void**)&e->d_scratch, sizeof(int32_t) * e->scratch_stride * e->nstreams));
     }
+    if (e->fine || e->cascade() || e->noise_shape)
+        HIPCHK(e, e->d_scratch.alloc(sizeof(int32_t) * ((size_t)e->xs_hist + 4096) * e->nstreams * (e->fine ? 2u : 1u)));
     if (e->noise_shape) {
-        if (!e->cascade()) {
-            e->scratch_stride = 4096;
-            CK(hipMalloc((void**)&e->d_scratch, sizeof(int32_t) * e->scratch_stride * e->nstreams));
-        }
-        for (int i = 0; i < 2; ++i) CK(hipMalloc((void**)&e->d_ns[i], sizeof(double) * 2 * e->nstreams));
-        CK(hipMalloc((void**)&e->d_ns_dump, 1024));
+        for (int i = 0; i < 2; ++i) HIPCHK(e, e->d_ns[i].alloc(sizeof(double) * 2 * e->nstreams));
+        HIPCHK(e, e->d_ns_dump.alloc(1024));
     }
-    const size_t hbytes = (size_t)e->nstreams * e->keep;
-    CK(hipMalloc((void**)&e->d_hist[0], hbytes));
-    CK(hipMalloc((void**)&e->d_hist[1], hbytes));
-    CK(hipMalloc((void**)&e->d_peak, sizeof(double) * e->nstreams));
-    const size_t njobs = (size_t)e->nstreams * (e->fine ? 2u : e->mono2_ok ? 3u : 1u);      // (32-bit taps: the second pass's jobs behind the first's; MONO2: the half-call jobs)
-    CK(hipMalloc((void**)&e->d_jobs, sizeof(StreamJob) * njobs));
-    CK(hipHostMalloc((void**)&e->h_jobs, sizeof(StreamJob) * njobs * JOB_SLOTS, hipHostMallocDefault));
-    for (int i = 0; i < JOB_SLOTS; ++i) CK(hipEventCreateWithFlags(&e->job_ev[i], hipEventDisableTiming));
-#undef CK
-    rc = reset_state(e);
-    if (rc != D2D_OK) { g_create_error = e->err; free_device(e); delete e; return rc; }
-    *out = e;
+    for (int b = 0; b < 2; ++b) HIPCHK(e, e->d_hist[b].alloc((size_t)e->nstreams * e->keep));
+    HIPCHK(e, e->d_peak.alloc(sizeof(double) * e->nstreams));
+    e->launch.njobs = (size_t)e->nstreams * (e->fine ? 2u : e->mono2_ok ? 3u : 1u);
+    HIPCHK(e, e->d_jobs.alloc(sizeof(StreamJob) * e->launch.njobs));
+    HIPCHK(e, e->h_jobs.alloc(sizeof(StreamJob) * e->launch.njobs * JOB_SLOTS));
+    for (int i = 0; i < JOB_SLOTS; ++i) HIPCHK(e, hipEventCreateWithFlags(&e->job_ev[i], hipEventDisableTiming));
+    build_launch_state(e);
+    return reset_state(e);
+}
+
+namespace d2d { thread_local const char* d2d_last_launched_kernel = nullptr; }
+
+extern "C" {
+
+const char* d2d_create_error(void) { return g_create_error.c_str(); }
+
+int d2d_create(const d2d_params* params, uint32_t n_files, d2d_engine** out) {
+    if (out) *out = nullptr;
+    if (!params || !out) { g_create_error = "null argument"; return D2D_ERR_PARAM; }
+    constexpr size_t legacy_size = offsetof(d2d_params, channel_first);           // ABI 1: no channel subset
+    constexpr size_t abi3_size = offsetof(d2d_params, tap_bits);                  // ABI 2, 3: no tap grid (ABI 4 and 5 have today's size: reserved0 became debug_flags)
+    if (params->struct_size != sizeof(d2d_params) && params->struct_size != legacy_size && params->struct_size != abi3_size) {
+        g_create_error = "d2d_params.struct_size mismatch"; return D2D_ERR_PARAM;
+    }
+    if (n_files < 1 || n_files > 65535) { g_create_error = "Invalid file count"; return D2D_ERR_PARAM; }
+    std::unique_ptr<d2d_engine> e(new d2d_engine());
+    memset(&e->p, 0, sizeof(e->p));
+    memcpy(&e->p, params, params->struct_size);
+    e->p.struct_size = sizeof(d2d_params);
+    e->n_files = n_files;
+    const int rc = init_engine(e.get());
+    if (rc != D2D_OK) { g_create_error = e->err; return rc; }
+    *out = e.release();
     return D2D_OK;
 }
 
@@ -462,7 +554,6 @@ void d2d_destroy(d2d_engine* e) {
     if (!e) return;
     hipSetDevice(e->p.device);
     hipDeviceSynchronize();
-    free_device(e);
     delete e;
 }
 
@@ -484,17 +575,19 @@ size_t d2d_next_frames(const d2d_engine* e, uint32_t file, size_t L) {
     return e->fc.resamp ? (size_t)(res_outputs_after(e, nfir1) - f.nres) : (size_t)(nfir1 - f.nfir);
 }
 
+// The scratch grows by doubling, to a multiple of 4 integers per line.  Unlike every other buffer it carries state across the reallocation:
+// the xs_hist samples in front of each line move to the new stride before the old buffer goes (which `nb` owning the new one keeps leak-free).
 static int grow_scratch(d2d_engine* e, size_t need_stride, hipStream_t s) {
-    if (need_stride <= e->scratch_stride) return D2D_OK;
-    size_t ns = (std::max(need_stride, e->scratch_stride * 2) + 3) & ~(size_t)3;
-    int32_t* nb = nullptr;
-    HIPCHK(e, hipMalloc((void**)&nb, sizeof(int32_t) * ns * e->nstreams * (e->fine ? 2u : 1u)));
+    const size_t old = e->scratch_stride();
+    if (need_stride <= old) return D2D_OK;
+    const size_t ns = (std::max(need_stride, old * 2) + 3) & ~(size_t)3;
+    Buf<int32_t> nb;
+    HIPCHK(e, nb.alloc(sizeof(int32_t) * ns * e->nstreams * (e->fine ? 2u : 1u)));
     const size_t P = (size_t)e->xs_hist;
-    if (P) HIPCHK(e, hipMemcpy2DAsync(nb, ns * sizeof(int32_t), e->d_scratch, e->scratch_stride * sizeof(int32_t),
+    if (P) HIPCHK(e, hipMemcpy2DAsync(nb, ns * sizeof(int32_t), e->d_scratch, old * sizeof(int32_t),
                                       P * sizeof(int32_t), e->nstreams, hipMemcpyDeviceToDevice, s));
     HIPCHK(e, hipStreamSynchronize(s));
-    HIPCHK(e, hipFree(e->d_scratch));
-    e->d_scratch = nb; e->scratch_stride = ns;
+    e->d_scratch = std::move(nb);       // (the old buffer leaves with nb)
     return D2D_OK;
 }
 
@@ -544,91 +637,111 @@ size_t d2d_slice_align_bytes(const d2d_engine* e) {
     return (size_t)((uint64_t)e->Mb * Mdn * (8192 / g));
 }
 
-// One call of every file: the plan, the job table and the launches that d2d_translate_batch_device and d2d_prime_batch_device share.
-// prime: the bytes are consumed and everything that carries over to the next call is updated (the planar copy the history is read from,
-// stage A of the cascade with its carried outputs, the bit history), but no frames are produced and the peaks stay.
-static int batch_call(d2d_engine* e, d2d_file_io* io, uint32_t n_files, hipStream_t s, const bool prime) {
-    if (!io || n_files != e->n_files) return e->fail(D2D_ERR_PARAM, "file count does not match the engine");
-    HIPCHK(e, hipSetDevice(e->p.device));
+}  // extern "C"
+
+namespace {
+
+// What the plan step of a call hands to the steps after it.
+struct CallPlan {
+    struct File { uint64_t nfir1, nres1, nframes; };     // FIR / stage-B outputs once the call is done, frames the call yields
+    std::vector<File> files;
+    uint32_t max_nx = 0, max_frames = 0, max_L = 0;      // the longest file's FIR outputs, frames and bytes per channel
+    bool run_fir = false;
+    bool mono2 = false;                                  // the call goes through the mono pair
+};
+
+}  // namespace
+
+// Plan: every file's checks and counts; no HIP call.  A failing file leaves every frames_out as it was.
+static int plan_call(d2d_engine* e, d2d_file_io* io, const bool prime, CallPlan& pl) {
     const size_t fb = d2d_frame_bytes(e);
-    const uint32_t C = e->C;
-    // plan
-    uint32_t max_nx = 0, max_frames = 0;
+    const uint32_t n_files = e->n_files;
     // a prime runs a FIR only where its outputs carry over: stage A of the cascade.  Every other engine's prime plans no outputs at all (max_nx,
-    // max_frames = 0), which is what keeps the FIR passes, the mono pair and the combining pass below out of it.
-    const bool run_fir = !prime || e->cascade();
-    std::vector<uint64_t> nfir1(n_files), nres1(n_files), nframes(n_files);
+    // max_frames = 0), which is what keeps the FIR passes, the mono pair and the combining pass out of it.
+    pl.run_fir = !prime || e->cascade();
+    pl.files.resize(n_files);
+    // MONO2: every file's call splits into two equal halves of whole outputs and whole 16-byte chunks, long enough to hold the second half's history
+    pl.mono2 = e->mono2_ok;
     for (uint32_t f = 0; f < n_files; ++f) {
         const FileState& st = e->files[f];
         const size_t L = io[f].bytes_per_channel;
         if (L >= (1ull << 31)) return e->fail(D2D_ERR_PARAM, "bytes_per_channel must be below 2 GiB per call");
         if (L && (!io[f].dsd || ((uintptr_t)io[f].dsd & 15))) return e->fail(D2D_ERR_PARAM, "dsd device pointer must be non-null and 16-byte aligned");
-        nfir1[f] = (st.pos + L) / (uint64_t)e->Mb;
-        nres1[f] = res_outputs_after(e, nfir1[f]);
-        const uint64_t nx = run_fir ? nfir1[f] - st.nfir : 0;
-        const uint64_t frames = prime ? 0 : e->fc.resamp ? nres1[f] - st.nres : nx;
-        nframes[f] = frames;
+        CallPlan::File& pf = pl.files[f];
+        pf.nfir1 = (st.pos + L) / (uint64_t)e->Mb;
+        pf.nres1 = res_outputs_after(e, pf.nfir1);
+        const uint64_t nx = pl.run_fir ? pf.nfir1 - st.nfir : 0;
+        const uint64_t frames = prime ? 0 : e->fc.resamp ? pf.nres1 - st.nres : nx;
+        pf.nframes = frames;
         if (frames * fb > io[f].pcm_capacity_bytes) return e->fail(D2D_ERR_CAPACITY, "pcm buffer too small");
         if (frames && (!io[f].pcm || ((uintptr_t)io[f].pcm & 15))) return e->fail(D2D_ERR_PARAM, "pcm device pointer must be non-null and 16-byte aligned");
         if (frames && st.ns_unknown && ((e->fc.resamp ? st.nres : st.nfir) & 8191u))
             return e->fail(D2D_ERR_STATE, "noise-shaped dither after d2d_seek / d2d_prime: frames can only start at an index that is a multiple of 8192 "
                                           "(cut the stream at multiples of d2d_slice_align_bytes)");
-        max_nx = std::max<uint32_t>(max_nx, (uint32_t)nx);
-        max_frames = std::max<uint32_t>(max_frames, (uint32_t)frames);
-    }
-    for (uint32_t f = 0; f < n_files; ++f) io[f].frames_out = (size_t)nframes[f];       // (written once every file has passed its checks)
-    if (e->cascade() || e->noise_shape || e->fine) {
-        int rc = grow_scratch(e, (size_t)e->xs_hist + (e->poly ? max_frames : max_nx), s);
-        if (rc) return rc;
-    }
-    if (!prime && e->noise_shape && e->cascade() && (size_t)max_frames + 8 > e->ys_stride) {
-        HIPCHK(e, hipStreamSynchronize(s));
-        if (e->d_ys) HIPCHK(e, hipFree(e->d_ys));
-        e->d_ys = nullptr; e->ys_stride = 0;
-        const size_t ns = ((size_t)max_frames + 8 + 1023) & ~(size_t)1023;
-        HIPCHK(e, hipMalloc((void**)&e->d_ys, sizeof(double) * ns * e->nstreams));
-        e->ys_stride = ns;
-    }
-    uint32_t max_L = 0;
-    for (uint32_t f = 0; f < n_files; ++f) max_L = std::max<uint32_t>(max_L, (uint32_t)io[f].bytes_per_channel);
-    if (e->deinterleave) {
-        const size_t need = (((size_t)max_L * e->Cin) + 4095) & ~(size_t)4095;
-        if (need > e->planar_stride) {
-            HIPCHK(e, hipStreamSynchronize(s));
-            if (e->d_planar) HIPCHK(e, hipFree(e->d_planar));
-            e->d_planar = nullptr; e->planar_stride = 0;
-            HIPCHK(e, hipMalloc((void**)&e->d_planar, need * n_files));
-            e->planar_stride = need;
+        pl.max_nx = std::max<uint32_t>(pl.max_nx, (uint32_t)nx);
+        pl.max_frames = std::max<uint32_t>(pl.max_frames, (uint32_t)frames);
+        pl.max_L = std::max<uint32_t>(pl.max_L, (uint32_t)L);
+        if (pl.mono2) {     // (a mono engine: file f is stream f, and the job's nout is the FIR's)
+            const uint64_t half = L / 2, nout = pf.nfir1 - st.nfir;
+            pl.mono2 = (L % 2 == 0) && (half % 16 == 0) && (half % (uint64_t)e->Mb == 0) && half >= e->keep && (nout % 2 == 0) &&
+                       (uint64_t)(uint32_t)st.nfir + (uint32_t)nout <= 0xFFFFFFFFull;
         }
     }
-    // job table: pinned slot -> device
+    pl.mono2 = pl.mono2 && pl.max_nx > 0;
+    for (uint32_t f = 0; f < n_files; ++f) io[f].frames_out = (size_t)pl.files[f].nframes;       // (written once every file has passed its checks)
+    return D2D_OK;
+}
+
+// Buffers: what the call's sizes ask of the scratch, the cascade's f64 line and the planar copy.  Each waits on the call's stream.
+static int reserve_call_buffers(d2d_engine* e, const CallPlan& pl, hipStream_t s, const bool prime) {
+    if (e->cascade() || e->noise_shape || e->fine) {
+        int rc = grow_scratch(e, (size_t)e->xs_hist + (e->poly ? pl.max_frames : pl.max_nx), s);
+        if (rc) return rc;
+    }
+    if (!prime && e->noise_shape && e->cascade()) {
+        const size_t ns = ((size_t)pl.max_frames + 8 + 1023) & ~(size_t)1023;
+        HIPCHK(e, e->d_ys.reserve(sizeof(double) * ns * e->nstreams, wait_stream(s)));
+    }
+    if (e->deinterleave) {
+        const size_t need = (((size_t)pl.max_L * e->Cin) + 4095) & ~(size_t)4095;
+        HIPCHK(e, e->d_planar.reserve(need * e->n_files, wait_stream(s)));
+    }
+    return D2D_OK;
+}
+
+// Jobs: the table in the next pinned slot (the mono pair's and the second pass's rows behind the streams'), its copy to the device and the
+// event that frees the slot.
+static int enqueue_jobs(d2d_engine* e, const d2d_file_io* io, const CallPlan& pl, hipStream_t s, const bool prime) {
+    const size_t fb = d2d_frame_bytes(e);
+    const uint32_t C = e->C, n_files = e->n_files;
     const int slot = e->job_slot;
     e->job_slot = (slot + 1) % JOB_SLOTS;
     if (e->job_ev_used[slot]) HIPCHK(e, hipEventSynchronize(e->job_ev[slot]));
-    const size_t njobs = (size_t)e->nstreams * (e->fine ? 2u : e->mono2_ok ? 3u : 1u);
-    StreamJob* hj = e->h_jobs + (size_t)slot * njobs;
+    StreamJob* hj = e->h_jobs + (size_t)slot * e->launch.njobs;
     const int cur = e->hist_cur;
+    const size_t scratch_stride = e->scratch_stride(), planar_stride = e->planar_stride();
     for (uint32_t f = 0; f < n_files; ++f) {
         const FileState& st = e->files[f];
+        const CallPlan::File& pf = pl.files[f];
         for (uint32_t c = 0; c < C; ++c) {
             const uint32_t sidx = f * C + c;
             StreamJob& j = hj[sidx];
-            j.in = e->deinterleave ? e->d_planar + (size_t)f * e->planar_stride : (const uint8_t*)io[f].dsd;
+            j.in = e->deinterleave ? e->d_planar + (size_t)f * planar_stride : (const uint8_t*)io[f].dsd;
             j.in_raw = e->deinterleave ? (const uint8_t*)io[f].dsd : nullptr;
             j.hist = e->d_hist[cur] + (size_t)sidx * e->keep;
             j.hist_next = e->d_hist[cur ^ 1] + (size_t)sidx * e->keep;
             j.out = prime ? nullptr : io[f].pcm;
-            j.xs = e->d_scratch ? e->d_scratch + (size_t)sidx * e->scratch_stride + e->xs_hist : nullptr;
+            j.xs = e->d_scratch ? e->d_scratch + (size_t)sidx * scratch_stride + e->xs_hist : nullptr;
             j.peak = e->d_peak + sidx;
             j.L = io[f].bytes_per_channel;
             j.e0 = (int64_t)((st.nfir + 1) * (uint64_t)e->Mb) - (int64_t)st.pos;
             j.n0 = st.nfir;
-            j.nout = (uint32_t)(nfir1[f] - st.nfir);
-            if (e->poly) { j.e0 = (int64_t)st.pos; j.n0 = st.nres; j.nout = (uint32_t)(nres1[f] - st.nres); }   // (PxArgs::jobs)
+            j.nout = (uint32_t)(pf.nfir1 - st.nfir);
+            if (e->poly) { j.e0 = (int64_t)st.pos; j.n0 = st.nres; j.nout = (uint32_t)(pf.nres1 - st.nres); }   // (PxArgs::jobs)
             j.ch = e->c0 + c;
             j.och = c;
             j.m0 = st.nres;
-            j.nres = e->fc.resamp && !prime ? (uint32_t)(nres1[f] - st.nres) : 0;
+            j.nres = e->fc.resamp && !prime ? (uint32_t)(pf.nres1 - st.nres) : 0;
             const uint64_t i0 = e->fc.resamp ? st.nres : st.nfir;     // index the dither counter runs on
             const uint64_t k = rng_key64(e->p.seed, e->c0 + c);
             j.rng_kstep = (uint32_t)k | 1u;
@@ -636,15 +749,7 @@ static int batch_call(d2d_engine* e, d2d_file_io* io, uint32_t n_files, hipStrea
             j.rng_lo0 = (uint32_t)i0;
         }
     }
-    // MONO2: every file's call splits into two equal halves of whole outputs and whole 16-byte chunks, long enough to hold the second half's history
-    bool mono2 = e->mono2_ok && max_nx > 0;
-    for (uint32_t f = 0; f < n_files && mono2; ++f) {
-        const StreamJob& j = hj[f];
-        const uint64_t half = j.L / 2;
-        mono2 = (j.L % 2 == 0) && (half % 16 == 0) && (half % (uint64_t)e->Mb == 0) && half >= e->keep && (j.nout % 2 == 0) &&
-                (uint64_t)(uint32_t)j.n0 + j.nout <= 0xFFFFFFFFull;
-    }
-    if (mono2)
+    if (pl.mono2)
         for (uint32_t f = 0; f < n_files; ++f) {
             StreamJob ja = hj[f];
             const uint64_t half = ja.L / 2;
@@ -657,110 +762,71 @@ static int batch_call(d2d_engine* e, d2d_file_io* io, uint32_t n_files, hipStrea
             hj[e->nstreams + 2 * f] = ja; hj[e->nstreams + 2 * f + 1] = jb;
         }
     if (e->fine)
-        for (uint32_t i = 0; i < e->nstreams; ++i) { hj[e->nstreams + i] = hj[i]; hj[e->nstreams + i].xs = hj[i].xs + (size_t)e->nstreams * e->scratch_stride; }
-    HIPCHK(e, hipMemcpyAsync(e->d_jobs, hj, sizeof(StreamJob) * njobs, hipMemcpyHostToDevice, s));
+        for (uint32_t i = 0; i < e->nstreams; ++i) { hj[e->nstreams + i] = hj[i]; hj[e->nstreams + i].xs = hj[i].xs + (size_t)e->nstreams * scratch_stride; }
+    HIPCHK(e, hipMemcpyAsync(e->d_jobs, hj, sizeof(StreamJob) * e->launch.njobs, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipEventRecord(e->job_ev[slot], s));
     e->job_ev_used[slot] = true;
+    return D2D_OK;
+}
 
-    std::pair<hipEvent_t, hipEvent_t>* ps = nullptr;
-    if (e->profiling && (max_nx || (prime && max_L))) {
-        if (e->step_used == e->step_pool.size()) {
-            std::pair<hipEvent_t, hipEvent_t> n{};
-            HIPCHK(e, hipEventCreate(&n.first));
-            HIPCHK(e, hipEventCreate(&n.second));
-            e->step_pool.push_back(n);
-        }
-        ps = &e->step_pool[e->step_used++];
-        HIPCHK(e, hipEventRecord(ps->first, s));
+// one FIR pass of a single-filter engine over every stream
+static int launch_fir_pass(d2d_engine* e, const FirArgs& a, uint32_t max_nx, hipStream_t s) {
+    if (e->kernel == D2D_KERNEL_LUT) {
+        const uint32_t per_tile = lut_outputs_per_tile(e->Mb);
+        HIPCHK(e, launch_fir_lut(a, e->Mb, (max_nx + per_tile - 1) / per_tile, e->nstreams, s));
+    } else if (e->mfma_v2) {
+        HIPCHK(e, launch_fir_mfma2(a, e->M, e->N, max_nx, e->nstreams, s));
+    } else {
+        HIPCHK(e, launch_fir_mfma(a, e->mfma, max_nx, e->nstreams, s));
     }
-    if (e->deinterleave) HIPCHK(e, launch_deinterleave(e->d_jobs, n_files, e->Cin, C, max_L, s));
+    return D2D_OK;
+}
 
-    FirArgs a{};
-    a.jobs = e->d_jobs;
-    fir_args_static(e, a);
-    std::pair<hipEvent_t, hipEvent_t>* pe = nullptr;
-    if (e->profiling && max_nx) {
-        if (e->prof_used == e->prof_pool.size()) {
-            std::pair<hipEvent_t, hipEvent_t> n{};
-            HIPCHK(e, hipEventCreate(&n.first));
-            HIPCHK(e, hipEventCreate(&n.second));
-            e->prof_pool.push_back(n);
-        }
-        pe = &e->prof_pool[e->prof_used++];
-        HIPCHK(e, hipEventRecord(pe->first, s));
-    }
+// Launch: every kernel of the call, in stream order, inside the two profiling brackets.
+static int launch_call(d2d_engine* e, const CallPlan& pl, hipStream_t s, const bool prime) {
+    const LaunchState& l = e->launch;
+    const uint32_t n_files = e->n_files, max_nx = pl.max_nx, max_frames = pl.max_frames;
+    EventPairs::Pair* ps = nullptr;
+    if (e->profiling && (max_nx || (prime && pl.max_L))) HIPCHK(e, e->step.open(s, &ps));
+    if (e->deinterleave) HIPCHK(e, launch_deinterleave(e->d_jobs, n_files, e->Cin, e->C, pl.max_L, s));
+
+    EventPairs::Pair* pe = nullptr;
+    if (e->profiling && max_nx) HIPCHK(e, e->prof.open(s, &pe));
     if (e->poly) {
-        PxArgs px{};
-        px.jobs = e->d_jobs; px.tables = e->d_fir_tables;
-        px.in_channels = e->Cin; px.B = e->B; px.keep = e->keep; px.msb = e->p.endianness == D2D_MSB_FIRST ? 1u : 0u;
-        px.to_scratch = e->noise_shape ? 1u : 0u;
-        px.il2 = e->il2 ? 1u : 0u;
-        px.epi = e->epi;
+        PxArgs px = l.px;
         if (e->poly_plain) HIPCHK(e, launch_poly_plain(px, *e->poly, max_frames, e->nstreams, s));
         else HIPCHK(e, launch_fir_px(px, *e->poly, max_frames, n_files, s));
-    } else if (mono2) {
-        FirArgs a2 = a;
-        a2.jobs = e->d_jobs + e->nstreams; a2.tables = e->d_fir_tables_m2;
-        a2.epi.channels = 2; a2.in_channels = 2; a2.B = 0x40000000u;     // (one "block" per half: the gather path's layout rule then reads half c at c * half)
-        a2.pipelined = (uint32_t)e->mono2_pipe; a2.mono2 = 1;
-        HIPCHK(e, launch_fir_mfma2(a2, e->M, e->N, max_nx / 2, 2 * n_files, s));
+    } else if (pl.mono2) {
+        HIPCHK(e, launch_fir_mfma2(l.fir_m2, e->M, e->N, max_nx / 2, 2 * n_files, s));
     } else if (max_nx) {
-        if (e->kernel == D2D_KERNEL_LUT) {
-            const uint32_t per_tile = lut_outputs_per_tile(e->Mb);
-            HIPCHK(e, launch_fir_lut(a, e->Mb, (max_nx + per_tile - 1) / per_tile, e->nstreams, s));
-        } else {
-            if (e->mfma_v2) HIPCHK(e, launch_fir_mfma2(a, e->M, e->N, max_nx, e->nstreams, s));
-            else HIPCHK(e, launch_fir_mfma(a, e->mfma, max_nx, e->nstreams, s));
-        }
+        int rc = launch_fir_pass(e, l.fir, max_nx, s);
+        if (rc) return rc;
     }
     if ((e->poly ? max_frames : max_nx) && d2d_last_launched_kernel) e->launched = d2d_last_launched_kernel;
     if (e->fine && max_nx) {
         // second pass: the residual taps, into the second half of the scratch
-        FirArgs al{};
-        al.jobs = e->d_jobs + e->nstreams;
-        fir_args_static(e, al, true);
-        if (e->kernel == D2D_KERNEL_LUT) {
-            const uint32_t per_tile = lut_outputs_per_tile(e->Mb);
-            HIPCHK(e, launch_fir_lut(al, e->Mb, (max_nx + per_tile - 1) / per_tile, e->nstreams, s));
-        } else {
-            if (e->mfma_v2) HIPCHK(e, launch_fir_mfma2(al, e->M, e->N, max_nx, e->nstreams, s));
-            else HIPCHK(e, launch_fir_mfma(al, e->mfma, max_nx, e->nstreams, s));
-        }
+        int rc = launch_fir_pass(e, l.fir_lo, max_nx, s);
+        if (rc) return rc;
     }
     if (pe) HIPCHK(e, hipEventRecord(pe->second, s));
     if (e->fine && max_nx) {
         // the matrix-core kernels write 2 sum(q b) - 2^S, which is sum(q s) only for a table that sums to 2^S: the residual table sums to 0
         const int64_t lo_bias = e->kernel == D2D_KERNEL_LUT ? 0 : ((int64_t)1 << e->S);
-        HIPCHK(e, launch_fine_combine(e->d_jobs, e->nstreams, max_nx, (size_t)e->nstreams * e->scratch_stride, lo_bias, e->S + 8, e->epi, s));
+        HIPCHK(e, launch_fine_combine(e->d_jobs, e->nstreams, max_nx, (size_t)e->nstreams * e->scratch_stride(), lo_bias, e->S + 8, e->epi, s));
     }
     if (e->cascade()) {
         if (!prime) {
-            Rs2Args r{};
-            r.jobs = e->d_jobs; r.tables = reinterpret_cast<const uint8_t*>(e->d_resamp);
-            r.S = e->S; r.epi = e->epi;
-            if (e->noise_shape) { r.ys = e->d_ys; r.ys_stride = (uint32_t)e->ys_stride; }
+            Rs2Args r = l.rs;
+            if (e->noise_shape) { r.ys = e->d_ys; r.ys_stride = (uint32_t)e->ys_stride(); }
             HIPCHK(e, launch_resample2(r, *e->fc.resamp, max_frames, n_files, s));
         }
         HIPCHK(e, launch_xhist(e->d_jobs, e->nstreams, (uint32_t)e->fc.resamp->P, s));
     }
     if (e->noise_shape && !prime) {
-        NoiseShapeArgs ns{};
-        ns.jobs = e->d_jobs; ns.state = e->d_ns[e->ns_cur]; ns.state_next = e->d_ns[e->ns_cur ^ 1]; ns.dump = e->d_ns_dump;
-        ns.scale_bits = e->poly ? e->poly->S : e->S; ns.nstreams = e->nstreams; ns.max_nout = e->fc.resamp ? max_frames : max_nx; ns.epi = e->epi;
-        if (e->cascade()) { ns.ys = e->d_ys; ns.ys_stride = (uint32_t)e->ys_stride; ns.res = 1; }
-        {
-            const bool noint = (e->p.debug_flags & D2D_DBG_NO_INTQ) != 0;
-            uint64_t sa = 0;
-            if (e->poly) {
-                for (int ph = 0; ph < e->poly->Lp; ++ph) {
-                    uint64_t sp = 0;
-                    for (int j = 0; j < e->poly->NP; ++j) { const int64_t q = e->poly->q[(size_t)ph * e->poly->NP + j]; sp += (uint64_t)(q < 0 ? -q : q); }
-                    sa = std::max(sa, sp);
-                }
-            } else { FirArgs fa{}; fir_args_static(e, fa); sa = fa.sum_abs_q; }
-            ns.intq = (!noint && sa + (1ull << 24) < (1ull << 31)) ? 1u : 0u;
-            ns.general = (e->p.debug_flags & D2D_DBG_NS_GENERAL) ? 1u : 0u;
-        }
+        NoiseShapeArgs ns = l.ns;
+        ns.state = e->d_ns[e->ns_cur]; ns.state_next = e->d_ns[e->ns_cur ^ 1];
+        ns.max_nout = e->fc.resamp ? max_frames : max_nx;
+        if (e->cascade()) { ns.ys = e->d_ys; ns.ys_stride = (uint32_t)e->ys_stride(); }
         // a stream whose call ends exactly on a segment boundary, or feeds nothing, writes no state: start the next buffer from the current one
         HIPCHK(e, hipMemcpyAsync(e->d_ns[e->ns_cur ^ 1], e->d_ns[e->ns_cur], sizeof(double) * 2 * e->nstreams, hipMemcpyDeviceToDevice, s));
         HIPCHK(e, launch_noise_shape(ns, s));
@@ -768,8 +834,13 @@ static int batch_call(d2d_engine* e, d2d_file_io* io, uint32_t n_files, hipStrea
     }
     HIPCHK(e, launch_history(e->d_jobs, e->nstreams, e->Cin, e->B, e->keep, s));
     if (ps) HIPCHK(e, hipEventRecord(ps->second, s));
-    e->hist_cur = cur ^ 1;
-    for (uint32_t f = 0; f < n_files; ++f) {
+    return D2D_OK;
+}
+
+// Commit: the call is enqueued; the files stand where it leaves them.
+static void commit_call(d2d_engine* e, const d2d_file_io* io, const CallPlan& pl, hipStream_t s, const bool prime) {
+    e->hist_cur ^= 1;
+    for (uint32_t f = 0; f < e->n_files; ++f) {
         FileState& st = e->files[f];
         if (e->noise_shape) {
             // frames began on a segment boundary: the shaper's state is the uninterrupted conversion's from here on; a prime leaves it unknown
@@ -777,12 +848,28 @@ static int batch_call(d2d_engine* e, d2d_file_io* io, uint32_t n_files, hipStrea
             else if (io[f].frames_out) st.ns_unknown = false;
         }
         st.pos += io[f].bytes_per_channel;
-        st.nfir = nfir1[f];
-        st.nres = nres1[f];
+        st.nfir = pl.files[f].nfir1;
+        st.nres = pl.files[f].nres1;
     }
     e->last_stream = s;
-    return D2D_OK;
 }
+
+// One call of every file: what d2d_translate_batch_device and d2d_prime_batch_device share.
+// prime: the bytes are consumed and everything that carries over to the next call is updated (the planar copy the history is read from,
+// stage A of the cascade with its carried outputs, the bit history), but no frames are produced and the peaks stay.
+static int batch_call(d2d_engine* e, d2d_file_io* io, uint32_t n_files, hipStream_t s, const bool prime) {
+    if (!io || n_files != e->n_files) return e->fail(D2D_ERR_PARAM, "file count does not match the engine");
+    HIPCHK(e, hipSetDevice(e->p.device));
+    CallPlan pl;
+    int rc = plan_call(e, io, prime, pl);
+    if (!rc) rc = reserve_call_buffers(e, pl, s, prime);
+    if (!rc) rc = enqueue_jobs(e, io, pl, s, prime);
+    if (!rc) rc = launch_call(e, pl, s, prime);
+    if (!rc) commit_call(e, io, pl, s, prime);
+    return rc;
+}
+
+extern "C" {
 
 int d2d_translate_batch_device(d2d_engine* e, d2d_file_io* io, uint32_t n_files, void* hip_stream) {
     if (!e) return D2D_ERR_PARAM;
@@ -792,18 +879,6 @@ int d2d_translate_batch_device(d2d_engine* e, d2d_file_io* io, uint32_t n_files,
 int d2d_prime_batch_device(d2d_engine* e, d2d_file_io* io, uint32_t n_files, void* hip_stream) {
     if (!e) return D2D_ERR_PARAM;
     return batch_call(e, io, n_files, (hipStream_t)hip_stream, true);
-}
-
-static int ensure_cap(d2d_engine* e, uint8_t** buf, size_t* cap, size_t need) {
-    if (need <= *cap) return D2D_OK;
-    size_t n = std::max(need, *cap * 2);
-    n = (n + 4095) & ~(size_t)4095;
-    HIPCHK(e, hipStreamSynchronize(e->own_stream));
-    if (*buf) HIPCHK(e, hipFree(*buf));
-    *buf = nullptr; *cap = 0;
-    HIPCHK(e, hipMalloc((void**)buf, n));
-    *cap = n;
-    return D2D_OK;
 }
 
 // Host memory the GPU can address itself (hipHostMalloc, hipHostRegister; device memory passes too): the kernels then read the DSD
@@ -823,6 +898,29 @@ static bool device_view(const void* p, void** dev) {
 }
 static bool host_staged_forced(const d2d_engine* e) { return (e->p.debug_flags & D2D_DBG_HOST_STAGED) != 0; }
 
+// the single-file staging (d_in, d_out) holds `need` bytes: doubling, in whole 4 KiB pages, once own_stream has let go of the old memory
+static int reserve_staging(d2d_engine* e, Buf<uint8_t>& b, size_t need) {
+    need = std::max<size_t>(need, 16);
+    if (need > b.bytes) need = (std::max(need, b.bytes * 2) + 4095) & ~(size_t)4095;
+    HIPCHK(e, b.reserve(need, wait_stream(e->own_stream)));
+    return D2D_OK;
+}
+
+// the caller's input where the GPU cannot read it in place: a copy in d_in, enqueued on own_stream
+static int stage_input(d2d_engine* e, const void* dsd, size_t in_bytes, const void** dev) {
+    int rc = reserve_staging(e, e->d_in, in_bytes);
+    if (rc) return rc;
+    if (in_bytes) HIPCHK(e, hipMemcpyAsync(e->d_in, dsd, in_bytes, hipMemcpyHostToDevice, e->own_stream));
+    *dev = e->d_in;
+    return D2D_OK;
+}
+
+// the most output a call of n bytes per channel can yield: the engine never emits more than ceil(bytes*8/M)+1 frames per call
+static size_t slice_out_bytes(const d2d_engine* e, size_t n) {
+    const double ratio = e->fc.resamp ? (double)e->fc.resamp->L / (double)e->fc.resamp->Mdn / (double)e->M : 1.0 / (double)e->M;
+    return ((size_t)((double)n * 8.0 * ratio) + 4) * d2d_frame_bytes(e);
+}
+
 int d2d_translate(d2d_engine* e, const uint8_t* dsd, size_t L, void* pcm, size_t cap, size_t* frames_out) {
     if (!e) return D2D_ERR_PARAM;
     if (frames_out) *frames_out = 0;
@@ -836,25 +934,18 @@ int d2d_translate(d2d_engine* e, const uint8_t* dsd, size_t L, void* pcm, size_t
     const size_t in_bytes = L * e->Cin;
     hipStream_t s = e->own_stream;
     void *vin = nullptr, *vout = nullptr;
-    if (in_bytes && out_bytes && !host_staged_forced(e) && device_view(dsd, &vin) && device_view(pcm, &vout)) {
-        d2d_file_io io{};
-        io.dsd = vin; io.bytes_per_channel = L; io.pcm = vout; io.pcm_capacity_bytes = cap;
-        int rc = d2d_translate_batch_device(e, &io, 1, s);
-        if (rc) return rc;
-        HIPCHK(e, hipStreamSynchronize(s));
-        if (frames_out) *frames_out = io.frames_out;
-        return D2D_OK;
-    }
-    int rc = ensure_cap(e, &e->d_in, &e->d_in_cap, std::max<size_t>(in_bytes, 16));
-    if (rc) return rc;
-    rc = ensure_cap(e, &e->d_out, &e->d_out_cap, std::max<size_t>(out_bytes, 16));
-    if (rc) return rc;
-    if (in_bytes) HIPCHK(e, hipMemcpyAsync(e->d_in, dsd, in_bytes, hipMemcpyHostToDevice, s));
+    const bool direct = in_bytes && out_bytes && !host_staged_forced(e) && device_view(dsd, &vin) && device_view(pcm, &vout);
     d2d_file_io io{};
-    io.dsd = e->d_in; io.bytes_per_channel = L; io.pcm = e->d_out; io.pcm_capacity_bytes = e->d_out_cap;
-    rc = d2d_translate_batch_device(e, &io, 1, s);
+    io.dsd = vin; io.bytes_per_channel = L; io.pcm = vout; io.pcm_capacity_bytes = cap;
+    if (!direct) {
+        int rc = reserve_staging(e, e->d_out, out_bytes);
+        if (!rc) rc = stage_input(e, dsd, in_bytes, &io.dsd);
+        if (rc) return rc;
+        io.pcm = e->d_out; io.pcm_capacity_bytes = e->d_out.bytes;
+    }
+    int rc = d2d_translate_batch_device(e, &io, 1, s);
     if (rc) return rc;
-    if (out_bytes) HIPCHK(e, hipMemcpyAsync(pcm, e->d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    if (!direct && out_bytes) HIPCHK(e, hipMemcpyAsync(pcm, e->d_out, out_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     if (frames_out) *frames_out = io.frames_out;
     return D2D_OK;
@@ -874,11 +965,8 @@ int d2d_prime(d2d_engine* e, const uint8_t* dsd, size_t L) {
     if (!host_staged_forced(e) && device_view(dsd, &vin)) {
         io.dsd = vin;
     } else {
-        const size_t in_bytes = L * e->Cin;
-        int rc = ensure_cap(e, &e->d_in, &e->d_in_cap, std::max<size_t>(in_bytes, 16));
+        int rc = stage_input(e, dsd, L * e->Cin, &io.dsd);
         if (rc) return rc;
-        HIPCHK(e, hipMemcpyAsync(e->d_in, dsd, in_bytes, hipMemcpyHostToDevice, s));
-        io.dsd = e->d_in;
     }
     int rc = batch_call(e, &io, 1, s, true);
     if (rc) { hipStreamSynchronize(s); return rc; }
@@ -931,20 +1019,12 @@ int d2d_translate_batch_host(d2d_engine* e, d2d_file_io* io, uint32_t n_files, s
             return D2D_OK;
         }
     }
-    // capacity of one slice's output: the engine never emits more than ceil(bytes*8/M)+1 frames per call
-    const double ratio = e->fc.resamp ? (double)e->fc.resamp->L / (double)e->fc.resamp->Mdn / (double)e->M : 1.0 / (double)e->M;
+    // double-buffered staging, one 256-byte aligned slice per file; a buffer that has to grow waits for the whole device
     const size_t in_stride = (slice * C + 255) & ~(size_t)255;
-    const size_t out_stride = (((size_t)((double)slice * 8.0 * ratio) + 4) * fb + 255) & ~(size_t)255;
-    if (!e->hb_in[0] || e->hb_in_stride < in_stride || e->hb_out_stride < out_stride) {
-        HIPCHK(e, hipDeviceSynchronize());
-        for (int b = 0; b < 2; ++b) {
-            if (e->hb_in[b]) hipFree(e->hb_in[b]);
-            if (e->hb_out[b]) hipFree(e->hb_out[b]);
-            e->hb_in[b] = e->hb_out[b] = nullptr;
-            HIPCHK(e, hipMalloc((void**)&e->hb_in[b], in_stride * n_files));
-            HIPCHK(e, hipMalloc((void**)&e->hb_out[b], out_stride * n_files));
-        }
-        e->hb_in_stride = in_stride; e->hb_out_stride = out_stride;
+    const size_t out_stride = (slice_out_bytes(e, slice) + 255) & ~(size_t)255;
+    for (int b = 0; b < 2; ++b) {
+        HIPCHK(e, e->hb_in[b].reserve(in_stride * n_files, wait_device()));
+        HIPCHK(e, e->hb_out[b].reserve(out_stride * n_files, wait_device()));
     }
     if (!e->hb_stream[0]) {
         for (int i = 0; i < 3; ++i) HIPCHK(e, hipStreamCreateWithFlags(&e->hb_stream[i], hipStreamNonBlocking));
@@ -1033,16 +1113,15 @@ int d2d_convert_stream(d2d_engine* e, d2d_read_fn read, void* ru, d2d_write_fn w
     // Pinned staging, two deep: while the GPU uploads, converts and downloads chunk k, the host reads
     // chunk k+1 and writes chunk k-1 (the callbacks are the file and sink I/O).
     const size_t fb = d2d_frame_bytes(e);
-    const double ratio = e->fc.resamp ? (double)e->fc.resamp->L / (double)e->fc.resamp->Mdn / (double)e->M : 1.0 / (double)e->M;
-    const size_t in_cap = chunk * e->Cin, out_cap = ((size_t)((double)chunk * 8.0 * ratio) + 4) * fb;
+    const size_t in_cap = chunk * e->Cin, out_cap = slice_out_bytes(e, chunk);
     struct Pinned {
-        uint8_t* in[2] = {nullptr, nullptr}; uint8_t* out[2] = {nullptr, nullptr};
+        Buf<uint8_t, true> in[2], out[2];
         hipEvent_t ev[2] = {nullptr, nullptr};
-        ~Pinned() { for (int b = 0; b < 2; ++b) { if (in[b]) hipHostFree(in[b]); if (out[b]) hipHostFree(out[b]); if (ev[b]) hipEventDestroy(ev[b]); } }
+        ~Pinned() { for (int b = 0; b < 2; ++b) if (ev[b]) hipEventDestroy(ev[b]); }
     } pin;
     for (int b = 0; b < 2; ++b) {
-        HIPCHK(e, hipHostMalloc((void**)&pin.in[b], std::max<size_t>(in_cap, 16), hipHostMallocDefault));
-        HIPCHK(e, hipHostMalloc((void**)&pin.out[b], std::max<size_t>(out_cap, 16), hipHostMallocDefault));
+        HIPCHK(e, pin.in[b].alloc(std::max<size_t>(in_cap, 16)));
+        HIPCHK(e, pin.out[b].alloc(std::max<size_t>(out_cap, 16)));
         HIPCHK(e, hipEventCreateWithFlags(&pin.ev[b], hipEventDisableTiming));
     }
     // the kernels read and write the pinned buffers themselves when the GPU can address them (they are hipHostMalloc'ed: it can)
@@ -1051,9 +1130,8 @@ int d2d_convert_stream(d2d_engine* e, d2d_read_fn read, void* ru, d2d_write_fn w
                         device_view(pin.out[0], &vout[0]) && device_view(pin.out[1], &vout[1]);
     int rc = D2D_OK;
     if (!direct) {
-        rc = ensure_cap(e, &e->d_in, &e->d_in_cap, std::max<size_t>(in_cap, 16));
-        if (rc) return rc;
-        rc = ensure_cap(e, &e->d_out, &e->d_out_cap, std::max<size_t>(out_cap, 16));
+        rc = reserve_staging(e, e->d_in, in_cap);
+        if (!rc) rc = reserve_staging(e, e->d_out, out_cap);
         if (rc) return rc;
     }
     hipStream_t s = e->own_stream;
@@ -1085,11 +1163,11 @@ int d2d_convert_stream(d2d_engine* e, d2d_read_fn read, void* ru, d2d_write_fn w
         if (got < 0) { drain(); return e->fail(D2D_ERR_IO, "read callback failed"); }
         if (got == 0) { rc = retire(b ^ 1); if (rc) { drain(); return rc; } break; }
         const size_t L = (size_t)got;
-        if (!direct) HIPCHK(e, hipMemcpyAsync(e->d_in, pin.in[b], L * e->Cin, hipMemcpyHostToDevice, s));
         d2d_file_io io{};
-        io.dsd = direct ? vin[b] : e->d_in; io.bytes_per_channel = L;
-        io.pcm = direct ? vout[b] : e->d_out; io.pcm_capacity_bytes = direct ? std::max<size_t>(out_cap, 16) : e->d_out_cap;
-        rc = d2d_translate_batch_device(e, &io, 1, s);
+        io.dsd = vin[b]; io.bytes_per_channel = L;
+        io.pcm = direct ? vout[b] : e->d_out; io.pcm_capacity_bytes = direct ? pin.out[b].bytes : e->d_out.bytes;
+        if (!direct) rc = stage_input(e, pin.in[b], L * e->Cin, &io.dsd);
+        if (!rc) rc = d2d_translate_batch_device(e, &io, 1, s);
         if (rc) { drain(); return rc; }
         pend_bytes[b] = io.frames_out * fb;
         pend_in[b] = (uint64_t)got;
@@ -1112,16 +1190,11 @@ int d2d_profile_enable(d2d_engine* e, int on) {
 int d2d_profile_read(d2d_engine* e, double* ms_total, uint64_t* launches) {
     if (!e) return D2D_ERR_PARAM;
     HIPCHK(e, hipSetDevice(e->p.device));
+    const size_t n = e->prof.used;
     double tot = 0.0;
-    for (size_t i = 0; i < e->prof_used; ++i) {
-        HIPCHK(e, hipEventSynchronize(e->prof_pool[i].second));
-        float ms = 0.f;
-        HIPCHK(e, hipEventElapsedTime(&ms, e->prof_pool[i].first, e->prof_pool[i].second));
-        tot += ms;
-    }
+    HIPCHK(e, e->prof.elapsed_ms(&tot));
     if (ms_total) *ms_total = tot;
-    if (launches) *launches = e->prof_used;
-    e->prof_used = 0;
+    if (launches) *launches = n;
     return D2D_OK;
 }
 
@@ -1129,19 +1202,13 @@ int d2d_profile_read_all(d2d_engine* e, double* fir_ms_total, double* step_ms_to
     if (!e) return D2D_ERR_PARAM;
     HIPCHK(e, hipSetDevice(e->p.device));
     double tot = 0.0;
-    for (size_t i = 0; i < e->step_used; ++i) {
-        HIPCHK(e, hipEventSynchronize(e->step_pool[i].second));
-        float ms = 0.f;
-        HIPCHK(e, hipEventElapsedTime(&ms, e->step_pool[i].first, e->step_pool[i].second));
-        tot += ms;
-    }
+    HIPCHK(e, e->step.elapsed_ms(&tot));
     if (step_ms_total) *step_ms_total = tot;
-    e->step_used = 0;
     return d2d_profile_read(e, fir_ms_total, launches);
 }
 
 size_t d2d_tables_bytes(const d2d_engine* e) {
-    return e ? sizeof(TableBlobHeader) + ((e->fir_table_bytes + 15) & ~(size_t)15) + e->resamp_bytes : 0;
+    return e ? sizeof(TableBlobHeader) + ((e->d_fir_tables.bytes + 15) & ~(size_t)15) + e->d_resamp.bytes : 0;
 }
 
 static TableBlobHeader make_header(const d2d_engine* e) {
@@ -1151,7 +1218,7 @@ static TableBlobHeader make_header(const d2d_engine* e) {
     h.table_variant = e->poly ? (e->poly_plain ? 7u : 6u) : e->kernel == D2D_KERNEL_MFMA && e->mfma_v2 ? (e->mfma_pipe ? (uint32_t)e->mfma_pipe : 2u) : 0u;
     if (e->taps32) { h.table_variant = 8u; h.scale_bits = (uint32_t)(e->S + 8); }      // the seven-digit fragments of the 32-bit taps
     if (e->poly) { h.ntaps = (uint32_t)e->poly->NP; h.M = (uint32_t)e->poly->Mp; h.scale_bits = (uint32_t)e->poly->S; h.filter_type = (uint32_t)'P'; }
-    h.fir_bytes = e->fir_table_bytes; h.resamp_bytes = e->resamp_bytes;
+    h.fir_bytes = e->d_fir_tables.bytes; h.resamp_bytes = e->d_resamp.bytes;
     return h;
 }
 
@@ -1166,9 +1233,9 @@ int d2d_tables_export_device(d2d_engine* e, void* dst, size_t cap, void* hip_str
     HIPCHK(e, hipMemcpyAsync(p, &h, sizeof(h), hipMemcpyHostToDevice, s));
     HIPCHK(e, hipStreamSynchronize(s));   // h is a stack object
     p += sizeof(h);
-    HIPCHK(e, hipMemcpyAsync(p, e->d_fir_tables, e->fir_table_bytes, hipMemcpyDeviceToDevice, s));
-    p += (e->fir_table_bytes + 15) & ~(size_t)15;
-    if (e->resamp_bytes) HIPCHK(e, hipMemcpyAsync(p, e->d_resamp, e->resamp_bytes, hipMemcpyDeviceToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(p, e->d_fir_tables, e->d_fir_tables.bytes, hipMemcpyDeviceToDevice, s));
+    p += (e->d_fir_tables.bytes + 15) & ~(size_t)15;
+    if (e->d_resamp) HIPCHK(e, hipMemcpyAsync(p, e->d_resamp, e->d_resamp.bytes, hipMemcpyDeviceToDevice, s));
     return D2D_OK;
 }
 
@@ -1183,9 +1250,9 @@ int d2d_tables_import_device(d2d_engine* e, const void* src, size_t bytes, void*
     HIPCHK(e, hipStreamSynchronize(s));
     if (memcmp(&h, &want, sizeof(h)) != 0) return e->fail(D2D_ERR_PARAM, "table blob does not match this engine's configuration");
     const uint8_t* p = (const uint8_t*)src + sizeof(h);
-    HIPCHK(e, hipMemcpyAsync(e->d_fir_tables, p, e->fir_table_bytes, hipMemcpyDeviceToDevice, s));
-    p += (e->fir_table_bytes + 15) & ~(size_t)15;
-    if (e->resamp_bytes) HIPCHK(e, hipMemcpyAsync(e->d_resamp, p, e->resamp_bytes, hipMemcpyDeviceToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->d_fir_tables, p, e->d_fir_tables.bytes, hipMemcpyDeviceToDevice, s));
+    p += (e->d_fir_tables.bytes + 15) & ~(size_t)15;
+    if (e->d_resamp) HIPCHK(e, hipMemcpyAsync(e->d_resamp, p, e->d_resamp.bytes, hipMemcpyDeviceToDevice, s));
     HIPCHK(e, hipStreamSynchronize(s));
     return D2D_OK;
 }
@@ -1212,36 +1279,27 @@ void d2d_debug_stamps3(unsigned long long* out8) { hipDeviceSynchronize(); mfma3
 const char* d2d_kernel_name(const d2d_engine* e) {
     if (!e) return "";
     if (!e->launched.empty()) return e->launched.c_str();      // what the last call launched; before the first call: what the dispatch will choose
+    auto num = [](long v) { return std::to_string(v); };
+    const int dkind = e->epi.dither == 'T' ? 1 : e->epi.dither == 'R' ? 2 : 0;
+    const bool scr = e->fc.resamp || e->noise_shape;           // the kernel writes integers to the scratch, not frames
     if (e->poly) {
         if (e->poly_plain) return "d2d_poly_plain_kernel";
-        d2d_engine* m = const_cast<d2d_engine*>(e);
         const bool intq = e->epi.gain == 1.0 && (e->epi.bits == 24 || e->epi.bits == 16) && e->epi.dither != 'F';
-        const int kind = e->noise_shape ? 4 : !intq ? 3 : e->epi.dither == 'T' ? 1 : e->epi.dither == 'R' ? 2 : 0;
-        m->kname = "d2d_fir_px_kernel<" + std::to_string(e->poly->Lp) + ", " + std::to_string(e->poly->Mp) + ", " + std::to_string(e->poly->NP) + ", " +
-                   std::to_string(px_groups(*e->poly)) + ", " + std::to_string(kind) + ">";
-        return m->kname.c_str();
+        const int kind = e->noise_shape ? 4 : !intq ? 3 : dkind;
+        e->kname = "d2d_fir_px_kernel<" + num(e->poly->Lp) + ", " + num(e->poly->Mp) + ", " + num(e->poly->NP) + ", " + num(px_groups(*e->poly)) + ", " +
+                   num(kind) + ">";
+    } else if (e->kernel != D2D_KERNEL_MFMA || !e->mfma_v2) {
+        return e->kernel == D2D_KERNEL_LUT ? lut_kernel_name(e->Mb) : mfma_kernel_name(e->mfma);
+    } else if (e->mfma_pipe == PIPE_FP6) {
+        e->kname = "d2d_fir_mx_kernel<" + num(e->Mb) + ", " + num(e->N) + ", " + num(mx_groups(e->Mb)) + ", " +
+                   num(scr || e->epi.sample_bytes == 4 ? 0 : dkind) + ", " + num(scr ? 0u : e->epi.sample_bytes) + ">";
+    } else if (e->mfma_pipe == PIPE_INT8) {
+        e->kname = "d2d_fir_mfma3_kernel<" + num(e->Mb) + ", " + num(mfma2_pairs(e->M, e->N)) + ", 0, " + num(scr ? 0 : dkind) + ", " +
+                   num(scr ? 0u : e->epi.sample_bytes) + ">";
+    } else {
+        e->kname = "d2d_fir_mfma2_kernel<" + num(e->Mb) + ", " + num(mfma2_pairs(e->M, e->N)) + ", " + num(e->C == 1 ? 1 : 2) + ">";
     }
-    if (e->kernel == D2D_KERNEL_MFMA && e->mfma_v2) {
-        d2d_engine* m = const_cast<d2d_engine*>(e);
-        if (e->mfma_pipe == 5) {
-            const int kind = e->epi.dither == 'T' ? 1 : e->epi.dither == 'R' ? 2 : 0;
-            const bool scr = e->fc.resamp || e->noise_shape;
-            m->kname = "d2d_fir_mx_kernel<" + std::to_string(e->Mb) + ", " + std::to_string(e->N) + ", " + std::to_string(mx_groups(e->Mb)) + ", " +
-                       std::to_string(scr || e->epi.sample_bytes == 4 ? 0 : kind) + ", " + std::to_string(scr ? 0u : e->epi.sample_bytes) + ">";
-            return m->kname.c_str();
-        }
-        if (e->mfma_pipe) {
-            const int kind = e->epi.dither == 'T' ? 1 : e->epi.dither == 'R' ? 2 : 0;
-            const bool scr = e->fc.resamp || e->noise_shape;
-            m->kname = "d2d_fir_mfma3_kernel<" + std::to_string(e->Mb) + ", " + std::to_string(mfma2_pairs(e->M, e->N)) + ", " +
-                       std::to_string(e->mfma_pipe == 4 ? e->N : 0) + ", " + std::to_string(scr ? 0 : kind) + ", " + std::to_string(scr ? 0u : e->epi.sample_bytes) + ">";
-            return m->kname.c_str();
-        }
-        m->kname = "d2d_fir_mfma2_kernel<" + std::to_string(e->Mb) + ", " + std::to_string(mfma2_pairs(e->M, e->N)) + ", " +
-                   std::to_string(e->C == 1 ? 1 : 2) + ">";
-        return m->kname.c_str();
-    }
-    return e->kernel == D2D_KERNEL_LUT ? lut_kernel_name(e->Mb) : mfma_kernel_name(e->mfma);
+    return e->kname.c_str();
 }
 
 }  // extern "C"

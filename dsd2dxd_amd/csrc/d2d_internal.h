@@ -10,6 +10,15 @@ constexpr uint32_t DSD64_RATE = 2822400u;
 constexpr uint8_t IDLE_BYTE = 0x69;   // dsd2pcm's idle pattern (DC-free), MSB-first-in-time
 constexpr int LUT_THREADS = 256;
 
+// Which software-pipelined kernel serves a two-group matrix-core shape: what mfma2_pipelined returns and FirArgs::pipelined carries.  The values are
+// fixed, they are also TableBlobHeader::table_variant.  4 stays reserved: it named the tables of the retired structured-sparse chain, and a blob
+// written then must never match an engine of today.
+enum PipeKind : int {
+    PIPE_NONE = 0,
+    PIPE_INT8 = 3,             // d2d_kernels_mfma3.hip: int8 fragments, every plane masked
+    PIPE_FP6 = 5,              // d2d_kernels_mx.hip: fp6 x fp4 digits
+};
+
 // One (file, channel) stream for one translate call.  All byte indices are "call-relative":
 // 0 = the first byte this call feeds for the channel; negative = carried history.
 struct StreamJob {
@@ -60,8 +69,7 @@ struct FirArgs {
     int32_t  scale_bits;       // S of the tap table (h = q * 2^-S)
     uint32_t in_channels;      // channels of the input layout (epi.channels = channels of the output frame; fewer for a channel subset)
     uint64_t sum_abs_q;        // sum |q_j| of the tap table (bounds |y*2^S|)
-    uint32_t pipelined;        // two-group MFMA kernels: 0, or the variant of the pipelined kernel whose tap table the engine built (3 dense, 4 sparse,
-                               // 5 the fp6 x fp4 kernel of d2d_kernels_mx.hip)
+    uint32_t pipelined;        // two-group MFMA kernels: the PipeKind of the pipelined kernel whose tap table the engine built, or PIPE_NONE
     uint32_t coop;             // 1 (d2d_kernels_mx.hip, scratch flavour): byte-interleaved 4- or 8-channel input, every channel converted: the kernel
                                // de-interleaves inside its staging, a block per (file, tile) with one wave per channel pair; B = 1 then
     uint32_t il2;              // 1 (pipelined frame kernels): byte-interleaved STEREO input (DFF, -f I), both channels converted: the kernel's staging
@@ -122,8 +130,8 @@ struct TableBlobHeader {
     uint32_t M;
     uint32_t scale_bits;
     uint32_t filter_type;
-    uint32_t table_variant;    // layout of the FIR table: 0 LUT / one-group MFMA, 2 two-group (plane 0 unmasked), 3 pipelined (every plane masked),
-                               // 4 structured-sparse, 5 fp6 digits, 6 / 7 the composed polyphase tables, 8 fp6 digits of the 32-bit taps -- it depends on
+    uint32_t table_variant;    // layout of the FIR table: 0 LUT / one-group MFMA, 2 two-group (plane 0 unmasked), PIPE_INT8 (3) pipelined (every plane
+                               // masked), 4 reserved (PipeKind), PIPE_FP6 (5) fp6 digits, 6 / 7 the composed polyphase tables, 8 fp6 digits of the 32-bit taps -- it depends on
                                // channels, depth, gain and dither, not only on the filter
     uint32_t reserved;
     uint64_t fir_bytes;

@@ -721,8 +721,8 @@ static bool mx_eligible(const FirArgs& a, const Mfma2Args& m, int MB, int N) {
 }
 
 int mfma2_pipelined(const FirArgs& a, int M, int N) {
-    if (a.taps32) return 5;                                   // (the engine has checked mx_wide_supported and mx_wide_exact)
-    if (a.dbg_flags & D2D_DBG_NO_PIPE) return 0;
+    if (a.taps32) return PIPE_FP6;                            // (the engine has checked mx_wide_supported and mx_wide_exact)
+    if (a.dbg_flags & D2D_DBG_NO_PIPE) return PIPE_NONE;
     const int MB = M / 8, NPG = mfma2_pairs(M, N);
     const bool nomx = (a.dbg_flags & D2D_DBG_NO_MX) != 0;
     Mfma2Args m{}; size_t smem = 0;
@@ -732,22 +732,22 @@ int mfma2_pipelined(const FirArgs& a, int M, int N) {
     if (MB == 16) {
         const bool noint16 = (a.dbg_flags & D2D_DBG_NO_INTQ) != 0;
         const bool range_ok = a.scale_bits >= 20 && a.scale_bits <= 30 && a.sum_abs_q != 0 && a.sum_abs_q < (1ull << 31) && a.mx_exact;
-        if (nomx || !mx_supported(MB, N) || !range_ok || noint16) return 0;
-        if (a.to_scratch) return a.epi.channels >= 2 && a.epi.channels % 2 == 0 ? 5 : 0;
+        if (nomx || !mx_supported(MB, N) || !range_ok || noint16) return PIPE_NONE;
+        if (a.to_scratch) return a.epi.channels >= 2 && a.epi.channels % 2 == 0 ? PIPE_FP6 : PIPE_NONE;
         const bool depth_ok = a.epi.bits == 32 ? true : ((a.epi.bits == 24 || a.epi.bits == 20 || a.epi.bits == 16) && m.fbits > 0 && m.fbits <= 16 && a.epi.dither != 'F');
         const bool mp = mx_pairs(a, MB, N) > 1u;
-        if ((a.epi.channels != 2 && !mp) || !depth_ok || a.epi.dither == 'N') return 0;
-        if (a.epi.gain == 1.0 && m.qsh == 0 && !(a.epi.bits == 32 && a.epi.dither == 'F')) return 5;
-        if (mp) return 0;                                          // (several pairs per wave: unit gain only)
-        return mx_gain_supported(MB, N) && !(a.dbg_flags & D2D_DBG_NO_GAINQ) ? 5 : 0;
+        if ((a.epi.channels != 2 && !mp) || !depth_ok || a.epi.dither == 'N') return PIPE_NONE;
+        if (a.epi.gain == 1.0 && m.qsh == 0 && !(a.epi.bits == 32 && a.epi.dither == 'F')) return PIPE_FP6;
+        if (mp) return PIPE_NONE;                                  // (several pairs per wave: unit gain only)
+        return mx_gain_supported(MB, N) && !(a.dbg_flags & D2D_DBG_NO_GAINQ) ? PIPE_FP6 : PIPE_NONE;
     }
-    // the fp6 x fp4 kernel (d2d_kernels_mx.hip) serves what the pipelined int8 kernel serves at M = 32 and 64: 5
-    if (!nomx && mx_supported(MB, N) && mx_eligible(a, m, MB, N)) return 5;
+    // the fp6 x fp4 kernel (d2d_kernels_mx.hip) serves what the pipelined int8 kernel serves at M = 32 and 64
+    if (!nomx && mx_supported(MB, N) && mx_eligible(a, m, MB, N)) return PIPE_FP6;
     // ... and stereo frames at another level than 0 dB (its gain flavours)
-    if (!nomx && m.gainq && mx_gain_supported(MB, N) && a.mx_exact && a.scale_bits >= 20 && a.scale_bits <= 30 && (a.epi.bits == 32 || a.epi.sample_bytes == 2 || a.epi.sample_bytes == 3)) return 5;
-    if (!mfma2_supported(M, N) && !mfma3_supported(MB, NPG, N) && !(a.to_scratch && mfma3_scr_supported(MB, NPG))) return 0;
-    if (!mfma3_eligible(a, m, MB, NPG, N)) return 0;
-    return 3;
+    if (!nomx && m.gainq && mx_gain_supported(MB, N) && a.mx_exact && a.scale_bits >= 20 && a.scale_bits <= 30 && (a.epi.bits == 32 || a.epi.sample_bytes == 2 || a.epi.sample_bytes == 3)) return PIPE_FP6;
+    if (!mfma2_supported(M, N) && !mfma3_supported(MB, NPG, N) && !(a.to_scratch && mfma3_scr_supported(MB, NPG))) return PIPE_NONE;
+    if (!mfma3_eligible(a, m, MB, NPG, N)) return PIPE_NONE;
+    return PIPE_INT8;
 }
 
 static void mfma2_geometry(const FirArgs& a, int MB, int NPG, Mfma2Args& m, size_t& smem) {
@@ -851,7 +851,7 @@ hipError_t launch_fir_mfma2(const FirArgs& a, int M, int N, uint32_t max_nout, u
     size_t smem = 0;
     mfma2_geometry(a, MB, NPG, m, smem);
     const uint32_t nrows = (nstreams / C) * m.ngroups;       // grid rows: one per (file, channel group)
-    if (a.pipelined == 5) {                                  // the fp6 kernel has its own LDS layout (and M = 128 no two-group one at all)
+    if (a.pipelined == PIPE_FP6) {                           // the fp6 kernel has its own LDS layout (and M = 128 no two-group one at all)
         m.npairs = mx_pairs(a, MB, N);
         if (m.npairs > 1u) return launch_fir_mx(m, MB, N, max_nout, nstreams / C, s);     // one block row per file
         if (MB == 16) m.gainq = (!a.to_scratch && (a.epi.gain != 1.0 || m.qsh != 0 || (a.epi.bits == 32 && a.epi.dither == 'F'))) ? 1u : 0u;
