@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "d2d_internal.h"
+#include "d2d_sample.h"
 
 namespace d2d {
 
@@ -14,6 +15,7 @@ namespace d2d {
 // so that loads and stores become global_* instead of flat_*.
 #define D2D_GLOBAL __attribute__((address_space(1)))
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
 template <typename T>
 __device__ __forceinline__ D2D_GLOBAL T* as_global(T* p) { return (D2D_GLOBAL T*)(p); }
 
@@ -78,68 +80,65 @@ __device__ __forceinline__ void stage_window(uint8_t* lds, const StreamJob& job,
     }
 }
 
-// [own] counter-based dither generator, identical to orc_rng() in oracle/d2d_oracle.c:
-// word = lowbias32(lo32(n) + k32 + hi32(n)*kstep).  The host folds hi32(n0) into job.rng_key; a
-// call spans fewer than 2^32 outputs, so lo32(n) wraps at most once inside it.
+// the dither word of output index n of the job's channel (d2d_sample.h: dither_word)
 __device__ __forceinline__ uint32_t rng32(const StreamJob& job, uint64_t n) {
-    const uint32_t lo = (uint32_t)n;
-    uint32_t x = lo + job.rng_key + (lo < job.rng_lo0 ? job.rng_kstep : 0u);
-    x ^= x >> 16; x *= 0x7feb352dU;
-    x ^= x >> 15; x *= 0x846ca68bU;
-    x ^= x >> 16;
-    return x;
+    return dither_word((uint32_t)n, job.rng_key, job.rng_kstep, job.rng_lo0);
 }
 
-// a5-a7 for the integer depths: level, dither, round half away from zero, clip.
-// Returns the value as it sits in the container (20-bit samples already shifted into 24 bits).
+// The two steps from x = round(y*scale) (integer depths) or x = round(y*gain) (float) on: dither, then round half away from zero and
+// clip, or Airwindows "Dither Float" when dither == 'F' and a plain cast otherwise.  The integer value is returned as it sits in the
+// container (20-bit samples already shifted into 24 bits).
+__device__ __forceinline__ int32_t finish_int(const Epilogue& ep, double x, uint32_t rnd) {
+    double d = 0.0;
+    if (ep.dither == 'T') d = dither_f64<DITHER_TRI>(dither_term<DITHER_TRI>(rnd));
+    else if (ep.dither == 'R') d = dither_f64<DITHER_RECT>(dither_term<DITHER_RECT>(rnd));
+    const int32_t iv = round_clip(x + d, (double)(1u << (ep.bits - 1)));
+    return ep.bits == 20 ? iv * 16 : iv;
+}
+__device__ __forceinline__ float finish_f32(const Epilogue& ep, double x, uint32_t rnd) {
+    if (ep.dither == 'F') x = dither_float(x, rnd);
+    return (float)x;
+}
+
+// a5-a7 from y: level, then the above.  The integer depths keep the operations this was first written with -- the dither
+// as a product and a difference (exact, like dither_f64's fma), the clip on the integer (what round_clip does on the f64): the same
+// value for every y (tests/test_sample_arithmetic.py), other instructions.
 __device__ __forceinline__ int32_t quantise_int(const Epilogue& ep, double y, uint32_t rnd) {
     const double x = y * ep.scale;
     double d = 0.0;
-    if (ep.dither == 'T') d = (double)((rnd & 0xFFFFu) + (rnd >> 16) + 1u) * 0x1p-16 - 1.0;
-    else if (ep.dither == 'R') d = (double)(2u * (rnd >> 16) + 1u) * 0x1p-17 - 0.5;
+    if (ep.dither == 'T') d = (double)dither_term<DITHER_TRI>(rnd) * 0x1p-16 - 1.0;
+    else if (ep.dither == 'R') d = (double)dither_term<DITHER_RECT>(rnd) * 0x1p-17 - 0.5;
     const double q = x + d;
-    const double r = trunc(q + copysign(0.5, q));      // == (q >= 0 ? floor(q + .5) : ceil(q - .5))
+    const double r = trunc(q + copysign(0.5, q));
     const int32_t lim = 1 << (ep.bits - 1);
     int32_t iv = (int32_t)fmax(fmin(r, 2147483520.0), -2147483648.0);
     iv = min(max(iv, -lim), lim - 1);
     return ep.bits == 20 ? iv * 16 : iv;
 }
+__device__ __forceinline__ float quantise_f32(const Epilogue& ep, double y, uint32_t rnd) { return finish_f32(ep, y * ep.gain, rnd); }
 
-// ... and for 32-bit float output (Airwindows "Dither Float" when dither == 'F', else a plain cast)
-__device__ __forceinline__ float quantise_f32(const Epilogue& ep, double y, uint32_t rnd) {
-    double x = y * ep.gain;
-    if (ep.dither == 'F') {
-        const uint32_t fb = __float_as_uint((float)x);
-        const int e = (int)((fb >> 23) & 0xFF);
-        const int expon = e ? e - 126 : 0;
-        const double t = ((double)rnd - 2147483647.0) * 5.5e-36;
-        x = x + ldexp(t, expon + 62);
-    }
-    return (float)x;
+// ---- the variants of the above that need inline asm (matrix-core kernels), device only ----
+// round_clip in the integer domain: v_cvt_i32_f64 truncates toward zero and saturates, the clip is one integer med3 (one bound has
+// to sit in a VGPR: one SGPR per VOP3 on gfx9).  qmin is uniform.
+__device__ __forceinline__ int32_t round_cvt(double q) {
+    int32_t ri;
+    const double t = q + copysign(0.5, q);
+    asm("v_cvt_i32_f64 %0, %1" : "=v"(ri) : "v"(t));
+    return ri;
 }
-
-// The same two steps for callers that already hold x = round(y*scale) (integer depths) or
-// x = round(y*gain) (float): identical arithmetic from `x` on.
-__device__ __forceinline__ int32_t finish_int(const Epilogue& ep, double x, uint32_t rnd) {
-    double d = 0.0;
-    if (ep.dither == 'T') d = fma((double)((rnd & 0xFFFFu) + (rnd >> 16) + 1u), 0x1p-16, -1.0);   // exact either way
-    else if (ep.dither == 'R') d = fma((double)(2u * (rnd >> 16) + 1u), 0x1p-17, -0.5);
-    const double q = x + d;
-    const double lim = (double)(1u << (ep.bits - 1));
-    const double r = fmax(fmin(trunc(q + copysign(0.5, q)), lim - 1.0), -lim);
-    const int32_t iv = (int32_t)r;
-    return ep.bits == 20 ? iv * 16 : iv;
+__device__ __forceinline__ int32_t round_clip_cvt(double q, int32_t qmin, int32_t qmax_v) {
+    int32_t o;
+    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(o) : "v"(round_cvt(q)), "s"(qmin), "v"(qmax_v));
+    return o;
 }
-
-__device__ __forceinline__ float finish_f32(const Epilogue& ep, double x, uint32_t rnd) {
-    if (ep.dither == 'F') {
-        const uint32_t fb = __float_as_uint((float)x);
-        const int e = (int)((fb >> 23) & 0xFF);
-        const int expon = e ? e - 126 : 0;
-        const double t = ((double)rnd - 2147483647.0) * 5.5e-36;
-        x = x + ldexp(t, expon + 62);
-    }
-    return (float)x;
+// pk = max(pk, |x|): plain v_max_f64 with the |.| source modifier (fmax() would canonicalise both operands first)
+__device__ __forceinline__ void peak_max_abs(double& pk, double x) {
+    asm("v_max_f64 %0, %1, |%2|" : "=v"(pk) : "v"(pk), "v"(x));
+}
+// 24-bit stereo frames k, k+1 (samples La Ra Lb Rb in the low three bytes) -> 12 bytes: [L0 L1 L2 R0 | R1 R2 L0' L1' | L2' R0' R1' R2']
+struct S24Pair { uint32_t w0, w1, w2; };
+__device__ __forceinline__ S24Pair pack_s24_stereo(uint32_t La, uint32_t Ra, uint32_t Lb, uint32_t Rb) {
+    return {__builtin_amdgcn_perm(Ra, La, 0x04020100u), __builtin_amdgcn_perm(Lb, Ra, 0x05040201u), __builtin_amdgcn_perm(Rb, Lb, 0x06050402u)};
 }
 
 // One sample straight to memory (used by the LUT and resampler kernels); returns |y*gain|.

@@ -346,9 +346,7 @@ __global__ __launch_bounds__(256) void d2d_noise_shape_stereo_kernel(NoiseShapeA
             vmax = max(vmax, (uint32_t)(v[u] < 0 ? -v[u] : v[u]));
             uint32_t z = zg + u;
             if (!plain) { const uint32_t l = lo + u; z = l + job.rng_key + (l < job.rng_lo0 ? job.rng_kstep : 0u); }
-            z ^= z >> 16; z *= 0x7feb352dU;
-            z ^= z >> 15; z *= 0x846ca68bU;
-            z ^= z >> 16;
+            z = lowbias32(z);
             int32_t iv;
             if constexpr (INTQ) {
                 // w = x - (2 e1 - e2), q = w + d, r = round half away (q), e = r - w: W, E in units of 2^-F LSB, T in 2^-16

@@ -377,7 +377,6 @@ __global__ __launch_bounds__(MFMA_MAX_THREADS, 3) void d2d_fir_mfma_kernel(MfmaA
                         }
                         const uint32_t nl0 = wt * 256u + (8 * r + 4 * h);
                         if constexpr (SCRATCH) {
-                            typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
                             if (FULL || nl0 + 3 < j0.nout) {
                                 *reinterpret_cast<D2D_GLOBAL i32x4*>(as_global(jobs[c].xs + nl0)) = i32x4{v[0], v[1], v[2], v[3]};
                             } else {
@@ -418,7 +417,6 @@ __global__ __launch_bounds__(MFMA_MAX_THREADS, 3) void d2d_fir_mfma_kernel(MfmaA
                     // stage A of the 48k cascade (or the input of the noise-shaping pass): the exact integers
                     // y * 2^S; a lane's four frames are consecutive, one 16-byte store
                     const uint32_t nl0 = wt * 256u + (8 * r + 4 * h);
-                    typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
                     if (FULL || nl0 + 3 < j0.nout) {
                         *reinterpret_cast<D2D_GLOBAL i32x4*>(as_global(jobs[c].xs + nl0)) = i32x4{(int32_t)xv[0], (int32_t)xv[1], (int32_t)xv[2], (int32_t)xv[3]};
                     } else {
@@ -434,20 +432,13 @@ __global__ __launch_bounds__(MFMA_MAX_THREADS, 3) void d2d_fir_mfma_kernel(MfmaA
                 if constexpr (KIND != 0) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const uint32_t nlo = (uint32_t)j0.n0 + wt * 256u + (8 * r + 4 * h + k);
-                        uint32_t z = nlo + rkey + (nlo < rlo0 ? rstep : 0u);
-                        z ^= z >> 16; z *= 0x7feb352dU;
-                        z ^= z >> 15; z *= 0x846ca68bU;
-                        z ^= z >> 16;
-                        zv[k] = z;
+                        zv[k] = dither_word((uint32_t)j0.n0 + wt * 256u + (8 * r + 4 * h + k), rkey, rstep, rlo0);
                     }
                 }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const bool ok = FULL || (wt * 256u + (8 * r + 4 * h + k) < j0.nout);
-                    // plain v_max_f64 with the |.| source modifier (fmax() would canonicalise both operands first)
-                    const double cand = ok ? xv[k] : 0.0;
-                    asm("v_max_f64 %0, %1, |%2|" : "=v"(pkx) : "v"(pkx), "v"(cand));
+                    peak_max_abs(pkx, ok ? xv[k] : 0.0);
                 }
                 pkw[c * 64 + lane] = pkx;
                 if (a.epi.bits == 32) {
@@ -459,17 +450,10 @@ __global__ __launch_bounds__(MFMA_MAX_THREADS, 3) void d2d_fir_mfma_kernel(MfmaA
                     int32_t iv[4];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        // dither term: T = lo16 + hi16 + 1 (x 2^-16, -1), R = 2*hi16 + 1 (x 2^-17, -1/2), none = 0
-                        double q = xv[k] + 0.0;                             // "none": what quantise_int() does (a -0 becomes +0)
-                        if constexpr (KIND == 1 || KIND == 2) {
-                            const uint32_t term = KIND == 1 ? (zv[k] & 0xFFFFu) + (zv[k] >> 16) + 1u : 2u * (zv[k] >> 16) + 1u;
-                            q = xv[k] + fma((double)term, m.dmul, m.dadd);
-                        }
-                        // round half away from zero; v_cvt_i32_f64 saturates, the clip is an integer med3
-                        int32_t ri;
-                        const double t = q + copysign(0.5, q);
-                        asm("v_cvt_i32_f64 %0, %1" : "=v"(ri) : "v"(t));
-                        iv[k] = min(max(ri, m.qmin_i), m.qmax_i) << m.qsh;
+                        // (dmul, dadd: the constants of dither_f64<KIND>, from the kernel's arguments)
+                        double q = xv[k] + 0.0;                             // "none": what finish_int() does (a -0 becomes +0)
+                        if constexpr (KIND == 1 || KIND == 2) q = xv[k] + fma((double)dither_term<KIND>(zv[k]), m.dmul, m.dadd);
+                        iv[k] = min(max(round_cvt(q), m.qmin_i), m.qmax_i) << m.qsh;
                     }
                     if (sb == 2) {
 #pragma unroll
@@ -522,42 +506,28 @@ __global__ __launch_bounds__(MFMA_MAX_THREADS, 3) void d2d_fir_mfma_kernel(MfmaA
                         // (narrow recombination: the wide case does not take this path)
                         const double accd = fma((double)(acc[4 * k + 2] + (acc[4 * k + 3] << 8)), 65536.0, (double)(acc[4 * k] + (acc[4 * k + 1] << 8)));
                         const double x = fma(accd, m.c1, -m.c0);
-                        asm("v_max_f64 %0, %1, |%2|" : "=v"(pk) : "v"(pk), "v"(x));
-                        double q = x;
+                        peak_max_abs(pk, x);
+                        double q;
                         if constexpr (KIND != 0) {
-                            const uint32_t nlo = (uint32_t)j0.n0 + wt * 256u + (8 * r + 4 * h + k);
-                            uint32_t z = nlo + key + (nlo < lo0 ? stp : 0u);
-                            z ^= z >> 16; z *= 0x7feb352dU;
-                            z ^= z >> 15; z *= 0x846ca68bU;
-                            z ^= z >> 16;
-                            const uint32_t term = KIND == 1 ? (z & 0xFFFFu) + (z >> 16) + 1u : 2u * (z >> 16) + 1u;
-                            q = x + fma((double)term, m.dmul, m.dadd);
+                            const uint32_t z = dither_word((uint32_t)j0.n0 + wt * 256u + (8 * r + 4 * h + k), key, stp, lo0);
+                            q = x + fma((double)dither_term<KIND>(z), m.dmul, m.dadd);
                         } else {
-                            q = x + 0.0;                                    // what quantise_int() does for "none" (a -0 becomes +0)
+                            q = x + 0.0;                                    // what finish_int() does for "none" (a -0 becomes +0)
                         }
-                        // round half away from zero: the conversion itself truncates toward zero (and saturates),
-                        // the clip is one integer med3 (one bound has to sit in a VGPR: one SGPR per VOP3 on gfx9)
-                        int32_t ri, o;
-                        const double t = q + copysign(0.5, q);
-                        asm("v_cvt_i32_f64 %0, %1" : "=v"(ri) : "v"(t));
-                        asm("v_med3_i32 %0, %1, %2, %3" : "=v"(o) : "v"(ri), "s"(m.qmin_i), "v"(qmax_v));
-                        return (uint32_t)o;                                   // (qsh == 0 on this path)
+                        return (uint32_t)round_clip_cvt(q, m.qmin_i, qmax_v);   // (qsh == 0 on this path)
                     };
-                    // frames k, k+1 -> 12 bytes: [L0 L1 L2 R0 | R1 R2 L0' L1' | L2' R0' R1' R2']
                     uint32_t w0, w1, w2, w3, w4, w5;
                     {
                         const uint32_t La = one(acc0, 0, key0, st0, lo00, pk0), Ra = one(acc1, 0, key1, st1, lo01, pk1);
                         const uint32_t Lb = one(acc0, 1, key0, st0, lo00, pk0), Rb = one(acc1, 1, key1, st1, lo01, pk1);
-                        w0 = __builtin_amdgcn_perm(Ra, La, 0x04020100u);
-                        w1 = __builtin_amdgcn_perm(Lb, Ra, 0x05040201u);
-                        w2 = __builtin_amdgcn_perm(Rb, Lb, 0x06050402u);
+                        const S24Pair p = pack_s24_stereo(La, Ra, Lb, Rb);
+                        w0 = p.w0; w1 = p.w1; w2 = p.w2;
                     }
                     {
                         const uint32_t La = one(acc0, 2, key0, st0, lo00, pk0), Ra = one(acc1, 2, key1, st1, lo01, pk1);
                         const uint32_t Lb = one(acc0, 3, key0, st0, lo00, pk0), Rb = one(acc1, 3, key1, st1, lo01, pk1);
-                        w3 = __builtin_amdgcn_perm(Ra, La, 0x04020100u);
-                        w4 = __builtin_amdgcn_perm(Lb, Ra, 0x05040201u);
-                        w5 = __builtin_amdgcn_perm(Rb, Lb, 0x06050402u);
+                        const S24Pair p = pack_s24_stereo(La, Ra, Lb, Rb);
+                        w3 = p.w0; w4 = p.w1; w5 = p.w2;
                     }
                     pkw[c0 * 64 + lane] = pk0; pkw[c1 * 64 + lane] = pk1;
                     const u32x4 o4 = {w0, w1, w2, w3};

@@ -291,31 +291,20 @@ __global__ __launch_bounds__(D2D_M2_THREADS) void d2d_fir_mfma2_kernel(Mfma2Args
                 }
                 return fma(accd, m.c1, -m.c0);                            // x = y*c0 with ONE rounding
             };
-            auto noise = [&](uint32_t nl) -> uint32_t {
+            auto noise = [&](uint32_t nl) -> uint32_t {      // (dither_word, written out: the compiler adds the uniform terms first this way)
                 const uint32_t nlo = (uint32_t)j0.n0 + nl;
-                uint32_t z = nlo + rkey[c] + (nlo < rlo0[c] ? rstep[c] : 0u);
-                z ^= z >> 16; z *= 0x7feb352dU;
-                z ^= z >> 15; z *= 0x846ca68bU;
-                z ^= z >> 16;
-                return z;
+                return lowbias32(nlo + rkey[c] + (nlo < rlo0[c] ? rstep[c] : 0u));
             };
             // one integer-depth sample: dither, round half away from zero, clip
             auto quant = [&](double x, uint32_t nl, auto kind_tag) -> int32_t {
                 constexpr int KIND = decltype(kind_tag)::value;
                 double q;
                 if constexpr (KIND == 1 || KIND == 2) {
-                    const uint32_t z = noise(nl);
-                    const uint32_t term = KIND == 1 ? (z & 0xFFFFu) + (z >> 16) + 1u : 2u * (z >> 16) + 1u;
-                    q = x + fma((double)term, m.dmul, m.dadd);
+                    q = x + fma((double)dither_term<KIND>(noise(nl)), m.dmul, m.dadd);      // (dmul, dadd: the constants of dither_f64<KIND>)
                 } else {
                     q = x + 0.0;                                          // what quantise_int() does for "none" (a -0 becomes +0)
                 }
-                int32_t ri, o;
-                const double t = q + copysign(0.5, q);
-                asm("v_cvt_i32_f64 %0, %1" : "=v"(ri) : "v"(t));         // truncates toward zero, saturates
-                const int32_t qmax_v = m.qmax_i;
-                asm("v_med3_i32 %0, %1, %2, %3" : "=v"(o) : "v"(ri), "s"(m.qmin_i), "v"(qmax_v));
-                return o;
+                return round_clip_cvt(q, m.qmin_i, m.qmax_i);
             };
             // all-integer variant for unit gain (level 0 dB): x = v * 2^-F LSB with v = sum q s an integer, the
             // dither term an integer number of 2^-16 LSB -- the same real numbers, no f64 instruction.
@@ -381,12 +370,8 @@ __global__ __launch_bounds__(D2D_M2_THREADS) void d2d_fir_mfma2_kernel(Mfma2Args
 #pragma unroll
                                 for (int k = 0; k < 4; ++k) {
                                     const v16i& A = acc[g];
-                                    // v0 = 2*sum q b = (A0 >> 6) + 4*A1 + 2^10*A2 + 2^18*A3  (A0 is a multiple of 128)
-                                    // (negative taps can take it below zero: signed, |v0 - 2^S| <= sum|q| keeps it inside int32)
-                                    uint32_t u0 = (uint32_t)(A[4 * k] >> 6);
-                                    u0 = ((uint32_t)A[4 * k + 1] << 2) + u0;
-                                    u0 = ((uint32_t)A[4 * k + 2] << 10) + u0;
-                                    u0 = ((uint32_t)A[4 * k + 3] << 18) + u0;
+                                    // v0 = 2*sum q b (negative taps can take it below zero: signed, |v0 - 2^S| <= sum|q| keeps it inside int32)
+                                    const uint32_t u0 = recombine_limbs(A[4 * k], A[4 * k + 1], A[4 * k + 2], A[4 * k + 3]);
                                     const int32_t v0 = (int32_t)u0;
                                     vmn[c] = min(vmn[c], v0); vmx[c] = max(vmx[c], v0);
                                     const uint32_t vhb = (uint32_t)(v0 >> kF);             // floor(x) + 2^(S-F)
@@ -399,9 +384,7 @@ __global__ __launch_bounds__(D2D_M2_THREADS) void d2d_fir_mfma2_kernel(Mfma2Args
                                     } else {
                                         uint32_t z = zb + (uint32_t)(8 * g + k);
                                         if (!(dbg & 128)) {
-                                        z ^= z >> 16; z *= kC1;
-                                        z ^= z >> 15; z *= kC2;
-                                        z ^= z >> 16;
+                                        z = lowbias32(z, kC1, kC2);
                                         }
                                         if constexpr (KIND == 1) {
                                             // units of 2^-16 LSB: x + (lo16 + hi16 + 1)*2^-16 - 1 + 1/2
@@ -438,7 +421,7 @@ __global__ __launch_bounds__(D2D_M2_THREADS) void d2d_fir_mfma2_kernel(Mfma2Args
                             for (int k = 0; k < 4; ++k) {
                                 const double x = recombine(acc[g], k, std::false_type{});
                                 const double cand = full || nl_base + 8u * g + k < j0.nout ? x : 0.0;
-                                asm("v_max_f64 %0, %1, |%2|" : "=v"(pk[c]) : "v"(pk[c]), "v"(cand));
+                                peak_max_abs(pk[c], cand);
                                 cur[4 * g + k] = (uint32_t)quant(x, nl_base + 8u * g + k, kind_tag);
                             }
                     }
@@ -449,12 +432,11 @@ __global__ __launch_bounds__(D2D_M2_THREADS) void d2d_fir_mfma2_kernel(Mfma2Args
                         if (full) {
 #pragma unroll
                             for (int g = 0; g < 2; ++g) {
-                                // frames k, k+1 -> 12 bytes: [L0 L1 L2 R0 | R1 R2 L0' L1' | L2' R0' R1' R2']
                                 const uint32_t La = held[4 * g], Ra = cur[4 * g], Lb = held[4 * g + 1], Rb = cur[4 * g + 1];
                                 const uint32_t Lc = held[4 * g + 2], Rc = cur[4 * g + 2], Ld = held[4 * g + 3], Rd = cur[4 * g + 3];
-                                pend4[g] = u32x4{__builtin_amdgcn_perm(Ra, La, 0x04020100u), __builtin_amdgcn_perm(Lb, Ra, 0x05040201u),
-                                                 __builtin_amdgcn_perm(Rb, Lb, 0x06050402u), __builtin_amdgcn_perm(Rc, Lc, 0x04020100u)};
-                                pend2[g] = u32x2{__builtin_amdgcn_perm(Ld, Rc, 0x05040201u), __builtin_amdgcn_perm(Rd, Ld, 0x06050402u)};
+                                const S24Pair p = pack_s24_stereo(La, Ra, Lb, Rb), q = pack_s24_stereo(Lc, Rc, Ld, Rd);
+                                pend4[g] = u32x4{p.w0, p.w1, p.w2, q.w0};
+                                pend2[g] = u32x2{q.w1, q.w2};
                             }
                             flush_pending(wt);
                         } else {
@@ -490,17 +472,13 @@ __global__ __launch_bounds__(D2D_M2_THREADS) void d2d_fir_mfma2_kernel(Mfma2Args
                         const uint32_t fl0 = 16u * r + 8u * g + 4u * h;                  // frame inside the tile
                         const uint32_t nl0 = wt * (uint32_t)M2_TILE + fl0;
                         if constexpr (EPI == 2 && !decltype(wide_tag)::value) {
-                            // the scratch wants the exact integer y * 2^S = sum q s itself: (A0 >> 6) + 4*A1 + 2^10*A2 + 2^18*A3 - 2^S in
-                            // int32 (A0 is a multiple of 128; wraps are harmless, |sum q s| < 2^31) -- no f64 instruction
+                            // the scratch wants the exact integer y * 2^S = sum q s itself: recombine_limbs - 2^S in int32 (wraps are
+                            // harmless, |sum q s| < 2^31) -- no f64 instruction
                             int32_t iv[4];
 #pragma unroll
                             for (int k = 0; k < 4; ++k) {
                                 const v16i& A = acc[g];
-                                uint32_t u0 = (uint32_t)(A[4 * k] >> 6);
-                                u0 = ((uint32_t)A[4 * k + 1] << 2) + u0;
-                                u0 = ((uint32_t)A[4 * k + 2] << 10) + u0;
-                                u0 = ((uint32_t)A[4 * k + 3] << 18) + u0;
-                                iv[k] = (int32_t)(u0 - (1u << a.scale_bits));
+                                iv[k] = (int32_t)(recombine_limbs(A[4 * k], A[4 * k + 1], A[4 * k + 2], A[4 * k + 3]) - (1u << a.scale_bits));
                             }
                             if (FULL || nl0 + 3 < j0.nout) {
                                 *reinterpret_cast<D2D_GLOBAL i32x4*>(as_global(jobs[c].xs + nl0)) = i32x4{iv[0], iv[1], iv[2], iv[3]};
@@ -528,8 +506,7 @@ __global__ __launch_bounds__(D2D_M2_THREADS) void d2d_fir_mfma2_kernel(Mfma2Args
 #pragma unroll
                             for (int k = 0; k < 4; ++k) {
                                 const bool ok = FULL || (nl0 + k < j0.nout);
-                                const double cand = ok ? xv[k] : 0.0;
-                                asm("v_max_f64 %0, %1, |%2|" : "=v"(pk[c]) : "v"(pk[c]), "v"(cand));
+                                peak_max_abs(pk[c], ok ? xv[k] : 0.0);
                             }
                             if (a.epi.bits == 32) {
 #pragma unroll

@@ -205,12 +205,7 @@ __global__ __launch_bounds__(512) void d2d_resample_mfma_kernel(Rs2Args a) {
                 return (uint64_t)(int64_t)A0 + ((uint64_t)(int64_t)A1 << 16) + ((uint64_t)A2 << 32) + (uint64_t)bias;
             };
             auto hash = [&](int32_t o) -> uint32_t {
-                const uint32_t nlo = rlo0 + (uint32_t)o;                      // lo32 of the absolute output index
-                uint32_t z = nlo + rkey + (nlo < rlo0 ? rstep : 0u);
-                z ^= z >> 16; z *= 0x7feb352dU;
-                z ^= z >> 15; z *= 0x846ca68bU;
-                z ^= z >> 16;
-                return z;
+                return dither_word(rlo0 + (uint32_t)o, rkey, rstep, rlo0);    // (lo32 of the absolute output index)
             };
             // every other format, and the samples the guard band sends here: the f64 definition
             auto careful_bits = [&](int64_t v, uint32_t z) -> uint32_t {
@@ -234,10 +229,7 @@ __global__ __launch_bounds__(512) void d2d_resample_mfma_kernel(Rs2Args a) {
                     const bool live = INNER || (uint32_t)o < nres;
                     uint32_t z;
                     if constexpr (INNER) {
-                        z = (uint32_t)o + key_t;
-                        z ^= z >> 16; z *= 0x7feb352dU;
-                        z ^= z >> 15; z *= 0x846ca68bU;
-                        z ^= z >> 16;
+                        z = lowbias32((uint32_t)o + key_t);
                     } else z = hash(o);
                     int64_t t = 0;
                     if constexpr (dkind == 1) t = (int64_t)(int32_t)((z & 0xFFFFu) + (z >> 16)) - 65535;

@@ -289,64 +289,51 @@ __global__ __launch_bounds__(D2D_M3_THREADS) void d2d_fir_mfma3_kernel(Mfma2Args
     double kCg = ldexp(a.epi.bits == 32 ? a.epi.gain : a.epi.scale, -a.scale_bits);
     double kLim = a.epi.bits == 32 ? 1.0 : (double)(1u << (a.epi.bits - 1));
     if constexpr (GN) asm volatile("" : "+v"(kCg), "+v"(kLim));
-    // the f64 requantiser from the hash word's dither term t (triangular: lo16 + hi16 + 1, rectangular: 2 hi16 + 1), as d2d_device.h: finish_int
+    // the f64 requantiser from the hash word's dither term t (d2d_sample.h: dither_term), as d2d_device.h: finish_int / finish_f32
     auto quant_gain = [&](int32_t v, uint32_t t) -> int32_t {
         const double x = (double)v * kCg;
         if constexpr (SBY == 4) {
-            if constexpr (DK == 3) {
-                // Airwindows "Dither Float" as d2d_device.h: quantise_f32 states it (t = the raw hash word)
-                const uint32_t fb = __float_as_uint((float)x);
-                const int e = (int)((fb >> 23) & 0xFFu);
-                const int expon = e ? e - 126 : 0;
-                const double tt = ((double)t - 2147483647.0) * 5.5e-36;
-                return __float_as_int((float)(x + ldexp(tt, expon + 62)));
-            }
+            if constexpr (DK == 3) return __float_as_int((float)dither_float(x, t));       // (t = the raw hash word)
             return __float_as_int((float)x);
         }
         double q = x;
-        if constexpr (DK == 1) q = x + fma((double)t, 0x1p-16, -1.0);
-        else if constexpr (DK == 2) q = x + fma((double)t, 0x1p-17, -0.5);
-        const double rq = fmax(fmin(trunc(q + copysign(0.5, q)), kLim - 1.0), -kLim);
-        return (int32_t)rq << m.qsh;                                   // (20-bit samples ride in 24 bits as r << 4)
+        if constexpr (DK == 1 || DK == 2) q = x + dither_f64<DK>(t);
+        return round_clip(q, kLim) << m.qsh;                           // (20-bit samples ride in 24 bits as r << 4)
     };
 
     // v = sum q s of sample k of a group's accumulators: (A0 >> 6) + 4*A1 + 2^10*A2 + 2^18*A3 (A0 is a multiple of 128; mod 2^32)
     auto recombine = [&](const v16i& A, int k) -> int32_t {
         return m3_lshl_add(A[4 * k + 3], k18, m3_lshl_add(A[4 * k + 2], k10, m3_lshl_add(A[4 * k + 1], k2, A[4 * k] >> 6)));
     };
-    auto noise = [&](uint32_t c, uint32_t nl) -> uint32_t {
-        const uint32_t nlo = (uint32_t)j0.n0 + nl;
-        uint32_t z = nlo + rkey[c] + (nlo < rlo0[c] ? rstep[c] : 0u);
-        z ^= z >> 16; z *= 0x7feb352dU;
-        z ^= z >> 15; z *= 0x846ca68bU;
-        z ^= z >> 16;
-        return z;
-    };
-    // the general per-sample requantiser (any tile): x = v * 2^-F LSB, dither in 2^-16 (2^-17) LSB, round half away, clip
+    auto noise = [&](uint32_t c, uint32_t nl) -> uint32_t { const uint32_t nlo = (uint32_t)j0.n0 + nl; return lowbias32(nlo + rkey[c] + (nlo < rlo0[c] ? rstep[c] : 0u)); };
+    // the general per-sample requantiser (any tile): the f64 one at any level, else the all-integer one (d2d_sample.h: requant_int states it;
+    // written out here: the shared form changed the hazard padding of single instantiations, profiles/sample_refactor_check.md)
     auto quant_slow = [&](int32_t v, uint32_t c, uint32_t nl) -> int32_t {
-        const int F = m.fbits;
-        const int32_t vh = v >> F;
-        const uint32_t vl = (uint32_t)v & ((1u << F) - 1u);
-        int32_t rr;
         if constexpr (GN) {
             uint32_t t = 0;
-            if constexpr (DK != 0) { const uint32_t z = noise(c, nl); t = DK == 1 ? (z & 0xFFFFu) + (z >> 16) + 1u : DK == 2 ? 2u * (z >> 16) + 1u : z; }
+            if constexpr (DK != 0) { const uint32_t z = noise(c, nl); t = DK == 3 ? z : dither_term<DK>(z); }
             return quant_gain(v, t);
-        } else if constexpr (DK == 2) {
-            const uint32_t z = noise(c, nl);
-            const int32_t w = (int32_t)(vl << (17 - F)) + (int32_t)(2u * (z >> 16) + 1u) - 65536;
-            const int32_t neg = (vh + (w >> 17)) >> 31;
-            rr = vh + ((w + 65536 + neg) >> 17);
         } else {
-            int32_t w = (int32_t)(vl << (16 - F));
-            if constexpr (DK == 1) {
+            const int F = m.fbits;
+            const int32_t vh = v >> F;
+            const uint32_t vl = (uint32_t)v & ((1u << F) - 1u);
+            int32_t rr;
+            if constexpr (DK == 2) {
                 const uint32_t z = noise(c, nl);
-                w += (int32_t)((z & 0xFFFFu) + (z >> 16)) - 65535;
+                const int32_t w = (int32_t)(vl << (17 - F)) + (int32_t)(2u * (z >> 16) + 1u) - 65536;
+                const int32_t neg = (vh + (w >> 17)) >> 31;
+                rr = vh + ((w + 65536 + neg) >> 17);
+            } else {
+                int32_t w = (int32_t)(vl << (16 - F));
+                if constexpr (DK == 1) {
+                    const uint32_t z = noise(c, nl);
+                    w += (int32_t)((z & 0xFFFFu) + (z >> 16)) - 65535;
+                }
+                const int32_t neg = (vh + (w >> 16)) >> 31;
+                rr = vh + ((w + 32768 + neg) >> 16);
             }
-            const int32_t neg = (vh + (w >> 16)) >> 31;
-            rr = vh + ((w + 32768 + neg) >> 16);
+            return min(max(rr, m.qmin_i), m.qmax_i);
         }
-        return min(max(rr, m.qmin_i), m.qmax_i);
     };
 
     // ---- the fast epilogue of one (tile, channel), cut into jobs that ride on the steps of a chain ----

@@ -14,7 +14,6 @@ namespace d2d {
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
 
 template <int I, int N, class F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -50,10 +49,12 @@ struct Mfma2Args {
 
 constexpr int M2_TILE = 512;          // outputs per wave-tile and channel
 
+// staged dword L lives at L + (L >> m2_lsh(MB)): one pad dword per row stride of 4 MB dwords
+__host__ __device__ constexpr int m2_lsh(int MB) { return MB == 1 ? 2 : MB == 2 ? 3 : MB == 4 ? 4 : MB == 8 ? 5 : 6; }
 template <int MB>
 struct M2Geom {
     static constexpr int RS = 4 * MB;                               // row stride in dwords (16 outputs)
-    static constexpr int LSH = MB == 1 ? 2 : MB == 2 ? 3 : MB == 4 ? 4 : MB == 8 ? 5 : 6;
+    static constexpr int LSH = m2_lsh(MB);
 };
 
 // plane 0 unmasked: a byte then weighs up to 128*128 + 254*128 in a limb sum; the int32 recombination needs the sums below 2^23
@@ -63,8 +64,7 @@ __host__ __device__ constexpr int m2_chunks(int MB, int NPG) { return (m2_span_d
 __host__ __device__ constexpr int m2_pf(int MB, int NPG) { return (m2_chunks(MB, NPG) + 63) / 64; }
 __host__ __device__ constexpr int m2_stream_bytes(int MB, int NPG) {
     const int dw = 4 * 64 * m2_pf(MB, NPG);
-    const int lsh = MB == 1 ? 2 : MB == 2 ? 3 : MB == 4 ? 4 : MB == 8 ? 5 : 6;
-    return (((dw + (dw >> lsh) + 4) * 4 + 15) & ~15) + 16;   // + a dummy slot for the dwords in front of the window
+    return (((dw + (dw >> m2_lsh(MB)) + 4) * 4 + 15) & ~15) + 16;   // + a dummy slot for the dwords in front of the window
 }
 
 __device__ __forceinline__ void wave_sync2() {

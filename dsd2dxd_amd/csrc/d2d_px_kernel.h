@@ -250,30 +250,13 @@ __global__ __launch_bounds__(PX_THREADS) void d2d_fir_px_kernel(PxArgs a) {
                     uint32_t z = 0;
                     if constexpr (KIND != 0) {
                         const uint32_t nlo = (uint32_t)m0 + (uint32_t)nl;                  // lo32 of the absolute output index
-                        z = nlo + rkey + (nlo < rlo0 ? rstep : 0u);
-                        z ^= z >> 16; z *= 0x7feb352dU;
-                        z ^= z >> 15; z *= 0x846ca68bU;
-                        z ^= z >> 16;
+                        z = lowbias32(nlo + rkey + (nlo < rlo0 ? rstep : 0u));
                     }
                     if constexpr (KIND == 3) {
                         const double x = (double)v * kCg;
                         rv = a.epi.bits == 32 ? __float_as_int(finish_f32(a.epi, x, z)) : finish_int(a.epi, x, z);
                     } else {
-                        // x = v * 2^-F LSB, dither in 2^-16 (2^-17) LSB, round half away from zero, clip: all integers
-                        const int32_t vh = v >> F;
-                        const uint32_t vl = (uint32_t)v & ((1u << F) - 1u);
-                        int32_t rr;
-                        if constexpr (KIND == 2) {
-                            const int32_t w = (int32_t)(vl << (17 - F)) + (int32_t)(2u * (z >> 16) + 1u) - 65536;
-                            const int32_t neg = (vh + (w >> 17)) >> 31;
-                            rr = vh + ((w + 65536 + neg) >> 17);
-                        } else {
-                            int32_t w = (int32_t)(vl << (16 - F));
-                            if constexpr (KIND == 1) w += (int32_t)((z & 0xFFFFu) + (z >> 16)) - 65535;
-                            const int32_t neg = (vh + (w >> 16)) >> 31;
-                            rr = vh + ((w + 32768 + neg) >> 16);
-                        }
-                        rv = min(max(rr, a.qmin_i), a.qmax_i);
+                        rv = requant_int<KIND>(v, F, z, a.qmin_i, a.qmax_i);
                     }
                 }
                 if (i < 2 || kh == 0) ob[c * TILE + o] = rv;

@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """One line per kernel of some `hipcc --cuda-device-only -S` listings: tools/isa_digest.py a.s b.s ... > digest.txt
 
-The line is the kernel's symbol, the sha256 of its instructions and its metadata (registers, spills, scratch, LDS, kernarg bytes).  Two
-trees whose digests `diff` empty ship the same device code: what a refactor of host code, file layout or the build has to show.  Comments
-are dropped and the numbers of local labels (.LBB<n>_: the kernel's position in its file) normalised, as in tools/isa_blocks.py."""
+The line is the kernel's symbol, the sha256 of its instructions, `mn=` the sha256 of its sorted instruction mnemonics and its metadata
+(registers, spills, scratch, LDS, kernarg bytes).  Two trees whose digests `diff` empty ship the same device code: what a refactor of
+host code, file layout or the build has to show.  A refactor of device code that only makes the compiler order or number things
+differently changes the first hash and leaves the second and the metadata alone: the same instructions in another order or in other
+registers (compare with `cut -d" " -f1,3-`).  Comments are dropped and the numbers of local labels (.LBB<n>_: the kernel's position in
+its file) normalised, as in tools/isa_blocks.py."""
 import hashlib, re, sys
 
 META = (".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size",
@@ -24,12 +27,14 @@ def kernels(path):
     out = {}
     for name in meta:
         start = next(i for i, l in enumerate(lines) if l.startswith(name + ":"))
-        h = hashlib.sha256()
+        h, mn = hashlib.sha256(), []
         for l in lines[start + 1:]:
             if l.startswith(".Lfunc_end") or ".amdhsa_kernel" in l: break
             t = re.sub(r"\.L([A-Za-z_]+)\d+_", r".L\1_", l.split(";")[0]).strip()
-            if t and not t.startswith(".section") and not t.startswith(".p2align"): h.update((" ".join(t.split()) + "\n").encode())
-        out[name] = h.hexdigest() + " " + " ".join("%s=%s" % (k[1:], meta[name].get(k, "-")) for k in META)
+            if t and not t.startswith(".section") and not t.startswith(".p2align"):
+                h.update((" ".join(t.split()) + "\n").encode())
+                if not t.startswith(".") and not t.endswith(":"): mn.append(t.split()[0])
+        out[name] = h.hexdigest() + " mn=" + hashlib.sha256("\n".join(sorted(mn)).encode()).hexdigest() + " " + " ".join("%s=%s" % (k[1:], meta[name].get(k, "-")) for k in META)
     return out
 
 
