@@ -193,6 +193,22 @@ size_t orc_max_frames(const orc_ctx* c, size_t bytes_per_channel) {
     return (size_t)(res_outputs_after(c, nx) - c->nres);
 }
 
+/* [own] A fresh context's state (idle bit history, zero stage-A history, zero shaper errors, zero peaks) standing at `pos` bytes per channel:
+ * the counterpart of the engine's d2d_seek.  Only the counters move; the filters' history is NOT that of the stream before `pos`, so a
+ * caller feeds a halo through orc_translate and discards the frames it yields.  Every index below is 64 bits wide on an LP64 host (size_t,
+ * uint64_t; the byte offsets inside a call are differences of such indices), so positions past 2^32 frames or bytes need nothing else. */
+int orc_seek(orc_ctx* c, uint64_t pos_bytes_per_channel) {
+    if (!c) return -1;
+    memset(c->hist_raw, c->p.endianness ? IDLE_BYTE : bitrev8(IDLE_BYTE), c->keep * c->C);
+    if (c->xhist) memset(c->xhist, 0, sizeof(double) * (size_t)c->r->P * c->C);
+    memset(c->ns_err, 0, sizeof(double) * 2 * (size_t)c->C);
+    memset(c->peak, 0, sizeof(double) * (size_t)c->C);
+    c->pos = pos_bytes_per_channel;
+    c->nfir = fir_outputs_after(c, c->pos);
+    c->nres = res_outputs_after(c, c->nfir);
+    return 0;
+}
+
 /* Channel c's byte j of a call holding L bytes per channel.  Planar = [ch0 blk][ch1 blk]...,
  * interleaved = c0 c1 c0 c1 (block size 1): README.md:9; src/main.rs:54-56,75-78.  [own] a final
  * short block keeps the same shape with the shorter length. */

@@ -67,6 +67,11 @@ int orc_translate_f64(orc_ctx* c, const uint8_t* dsd, size_t bytes_per_channel,
 int orc_translate_stream(orc_ctx* c, const uint8_t* dsd, size_t bytes_per_channel,
                          void* pcm_out, size_t pcm_capacity_bytes, size_t* frames_out);
 
+/* Back to a fresh context's state (idle history, zero stage-A history, zero shaper errors, zero peaks) standing at `pos_bytes_per_channel`:
+ * pos = that, FIR outputs = pos / Mb, frames = what an uninterrupted conversion has produced by then.  No halo is applied: feed one
+ * through orc_translate and discard its frames (the engine's d2d_seek + d2d_prime). */
+int orc_seek(orc_ctx* c, uint64_t pos_bytes_per_channel);
+
 double orc_peak(const orc_ctx* c, uint32_t channel);      /* max |sample*gain| so far */
 float  orc_peak_dbfs(const orc_ctx* c);                    /* 20*log10(max over channels) */
 

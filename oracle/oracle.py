@@ -82,6 +82,7 @@ def _load(path):
     L.orc_use_fine_taps.argtypes = [C.c_void_p]
     L.orc_use_f64_resamp_coef.argtypes = [C.c_void_p]
     L.orc_use_cascade.argtypes = [C.c_void_p]
+    L.orc_seek.argtypes = [C.c_void_p, C.c_uint64]
     L.orc_rng.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64]
     L.orc_rng.restype = C.c_uint32
     _lib = L
@@ -184,6 +185,15 @@ class Oracle:
         if rc:
             raise OracleError(f"translate failed: {rc}")
         return out, frames.value
+
+    def seek(self, pos):
+        """a fresh context's state standing at `pos` bytes per channel (orc_seek); the halo is the caller's to feed and discard"""
+        if lib().orc_seek(self._h, pos):
+            raise OracleError("seek failed")
+
+    def max_frames(self, bytes_per_channel):
+        """frames a call feeding that many more bytes per channel yields (orc_max_frames); on a fresh context: F(position)"""
+        return lib().orc_max_frames(self._h, bytes_per_channel)
 
     def peak(self, ch):
         return lib().orc_peak(self._h, ch)
