@@ -19,6 +19,9 @@
 //   * One matrix column serves 6 G consecutive outputs (G groups of six phases); group g reads the tap fragments of group 0
 //     6 M / 64 steps later, a step being 64 stream bits (lane half h takes dword 2u + h).  M = 32, E filter: 12 fragments, 15 steps and
 //     24 MFMAs per 384 outputs = 32 per 512 (the int8 form: 52), 100 operand-expansion instructions per 512 outputs (136).
+//   * The stereo frame flavours at M = 32 hold their (at most twelve) fragments in registers for the life of a wave instead of reading
+//     them from LDS in every chain; the registers are those of the draining accumulator set, emptied in one burst at the start of a
+//     region (d2d_mx.h: mx_resident; d2d_mx_kernel.h: RES, burst).
 //
 // Frames leave through a per-wave LDS slice (a lane owns runs of three samples, not of four): samples in as dwords, out as groups of
 // four frames, packed and stored as in the int8 kernel.

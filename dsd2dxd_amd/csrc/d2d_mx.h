@@ -57,6 +57,17 @@ __host__ __device__ constexpr int mx_slot(int MB, int NT, int G, int u, int g, i
 // M = 128: one group (the fragments of a second one would be held for twelve steps: 84 registers)
 __host__ __device__ constexpr int mx_g(int MB) { return MB == 4 ? D2D_MX_G4 : MB == 16 ? 1 : D2D_MX_G8; }
 
+// Resident tap fragments (M = 32: at most twelve fragments of six registers): a wave loads its variant of the table into registers at kernel entry
+// and the chain reads no fragment from LDS.  D2D_MX_NRES < NF keeps only the first NRES there (the others come from LDS as everywhere else).
+#ifndef D2D_MX_RESIDENT
+#define D2D_MX_RESIDENT 1   // 0: no resident fragments anywhere (A/B builds)
+#endif
+#ifndef D2D_MX_NRES
+#define D2D_MX_NRES 64
+#endif
+__host__ __device__ constexpr bool mx_resident(int MB, int NT, int PH = 6) { return D2D_MX_RESIDENT && MB == 4 && mx_nf(MB, NT, PH) <= 12; }
+__host__ __device__ constexpr int mx_nres(int MB, int NT, int PH = 6) { return !mx_resident(MB, NT, PH) ? 0 : D2D_MX_NRES < mx_nf(MB, NT, PH) ? D2D_MX_NRES : mx_nf(MB, NT, PH); }
+
 // ---- the compiled kernels: ONE row per object --------------------------------------------------------------------------------
 // X(unit, MB, NT, flavour, NPR).  Unit n is d2d_mx_unit.hip compiled with -DD2D_MX_UNIT=n (unit 0 rides in d2d_kernels_mx.hip, next to the
 // dispatcher) and holds every sample format of its row: launch_mx_formats in d2d_mx_kernel.h.  The dispatcher's table, launch_fir_mx and

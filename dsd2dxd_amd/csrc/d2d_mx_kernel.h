@@ -25,6 +25,7 @@ __device__ unsigned long long d2d_mx_stamps[8] = {~0ull, 0, 0, 0, 0, 0, 0, 0};
 #endif
 
 typedef int v8i __attribute__((ext_vector_type(8)));
+typedef int v6i __attribute__((ext_vector_type(6)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 typedef int32_t i32x3 __attribute__((ext_vector_type(3)));
 
@@ -55,6 +56,10 @@ __host__ __device__ constexpr uint32_t mx_pack_sel(int SBY, int o) {
     for (int j = 0; j < 4; ++j) { const int t = o + j; sel |= (uint32_t)(t < SBY ? t : 4 + (t - SBY)) << (8 * j); }
     return sel;
 }
+
+// Fragments a wave of this instantiation keeps in registers (d2d_mx.h: mx_resident): the stereo frame flavours of the M = 32 rows.  The
+// scratch flavour, several pairs per wave and the 32-bit taps read them from LDS like M = 64 and M = 128.
+__host__ __device__ constexpr int mx_nres_of(int MB, int NT, int SBY, int NPR, int ND) { return SBY != 0 && NPR == 1 && ND == 5 ? mx_nres(MB, NT) : 0; }
 
 // KIND: 0 no dither, 1 triangular, 2 rectangular (unit gain, all-integer requantiser); 4, 5, 6: the same dithers at any level in dB (the
 // f64 requantiser of the definition inside the pipelined epilogue, no careful path).  Stereo; SBY = bytes per sample: 3 (24-bit packed frames), 2 (16-bit),
@@ -87,6 +92,10 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
     constexpr bool GN = KIND >= 4;                                  // any level: x = fl(v * (scale * 2^-S)), q = x + d, round half away, clip -- in f64
     static_assert(!GN || !SCR, "the scratch holds integers");
     static_assert(!WIDE || (GN && NPR == 1 && MB < 16), "32-bit taps: the f64 requantiser, stereo");
+    // RES: the first NRES tap fragments live in registers from kernel entry on (all of them unless -DD2D_MX_NRES says fewer: then the LDS table stays
+    // for the rest), and a region takes the draining accumulator set's integers in one burst before its chain starts (run_loop)
+    constexpr int NRES = mx_nres_of(MB, NT, SBY, NPR, ND);
+    constexpr bool RES = NRES > 0;
     constexpr uint32_t dbg = D2D_MX_ABL;                  // compile-time ablation mask: 1 no chain, 2 no epilogue, 4 no staging, 8 never slow, 64 no stores
     const FirArgs& a = m.f;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -104,12 +113,12 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
 
     const int64_t first0 = j0.e0 - (int64_t)a.Wb;          // first byte of output 0's window
     const uint32_t sh = (uint32_t)(first0 & 3);            // its misalignment inside the staged dword
-    {   // tap fragments: L2 -> LDS once per block; the variant for this byte misalignment
+    if constexpr (NRES < NF) {   // tap fragments: L2 -> LDS once per block; the variant for this byte misalignment
         const uint4* s = reinterpret_cast<const uint4*>(a.tables) + (size_t)sh * TBL16;
         uint4* dl = reinterpret_cast<uint4*>(smem);
         for (uint32_t i = tid; i < TBL16; i += blockDim.x) dl[i] = s[i];
+        __syncthreads();
     }
-    __syncthreads();
 
     const uint32_t nwt = (j0.nout + (TILE - 1)) / TILE;            // wave-tiles in this file
     const uint32_t wstride = coop ? gridDim.x : gridDim.x * m.nwaves;
@@ -287,6 +296,19 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
     // tap fragment f: 16 bytes per lane at f * 1536 + 16 lane, 8 more at f * 1536 + 1024 + 8 lane
     const uint8_t* tp16 = smem + 16u * lane;
     const uint8_t* tp8 = smem + 1024u + 8u * lane;
+    // RES: the same 24 bytes per lane and fragment, straight from the table into the six registers of an MFMA operand, once per wave
+    v6i RF[RES ? NRES : 1];
+    if constexpr (RES) {
+        const uint8_t* tb = reinterpret_cast<const uint8_t*>(a.tables) + (size_t)sh * (TBL16 * 16u);
+#pragma unroll
+        for (int f = 0; f < NRES; ++f) {
+            const v4i x = *reinterpret_cast<D2D_GLOBAL const v4i*>(as_global(tb + MX_FRAG_BYTES * f) + 16u * lane);
+            const u32x2 y = *reinterpret_cast<D2D_GLOBAL const u32x2*>(as_global(tb + MX_FRAG_BYTES * f + 1024) + 8u * lane);
+            RF[f] = v6i{x.x, x.y, x.z, x.w, (int)y.x, (int)y.y};
+        }
+#pragma unroll
+        for (int f = 0; f < NRES; ++f) asm volatile("" : "+v"(RF[f]));
+    }
     uint32_t kmA = 0x11111111u, kmB = 0x22222222u;
     asm volatile("" : "+v"(kmA), "+v"(kmB));
     int scA = 0x7f7f7f7f, scB = (int)0x82828282u;          // e8m0 scales: A x 1, B x 8 (every product becomes an integer)
@@ -318,18 +340,20 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
 #define D2D_MX_AHEAD 2
 #endif
         constexpr int AHEAD = D2D_MX_AHEAD;
-        static_for<0, AHEAD>([&](auto uc) { rdW(uc); rdF(uc); });
+        static_for<0, AHEAD>([&](auto uc) { rdW(uc); if constexpr (decltype(uc)::value >= NRES) rdF(uc); });
         static_for<0, TP>([&](auto uc) {
             constexpr int u = decltype(uc)::value;
             if constexpr (u + AHEAD < TP) rdW(std::integral_constant<int, u + AHEAD>{});
-            if constexpr (u + AHEAD < NF) rdF(std::integral_constant<int, u + AHEAD>{});
+            if constexpr (u + AHEAD < NF && u + AHEAD >= NRES) rdF(std::integral_constant<int, u + AHEAD>{});
             const uint32_t w = W[u], w2 = w >> 2;
             const v8i Bv = {(int)(w & kmA), (int)(w & kmB), (int)(w2 & kmA), (int)(w2 & kmB), 0, 0, 0, 0};
             static_for<0, G>([&](auto gc) {
                 constexpr int g = decltype(gc)::value;
                 constexpr int f = u - DLY * g;
                 if constexpr (f >= 0 && f < NF) {
-                    const v8i Av = {F4[f].x, F4[f].y, F4[f].z, F4[f].w, (int)F2[f].x, (int)F2[f].y, 0, 0};
+                    v8i Av;
+                    if constexpr (f < NRES) Av = v8i{RF[f][0], RF[f][1], RF[f][2], RF[f][3], RF[f][4], RF[f][5], 0, 0};
+                    else Av = v8i{F4[f].x, F4[f].y, F4[f].z, F4[f].w, (int)F2[f].x, (int)F2[f].y, 0, 0};
                     if constexpr (f == 0) acc[g] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(Av, Bv, cinit, 2, 4, 0, scA, 0, scB);
                     else acc[g] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(Av, Bv, acc[g], 2, 4, 0, scA, 0, scB);
                     // whatever else the wave does rides BEHIND an MFMA: an in-order wave that issues two MFMAs back to back sits out the
@@ -351,6 +375,7 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
     // asm, no wait states are inserted, and the chain's last MFMA, still in flight, lands its zero row on top of the value (round 4: sample 0 of
     // every lane of a mono pair's second half came out as -2^S -> the negative rail, after a change that moved the allocation).
     // (the in/out form of `pin`: with an input-only operand of sixteen registers the kernel silently fails to instantiate -- no diagnostic, no code object)
+    // (RES: no set is held -- a region's `burst` below takes all it needs from the draining set at once and guards the same hazard its own way)
     auto hold_acc = [&](v16f (&acc)[G]) {
 #pragma unroll
         for (int g = 0; g < G; ++g) asm volatile("" : "+v"(acc[g]));
@@ -528,6 +553,40 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
             if constexpr ((j * NSLOT) / NJ == k) fast_job(f, o, jc);
         });
     };
+    // RES: the draining set gives up ALL its integers in one burst at the start of a region, before the chain's first MFMA, and is dead from
+    // then on: its registers carry the rest of the region's temporaries while the fragments stay resident.  The burst opens with the in/out
+    // pin of the whole set and holds compiler-visible instructions only (the shift-add in plain C, not mx_lshl_add): the first read of a
+    // register of the previous chain's last MFMA gets the compiler's wait states, and the scheduling barrier that closes the burst keeps
+    // every inline-asm instruction of the jobs behind it.  That is what hold_acc is for in the other flavours (above: the round-4 hazard).
+    auto burst = [&](v16f (&o)[G], vint (&vv)[NS]) {
+        pin(o);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            const v16f& A = o[i / PHH];
+            const int q = i % PHH;
+            const float lo = __builtin_fmaf(A[5 * q + 2], k1024, __builtin_fmaf(A[5 * q + 1], k32, A[5 * q]));
+            const float hi = __builtin_fmaf(A[5 * q + 4], k32, A[5 * q + 3]);
+            vv[i] = (vint)(int32_t)(((uint32_t)(int32_t)hi << 15) + (uint32_t)(int32_t)lo);
+            asm volatile("" : "+v"(vv[i]));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // ... and the hash and finish jobs ride behind the chain's MFMAs as before, respaced: job j behind MFMA (j * NSLOT) / NJR
+    constexpr int NJR = (JPS - 1) * NS;
+    auto res_job = [&](Fast& f, const vint (&vv)[NS], const v16f (&o)[G], auto jc) {
+        constexpr int j = decltype(jc)::value;
+        constexpr int i = j / (JPS - 1);
+        constexpr bool fin = DK == 0 || (j % 2) == 1;
+        if constexpr (fin) f.v = vv[i];
+        fast_job(f, o, std::integral_constant<int, i * JPS + (fin ? JPS - 1 : 0)>{});
+    };
+    auto res_hook = [&](Fast& f, const vint (&vv)[NS], const v16f (&o)[G], auto kc) {
+        constexpr int k = decltype(kc)::value;
+        static_for<0, NJR>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            if constexpr ((j * NSLOT) / NJR == k) res_job(f, vv, o, jc);
+        });
+    };
     auto fast_failed = [&](const Fast& f, uint32_t tile) -> bool {
         const uint32_t first = (uint32_t)j0.n0 + tile * (uint32_t)TILE;
         const bool full = tile * (uint32_t)TILE + (uint32_t)TILE <= j0.nout;
@@ -537,8 +596,8 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
         const bool bad = (KIND == 1 && (f.tie & 0xFFFFu) == 0) || f.tmx > kSafe + kBias || f.tmn < kBias - kSafe;
         return __builtin_amdgcn_ballot_w64(bad) != 0;
     };
-    // the careful way, sample by sample, from a chain's accumulators
-    auto redo_acc = [&](v16f (&t)[G], uint32_t tile, auto cc, int32_t (&out)[NS]) {
+    // the careful way, sample by sample, from the integers vb_of(i) of a (tile, channel)
+    auto redo_from = [&](auto&& vb_of, uint32_t tile, auto cc, int32_t (&out)[NS]) {
         constexpr uint32_t c = decltype(cc)::value;
         const bool full = tile * (uint32_t)TILE + (uint32_t)TILE <= j0.nout;
         const uint32_t nl_base = tile * (uint32_t)TILE + lane_fr;
@@ -546,7 +605,7 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
 #pragma unroll
         for (int i = 0; i < NS; ++i) {
             const uint32_t nl = nl_base + (uint32_t)PH * (i / PHH) + (i % PHH);
-            const vint vb = recombine(t[i / PHH], i % PHH), v = vb - kBias;
+            const vint vb = vb_of(i), v = vb - kBias;
             if constexpr (SBY == 4 && !GN) out[i] = __float_as_int((float)v * kFs); else out[i] = quant_slow(v, cc, nl);
             const bool live = full || nl < j0.nout;
             lo = live && vb < lo ? vb : lo;
@@ -554,7 +613,15 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
         }
         if constexpr (WIDE) { const vint d = hi - kBias > kBias - lo ? hi - kBias : kBias - lo; vdev[c] = d > vdev[c] ? d : vdev[c]; }
         else vdev[c] = mx_max3(vdev[c], hi - kBias, kBias - lo);
+    };
+    // ... from a chain's accumulators
+    auto redo_acc = [&](v16f (&t)[G], uint32_t tile, auto cc, int32_t (&out)[NS]) {
+        redo_from([&](int i) { return recombine(t[i / PHH], i % PHH); }, tile, cc, out);
         hold_acc(t);
+    };
+    // ... RES: from the integers a burst took (the set they came from is long overwritten)
+    auto redo_v = [&](const vint (&vv)[NS], uint32_t tile, auto cc, int32_t (&out)[NS]) {
+        redo_from([&](int i) { return vv[i]; }, tile, cc, out);
     };
     // ... after the channel's chain run again (its stream bytes are still in that channel's buffer): the tiles at a call's edges
     auto redo = [&](uint32_t cbuf, uint32_t tile, auto cc, int32_t (&out)[NS]) {
@@ -850,8 +917,15 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
             stamp(0);
             {
                 Fast f;
+                [[maybe_unused]] vint vv[NS];
                 fast_begin(f, tp, CHP{});
-                if (dbg & 2) chain(0u, accA, no_hook);
+                if constexpr (RES) {
+                    burst(accB, vv);
+                    if (dbg & 2) chain(0u, accA, no_hook);
+                    else if (dbg & 1) { static_for<0, NJR>([&](auto jc) { res_job(f, vv, accB, jc); }); for (int g = 0; g < G; ++g) accA[g] = cinit + (float)lane; }
+                    else chain(0u, accA, [&](auto uc) { res_hook(f, vv, accB, uc); });
+                }
+                else if (dbg & 2) chain(0u, accA, no_hook);
                 else if (dbg & 1) { static_for<0, NJ>([&](auto jc) { fast_job(f, accB, jc); }); for (int g = 0; g < G; ++g) accA[g] = cinit + (float)lane; }
                 else chain(0u, accA, [&](auto uc) { fast_hook(f, accB, uc); });
                 pin(accA);                      // the chain ends HERE (or the compiler sinks its MFMAs into the blocks that use them, behind the epilogue)
@@ -859,12 +933,12 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
                 if (prev) {
                     if constexpr (SCR) put_samples(chp, f.res);
                     else {
-                        if (!(dbg & 3) && fast_failed(f, tp)) { int32_t o[NS]; redo_acc(accB, tp, CHP{}, o); put_samples(chp, o); } else merge_extremes(f, CHP{});
+                        if (!(dbg & 3) && fast_failed(f, tp)) { int32_t o[NS]; if constexpr (RES) redo_v(vv, tp, CHP{}, o); else redo_acc(accB, tp, CHP{}, o); put_samples(chp, o); } else merge_extremes(f, CHP{});
                     }
                 }
                 // (the scratch flavour's region tails run no inline-asm instruction, and its next epilogue starts a whole staging phase later; holding
                 // the sets there cost <8, 688, 2, 0, 0> thirty spilled registers and config 5 a fifth of its stage A)
-                if constexpr (!SCR) hold_acc(accB);
+                if constexpr (!SCR && !RES) hold_acc(accB);
             }
             // ---- region B ----
             stamp(2);
@@ -886,17 +960,24 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
             stamp(0);
             {
                 Fast f;
+                [[maybe_unused]] vint vv[NS];
                 fast_begin(f, wt, CHA{});
-                if (dbg & 2) chain(1u, accB, no_hook);
+                if constexpr (RES) {
+                    burst(accA, vv);
+                    if (dbg & 2) chain(1u, accB, no_hook);
+                    else if (dbg & 1) { static_for<0, NJR>([&](auto jc) { res_job(f, vv, accA, jc); }); for (int g = 0; g < G; ++g) accB[g] = cinit - (float)lane; }
+                    else chain(1u, accB, [&](auto uc) { res_hook(f, vv, accA, uc); });
+                }
+                else if (dbg & 2) chain(1u, accB, no_hook);
                 else if (dbg & 1) { static_for<0, NJ>([&](auto jc) { fast_job(f, accA, jc); }); for (int g = 0; g < G; ++g) accB[g] = cinit - (float)lane; }
                 else chain(1u, accB, [&](auto uc) { fast_hook(f, accA, uc); });
                 pin(accB);
                 stamp(1);
                 if constexpr (SCR) put_samples(0, f.res);
                 else {
-                    if (!(dbg & 3) && fast_failed(f, wt)) { int32_t o[NS]; redo_acc(accA, wt, CHA{}, o); put_samples(CHA::value, o); } else merge_extremes(f, CHA{});
+                    if (!(dbg & 3) && fast_failed(f, wt)) { int32_t o[NS]; if constexpr (RES) redo_v(vv, wt, CHA{}, o); else redo_acc(accA, wt, CHA{}, o); put_samples(CHA::value, o); } else merge_extremes(f, CHA{});
                 }
-                if constexpr (!SCR) hold_acc(accA);
+                if constexpr (!SCR && !RES) hold_acc(accA);
             }
             });
             have_prev = true; pw = wt;
@@ -907,11 +988,13 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
             using CHL = std::integral_constant<uint32_t, chl>;
             Fast f;
             fast_begin(f, pw, CHL{});
-            static_for<0, NJ>([&](auto jc) { fast_job(f, accB, jc); });
+            [[maybe_unused]] vint vv[NS];
+            if constexpr (RES) { burst(accB, vv); static_for<0, NJR>([&](auto jc) { res_job(f, vv, accB, jc); }); }
+            else static_for<0, NJ>([&](auto jc) { fast_job(f, accB, jc); });
             if constexpr (SCR) { hold_acc(accB); put_samples(1, f.res); wave_sync2(); store_scr_tile(pw); wave_sync2(); }
             else {
-                if (fast_failed(f, pw)) { int32_t o[NS]; redo_acc(accB, pw, CHL{}, o); put_samples(chl, o); } else merge_extremes(f, CHL{});
-                hold_acc(accB);
+                if (fast_failed(f, pw)) { int32_t o[NS]; if constexpr (RES) redo_v(vv, pw, CHL{}, o); else redo_acc(accB, pw, CHL{}, o); put_samples(chl, o); } else merge_extremes(f, CHL{});
+                if constexpr (!RES) hold_acc(accB);
                 wave_sync2();
                 store_tile(pw);
                 wave_sync2();
@@ -1036,7 +1119,7 @@ static hipError_t launch_mx_t(Mfma2Args& m, uint32_t max_nout, uint32_t nrows, h
     if (e != hipSuccess) return e;
     constexpr uint32_t TILE = 32u * (uint32_t)PH * G;
     // LDS: the shared tap table, then per wave two stream buffers and the output slice; eight waves per block = two per SIMD
-    m.off_waves = (uint32_t)mx_nf(MB, NT, PH) * MX_FRAG_BYTES;
+    m.off_waves = mx_nres_of(MB, NT, SBY, NPR, ND) == mx_nf(MB, NT, PH) ? 0u : (uint32_t)mx_nf(MB, NT, PH) * MX_FRAG_BYTES;    // (no table where every fragment is resident)
     m.off_out = 2u * (uint32_t)mx_stream_bytes(MB, NT, G, PH);
     m.wave_lds = m.off_out + 2u * (uint32_t)NPR * TILE * 4u; // the slice: a row of TILE dwords per channel (the scratch flavour too: its integers leave as rows of the slice)
     const uint32_t wdbg = (m.f.dbg_flags >> 8) & 0xFFu;   // diagnostic override (d2d_params.debug_flags bits 8..15)

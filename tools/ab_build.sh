@@ -4,7 +4,7 @@
 # development only; bench.py names such a library in its line and cites no counter traffic for it).
 #   tools/ab_build.sh <name> <target> [flags...]     target: mx | mxm | mfma3 | kernels | px
 #     mx       the fp6 kernel, E_M32 shape only (-DD2D_MX_DEV: the dispatcher with unit 0, and the shape's gain unit):
-#              -DD2D_MX_ABL=<mask> -DD2D_MX_STAMPS=1 -DD2D_MX_G4=<groups> -DD2D_MX_NOFLAT=1
+#              -DD2D_MX_ABL=<mask> -DD2D_MX_STAMPS=1 -DD2D_MX_G4=<groups> -DD2D_MX_NOFLAT=1 -DD2D_MX_NRES=<resident fragments> -DD2D_MX_RESIDENT=0
 #     mxm      the fp6 kernel, the three-pairs-per-wave unit of the E_M32 shape: -DD2D_MX_ABL=<mask>
 #     mfma3    the pipelined int8 kernel, E_M8 shape only (-DD2D_M3_DEV: the dispatcher with unit 0): -DD2D_M3_ABL=<mask> -DD2D_M3_STAMPS=1
 #     kernels  d2d_kernels.hip (LUT, resampler, de-interleave, noise shaping)
