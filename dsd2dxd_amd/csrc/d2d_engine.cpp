@@ -986,8 +986,15 @@ int d2d_translate_batch_host(d2d_engine* e, d2d_file_io* io, uint32_t n_files, s
     // bytes: the staging buffers are 256-byte aligned per file whatever the slice length.)
     if (e->B > 1) slice = std::max<size_t>(e->B, slice / e->B * e->B);
     size_t max_L = 0;
+    // every file's whole call against its buffer before anything is staged: the pipeline below converts and downloads slice by slice, and a
+    // buffer that only a later slice overflows would otherwise fail with earlier slices in the caller's memory and the files moved on
     for (uint32_t f = 0; f < n_files; ++f) {
         if (io[f].bytes_per_channel && !io[f].dsd) return e->fail(D2D_ERR_PARAM, "null dsd pointer");
+        const size_t frames = d2d_next_frames(e, f, io[f].bytes_per_channel);
+        if (frames * fb > io[f].pcm_capacity_bytes) return e->fail(D2D_ERR_CAPACITY, "pcm buffer too small");
+        if (frames && !io[f].pcm) return e->fail(D2D_ERR_PARAM, "null pcm pointer");
+    }
+    for (uint32_t f = 0; f < n_files; ++f) {
         max_L = std::max(max_L, io[f].bytes_per_channel);
         io[f].frames_out = 0;
     }

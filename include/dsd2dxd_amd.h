@@ -138,6 +138,16 @@ size_t d2d_next_frames(const d2d_engine* e, uint32_t file, size_t bytes_per_chan
 int d2d_translate(d2d_engine* e, const uint8_t* dsd, size_t bytes_per_channel,
                   void* pcm, size_t pcm_capacity_bytes, size_t* frames_out);
 
+/* WHAT A CALL MAY TOUCH (every translate and prime entry point; tests/test_gpu_containment.py pins it on every kernel route):
+ *   1. A successful translate call writes exactly the bytes [0, frames_out * d2d_frame_bytes) of each file's `pcm` and no other
+ *      byte of caller memory.  A file that yields no frames has no byte written.  pcm_capacity_bytes is only checked: the
+ *      kernels never see it, so frames_out * d2d_frame_bytes is all a buffer has to hold, and files may lie back to back.
+ *   2. d2d_prime and d2d_prime_batch_device write no PCM at all.
+ *   3. The result depends only on the declared channels * bytes_per_channel input bytes of each file.
+ *   4. A call that fails with D2D_ERR_CAPACITY or D2D_ERR_PARAM writes no PCM byte and leaves d2d_tell and d2d_peak of every file
+ *      as they were; the engine goes on converting correctly.  (d2d_translate_batch_host checks every file's whole call --
+ *      d2d_next_frames(e, f, bytes_per_channel) * d2d_frame_bytes against its capacity -- before it stages the first slice.) */
+
 /* One file of a batch: device-resident input and output for the many-file path. */
 typedef struct d2d_file_io {
     const void* dsd;            /* DEVICE pointer, 16-byte aligned                              */

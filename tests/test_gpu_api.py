@@ -124,10 +124,11 @@ def test_runtime_errors(engine_lib):
     e = engine_lib.Engine(**KW)
     L = engine_lib.lib()
     buf = np.zeros(4096 * 2, dtype=np.uint8)
-    out = np.zeros(16, dtype=np.uint8)
+    out = np.arange(16, dtype=np.uint8) ^ 0xA5
     fr = C.c_size_t()
     rc = L.d2d_translate(e._h, buf.ctypes.data, 4096, out.ctypes.data, out.size, C.byref(fr))
     assert rc == -20 and b"too small" in L.d2d_last_error(e._h)          # D2D_ERR_CAPACITY
+    assert np.array_equal(out, np.arange(16, dtype=np.uint8) ^ 0xA5) and e.tell() == (0, 0) and fr.value == 0      # ... and nothing written, nothing consumed
     eb = engine_lib.Engine(n_files=2, **KW)
     rc = L.d2d_translate(eb._h, buf.ctypes.data, 2048, out.ctypes.data, out.size, C.byref(fr))
     assert rc == -40                                                     # single-file entry point on a batch engine
@@ -211,7 +212,7 @@ def test_host_resident_batch_pipeline(engine_lib, oracle_mod, out_rate, fmt, pin
     for i, (r, rf) in enumerate(want):
         assert ios[i].frames_out == rf, (i, ios[i].frames_out, rf)
         assert np.array_equal(outs[i][:rf * fb].numpy(), r[:rf * fb]), i
-    # too small an output buffer is reported, not overrun
+    # too small an output buffer is reported (that nothing is written or consumed then: tests/test_gpu_containment.py::test_refused_host_batch_changes_nothing)
     e2 = engine_lib.Engine(n_files=len(lens), kernel=2, debug=debug, **kw)
     ios[3].pcm_capacity_bytes = 64
     with pytest.raises(Exception, match="pcm buffer too small"):
