@@ -28,6 +28,7 @@
 #include "d2d_mfma.h"
 #include "d2d_mx.h"
 #include "d2d_px.h"
+#include "d2d_tables.h"
 
 using namespace d2d;
 
@@ -301,9 +302,7 @@ static void fir_args_static(const d2d_engine* e, FirArgs& a, bool lo_pass = fals
     a.scale_bits = e->S + (e->taps32 ? 8 : 0);
     a.taps32 = e->taps32 ? 1u : 0u;
     a.in_channels = e->Cin;
-    uint64_t sa = 0;
-    for (int j = 0; j < e->N; ++j) { const int64_t q = tap_q(fd, j); sa += (uint64_t)(q < 0 ? -q : q); }
-    a.sum_abs_q = sa;
+    a.sum_abs_q = sum_abs_q(fd);
     a.epi = e->epi;
     a.pipelined = (uint32_t)(lo_pass ? e->mfma_pipe_lo : e->mfma_pipe);
     a.mx_exact = mx_exact(fd) ? 1u : 0u;
@@ -340,15 +339,7 @@ static void build_launch_state(d2d_engine* e) {
     ns.scale_bits = e->poly ? e->poly->S : e->S; ns.nstreams = e->nstreams; ns.epi = e->epi;
     ns.res = e->cascade() ? 1u : 0u;
     // the all-integer loop: the largest |y * 2^S| any output can reach (composed polyphase: its heaviest phase) leaves room for a few LSB
-    uint64_t sa = l.fir.sum_abs_q;
-    if (e->poly) {
-        sa = 0;
-        for (int ph = 0; ph < e->poly->Lp; ++ph) {
-            uint64_t sp = 0;
-            for (int j = 0; j < e->poly->NP; ++j) { const int64_t q = e->poly->q[(size_t)ph * e->poly->NP + j]; sp += (uint64_t)(q < 0 ? -q : q); }
-            sa = std::max(sa, sp);
-        }
-    }
+    const uint64_t sa = e->poly ? max_phase_sum_abs(*e->poly) : l.fir.sum_abs_q;
     ns.intq = (!(e->p.debug_flags & D2D_DBG_NO_INTQ) && sa + (1ull << 24) < (1ull << 31)) ? 1u : 0u;
     ns.general = (e->p.debug_flags & D2D_DBG_NS_GENERAL) ? 1u : 0u;
 }
@@ -383,9 +374,7 @@ static int init_engine(d2d_engine* e) {
     if (e->p.tap_bits == 32) {
         if (e->fc.resamp || e->noise_shape) return e->fail(D2D_ERR_PARAM, "32-bit taps serve the 44.1k-family rates with dither T, R, F or X");
         e->fine = true;
-        e->lo_half.resize((size_t)f.ntaps / 2);
-        for (int k = 0; k < f.ntaps / 2; ++k) e->lo_half[(size_t)k] = (int32_t)((int64_t)f.half32[k] - ((int64_t)f.half[k] << 8));
-        e->lo_def = f; e->lo_def.half = e->lo_half.data(); e->lo_def.half32 = nullptr;
+        e->lo_def = residual_def(f, e->lo_half);
     }
     e->epi.sample_bytes = (uint32_t)sample_bytes_of(e->p.bit_depth);
     e->epi.channels = e->C;
@@ -477,15 +466,12 @@ static int init_engine(d2d_engine* e) {
                 e->il2 = true; e->deinterleave = false; e->B = 1;
             }
         }
-        const std::vector<int8_t> t = e->mfma_pipe == PIPE_FP6 ? build_mx_tables(f, msb, e->taps32)
-                                    : e->mfma_v2 ? build_mfma2_tables(f, msb, !e->mfma_pipe) : build_mfma_tables(f, e->mfma, msb);
+        const std::vector<int8_t> t = build_fir_table(f, e->mfma_pipe, e->mfma_v2, e->mfma, msb, e->taps32);
         HIPCHK(e, e->d_fir_tables.upload(t.data(), t.size()));
         if (e->fine) {
             // the residual table goes through the same builders; which pipelined kernel serves it is decided on ITS digits
             if (e->mfma_v2) { FirArgs a{}; fir_args_static(e, a, true); e->mfma_pipe_lo = mfma2_pipelined(a, e->M, e->N); }
-            const d2d_filter_def& fl = e->lo_def;
-            const std::vector<int8_t> tl = e->mfma_pipe_lo == PIPE_FP6 ? build_mx_tables(fl, msb)
-                                         : e->mfma_v2 ? build_mfma2_tables(fl, msb, !e->mfma_pipe_lo) : build_mfma_tables(fl, e->mfma, msb);
+            const std::vector<int8_t> tl = build_fir_table(e->lo_def, e->mfma_pipe_lo, e->mfma_v2, e->mfma, msb, false);
             HIPCHK(e, e->d_fir_tables_lo.upload(tl.data(), tl.size()));
         }
     }
@@ -496,7 +482,7 @@ static int init_engine(d2d_engine* e) {
         a2.epi.channels = 2; a2.in_channels = 2;
         const int p2 = mfma2_pipelined(a2, e->M, e->N);
         if (p2 == PIPE_FP6 || p2 == PIPE_INT8) {
-            const std::vector<int8_t> t2 = p2 == PIPE_FP6 ? build_mx_tables(f, msb) : build_mfma2_tables(f, msb, false);
+            const std::vector<int8_t> t2 = build_fir_table(f, p2, true, e->mfma, msb, false);
             e->mono2_pipe = p2;
             HIPCHK(e, e->d_fir_tables_m2.upload(t2.data(), t2.size()));
             e->mono2_ok = true;

@@ -1,5 +1,4 @@
-// d2d_filters.h -- which tap table serves which (filter type, DSD rate, output rate), and the
-// host-side construction of the device tables from the frozen designs in filters/filter_tables.inc.
+// d2d_filters.h -- which tap table serves which (filter type, DSD rate, output rate); d2d_tables.cpp builds the device tables from them.
 //
 // The legal combinations follow the reference CLI's documentation:
 //   /root/reference/src/main.rs:62-67 (filter availability), :85-92 (rates per DSD rate),
@@ -66,12 +65,6 @@ inline int choose_filters(const d2d_params& p, FilterChoice& out, std::string& e
     return D2D_OK;
 }
 
-// full tap j (0..N-1) as the integer q_j (tap = q_j * 2^-S); 2nd half stored centre-outward
-inline int32_t tap_q(const d2d_filter_def& f, int j) {
-    const int h = f.ntaps / 2;
-    return j >= h ? f.half[j - h] : f.half[h - 1 - j];
-}
-
 // LUT kernel geometry for decimation byte count MB
 struct LutLayout {
     int R, LS, pad, nq, ntab;
@@ -84,29 +77,6 @@ inline LutLayout lut_layout(int MB, int Wb) {
     g.nq = (Wb + (g.R - 1) * MB + 7) / 8;
     g.ntab = g.pad + 16 * g.nq;
     return g;
-}
-
-// Nibble tables [ntab][16] of f64.  Table pad+2w serves the HIGH nibble of window byte w, table
-// pad+2w+1 its LOW nibble, whatever the stream's bit order: for MSB-first streams the high nibble
-// holds the four EARLIER samples (bit 7 first), for LSB-first streams the LATER four (bit 4 first).
-inline std::vector<double> build_lut_tables(const d2d_filter_def& f, int MB, bool msb_first) {
-    const int Wb = f.ntaps / 8;
-    const LutLayout g = lut_layout(MB, Wb);
-    std::vector<double> t((size_t)g.ntab * 16, 0.0);
-    const double scale = 1.0 / (double)(1ull << f.S);   // exact power of two
-    for (int w = 0; w < Wb; ++w)
-        for (int nib = 0; nib < 2; ++nib)              // 0 = high nibble of the byte, 1 = low nibble
-            for (int x = 0; x < 16; ++x) {
-                int64_t acc = 0;
-                for (int i = 0; i < 4; ++i) {
-                    // bit i of the nibble value x  ->  time position inside the byte
-                    int tpos = msb_first ? (nib == 0 ? 3 - i : 7 - i) : (nib == 0 ? 4 + i : i);
-                    int64_t q = tap_q(f, 8 * w + tpos);
-                    acc += ((x >> i) & 1) ? q : -q;
-                }
-                t[(size_t)(g.pad + 2 * w + nib) * 16 + x] = (double)acc * scale;
-            }
-    return t;
 }
 
 }  // namespace d2d

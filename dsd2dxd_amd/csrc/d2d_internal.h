@@ -74,7 +74,7 @@ struct FirArgs {
                                // de-interleaves inside its staging, a block per (file, tile) with one wave per channel pair; B = 1 then
     uint32_t il2;              // 1 (pipelined frame kernels): byte-interleaved STEREO input (DFF, -f I), both channels converted: the kernel's staging
                                // pulls the channels apart (one v_perm_b32 per channel and eight input bytes); B = 1, no planar copy
-    uint32_t mx_exact;         // 1: the table's base-32 digit sums recombine exactly in f32 (d2d_mx.h: mx_exact)
+    uint32_t mx_exact;         // 1: the table's base-32 digit sums recombine exactly in f32 (d2d_tables.h: mx_exact)
     uint32_t dbg_flags;        // d2d_params.debug_flags (D2D_DBG_*), fixed when the engine was created
     uint32_t taps32;           // 1 (d2d_kernels_mx.hip, stereo frames): the 32-bit tap grid in ONE pass -- `tables` hold the seven-digit fragments of the half32
                                // taps, scale_bits = S + 8, v = sum q32 s is a 64-bit integer, the f64 requantiser finishes (tap_bits = 32, round 4)

@@ -615,47 +615,6 @@ bool mfma_supported(int M, int N) {
     return M == 8 || M == 16 || M == 32 || M == 64 || M == 128;
 }
 
-MfmaLayout mfma_layout(int M, int N) {
-    MfmaLayout g;
-    g.M = M; g.N = N;
-    const int wd = (N + 7 * M + 24 + 31) / 32;   // dwords of one row's window (+ up to 3 bytes of misalignment)
-    const int U = (wd + 1) / 2;
-    g.ksteps = 2 * U;
-    return g;
-}
-
-// Tap fragments [4 byte shifts][ksteps + 6][64 lanes][16 bytes].  Lane l supplies matrix row (l & 31) = 4*phase + limb
-// for the K slots (l >> 5)*16 + j; slot (ks, h, j) reads bit `wb` of the row window (see the
-// kernel's A00/A01), which sits at bit position p = wb & 7 of its stream byte and therefore arrives
-// as 2^p (p = 7: -128): the table holds q * 2^(7-p), negated for p = 7.
-std::vector<int8_t> build_mfma_tables(const d2d_filter_def& f, const MfmaLayout& g, bool msb_first) {
-    const int U = g.ksteps / 2;
-    const size_t per = (size_t)(g.ksteps + 6) * 64 * 16;           // +6 zero steps: the kernel's read-ahead
-    std::vector<int8_t> t(4 * per, 0);
-    for (int sh = 0; sh < 4; ++sh)                                  // window starts `sh` bytes into its first dword
-        for (int ks = 0; ks < g.ksteps; ++ks)
-            for (int l = 0; l < 64; ++l) {
-                const int row = l & 31, h = l >> 5, limb = row & 3;
-                // D row i lands in lane half (i >> 2) & 1, register group i >> 3: give that slot output
-                // phase 4*half + group, so lane (r, half) owns the four CONSECUTIVE outputs 8r + 4*half + k
-                const int ph = 4 * ((row >> 2) & 1) + (row >> 3);
-                for (int j = 0; j < 16; ++j) {
-                    const int p = 4 * (ks & 1) + (j >> 2);                        // register v = j>>2 of step ks
-                    const int wb = 32 * (h * U + (ks >> 1)) + 8 * (j & 3) + p;     // bit of the LDS row words
-                    const int tau = (msb_first ? (wb & ~7) + 7 - (wb & 7) : wb) - 8 * sh;   // its time index in the window
-                    const int tap = tau - ph * g.M;
-                    int8_t v = 0;
-                    if (tau >= 0 && tap >= 0 && tap < f.ntaps) {
-                        int64_t q = tap_q(f, tap);
-                        q = p == 7 ? -q : q * (int64_t)(1 << (7 - p));
-                        v = limb256(q, limb);
-                    }
-                    t[sh * per + ((size_t)ks * 64 + l) * 16 + j] = v;
-                }
-            }
-    return t;
-}
-
 static void mfma_geometry(const FirArgs& a, const MfmaLayout& g, MfmaArgs& m, size_t& smem) {
     // channels per block: all of a mono/stereo file, one pair of a multichannel one
     m.ngroups = a.epi.channels <= 2 ? 1u : (a.epi.channels + 1u) / 2u;

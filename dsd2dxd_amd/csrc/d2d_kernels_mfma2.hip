@@ -598,44 +598,6 @@ __global__ __launch_bounds__(D2D_M2_THREADS) void d2d_fir_mfma2_kernel(Mfma2Args
 
 // ---- host side -------------------------------------------------------------------------------
 
-int mfma2_pairs(int M, int N) { return (N + 7 * M + 24 + 63) / 64; }
-
-// Tap fragments [4 byte shifts][2*NPG][64 lanes][16 bytes].  Fragment 2*pp + n serves pair step pp of a
-// group's window, bit positions 4n .. 4n+3 of every byte.  Lane l supplies matrix row (l & 31) =
-// 4*slot + limb for the K slots of lane half hh = l >> 5, i.e. the staged dword 2*pp + hh of the window;
-// slot j of the lane = byte (j & 3), plane (j >> 2) -> bit position p = 4n + (j >> 2) of that byte,
-// which arrives as 2^p (p = 7: -128): the table holds q * 2^(7-p), negated for p = 7.
-std::vector<int8_t> build_mfma2_tables(const d2d_filter_def& f, bool msb_first, bool unmask0_wanted) {
-    const int NPG = mfma2_pairs(f.M, f.ntaps);
-    const bool unmask0 = unmask0_wanted && m2_unmask0(NPG);
-    const size_t per = (size_t)(2 * NPG) * 64 * 16;
-    std::vector<int8_t> t(4 * per, 0);
-    for (int sh = 0; sh < 4; ++sh)                                  // window starts `sh` bytes into its first dword
-        for (int fr = 0; fr < 2 * NPG; ++fr)
-            for (int l = 0; l < 64; ++l) {
-                const int pp = fr >> 1, n = fr & 1;
-                const int row = l & 31, hh = l >> 5, limb = row & 3;
-                // D row i lands in lane half (i >> 2) & 1, register group i >> 3: give that slot output
-                // phase 4*half + group, so lane (r, half) owns the four CONSECUTIVE outputs 4*half + k of a group
-                const int ph = 4 * ((row >> 2) & 1) + (row >> 3);
-                for (int j = 0; j < 16; ++j) {
-                    const int p = 4 * n + (j >> 2);
-                    auto entry = [&](int pp_) -> int64_t {                                   // q * 2^(7-p) (p = 7: -q) of bit position pp_ of this byte
-                        const int wb_ = 32 * (2 * pp + hh) + 8 * (j & 3) + pp_;                    // bit of the staged window
-                        const int tau_ = (msb_first ? (wb_ & ~7) + 7 - (wb_ & 7) : wb_) - 8 * sh;  // its time index in the window
-                        const int tap_ = tau_ - ph * f.M;
-                        if (tau_ < 0 || tap_ < 0 || tap_ >= f.ntaps) return 0;
-                        const int64_t q = tap_q(f, tap_);
-                        return pp_ == 7 ? -q : q * (int64_t)(1 << (7 - pp_));
-                    };
-                    int64_t T = entry(p);
-                    if (unmask0 && p != 0) T -= entry(0);                                 // plane 0 arrives unmasked (see the kernel)
-                    t[sh * per + ((size_t)fr * 64 + l) * 16 + j] = limb256(T, limb);
-                }
-            }
-    return t;
-}
-
 // (MB, NPG) pairs with a compiled kernel
 // M = 32 and 64 only: with 1 or 2 bytes per output a 512-output tile holds so little stream that the per-tile work
 // (staging, waits, the epilogue) outweighs the shorter chain and the one-group kernel is faster (measured: DSD64 -> 352.8 kHz

@@ -30,7 +30,7 @@ namespace d2d {
 
 // ---- host side -------------------------------------------------------------------------------
 // This object is unit 0 of D2D_M3_UNIT_LIST (the E_M8 shape) and holds the dispatcher.  (The tap tables are the two-group kernel's:
-// build_mfma2_tables in d2d_kernels_mfma2.hip, every plane masked.)
+// build_mfma2_tables in d2d_tables.cpp, every plane masked.)
 #define X(unit, mb, npg, nt0, nt1) +1
 static_assert(D2D_M3_UNITS == 0 D2D_M3_UNIT_LIST(X), "the Makefile's M3_UNITS is not the length of D2D_M3_UNIT_LIST (d2d_m3.h)");
 #undef X

@@ -23,15 +23,11 @@
 //
 // Replaces: the 48 kHz-family path inside Rdsd2Pcm::do_conversion (/root/reference/src/main.rs:345,429); the crate that holds it is
 // absent from the reference.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
 #include "d2d_px_kernel.h"
 
 namespace d2d {
 
-// This object is unit 0 of D2D_PX_UNIT_LIST and holds the plain kernel, the table builder and the dispatcher.
+// This object is unit 0 of D2D_PX_UNIT_LIST and holds the plain kernel and the dispatcher (the table builder: d2d_tables.cpp).
 #define X(unit, lp, mp, np, g) +1
 static_assert(D2D_PX_UNITS == 0 D2D_PX_UNIT_LIST(X), "the Makefile's PX_UNITS is not the length of D2D_PX_UNIT_LIST (d2d_px.h)");
 #undef X
@@ -49,7 +45,6 @@ static const PxRow* px_find(const d2d_poly_def& p) {
     return nullptr;
 }
 bool px_supported(const d2d_poly_def& p) { return px_find(p) != nullptr; }
-int px_groups(const d2d_poly_def& p) { const PxRow* r = px_find(p); return r ? r->G : 0; }
 
 // ---- the plain form: one output per lane, bit by bit ----
 constexpr int PXP_THREADS = 256;
@@ -111,85 +106,6 @@ hipError_t launch_poly_plain(PxArgs& a, const d2d_poly_def& p, uint32_t max_nout
     hipLaunchKernelGGL(d2d_poly_plain_kernel, dim3(gx, nstreams), dim3(PXP_THREADS), smem, s, a, span);
     d2d_last_launched_kernel = "d2d_poly_plain_kernel";
     return hipGetLastError();
-}
-
-// balanced base-32 digit l of v: v = sum d_l 32^l, every d in [-16, 15]
-static int px_digit32(int64_t v, int l) {
-    int dd = 0;
-    for (int i = 0; i <= l; ++i) {
-        dd = (int)(((v + 16) & 31) - 16);
-        v = (v - dd) / 32;
-    }
-    return dd;
-}
-// e2m3 code of x (a multiple of 1/8 up to 2, of 1/4 up to 4)
-static uint32_t px_e2m3(double x) {
-    const uint32_t sg = x < 0 ? 32u : 0u;
-    const double ax = fabs(x);
-    for (uint32_t c = 0; c < 32; ++c) {
-        const uint32_t e = c >> 3, mm = c & 7;
-        const double v = e ? (1.0 + mm / 8.0) * (double)(1 << (e - 1)) : mm * 0.125;
-        if (v == ax) return ax == 0 ? 0u : (sg | c);
-    }
-    fprintf(stderr, "d2d: %g is not an e2m3 number\n", x);
-    abort();
-}
-
-// The kernel recombines v = lo + 2^15 hi with lo = S0 + 32 S1 + 2^10 S2 and hi = S3 + 32 S4 in f32: exact while every value that can occur
-// stays below 2^24; a digit sum over any subset of a window's bits is bounded by the sum of the digits' magnitudes (per phase).
-bool px_exact(const d2d_poly_def& p) {
-    if (p.S < 20 || p.S > 30) return false;
-    for (int ph = 0; ph < p.Lp; ++ph) {
-        int64_t sa[5] = {0, 0, 0, 0, 0}, sq = 0;
-        for (int j = 0; j < p.NP; ++j) {
-            const int64_t q = p.q[(size_t)ph * p.NP + j], q2 = 2 * q;
-            if (q2 > 16236247 || q2 < -17318416) return false;            // 2 Q has to fit five digits
-            sq += q;
-            for (int l = 0; l < 5; ++l) { const int d = px_digit32(q2, l); sa[l] += d < 0 ? -d : d; }
-        }
-        if (sq != ((int64_t)1 << p.S)) return false;                       // the accumulators' start value assumes unity DC gain per phase
-        const int64_t lo = sa[0] + 32 * sa[1] + 1024 * sa[2], hi = sa[3] + 32 * (sa[4] + ((int64_t)1 << (p.S - 20)));
-        if (lo >= (1 << 24) || hi >= (1 << 24)) return false;
-    }
-    return true;
-}
-
-// Tap fragments [slot (step u, group g) in issue order][64 lanes x 16 bytes | 64 lanes x 8 bytes].  A lane l = matrix row l & 31, K half
-// l >> 5; its element e (a 6-bit e2m3 code at bits [6e, 6e+6) of the lane's 192) meets B register e >> 3, nibble e & 7 = bit 4 (e & 7) + (e >> 3)
-// of the lane half's dword = bit x = 64 u + 32 (l >> 5) + that of the column's window, which arrives as 0.5 (even register) or 1.0 (odd).
-// D row i lands in lane half (i >> 2) & 1, register 4 (i >> 3) + (i & 3) = 5 i' + digit: output 3 half + i' of the group.  Output o of the
-// column (o = 5 g + 3 half + i') meets window bit x with tap j = q_o + NP - 1 - x of phase (o Mp) mod Lp.
-std::vector<int8_t> build_px_tables(const d2d_poly_def& p) {
-    const int G = px_groups(p), LP = p.Lp, MP = p.Mp, NP = p.NP;
-    const int TP = px_tp(LP, MP, NP, G), NSLOT = px_nslot(LP, MP, NP, G);
-    std::vector<int8_t> t((size_t)NSLOT * PX_FRAG_BYTES, 0);
-    for (int u = 0; u < TP; ++u)
-        for (int g = 0; g < G; ++g) {
-            if (!px_active(LP, MP, NP, u, g)) continue;
-            int8_t* fbp = &t[(size_t)px_slot(LP, MP, NP, G, u, g) * PX_FRAG_BYTES];
-            for (int l = 0; l < 64; ++l) {
-                const int row = l & 31, kh = l >> 5;
-                const int half = (row >> 2) & 1, rr = 4 * (row >> 3) + (row & 3);
-                uint32_t regs[6] = {0, 0, 0, 0, 0, 0};
-                const int ii = rr / 5, dg = rr % 5;
-                const int og = 3 * half + ii < 5 ? 3 * half + ii : 4;         // (half 1's third slot repeats output 4: a real sample for the pipelined epilogue's extremes, stored nowhere)
-                if (rr < 15) {
-                    const int o = 5 * g + og;
-                    const int qo = px_q(LP, MP, o), ph = (int)(((long long)o * MP) % LP);
-                    for (int e = 0; e < 32; ++e) {
-                        const int x = 64 * u + 32 * kh + 4 * (e & 7) + (e >> 3);
-                        const int j = qo + NP - 1 - x;
-                        if (j < 0 || j >= NP) continue;
-                        const int d = px_digit32(2 * (int64_t)p.q[(size_t)ph * NP + j], dg);
-                        const uint32_t code = px_e2m3(((e >> 3) & 1) ? d * 0.125 : d * 0.25);
-                        for (int b = 0; b < 6; ++b) if ((code >> b) & 1) regs[(6 * e + b) >> 5] |= 1u << ((6 * e + b) & 31);
-                    }
-                }
-                memcpy(fbp + (size_t)l * 16, regs, 16);
-                memcpy(fbp + 1024 + (size_t)l * 8, regs + 4, 8);
-            }
-        }
-    return t;
 }
 
 hipError_t launch_fir_px(PxArgs& a, const d2d_poly_def& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {

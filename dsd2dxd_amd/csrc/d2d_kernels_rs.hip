@@ -27,16 +27,12 @@
 // Replaces: the second stage of the 48 kHz-family path inside Rdsd2Pcm::do_conversion (/root/reference/src/main.rs:345,429;
 // README.md:230 "cascaded FIR filters"); the crate that holds it is absent from the reference.
 #include <hip/hip_runtime.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <type_traits>
-#include <vector>
 
 #include "d2d_device.h"
-#include "d2d_filters.h"
 #include "d2d_launch.h"
+#include "d2d_tables.h"
 
 namespace d2d {
 
@@ -47,9 +43,6 @@ typedef uint32_t u32x4_a2 __attribute__((ext_vector_type(4), aligned(2)));
 typedef uint32_t u32x2_a2 __attribute__((ext_vector_type(2), aligned(2)));
 
 constexpr int RS2_NCOL = 16;            // matrix columns per wave-tile: 16 cycles of one channel, or 8 cycles of a channel pair
-// bytes between two rows of a limb plane: the samples a row needs (P + 146) rounded up to 16, plus 16 or 32 so that the pitch is an
-// ODD number of 16-byte slots (the 64 lanes' 16-byte reads then fall on all banks)
-__host__ __device__ constexpr int rs2_rp(int P) { return 16 * ((P + 146 + 15) / 16 + (((P + 146 + 15) / 16) % 2 ? 2 : 1)); }
 constexpr uint32_t RS2_C0 = 0x00808080u;
 constexpr int64_t RS2_GUARD = 8;        // numerator units: 2^-28 LSB at F = 31
 
@@ -329,50 +322,6 @@ __global__ __launch_bounds__(512) void d2d_resample_mfma_kernel(Rs2Args a) {
 }
 
 // ---- host side -------------------------------------------------------------------------------
-static inline int8_t rs2_limb(int64_t v, int l) {
-    int8_t dgt = 0;
-    for (int i = 0; i <= l; ++i) {
-        const int64_t dd = ((v + 128) & 255) - 128;
-        dgt = (int8_t)dd;
-        v = (v - dd) / 256;
-    }
-    return dgt;
-}
-
-uint32_t resamp2_nstep(const d2d_resamp_def& r) {
-    int need = 0;
-    for (int rho = 0; rho < r.L / 4; ++rho) {
-        const int b0 = (r.Mdn * 4 * rho) / r.L, b3 = (r.Mdn * (4 * rho + 3)) / r.L;
-        need = std::max(need, b3 + r.P - (b0 & ~15));
-    }
-    return (uint32_t)((need + 63) / 64);
-}
-
-// [L/4 blocks][NSTEP][64 lanes][16 bytes], then the blocks' row offsets (uint32, padded to 16 bytes).  A lane l = matrix row l & 15
-// = (phase p = row / 4, digit a = row % 4), K group l / 16; its byte j is K slot kappa = 64 s + 16 (l / 16) + j = the row's sample
-// rowoff + kappa = X[147 c - (P-1) + rowoff + kappa], which tap k = b_r + (P-1) - rowoff - kappa of residue r = 4 rho + p multiplies.
-std::vector<int8_t> build_resamp2_table(const d2d_resamp_def& r) {
-    const int NB = r.L / 4, NSTEP = (int)resamp2_nstep(r);
-    std::vector<int8_t> t((size_t)NB * NSTEP * 1024 + (((size_t)NB * 4 + 15) & ~(size_t)15), 0);
-    uint32_t* ro = reinterpret_cast<uint32_t*>(t.data() + (size_t)NB * NSTEP * 1024);
-    for (int rho = 0; rho < NB; ++rho) {
-        const int rowoff = ((r.Mdn * 4 * rho) / r.L) & ~15;
-        ro[rho] = (uint32_t)rowoff;
-        for (int s = 0; s < NSTEP; ++s)
-            for (int l = 0; l < 64; ++l) {
-                const int row = l & 15, p = row >> 2, a_ = row & 3, kgp = l >> 4;
-                const int res = 4 * rho + p, b = (r.Mdn * res) / r.L, phase = (r.Mdn * res) % r.L;
-                for (int j = 0; j < 16; ++j) {
-                    const int kappa = 64 * s + 16 * kgp + j;
-                    const int k = b + (r.P - 1) - rowoff - kappa;
-                    if (k < 0 || k >= r.P) continue;
-                    t[((size_t)(rho * NSTEP + s) * 64 + l) * 16 + j] = rs2_limb((int64_t)r.q[(size_t)phase * r.P + k], a_);
-                }
-            }
-    }
-    return t;
-}
-
 hipError_t launch_resample2(Rs2Args& a, const d2d_resamp_def& r, uint32_t max_out, uint32_t nfiles, hipStream_t s) {
     if (nfiles == 0 || max_out == 0) return hipSuccess;
     const uint32_t NSTEP = resamp2_nstep(r);

@@ -6,8 +6,6 @@
 #include <mutex>
 #include <string>
 
-#include <vector>
-
 #include "../../filters/filter_tables.inc"
 #include "d2d_internal.h"
 
@@ -96,7 +94,6 @@ uint32_t lut_outputs_per_tile(int MB);
 const char* lut_kernel_name(int MB);
 hipError_t launch_fir_lut(const FirArgs& a, int MB, uint32_t max_tiles, uint32_t nstreams, hipStream_t s);
 hipError_t launch_resample2(Rs2Args& a, const d2d_resamp_def& r, uint32_t max_out, uint32_t nfiles, hipStream_t s);
-std::vector<int8_t> build_resamp2_table(const d2d_resamp_def& r);
 hipError_t launch_deinterleave(const StreamJob* jobs, uint32_t nfiles, uint32_t C, uint32_t streams_per_file, uint32_t max_L, hipStream_t s);
 hipError_t launch_noise_shape(const NoiseShapeArgs& a, hipStream_t s);
 // tap_bits = 32: frames from the two scratch halves, v = 256 v_hi + v_lo + lo_bias, y = v * 2^-sbits (d2d_kernels.hip)

@@ -3,8 +3,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <vector>
-
 #include "d2d_filters.h"
 #include "d2d_internal.h"
 
@@ -99,12 +97,9 @@ template <int UNIT> hipError_t launch_mx_unit(Mfma2Args& m, uint32_t max_nout, u
 bool mx_supported(int MB, int NT);                 // is a kernel compiled for this shape?
 bool mx_pairs_supported(int MB, int NT, int npairs);   // ... for `npairs` channel pairs per wave (planar multichannel frames)?
 bool mx_gain_supported(int MB, int NT);            // ... and its gain flavours (frames at another level than 0 dB)?
-bool mx_exact(const d2d_filter_def& f);            // do the digit sums of this table recombine exactly in f32?
 bool mx_wide_supported(int MB, int NT);            // ... the one-pass form of the 32-bit tap grid (seven digits, four phases per group)?
-bool mx_wide_exact(const d2d_filter_def& f);       // ... and do the seven digit sums of its half32 taps recombine exactly?
 int mx_groups(int MB);
 void mx_debug_stamps(unsigned long long out[8]);   // diagnostic (-DD2D_MX_STAMPS=1 builds)
-std::vector<int8_t> build_mx_tables(const d2d_filter_def& f, bool msb_first, bool wide = false);   // wide: the 32-bit taps (f.half32)
 hipError_t launch_fir_mx(Mfma2Args& m, int MB, int NT, uint32_t max_nout, uint32_t nrows, hipStream_t s);
 
 }  // namespace d2d

@@ -11,8 +11,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <vector>
-
 #include "../../filters/filter_tables.inc"
 #include "d2d_internal.h"
 
@@ -104,9 +102,12 @@ struct PxArgs {
 template <int UNIT> hipError_t launch_px_unit(PxArgs& a, uint32_t max_nout, uint32_t nfiles, hipStream_t s);   // d2d_px_kernel.h; one explicit instantiation per object
 
 bool px_supported(const d2d_poly_def& p);                                   // is a matrix-core kernel compiled for this table?
-bool px_exact(const d2d_poly_def& p);                                       // do the table's base-32 digit sums recombine exactly in f32?
-int px_groups(const d2d_poly_def& p);
-std::vector<int8_t> build_px_tables(const d2d_poly_def& p);
+inline int px_groups(const d2d_poly_def& p) {      // groups per column a table is compiled with (0: no row)
+#define X(unit, lp, mp, np, g) if (p.Lp == lp && p.Mp == mp && p.NP == np) return g;
+    D2D_PX_UNIT_LIST(X)
+#undef X
+    return 0;
+}
 hipError_t launch_fir_px(PxArgs& a, const d2d_poly_def& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s);
 hipError_t launch_poly_plain(PxArgs& a, const d2d_poly_def& p, uint32_t max_nout, uint32_t nstreams, hipStream_t s);
 
