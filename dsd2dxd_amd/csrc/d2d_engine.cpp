@@ -28,6 +28,7 @@
 #include "d2d_mfma.h"
 #include "d2d_mx.h"
 #include "d2d_px.h"
+#include "d2d_route.h"
 #include "d2d_tables.h"
 
 using namespace d2d;
@@ -140,14 +141,11 @@ struct d2d_engine {
     uint32_t n_files = 1;
     FilterChoice fc;
     int M = 0, Mb = 0, N = 0, Wb = 0, S = 0;
-    uint32_t B = 1, keep = 0, nstreams = 0;
+    uint32_t nstreams = 0;
     uint32_t Cin = 0;          // channels of the input layout
     uint32_t C = 0, c0 = 0;    // channels converted (streams per file, width of the output frame) and the first of them
-    uint32_t kernel = D2D_KERNEL_LUT;
-    LutLayout lut{};
+    FirRoute route;            // which kernel, table layout and staging serve this engine (d2d_route.h: choose_route)
     MfmaLayout mfma{};
-    bool mfma_v2 = false;      // the two-group matrix-core kernel (d2d_kernels_mfma2.hip) serves this shape
-    int mfma_pipe = PIPE_NONE; // ... through a software-pipelined variant: PIPE_INT8 (d2d_kernels_mfma3.hip) or PIPE_FP6 (d2d_kernels_mx.hip)
     mutable std::string kname; // d2d_kernel_name's answer before the first call
     std::string launched;      // the FIR kernel the last call really enqueued (d2d_last_launched_kernel)
     Epilogue epi{};
@@ -182,30 +180,20 @@ struct d2d_engine {
     Buf<uint8_t> d_in, d_out;
     // planar copies of byte-interleaved inputs (one slice per file), see d2d_deinterleave_kernel
     Buf<uint8_t> d_planar;
-    bool deinterleave = false;
-    bool coop = false;                    // byte-interleaved 4/8-channel input de-interleaved inside the fp6 kernel's staging (FirArgs::coop)
-    // tap_bits = 32: the FIR runs twice into the scratch (the 24-bit table, then the residual table q32 - 256 q) and d2d_fine_combine_kernel
-    // finishes v = 256 v_hi + v_lo; the second half of the scratch, of the job table and `lo_*` belong to the second pass
-    bool fine = false;
-    bool taps32 = false;                  // tap_bits = 32 in ONE pass (round 4): stereo at M = 32 on the fp6 kernel's seven-digit flavour -- one table, no scratch, no combining pass
+    // route.fine (tap_bits = 32 in two passes): the second half of the scratch, of the job table and the residual table belong to the second pass
     std::vector<int32_t> lo_half;
     d2d_filter_def lo_def{};
     Buf<uint8_t> d_fir_tables_lo;
-    int mfma_pipe_lo = PIPE_NONE;
     // DSD64 / DSD128 -> 48k multiples: one polyphase pass over the bits (d2d_kernels_px.hip); fc.fir / fc.resamp only count frames then
     const d2d_poly_def* poly = nullptr;
-    bool poly_plain = false;              // ... through the bit-by-bit kernel (D2D_KERNEL_LUT engines)
     bool cascade() const { return fc.resamp && !poly; }      // the two-kernel 48k path (DSD256 / DSD512 input)
-    // MONO2 (round 4): a mono stream on the fp6 pipelined kernel as a planar PAIR -- the two halves of a call converted side by side (FirArgs::mono2);
-    // calls it does not fit (odd sizes, very short ones) take the engine's ordinary mono kernel: same bytes either way
-    bool mono2_ok = false;
-    int mono2_pipe = PIPE_NONE;           // PIPE_FP6: the fp6 kernel (M = 32, 64, 128), PIPE_INT8: the int8 pipelined kernel (M = 8, 16)
+    // route.mono2_pipe: calls the mono pair does not fit (odd sizes, very short ones) take the engine's ordinary mono kernel: same bytes either way
+    bool mono2_ok() const { return route.mono2_pipe != PIPE_NONE; }
     Buf<uint8_t> d_fir_tables_m2;
-    bool il2 = false;                     // byte-interleaved stereo input de-interleaved inside the pipelined frame kernels' staging (FirArgs::il2)
     LaunchState launch;
 
     // strides of the per-stream / per-file buffers, in elements: what the buffers hold, never a second record of it
-    size_t scratch_stride() const { return d_scratch.count() / ((size_t)nstreams * (fine ? 2u : 1u)); }
+    size_t scratch_stride() const { return d_scratch.count() / ((size_t)nstreams * (route.fine ? 2u : 1u)); }
     size_t ys_stride() const { return d_ys.count() / nstreams; }
     size_t planar_stride() const { return d_planar.bytes / n_files; }
 
@@ -243,8 +231,6 @@ static uint64_t rng_key64(uint64_t seed, uint32_t channel) {
     return z ^ (z >> 31);
 }
 
-static size_t sample_bytes_of(uint32_t bits) { return bits == 16 ? 2 : (bits == 32 ? 4 : 3); }
-
 static int validate(const d2d_params& p, std::string& err) {
     if (p.channels < 1 || p.channels > 64) { err = "Invalid channel count"; return D2D_ERR_PARAM; }
     if (p.bit_depth != 16 && p.bit_depth != 20 && p.bit_depth != 24 && p.bit_depth != 32) {
@@ -281,7 +267,7 @@ static int reset_state(d2d_engine* e) {
 // one file back to the device state of a fresh engine, in both ping-pong buffers; the other files' rows stay
 static int clear_file_state(d2d_engine* e, uint32_t file) {
     const size_t s0 = (size_t)file * e->C;
-    for (int b = 0; b < 2; ++b) HIPCHK(e, hipMemset(e->d_hist[b] + s0 * e->keep, idle_byte(e), (size_t)e->C * e->keep));
+    for (int b = 0; b < 2; ++b) HIPCHK(e, hipMemset(e->d_hist[b] + s0 * e->route.keep, idle_byte(e), (size_t)e->C * e->route.keep));
     HIPCHK(e, hipMemset(e->d_peak + s0, 0, sizeof(double) * e->C));
     if (e->d_scratch && e->xs_hist)     // the stage-A history in front of each of the file's scratch lines
         HIPCHK(e, hipMemset2D(e->d_scratch + s0 * e->scratch_stride(), e->scratch_stride() * sizeof(int32_t), 0, (size_t)e->xs_hist * sizeof(int32_t), e->C));
@@ -289,48 +275,26 @@ static int clear_file_state(d2d_engine* e, uint32_t file) {
     return D2D_OK;
 }
 
-// The part of a FIR launch's arguments that is fixed when the engine is created.  d2d_create also calls it on the half-built engine, to ask
-// mfma2_pipelined what would serve a format.
-static void fir_args_static(const d2d_engine* e, FirArgs& a, bool lo_pass = false) {
-    const d2d_filter_def& fd = lo_pass ? e->lo_def : *e->fc.fir;
-    a.tables = lo_pass ? e->d_fir_tables_lo : e->d_fir_tables;
-    a.Wb = (uint32_t)e->Wb;
-    a.ntab = (uint32_t)e->lut.ntab; a.pad = (uint32_t)e->lut.pad; a.nq = (uint32_t)e->lut.nq;
-    a.B = e->B; a.keep = e->keep;
-    a.to_scratch = (e->cascade() || e->noise_shape || e->fine) ? 1u : 0u;
-    a.ksteps = (uint32_t)e->mfma.ksteps;
-    a.scale_bits = e->S + (e->taps32 ? 8 : 0);
-    a.taps32 = e->taps32 ? 1u : 0u;
-    a.in_channels = e->Cin;
-    a.sum_abs_q = sum_abs_q(fd);
-    a.epi = e->epi;
-    a.pipelined = (uint32_t)(lo_pass ? e->mfma_pipe_lo : e->mfma_pipe);
-    a.mx_exact = mx_exact(fd) ? 1u : 0u;
-    a.coop = e->coop ? 1u : 0u;
-    a.il2 = e->il2 ? 1u : 0u;
-    a.dbg_flags = e->p.debug_flags;
-}
-
-// d2d_engine::launch, once il2, coop, taps32, mfma_pipe, mfma_pipe_lo and mono2_pipe are final and every table and the job table exist
+// d2d_engine::launch, once the route is chosen and every table and the job table exist
 static void build_launch_state(d2d_engine* e) {
     LaunchState& l = e->launch;
-    l.fir.jobs = e->d_jobs;
-    fir_args_static(e, l.fir);
-    if (e->fine) {
-        l.fir_lo.jobs = e->d_jobs + e->nstreams;
-        fir_args_static(e, l.fir_lo, true);
+    l.fir = fir_args_static(e->p, e->fc, e->epi, e->route);
+    l.fir.jobs = e->d_jobs; l.fir.tables = e->d_fir_tables;
+    if (e->route.fine) {
+        l.fir_lo = fir_args_static(e->p, e->fc, e->epi, e->route, &e->lo_def);
+        l.fir_lo.jobs = e->d_jobs + e->nstreams; l.fir_lo.tables = e->d_fir_tables_lo;
     }
-    if (e->mono2_ok) {
+    if (e->mono2_ok()) {
         l.fir_m2 = l.fir;
         l.fir_m2.jobs = e->d_jobs + e->nstreams; l.fir_m2.tables = e->d_fir_tables_m2;
         l.fir_m2.epi.channels = 2; l.fir_m2.in_channels = 2;
         l.fir_m2.B = 0x40000000u;     // (one "block" per half: the gather path's layout rule then reads half c at c * half)
-        l.fir_m2.pipelined = (uint32_t)e->mono2_pipe; l.fir_m2.mono2 = 1;
+        l.fir_m2.pipelined = (uint32_t)e->route.mono2_pipe; l.fir_m2.mono2 = 1;
     }
     l.px.jobs = e->d_jobs; l.px.tables = e->d_fir_tables;
-    l.px.in_channels = e->Cin; l.px.B = e->B; l.px.keep = e->keep; l.px.msb = e->p.endianness == D2D_MSB_FIRST ? 1u : 0u;
+    l.px.in_channels = e->Cin; l.px.B = e->route.B; l.px.keep = e->route.keep; l.px.msb = e->p.endianness == D2D_MSB_FIRST ? 1u : 0u;
     l.px.to_scratch = e->noise_shape ? 1u : 0u;
-    l.px.il2 = e->il2 ? 1u : 0u;
+    l.px.il2 = e->route.il2 ? 1u : 0u;
     l.px.epi = e->epi;
     l.rs.jobs = e->d_jobs; l.rs.tables = e->d_resamp;
     l.rs.S = e->S; l.rs.epi = e->epi;
@@ -348,73 +312,20 @@ static void build_launch_state(d2d_engine* e) {
 static int init_engine(d2d_engine* e) {
     int rc = validate(e->p, e->err);
     if (rc == D2D_OK) rc = choose_filters(e->p, e->fc, e->err);
+    if (rc == D2D_OK) rc = choose_route(e->p, e->fc, e->route, e->err);
     if (rc != D2D_OK) return rc;
     const d2d_filter_def& f = *e->fc.fir;
     e->M = f.M; e->Mb = f.M / 8; e->N = f.ntaps; e->Wb = f.ntaps / 8; e->S = f.S;
     e->Cin = e->p.channels;
-    e->C = e->p.channel_count ? e->p.channel_count : e->p.channels - e->p.channel_first;
+    e->epi = epilogue_of(e->p);
+    e->C = e->epi.channels;
     e->c0 = e->p.channel_first;
-    e->B = e->p.fmt == D2D_FMT_INTERLEAVED ? 1u : e->p.block_size;   // README.md:9
-    if (e->B == 1) {   // byte interleaved: mono is already planar; otherwise a planar copy is made per call
-        e->deinterleave = e->Cin > 1;
-        e->B = 4096;
-    }
     e->nstreams = e->n_files * e->C;
     e->files.resize(e->n_files);
-    e->epi.gain = pow(10.0, e->p.level_db / 20.0);
-    e->epi.scale = e->p.bit_depth == 32 ? e->epi.gain : ldexp(e->epi.gain, (int)e->p.bit_depth - 1);
-    e->epi.seed = e->p.seed;
-    e->epi.bits = e->p.bit_depth;
-    e->epi.dither = e->p.dither;
-    if (e->p.dither == 'N') {
-        if (e->p.bit_depth == 32) e->epi.dither = 'X';                     // float output: nothing to shape
-        else e->noise_shape = true;
-    }
-    if (e->p.tap_bits != 0 && e->p.tap_bits != 24 && e->p.tap_bits != 32) return e->fail(D2D_ERR_PARAM, "Invalid tap grid; must be 24 or 32 bits");
-    if (e->p.tap_bits == 32) {
-        if (e->fc.resamp || e->noise_shape) return e->fail(D2D_ERR_PARAM, "32-bit taps serve the 44.1k-family rates with dither T, R, F or X");
-        e->fine = true;
-        e->lo_def = residual_def(f, e->lo_half);
-    }
-    e->epi.sample_bytes = (uint32_t)sample_bytes_of(e->p.bit_depth);
-    e->epi.channels = e->C;
+    e->noise_shape = e->epi.dither == 'N';
     e->poly = e->fc.poly;
-    e->lut = lut_layout(e->Mb, e->Wb);
     e->mfma = mfma_layout(e->M, e->N);
-    uint32_t mfma_waves = 0;
-    bool mfma_ok = mfma_supported(e->M, e->N) &&
-                   mfma_smem_bytes(e->mfma, e->C, e->epi.sample_bytes, &mfma_waves) <= 160 * 1024;
-    {   // the two-group kernel wherever its shape is compiled and four waves fit in LDS (D2D_MFMA_V1=1: the older one)
-        const bool v1 = (e->p.debug_flags & D2D_DBG_MFMA_V1) != 0;
-        uint32_t w2 = 0;
-        if (!v1 && mfma2_supported(e->M, e->N) &&
-            mfma2_smem_bytes(e->M, e->N, e->C, e->epi.sample_bytes, &w2) <= 160 * 1024 && w2 >= 4) {
-            e->mfma_v2 = true; mfma_ok = true; mfma_waves = w2;
-        }
-        // M = 8 and 16: the two-group geometry only through the pipelined kernel (stereo 16/24-bit/float frames at 0 dB); every other
-        // format of those rates stays on the one-group kernel
-        if (!v1 && !e->mfma_v2 && (e->M < 32 || e->M == 128) && e->p.kernel != D2D_KERNEL_LUT) {
-            FirArgs a{}; fir_args_static(e, a);
-            if (mfma2_pipelined(a, e->M, e->N)) { e->mfma_v2 = true; mfma_ok = true; mfma_waves = 8; }
-        }
-    }
-    // AUTO: the matrix-core kernel whenever a full 4-wave block fits in LDS (it works per channel pair,
-    // so only an extremely long window can fail this; then the LUT kernel)
-    e->kernel = e->p.kernel == D2D_KERNEL_AUTO ? (mfma_ok && mfma_waves >= 4 ? D2D_KERNEL_MFMA : D2D_KERNEL_LUT) : e->p.kernel;
-    if (e->poly) {
-        // the matrix-core form wherever a kernel is compiled for the table and its digit sums are exact in f32 (all six shipped tables)
-        const bool px_ok = px_supported(*e->poly) && px_exact(*e->poly);
-        e->kernel = e->p.kernel == D2D_KERNEL_AUTO ? (px_ok ? D2D_KERNEL_MFMA : D2D_KERNEL_LUT) : e->p.kernel;
-        mfma_ok = px_ok;
-        e->poly_plain = e->kernel == D2D_KERNEL_LUT;
-        e->mfma_v2 = false;
-    }
-    if (e->kernel == D2D_KERNEL_MFMA && !mfma_ok)
-        return e->fail(D2D_ERR_PARAM, "MFMA kernel does not support this configuration (decimation or LDS budget)");
-    e->keep = (uint32_t)(e->Wb + e->Mb);
-    // (direct polyphase: the oldest bit an output of the next call can need lies NP - D + M bits before the call's first byte)
-    if (e->poly) e->keep = std::max<uint32_t>(e->keep, (uint32_t)((e->poly->NP - e->poly->D + e->M + 7) / 8 + 2));
-    e->keep = (e->keep + 15u) & ~15u;
+    const FirRoute& r = e->route;
 
     // ---- device side: fail loudly when there is no GPU ----
     int ndev = 0;
@@ -425,68 +336,35 @@ static int init_engine(d2d_engine* e) {
     if (e->p.device < 0 || e->p.device >= ndev) return e->fail(D2D_ERR_DEVICE, "Invalid device ordinal");
     HIPCHK(e, hipSetDevice(e->p.device));
     HIPCHK(e, hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
+    // ---- the tables the route names ----
     const bool msb = e->p.endianness == D2D_MSB_FIRST;
     if (e->poly) {
-        if (e->poly_plain) {
+        if (r.poly_plain) {
             HIPCHK(e, e->d_fir_tables.upload(e->poly->q, (size_t)e->poly->Lp * e->poly->NP * sizeof(int32_t)));
         } else {
-            // byte-interleaved stereo (DFF files, the CLI's default -f I): de-interleaved inside the kernel's staging, no planar copy (D2D_NO_COOP=1: the pre-pass)
-            if (e->deinterleave && e->Cin == 2 && e->C == 2 && !(e->p.debug_flags & D2D_DBG_NO_COOP)) { e->il2 = true; e->deinterleave = false; e->B = 1; }
             const std::vector<int8_t> t = build_px_tables(*e->poly);
             HIPCHK(e, e->d_fir_tables.upload(t.data(), t.size()));
         }
-    } else if (e->kernel == D2D_KERNEL_LUT) {
+    } else if (r.kernel == D2D_KERNEL_LUT) {
         const std::vector<double> t = build_lut_tables(f, e->Mb, msb);
         HIPCHK(e, e->d_fir_tables.upload(t.data(), t.size() * sizeof(double)));
-        if (e->fine) {
+    } else {
+        const std::vector<int8_t> t = build_fir_table(f, r.mfma_pipe, r.mfma_v2, e->mfma, msb, r.taps32);
+        HIPCHK(e, e->d_fir_tables.upload(t.data(), t.size()));
+    }
+    if (r.fine) {      // the residual table goes through the same builders
+        e->lo_def = residual_def(f, e->lo_half);
+        if (r.kernel == D2D_KERNEL_LUT) {
             const std::vector<double> tl = build_lut_tables(e->lo_def, e->Mb, msb);
             HIPCHK(e, e->d_fir_tables_lo.upload(tl.data(), tl.size() * sizeof(double)));
-        }
-    } else {
-        // 32-bit taps in ONE pass (round 4) where the fp6 kernel's seven-digit flavour is compiled for the table and its digit sums are exact: stereo frames,
-        // any depth, dither and level (D2D_DBG_TAPS32_2PASS: the two scratch passes and the combining pass, which serve everything else)
-        if (e->fine && e->mfma_v2 && e->C == 2 && e->Cin == 2 && mx_wide_supported(e->M / 8, e->N) && mx_wide_exact(f) &&
-            !(e->p.debug_flags & (D2D_DBG_TAPS32_2PASS | D2D_DBG_NO_MX | D2D_DBG_NO_PIPE | D2D_DBG_MFMA_V1 | D2D_DBG_NO_GAINQ))) {
-            e->fine = false; e->taps32 = true;
-        }
-        if (e->mfma_v2) { FirArgs a{}; fir_args_static(e, a); e->mfma_pipe = mfma2_pipelined(a, e->M, e->N); }
-        // byte-interleaved 4- or 8-channel input into the scratch (48k family, noise shaping) through the fp6 kernel: no planar copy, the
-        // kernel's staging de-interleaves (D2D_DBG_NO_COOP: the pre-pass)
-        {
-            const bool nocoop = (e->p.debug_flags & D2D_DBG_NO_COOP) != 0;
-            if (e->deinterleave && e->mfma_pipe == PIPE_FP6 && (e->fc.resamp || e->noise_shape) && !e->fine && e->C == e->Cin && (e->Cin == 8 || e->Cin == 4) &&
-                !nocoop) {
-                e->coop = true; e->deinterleave = false; e->B = 1;
-            }
-            // byte-interleaved stereo (DFF files, the CLI's default -f I) into frames through a pipelined kernel (fp6: M = 32, 64; int8: M = 8, 16):
-            // the same, inside one wave
-            // (the scratch flavours too: stereo DFF input into the 48k cascade and the noise shaper; not the two passes of 32-bit taps)
-            if (e->deinterleave && ((e->mfma_pipe == PIPE_FP6 || (e->mfma_pipe == PIPE_INT8 && e->M < 64)) && !e->fine) && e->Cin == 2 && e->C == 2 &&
-                !nocoop) {
-                e->il2 = true; e->deinterleave = false; e->B = 1;
-            }
-        }
-        const std::vector<int8_t> t = build_fir_table(f, e->mfma_pipe, e->mfma_v2, e->mfma, msb, e->taps32);
-        HIPCHK(e, e->d_fir_tables.upload(t.data(), t.size()));
-        if (e->fine) {
-            // the residual table goes through the same builders; which pipelined kernel serves it is decided on ITS digits
-            if (e->mfma_v2) { FirArgs a{}; fir_args_static(e, a, true); e->mfma_pipe_lo = mfma2_pipelined(a, e->M, e->N); }
-            const std::vector<int8_t> tl = build_fir_table(e->lo_def, e->mfma_pipe_lo, e->mfma_v2, e->mfma, msb, false);
+        } else {
+            const std::vector<int8_t> tl = build_fir_table(e->lo_def, r.mfma_pipe_lo, r.mfma_v2, e->mfma, msb, false);
             HIPCHK(e, e->d_fir_tables_lo.upload(tl.data(), tl.size()));
         }
     }
-    if (!e->poly && e->kernel == D2D_KERNEL_MFMA && e->Cin == 1 && e->C == 1 && !e->fine && !e->noise_shape && !e->fc.resamp &&
-        !(e->p.debug_flags & (D2D_DBG_NO_PIPE | D2D_DBG_MFMA_V1 | D2D_DBG_NO_MX))) {
-        // would the stereo conversion of this format run a pipelined kernel?  Then so can a mono stream, two halves of a call at a time
-        FirArgs a2{}; fir_args_static(e, a2);
-        a2.epi.channels = 2; a2.in_channels = 2;
-        const int p2 = mfma2_pipelined(a2, e->M, e->N);
-        if (p2 == PIPE_FP6 || p2 == PIPE_INT8) {
-            const std::vector<int8_t> t2 = build_fir_table(f, p2, true, e->mfma, msb, false);
-            e->mono2_pipe = p2;
-            HIPCHK(e, e->d_fir_tables_m2.upload(t2.data(), t2.size()));
-            e->mono2_ok = true;
-        }
+    if (e->mono2_ok()) {
+        const std::vector<int8_t> t2 = build_fir_table(f, r.mono2_pipe, true, e->mfma, msb, false);
+        HIPCHK(e, e->d_fir_tables_m2.upload(t2.data(), t2.size()));
     }
     // the scratch: a line of 4096 stage-A integers per stream (the cascade: behind the P carried ones; two-pass 32-bit taps: one line per pass)
     if (e->cascade()) {
@@ -494,15 +372,15 @@ static int init_engine(d2d_engine* e) {
         HIPCHK(e, e->d_resamp.upload(rt.data(), rt.size()));
         e->xs_hist = (uint32_t)e->fc.resamp->P;
     }
-    if (e->fine || e->cascade() || e->noise_shape)
-        HIPCHK(e, e->d_scratch.alloc(sizeof(int32_t) * ((size_t)e->xs_hist + 4096) * e->nstreams * (e->fine ? 2u : 1u)));
+    if (e->route.fine || e->cascade() || e->noise_shape)
+        HIPCHK(e, e->d_scratch.alloc(sizeof(int32_t) * ((size_t)e->xs_hist + 4096) * e->nstreams * (e->route.fine ? 2u : 1u)));
     if (e->noise_shape) {
         for (int i = 0; i < 2; ++i) HIPCHK(e, e->d_ns[i].alloc(sizeof(double) * 2 * e->nstreams));
         HIPCHK(e, e->d_ns_dump.alloc(1024));
     }
-    for (int b = 0; b < 2; ++b) HIPCHK(e, e->d_hist[b].alloc((size_t)e->nstreams * e->keep));
+    for (int b = 0; b < 2; ++b) HIPCHK(e, e->d_hist[b].alloc((size_t)e->nstreams * e->route.keep));
     HIPCHK(e, e->d_peak.alloc(sizeof(double) * e->nstreams));
-    e->launch.njobs = (size_t)e->nstreams * (e->fine ? 2u : e->mono2_ok ? 3u : 1u);
+    e->launch.njobs = (size_t)e->nstreams * (e->route.fine ? 2u : e->mono2_ok() ? 3u : 1u);
     HIPCHK(e, e->d_jobs.alloc(sizeof(StreamJob) * e->launch.njobs));
     HIPCHK(e, e->h_jobs.alloc(sizeof(StreamJob) * e->launch.njobs * JOB_SLOTS));
     for (int i = 0; i < JOB_SLOTS; ++i) HIPCHK(e, hipEventCreateWithFlags(&e->job_ev[i], hipEventDisableTiming));
@@ -568,7 +446,7 @@ static int grow_scratch(d2d_engine* e, size_t need_stride, hipStream_t s) {
     if (need_stride <= old) return D2D_OK;
     const size_t ns = (std::max(need_stride, old * 2) + 3) & ~(size_t)3;
     Buf<int32_t> nb;
-    HIPCHK(e, nb.alloc(sizeof(int32_t) * ns * e->nstreams * (e->fine ? 2u : 1u)));
+    HIPCHK(e, nb.alloc(sizeof(int32_t) * ns * e->nstreams * (e->route.fine ? 2u : 1u)));
     const size_t P = (size_t)e->xs_hist;
     if (P) HIPCHK(e, hipMemcpy2DAsync(nb, ns * sizeof(int32_t), e->d_scratch, old * sizeof(int32_t),
                                       P * sizeof(int32_t), e->nstreams, hipMemcpyDeviceToDevice, s));
@@ -608,7 +486,7 @@ int d2d_tell(const d2d_engine* e, uint32_t file, uint64_t* pos, uint64_t* next_f
 //   p - Mb - P Mb and its window reaches Wb further back: Wb + (P + 1) Mb.
 size_t d2d_preroll_bytes(const d2d_engine* e) {
     if (!e) return 0;
-    if (e->poly) return e->keep;
+    if (e->poly) return e->route.keep;
     if (e->cascade()) return (size_t)e->Wb + ((size_t)e->fc.resamp->P + 1) * (size_t)e->Mb;
     return (size_t)e->Wb + (size_t)e->Mb;
 }
@@ -647,7 +525,7 @@ static int plan_call(d2d_engine* e, d2d_file_io* io, const bool prime, CallPlan&
     pl.run_fir = !prime || e->cascade();
     pl.files.resize(n_files);
     // MONO2: every file's call splits into two equal halves of whole outputs and whole 16-byte chunks, long enough to hold the second half's history
-    pl.mono2 = e->mono2_ok;
+    pl.mono2 = e->mono2_ok();
     for (uint32_t f = 0; f < n_files; ++f) {
         const FileState& st = e->files[f];
         const size_t L = io[f].bytes_per_channel;
@@ -669,7 +547,7 @@ static int plan_call(d2d_engine* e, d2d_file_io* io, const bool prime, CallPlan&
         pl.max_L = std::max<uint32_t>(pl.max_L, (uint32_t)L);
         if (pl.mono2) {     // (a mono engine: file f is stream f, and the job's nout is the FIR's)
             const uint64_t half = L / 2, nout = pf.nfir1 - st.nfir;
-            pl.mono2 = (L % 2 == 0) && (half % 16 == 0) && (half % (uint64_t)e->Mb == 0) && half >= e->keep && (nout % 2 == 0) &&
+            pl.mono2 = (L % 2 == 0) && (half % 16 == 0) && (half % (uint64_t)e->Mb == 0) && half >= e->route.keep && (nout % 2 == 0) &&
                        (uint64_t)(uint32_t)st.nfir + (uint32_t)nout <= 0xFFFFFFFFull;
         }
     }
@@ -680,7 +558,7 @@ static int plan_call(d2d_engine* e, d2d_file_io* io, const bool prime, CallPlan&
 
 // Buffers: what the call's sizes ask of the scratch, the cascade's f64 line and the planar copy.  Each waits on the call's stream.
 static int reserve_call_buffers(d2d_engine* e, const CallPlan& pl, hipStream_t s, const bool prime) {
-    if (e->cascade() || e->noise_shape || e->fine) {
+    if (e->cascade() || e->noise_shape || e->route.fine) {
         int rc = grow_scratch(e, (size_t)e->xs_hist + (e->poly ? pl.max_frames : pl.max_nx), s);
         if (rc) return rc;
     }
@@ -688,7 +566,7 @@ static int reserve_call_buffers(d2d_engine* e, const CallPlan& pl, hipStream_t s
         const size_t ns = ((size_t)pl.max_frames + 8 + 1023) & ~(size_t)1023;
         HIPCHK(e, e->d_ys.reserve(sizeof(double) * ns * e->nstreams, wait_stream(s)));
     }
-    if (e->deinterleave) {
+    if (e->route.deinterleave) {
         const size_t need = (((size_t)pl.max_L * e->Cin) + 4095) & ~(size_t)4095;
         HIPCHK(e, e->d_planar.reserve(need * e->n_files, wait_stream(s)));
     }
@@ -712,10 +590,10 @@ static int enqueue_jobs(d2d_engine* e, const d2d_file_io* io, const CallPlan& pl
         for (uint32_t c = 0; c < C; ++c) {
             const uint32_t sidx = f * C + c;
             StreamJob& j = hj[sidx];
-            j.in = e->deinterleave ? e->d_planar + (size_t)f * planar_stride : (const uint8_t*)io[f].dsd;
-            j.in_raw = e->deinterleave ? (const uint8_t*)io[f].dsd : nullptr;
-            j.hist = e->d_hist[cur] + (size_t)sidx * e->keep;
-            j.hist_next = e->d_hist[cur ^ 1] + (size_t)sidx * e->keep;
+            j.in = e->route.deinterleave ? e->d_planar + (size_t)f * planar_stride : (const uint8_t*)io[f].dsd;
+            j.in_raw = e->route.deinterleave ? (const uint8_t*)io[f].dsd : nullptr;
+            j.hist = e->d_hist[cur] + (size_t)sidx * e->route.keep;
+            j.hist_next = e->d_hist[cur ^ 1] + (size_t)sidx * e->route.keep;
             j.out = prime ? nullptr : io[f].pcm;
             j.xs = e->d_scratch ? e->d_scratch + (size_t)sidx * scratch_stride + e->xs_hist : nullptr;
             j.peak = e->d_peak + sidx;
@@ -742,12 +620,12 @@ static int enqueue_jobs(d2d_engine* e, const d2d_file_io* io, const CallPlan& pl
             ja.L = half; ja.nout /= 2; ja.ch = 0; ja.och = 0;
             StreamJob jb = ja;
             jb.ch = 1;
-            jb.hist = ja.in + half - e->keep;                           // the end of the first half
+            jb.hist = ja.in + half - e->route.keep;                           // the end of the first half
             jb.out = (uint8_t*)ja.out + (size_t)ja.nout * fb;
             jb.rng_key = ja.rng_key + ja.nout;                          // (the kernel hashes (first half's index + key): the second half's indices lie nout further on)
             hj[e->nstreams + 2 * f] = ja; hj[e->nstreams + 2 * f + 1] = jb;
         }
-    if (e->fine)
+    if (e->route.fine)
         for (uint32_t i = 0; i < e->nstreams; ++i) { hj[e->nstreams + i] = hj[i]; hj[e->nstreams + i].xs = hj[i].xs + (size_t)e->nstreams * scratch_stride; }
     HIPCHK(e, hipMemcpyAsync(e->d_jobs, hj, sizeof(StreamJob) * e->launch.njobs, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipEventRecord(e->job_ev[slot], s));
@@ -757,10 +635,10 @@ static int enqueue_jobs(d2d_engine* e, const d2d_file_io* io, const CallPlan& pl
 
 // one FIR pass of a single-filter engine over every stream
 static int launch_fir_pass(d2d_engine* e, const FirArgs& a, uint32_t max_nx, hipStream_t s) {
-    if (e->kernel == D2D_KERNEL_LUT) {
+    if (e->route.kernel == D2D_KERNEL_LUT) {
         const uint32_t per_tile = lut_outputs_per_tile(e->Mb);
         HIPCHK(e, launch_fir_lut(a, e->Mb, (max_nx + per_tile - 1) / per_tile, e->nstreams, s));
-    } else if (e->mfma_v2) {
+    } else if (e->route.mfma_v2) {
         HIPCHK(e, launch_fir_mfma2(a, e->M, e->N, max_nx, e->nstreams, s));
     } else {
         HIPCHK(e, launch_fir_mfma(a, e->mfma, max_nx, e->nstreams, s));
@@ -774,13 +652,13 @@ static int launch_call(d2d_engine* e, const CallPlan& pl, hipStream_t s, const b
     const uint32_t n_files = e->n_files, max_nx = pl.max_nx, max_frames = pl.max_frames;
     EventPairs::Pair* ps = nullptr;
     if (e->profiling && (max_nx || (prime && pl.max_L))) HIPCHK(e, e->step.open(s, &ps));
-    if (e->deinterleave) HIPCHK(e, launch_deinterleave(e->d_jobs, n_files, e->Cin, e->C, pl.max_L, s));
+    if (e->route.deinterleave) HIPCHK(e, launch_deinterleave(e->d_jobs, n_files, e->Cin, e->C, pl.max_L, s));
 
     EventPairs::Pair* pe = nullptr;
     if (e->profiling && max_nx) HIPCHK(e, e->prof.open(s, &pe));
     if (e->poly) {
         PxArgs px = l.px;
-        if (e->poly_plain) HIPCHK(e, launch_poly_plain(px, *e->poly, max_frames, e->nstreams, s));
+        if (e->route.poly_plain) HIPCHK(e, launch_poly_plain(px, *e->poly, max_frames, e->nstreams, s));
         else HIPCHK(e, launch_fir_px(px, *e->poly, max_frames, n_files, s));
     } else if (pl.mono2) {
         HIPCHK(e, launch_fir_mfma2(l.fir_m2, e->M, e->N, max_nx / 2, 2 * n_files, s));
@@ -789,15 +667,15 @@ static int launch_call(d2d_engine* e, const CallPlan& pl, hipStream_t s, const b
         if (rc) return rc;
     }
     if ((e->poly ? max_frames : max_nx) && d2d_last_launched_kernel) e->launched = d2d_last_launched_kernel;
-    if (e->fine && max_nx) {
+    if (e->route.fine && max_nx) {
         // second pass: the residual taps, into the second half of the scratch
         int rc = launch_fir_pass(e, l.fir_lo, max_nx, s);
         if (rc) return rc;
     }
     if (pe) HIPCHK(e, hipEventRecord(pe->second, s));
-    if (e->fine && max_nx) {
+    if (e->route.fine && max_nx) {
         // the matrix-core kernels write 2 sum(q b) - 2^S, which is sum(q s) only for a table that sums to 2^S: the residual table sums to 0
-        const int64_t lo_bias = e->kernel == D2D_KERNEL_LUT ? 0 : ((int64_t)1 << e->S);
+        const int64_t lo_bias = e->route.kernel == D2D_KERNEL_LUT ? 0 : ((int64_t)1 << e->S);
         HIPCHK(e, launch_fine_combine(e->d_jobs, e->nstreams, max_nx, (size_t)e->nstreams * e->scratch_stride(), lo_bias, e->S + 8, e->epi, s));
     }
     if (e->cascade()) {
@@ -818,7 +696,7 @@ static int launch_call(d2d_engine* e, const CallPlan& pl, hipStream_t s, const b
         HIPCHK(e, launch_noise_shape(ns, s));
         e->ns_cur ^= 1;
     }
-    HIPCHK(e, launch_history(e->d_jobs, e->nstreams, e->Cin, e->B, e->keep, s));
+    HIPCHK(e, launch_history(e->d_jobs, e->nstreams, e->Cin, e->route.B, e->route.keep, s));
     if (ps) HIPCHK(e, hipEventRecord(ps->second, s));
     return D2D_OK;
 }
@@ -970,7 +848,7 @@ int d2d_translate_batch_host(d2d_engine* e, d2d_file_io* io, uint32_t n_files, s
     // whole planar blocks per slice, for ANY block size (-s takes any value, src/main.rs:75-78): every slice then
     // starts on a block-group boundary, which is what the kernels' addressing of a call assumes.  (No rounding to 16
     // bytes: the staging buffers are 256-byte aligned per file whatever the slice length.)
-    if (e->B > 1) slice = std::max<size_t>(e->B, slice / e->B * e->B);
+    if (e->route.B > 1) slice = std::max<size_t>(e->route.B, slice / e->route.B * e->route.B);
     size_t max_L = 0;
     // every file's whole call against its buffer before anything is staged: the pipeline below converts and downloads slice by slice, and a
     // buffer that only a later slice overflows would otherwise fail with earlier slices in the caller's memory and the files moved on
@@ -991,10 +869,10 @@ int d2d_translate_batch_host(d2d_engine* e, d2d_file_io* io, uint32_t n_files, s
         // of it at once (4 B per stage-A sample, 8 more per output where the two combine; two int32 halves with 32-bit taps) within half of
         // the free device memory -- otherwise the sliced pipeline below, which needs one slice of scratch
         bool direct = max_L < (1ull << 31);
-        if (direct && (e->cascade() || e->noise_shape || e->fine)) {
+        if (direct && (e->cascade() || e->noise_shape || e->route.fine)) {
             size_t free_b = 0, total_b = 0;
             HIPCHK(e, hipMemGetInfo(&free_b, &total_b));
-            const double per_stream = (double)max_L / (double)e->Mb * (e->cascade() && e->noise_shape ? 12.0 : e->fine ? 8.0 : 4.0);
+            const double per_stream = (double)max_L / (double)e->Mb * (e->cascade() && e->noise_shape ? 12.0 : e->route.fine ? 8.0 : 4.0);
             direct = per_stream * (double)e->nstreams < 0.5 * (double)free_b;
         }
         for (uint32_t f = 0; f < n_files && direct; ++f) {
@@ -1102,7 +980,7 @@ int d2d_convert_stream(d2d_engine* e, d2d_read_fn read, void* ru, d2d_write_fn w
     if (e->n_files != 1) return e->fail(D2D_ERR_STATE, "d2d_convert_stream needs a single-file engine");
     HIPCHK(e, hipSetDevice(e->p.device));
     if (chunk == 0) chunk = 1u << 22;
-    if (e->B > 1) chunk = std::max<size_t>(e->B, chunk / e->B * e->B);   // whole planar blocks per read
+    if (e->route.B > 1) chunk = std::max<size_t>(e->route.B, chunk / e->route.B * e->route.B);   // whole planar blocks per read
     // Pinned staging, two deep: while the GPU uploads, converts and downloads chunk k, the host reads
     // chunk k+1 and writes chunk k-1 (the callbacks are the file and sink I/O).
     const size_t fb = d2d_frame_bytes(e);
@@ -1206,10 +1084,10 @@ size_t d2d_tables_bytes(const d2d_engine* e) {
 
 static TableBlobHeader make_header(const d2d_engine* e) {
     TableBlobHeader h{};
-    h.magic = 0x54443244u; h.abi = D2D_ABI_VERSION; h.kernel = e->kernel; h.endianness = e->p.endianness;
+    h.magic = 0x54443244u; h.abi = D2D_ABI_VERSION; h.kernel = e->route.kernel; h.endianness = e->p.endianness;
     h.ntaps = (uint32_t)e->N; h.M = (uint32_t)e->M; h.scale_bits = (uint32_t)e->S; h.filter_type = (uint32_t)e->fc.fir->type;
-    h.table_variant = e->poly ? (e->poly_plain ? 7u : 6u) : e->kernel == D2D_KERNEL_MFMA && e->mfma_v2 ? (e->mfma_pipe ? (uint32_t)e->mfma_pipe : 2u) : 0u;
-    if (e->taps32) { h.table_variant = 8u; h.scale_bits = (uint32_t)(e->S + 8); }      // the seven-digit fragments of the 32-bit taps
+    h.table_variant = e->route.table_variant;
+    if (e->route.taps32) h.scale_bits = (uint32_t)(e->S + 8);      // the seven-digit fragments of the 32-bit taps
     if (e->poly) { h.ntaps = (uint32_t)e->poly->NP; h.M = (uint32_t)e->poly->Mp; h.scale_bits = (uint32_t)e->poly->S; h.filter_type = (uint32_t)'P'; }
     h.fir_bytes = e->d_fir_tables.bytes; h.resamp_bytes = e->d_resamp.bytes;
     return h;
@@ -1217,7 +1095,7 @@ static TableBlobHeader make_header(const d2d_engine* e) {
 
 int d2d_tables_export_device(d2d_engine* e, void* dst, size_t cap, void* hip_stream) {
     if (!e || !dst) return D2D_ERR_PARAM;
-    if (e->fine) return e->fail(D2D_ERR_STATE, "an engine with 32-bit taps holds two tap tables; the blob format carries one");
+    if (e->route.fine) return e->fail(D2D_ERR_STATE, "an engine with 32-bit taps holds two tap tables; the blob format carries one");
     if (cap < d2d_tables_bytes(e)) return e->fail(D2D_ERR_CAPACITY, "table blob buffer too small");
     HIPCHK(e, hipSetDevice(e->p.device));
     hipStream_t s = (hipStream_t)hip_stream;
@@ -1234,7 +1112,7 @@ int d2d_tables_export_device(d2d_engine* e, void* dst, size_t cap, void* hip_str
 
 int d2d_tables_import_device(d2d_engine* e, const void* src, size_t bytes, void* hip_stream) {
     if (!e || !src) return D2D_ERR_PARAM;
-    if (e->fine) return e->fail(D2D_ERR_STATE, "an engine with 32-bit taps holds two tap tables; the blob format carries one");
+    if (e->route.fine) return e->fail(D2D_ERR_STATE, "an engine with 32-bit taps holds two tap tables; the blob format carries one");
     if (bytes < d2d_tables_bytes(e)) return e->fail(D2D_ERR_PARAM, "table blob too small");
     HIPCHK(e, hipSetDevice(e->p.device));
     hipStream_t s = (hipStream_t)hip_stream;
@@ -1259,7 +1137,7 @@ int d2d_get_info(const d2d_engine* e, d2d_info* out) {
         out->decimation = 0; out->ntaps = (uint32_t)e->poly->NP; out->scale_bits = (uint32_t)e->poly->S;
         out->resamp_L = (uint32_t)e->poly->Lp; out->resamp_M = (uint32_t)e->poly->Mp; out->resamp_P = (uint32_t)e->poly->NP;
     }
-    out->kernel = e->kernel; out->abi_version = D2D_ABI_VERSION;
+    out->kernel = e->route.kernel; out->abi_version = D2D_ABI_VERSION;
     strncpy(out->filter_name, e->poly ? e->poly->name : e->fc.fir->name, sizeof(out->filter_name) - 1);
     return D2D_OK;
 }
@@ -1272,26 +1150,7 @@ void d2d_debug_stamps3(unsigned long long* out8) { hipDeviceSynchronize(); mfma3
 const char* d2d_kernel_name(const d2d_engine* e) {
     if (!e) return "";
     if (!e->launched.empty()) return e->launched.c_str();      // what the last call launched; before the first call: what the dispatch will choose
-    auto num = [](long v) { return std::to_string(v); };
-    const int dkind = e->epi.dither == 'T' ? 1 : e->epi.dither == 'R' ? 2 : 0;
-    const bool scr = e->fc.resamp || e->noise_shape;           // the kernel writes integers to the scratch, not frames
-    if (e->poly) {
-        if (e->poly_plain) return "d2d_poly_plain_kernel";
-        const bool intq = e->epi.gain == 1.0 && (e->epi.bits == 24 || e->epi.bits == 16) && e->epi.dither != 'F';
-        const int kind = e->noise_shape ? 4 : !intq ? 3 : dkind;
-        e->kname = "d2d_fir_px_kernel<" + num(e->poly->Lp) + ", " + num(e->poly->Mp) + ", " + num(e->poly->NP) + ", " + num(px_groups(*e->poly)) + ", " +
-                   num(kind) + ">";
-    } else if (e->kernel != D2D_KERNEL_MFMA || !e->mfma_v2) {
-        return e->kernel == D2D_KERNEL_LUT ? lut_kernel_name(e->Mb) : mfma_kernel_name(e->mfma);
-    } else if (e->mfma_pipe == PIPE_FP6) {
-        e->kname = "d2d_fir_mx_kernel<" + num(e->Mb) + ", " + num(e->N) + ", " + num(mx_groups(e->Mb)) + ", " +
-                   num(scr || e->epi.sample_bytes == 4 ? 0 : dkind) + ", " + num(scr ? 0u : e->epi.sample_bytes) + ">";
-    } else if (e->mfma_pipe == PIPE_INT8) {
-        e->kname = "d2d_fir_mfma3_kernel<" + num(e->Mb) + ", " + num(mfma2_pairs(e->M, e->N)) + ", 0, " + num(scr ? 0 : dkind) + ", " +
-                   num(scr ? 0u : e->epi.sample_bytes) + ">";
-    } else {
-        e->kname = "d2d_fir_mfma2_kernel<" + num(e->Mb) + ", " + num(mfma2_pairs(e->M, e->N)) + ", " + num(e->C == 1 ? 1 : 2) + ">";
-    }
+    if (e->kname.empty()) e->kname = route_kernel_name(e->route, e->fc, e->epi);
     return e->kname.c_str();
 }
 

@@ -570,16 +570,6 @@ hipError_t launch_fir_lut(const FirArgs& a, int MB, uint32_t max_tiles, uint32_t
 
 uint32_t lut_outputs_per_tile(int MB) { return LUT_THREADS * (MB >= 8 ? 1 : 8 / MB); }
 
-const char* lut_kernel_name(int MB) {
-    switch (MB) {
-        case 1: return "d2d_fir_lut_kernel<1>";
-        case 2: return "d2d_fir_lut_kernel<2>";
-        case 4: return "d2d_fir_lut_kernel<4>";
-        case 8: return "d2d_fir_lut_kernel<8>";
-        default: return "d2d_fir_lut_kernel<16>";
-    }
-}
-
 hipError_t launch_deinterleave(const StreamJob* jobs, uint32_t nfiles, uint32_t C, uint32_t spf, uint32_t max_L, hipStream_t s) {
     if (nfiles == 0 || max_L == 0) return hipSuccess;
     uint32_t gx = (max_L + DI_TILE - 1) / DI_TILE;

@@ -32,7 +32,7 @@
 
 #include "d2d_device.h"
 #include "d2d_launch.h"
-#include "d2d_mfma.h"
+#include "d2d_route.h"
 
 namespace d2d {
 
@@ -43,37 +43,8 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 constexpr int MFMA_MAX_THREADS = 768;   // 12 waves = 3 per SIMD, what 168 VGPRs allow
 constexpr int MFMA_PF = 3;   // 16-byte chunks per lane fetched one wave-tile ahead
 
-// Diagnostics (phase ablations, in-kernel cycle stamps, start staggering, the MFMA-phase token) exist
-// only in a build with -DD2D_DIAG=1 (make DIAG=1); the production kernel carries none of their state.
-#ifndef D2D_DIAG
-#define D2D_DIAG 0
-#endif
-
 // diagnostic build only (D2D_DBG bit 4): wave-cycles per phase, summed over all waves
 __device__ unsigned long long d2d_stamp_acc[8];
-
-struct MfmaArgs {
-    FirArgs f;
-    double c1, c0;        // x = fma(acc128, c1, -c0) == round(y*c0): c1 = 2^(1-S-7)*c0, c0 = scale | gain | 1
-    // integer-depth epilogue as data: d = fma(term, dmul, dadd), clamp to [qmin_i, qmax_i], << qsh
-    double dmul, dadd;
-    uint32_t dsel;        // 1: triangular term, 0: rectangular term
-    uint32_t dkind;       // 0: no dither, 1: triangular, 2: rectangular (chooses the register epilogue's instantiation)
-    uint32_t qsh;         // 4 for 20-bit samples in a 24-bit container, else 0
-    int32_t qmin_i, qmax_i;
-    uint32_t wide;        // 1: limb sums may exceed 2^23, recombine in f64
-    uint32_t U;           // dwords of row window per lane half; K steps = 2U
-    uint32_t span;        // logical staged bytes per channel (multiple of 16)
-    uint32_t ppair;       // physical LDS bytes per channel PAIR (dword-interleaved, padded rows)
-    uint32_t ls;          // log2(row stride in dwords) = log2(2*MB)
-    uint32_t off_waves;   // LDS: start of the per-wave regions (after the shared tap table)
-    uint32_t wave_lds;    // LDS bytes per wave
-    uint32_t off_out, off_pk;   // inside a wave's region
-    uint32_t nwaves;      // waves per block
-    uint32_t ngroups;     // channel groups per file: 1 for mono/stereo, else one block column per channel PAIR
-    uint32_t dbg;         // diagnostic ablation mask (env D2D_DBG), 0 in production
-    uint32_t stagger;     // start offset between wave slots, in units of 1024 cycles
-};
 
 __device__ __forceinline__ void wave_sync() {
     // LDS operations of one wave execute in order; this only stops the compiler from moving them.
@@ -610,61 +581,7 @@ __global__ __launch_bounds__(MFMA_MAX_THREADS, 3) void d2d_fir_mfma_kernel(MfmaA
 
 // ---- host side -------------------------------------------------------------------------------
 
-bool mfma_supported(int M, int N) {
-    (void)N;
-    return M == 8 || M == 16 || M == 32 || M == 64 || M == 128;
-}
-
-static void mfma_geometry(const FirArgs& a, const MfmaLayout& g, MfmaArgs& m, size_t& smem) {
-    // channels per block: all of a mono/stereo file, one pair of a multichannel one
-    m.ngroups = a.epi.channels <= 2 ? 1u : (a.epi.channels + 1u) / 2u;
-    const uint32_t C = a.epi.channels <= 2 ? a.epi.channels : 2u;
-    const int MB = g.M / 8;
-    m.f = a;
-    m.c0 = a.to_scratch ? ldexp(1.0, a.scale_bits) : (a.epi.bits == 32 ? a.epi.gain : a.epi.scale);   // scratch: the integer y*2^S
-    m.c1 = ldexp(m.c0, 1 - a.scale_bits - 7);     // exact: a power-of-two multiple of c0
-    m.dsel = a.epi.dither == 'T' ? 1u : 0u;
-    m.dkind = a.epi.dither == 'T' ? 1u : (a.epi.dither == 'R' ? 2u : 0u);
-    m.dmul = a.epi.dither == 'T' ? 0x1p-16 : (a.epi.dither == 'R' ? 0x1p-17 : 0.0);
-    m.dadd = a.epi.dither == 'T' ? -1.0 : (a.epi.dither == 'R' ? -0.5 : 0.0);
-    m.qsh = a.epi.bits == 20 ? 4u : 0u;
-    m.qmin_i = a.epi.bits == 32 ? 0 : -(1 << (a.epi.bits - 1)); m.qmax_i = a.epi.bits == 32 ? 0 : (1 << (a.epi.bits - 1)) - 1;
-    m.U = (uint32_t)g.ksteps / 2;
-    // |limb sum| <= (bytes of row window) * 255 * 128; below 2^23 the pairs recombine in int32
-    m.wide = (uint64_t)g.ksteps * 4u * 255u * 128u >= (1u << 23) ? 1u : 0u;
-    int ls = 0;
-    while ((1 << ls) < 2 * MB) ++ls;
-    m.ls = (uint32_t)ls;
-    // logical staged bytes per channel: 16-byte alignment slack + 31 row strides + one row window
-    // (+3 dwords read ahead) + slack for the in-register byte realignment
-    m.span = (16u + 31u * 8u * MB + (2 * m.U + 5) * 4u + 16u + 15u) & ~15u;
-    const uint32_t ldw = m.span / 4;
-    m.ppair = ((2u * (ldw + (ldw >> ls) + 2u)) * 4u + 15u) & ~15u;
-    m.off_waves = ((uint32_t)g.ksteps + 6u) * 1024u + 64u;   // + MFMA-phase tokens
-    m.off_out = ((C + 1) / 2) * m.ppair;
-    m.off_pk = m.off_out + ((256u * C * a.epi.sample_bytes + 15u) & ~15u);
-    m.wave_lds = m.off_pk + C * 64u * 8u + ((C * 16u + 15u) & ~15u);   // peaks + per-channel dither keys
-#if D2D_DIAG
-    { static const char* e = getenv("D2D_DBG"); m.dbg = e ? (uint32_t)atoi(e) : 0u; }          // (make DIAG=1 builds only: never the shipped library)
-    { static const char* e = getenv("D2D_STAGGER"); m.stagger = e ? (uint32_t)atoi(e) : 0u; }
-#endif
-    const uint32_t wdbg = (a.dbg_flags >> 8) & 0xFFu;      // diagnostic override (d2d_params.debug_flags bits 8..15)
-    m.nwaves = wdbg ? wdbg : 12u;
-    if (m.nwaves < 1 || m.nwaves > 12) m.nwaves = 12;
-    // largest block that fits the CU's LDS, keeping the waves evenly spread over the four SIMDs
-    while (m.nwaves > 1 && (size_t)m.off_waves + (size_t)m.nwaves * m.wave_lds > 160 * 1024)
-        m.nwaves = m.nwaves > 8 ? 8 : m.nwaves > 4 ? 4 : m.nwaves >> 1;
-    smem = (size_t)m.off_waves + (size_t)m.nwaves * m.wave_lds;
-}
-
-size_t mfma_smem_bytes(const MfmaLayout& g, uint32_t channels, uint32_t sample_bytes, uint32_t* waves_per_block) {
-    FirArgs a{};
-    a.epi.channels = channels; a.epi.sample_bytes = sample_bytes; a.epi.bits = 24;
-    MfmaArgs m{}; size_t smem = 0;
-    mfma_geometry(a, g, m, smem);
-    if (waves_per_block) *waves_per_block = m.nwaves;
-    return smem;
-}
+// (mfma_supported, mfma_geometry: d2d_route.cpp)
 
 template <int MB>
 static hipError_t launch_mfma_t(const MfmaArgs& m, size_t smem, uint32_t nwt_max, uint32_t nfiles, hipStream_t s) {
@@ -705,16 +622,6 @@ void mfma_debug_stamps(unsigned long long out[8]) {
     (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(d2d_stamp_acc), sizeof(unsigned long long) * 8);
     unsigned long long z[8] = {0};
     (void)hipMemcpyToSymbol(HIP_SYMBOL(d2d_stamp_acc), z, sizeof(z));
-}
-
-const char* mfma_kernel_name(const MfmaLayout& g) {
-    switch (g.M / 8) {
-        case 1: return "d2d_fir_mfma_kernel<1>";
-        case 2: return "d2d_fir_mfma_kernel<2>";
-        case 4: return "d2d_fir_mfma_kernel<4>";
-        case 8: return "d2d_fir_mfma_kernel<8>";
-        default: return "d2d_fir_mfma_kernel<16>";
-    }
 }
 
 }  // namespace d2d

@@ -25,9 +25,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "d2d_m3.h"
 #include "d2d_mfma2_dev.h"
-#include "d2d_mx.h"
+#include "d2d_route.h"
 
 namespace d2d {
 
@@ -598,146 +597,7 @@ __global__ __launch_bounds__(D2D_M2_THREADS) void d2d_fir_mfma2_kernel(Mfma2Args
 
 // ---- host side -------------------------------------------------------------------------------
 
-// (MB, NPG) pairs with a compiled kernel
-// M = 32 and 64 only: with 1 or 2 bytes per output a 512-output tile holds so little stream that the per-tile work
-// (staging, waits, the epilogue) outweighs the shorter chain and the one-group kernel is faster (measured: DSD64 -> 352.8 kHz
-// float 451 against 514 Gsamples/s, the M = 8 stage A of the 48k cascade 4.7 against 3.8 ms)
-#define D2D_M2_SHAPES(X) X(4, 10) X(4, 12) X(4, 13) X(8, 19) X(8, 24) X(8, 25)
-
-bool mfma2_supported(int M, int N) {
-    const int MB = M / 8, NPG = mfma2_pairs(M, N);
-#define X(mb, npg) if (MB == mb && NPG == npg) return true;
-    D2D_M2_SHAPES(X)
-#undef X
-    return false;
-}
-
-// the epilogue flavour of a launch: 2 = the integers for the stage-A scratch, 1 = stereo 24-bit packed in registers, 0 = anything via LDS
-static int mfma2_epilogue(const FirArgs& a, const Mfma2Args& m) {
-    if (a.to_scratch) return 2;
-    return a.epi.channels == 2 && a.epi.sample_bytes == 3 && m.qsh == 0 && !m.wide ? 1 : 0;
-}
-
-// the pipelined kernel serves the register-packed stereo flavour with the all-integer requantiser; its accumulators start
-// from -2^(S-18) in the limb-3 rows
-static bool mfma3_eligible(const FirArgs& a, const Mfma2Args& m, int MB, int NPG, int NT) {
-    // stereo, 24-bit packed or 16-bit frames, the all-integer requantiser (unit gain)
-    // the exact integers for the stage-A scratch: every channel pair of an even channel count
-    if (a.to_scratch) return a.epi.channels >= 2 && a.epi.channels % 2 == 0 && !m.wide && a.scale_bits >= 18 && a.scale_bits <= 30 &&
-                             a.sum_abs_q != 0 && a.sum_abs_q < (1ull << 31) && mfma3_scr_supported(MB, NPG);
-    const bool frames_ok = !a.to_scratch && a.epi.channels == 2 && (a.epi.sample_bytes == 3 || a.epi.sample_bytes == 2) && m.qsh == 0 && !m.wide;
-    const bool shape_ok = a.scale_bits >= 18 && a.scale_bits <= 30 && mfma3_supported(MB, NPG, NT);
-    // ... or 32-bit float at 0 dB without the float dither: the sample is (float)v * 2^-S
-    const bool noint = (a.dbg_flags & D2D_DBG_NO_INTQ) != 0;
-    const bool float_ok = !noint && !a.to_scratch && a.epi.channels == 2 && a.epi.bits == 32 && a.epi.dither != 'F' && a.epi.gain == 1.0 && !m.wide &&
-                          a.sum_abs_q != 0 && a.sum_abs_q < (1ull << 31);
-    // (M = 8 float frames too since the pipelined kernel stages that shape's frames through LDS: 4.18 against 4.50 ms on the one-group kernel)
-    if (float_ok && shape_ok) return true;
-    if (m.gainq && shape_ok && MB < 4) return true;            // another level in dB, M = 8 and 16: the f64 requantiser inside the pipelined epilogue
-    return frames_ok && m.intq && shape_ok;
-}
-
-static void mfma2_geometry(const FirArgs& a, int MB, int NPG, Mfma2Args& m, size_t& smem);
-
-// Planar frames of an even channel count above two on the fp6 kernel: a wave converts every pair of a tile and stores whole frames
-// (d2d_kernels_mx.hip, NPR).  The pairs per wave, or 1.  (Byte-interleaved multichannel input reaches the kernel as the engine's planar copy.)
-static uint32_t mx_pairs(const FirArgs& a, int MB, int N) {
-    const uint32_t C = a.epi.channels;
-    if (a.to_scratch || a.mono2 || a.il2 || a.coop || C < 4 || C % 2) return 1u;
-    if (a.B < 16 || (a.B & (a.B - 1)) != 0) return 1u;
-    return mx_pairs_supported(MB, N, (int)(C / 2u)) ? C / 2u : 1u;
-}
-
-// the same conversions as mfma3_eligible, shape apart (the caller checks mx_supported and the engine mx_exact)
-static bool mx_eligible(const FirArgs& a, const Mfma2Args& m, int MB, int N) {
-    const bool range_ok = a.scale_bits >= 20 && a.scale_bits <= 30 && a.sum_abs_q != 0 && a.sum_abs_q < (1ull << 31) && a.mx_exact;
-    if (a.to_scratch) return a.epi.channels >= 2 && a.epi.channels % 2 == 0 && range_ok;
-    const bool noint = (a.dbg_flags & D2D_DBG_NO_INTQ) != 0;
-    const bool stereo = (a.epi.channels == 2 || mx_pairs(a, MB, N) > 1u) && m.qsh == 0;       // (or whole frames of several pairs)
-    const bool float_ok = !noint && stereo && a.epi.bits == 32 && a.epi.dither != 'F' && a.epi.gain == 1.0;
-    const bool frames_ok = stereo && (a.epi.sample_bytes == 3 || a.epi.sample_bytes == 2) && m.intq;
-    return range_ok && (float_ok || frames_ok);
-}
-
-int mfma2_pipelined(const FirArgs& a, int M, int N) {
-    if (a.taps32) return PIPE_FP6;                            // (the engine has checked mx_wide_supported and mx_wide_exact)
-    if (a.dbg_flags & D2D_DBG_NO_PIPE) return PIPE_NONE;
-    const int MB = M / 8, NPG = mfma2_pairs(M, N);
-    const bool nomx = (a.dbg_flags & D2D_DBG_NO_MX) != 0;
-    Mfma2Args m{}; size_t smem = 0;
-    mfma2_geometry(a, MB, NPG, m, smem);
-    // M = 128 (DSD256 -> 88.2 kHz, DSD512 -> 176.4 kHz): only the fp6 kernel has the LDS for that tap table; its conditions are its own
-    // (S = 30: no biased accumulators, and the int8 kernels' limb-sum bound `wide` does not apply)
-    if (MB == 16) {
-        const bool noint16 = (a.dbg_flags & D2D_DBG_NO_INTQ) != 0;
-        const bool range_ok = a.scale_bits >= 20 && a.scale_bits <= 30 && a.sum_abs_q != 0 && a.sum_abs_q < (1ull << 31) && a.mx_exact;
-        if (nomx || !mx_supported(MB, N) || !range_ok || noint16) return PIPE_NONE;
-        if (a.to_scratch) return a.epi.channels >= 2 && a.epi.channels % 2 == 0 ? PIPE_FP6 : PIPE_NONE;
-        const bool depth_ok = a.epi.bits == 32 ? true : ((a.epi.bits == 24 || a.epi.bits == 20 || a.epi.bits == 16) && m.fbits > 0 && m.fbits <= 16 && a.epi.dither != 'F');
-        const bool mp = mx_pairs(a, MB, N) > 1u;
-        if ((a.epi.channels != 2 && !mp) || !depth_ok || a.epi.dither == 'N') return PIPE_NONE;
-        if (a.epi.gain == 1.0 && m.qsh == 0 && !(a.epi.bits == 32 && a.epi.dither == 'F')) return PIPE_FP6;
-        if (mp) return PIPE_NONE;                                  // (several pairs per wave: unit gain only)
-        return mx_gain_supported(MB, N) && !(a.dbg_flags & D2D_DBG_NO_GAINQ) ? PIPE_FP6 : PIPE_NONE;
-    }
-    // the fp6 x fp4 kernel (d2d_kernels_mx.hip) serves what the pipelined int8 kernel serves at M = 32 and 64
-    if (!nomx && mx_supported(MB, N) && mx_eligible(a, m, MB, N)) return PIPE_FP6;
-    // ... and stereo frames at another level than 0 dB (its gain flavours)
-    if (!nomx && m.gainq && mx_gain_supported(MB, N) && a.mx_exact && a.scale_bits >= 20 && a.scale_bits <= 30 && (a.epi.bits == 32 || a.epi.sample_bytes == 2 || a.epi.sample_bytes == 3)) return PIPE_FP6;
-    if (!mfma2_supported(M, N) && !mfma3_supported(MB, NPG, N) && !(a.to_scratch && mfma3_scr_supported(MB, NPG))) return PIPE_NONE;
-    if (!mfma3_eligible(a, m, MB, NPG, N)) return PIPE_NONE;
-    return PIPE_INT8;
-}
-
-static void mfma2_geometry(const FirArgs& a, int MB, int NPG, Mfma2Args& m, size_t& smem) {
-    m.ngroups = a.epi.channels <= 2 ? 1u : (a.epi.channels + 1u) / 2u;
-    m.npairs = 1u;
-    const uint32_t C = a.epi.channels <= 2 ? a.epi.channels : 2u;
-    m.f = a;
-    m.c0 = a.to_scratch ? ldexp(1.0, a.scale_bits) : (a.epi.bits == 32 ? a.epi.gain : a.epi.scale);   // scratch: the integer y*2^S
-    m.c1 = ldexp(m.c0, 1 - a.scale_bits - 7);     // exact: a power-of-two multiple of c0
-    m.dkind = a.epi.dither == 'T' ? 1u : (a.epi.dither == 'R' ? 2u : 0u);
-    m.dmul = a.epi.dither == 'T' ? 0x1p-16 : (a.epi.dither == 'R' ? 0x1p-17 : 0.0);
-    m.dadd = a.epi.dither == 'T' ? -1.0 : (a.epi.dither == 'R' ? -0.5 : 0.0);
-    m.qsh = a.epi.bits == 20 ? 4u : 0u;
-    m.qmin_i = a.epi.bits == 32 ? 0 : -(1 << (a.epi.bits - 1)); m.qmax_i = a.epi.bits == 32 ? 0 : (1 << (a.epi.bits - 1)) - 1;
-    // |limb sum| <= (bytes of a group's window) * 255 * 128; below 2^23 the pairs recombine in int32
-    m.wide = m2_unmask0(NPG) ? 0u : ((uint64_t)NPG * 8u * 255u * 128u >= (1u << 23) ? 1u : 0u);
-    m.fbits = a.scale_bits - ((int)a.epi.bits - 1);
-    const bool noint = (a.dbg_flags & D2D_DBG_NO_INTQ) != 0;
-    // (the fast form carries v0 = v + 2^S in an int32: 2^S + sum|q| has to stay below 2^31)
-    m.intq = (!noint && !a.to_scratch && a.epi.bits != 32 && a.epi.gain == 1.0 && !m.wide && m.fbits > 0 && m.fbits <= 16 &&
-              a.sum_abs_q != 0 && (1ull << a.scale_bits) + a.sum_abs_q < (1ull << 31)) ? 1u : 0u;
-    // stereo 16/24-bit (dither T, R, none) or float (no float dither) frames at another level than 0 dB, and 20-bit frames and the float dither (the CLI's default for -b 32) at any level
-    // (the all-integer requantiser has no 20-in-24 form; the f64 one shifts its result)
-    m.gainq = (!noint && !(a.dbg_flags & D2D_DBG_NO_GAINQ) && !a.to_scratch && a.epi.channels == 2 && (a.epi.gain != 1.0 || m.qsh != 0 || (a.epi.bits == 32 && a.epi.dither == 'F')) && !m.wide &&
-               (a.epi.dither != 'F' || a.epi.bits == 32) && a.epi.dither != 'N' && (a.epi.bits == 32 || (m.fbits > 0 && m.fbits <= 16)) && a.sum_abs_q != 0 && a.sum_abs_q < (1ull << 31)) ? 1u : 0u;
-    m.off_waves = (uint32_t)(2 * NPG) * 1024u;
-    m.off_out = (uint32_t)m2_stream_bytes(MB, NPG);
-    // (only the LDS-staged epilogue needs the output slice)
-    const bool lds_out = mfma2_epilogue(a, m) == 0;
-    m.wave_lds = m.off_out + (lds_out ? (((uint32_t)M2_TILE * C * a.epi.sample_bytes + 15u) & ~15u) : 0u);
-#if D2D_DIAG
-    { static const char* e = getenv("D2D_DBG"); m.dbg = e ? (uint32_t)atoi(e) : 0u; }     // (make DIAG=1 builds only: never the shipped library)
-#endif
-    const uint32_t wdbg = (a.dbg_flags >> 8) & 0xFFu;      // diagnostic override (d2d_params.debug_flags bits 8..15)
-    m.nwaves = wdbg ? wdbg : 12u;
-    if (m.nwaves < 1 || m.nwaves > 12) m.nwaves = 12;
-    // largest block that fits the CU's LDS, keeping the waves evenly spread over the four SIMDs
-    while (m.nwaves > 1 && (size_t)m.off_waves + (size_t)m.nwaves * m.wave_lds > 160 * 1024)
-        m.nwaves = m.nwaves > 8 ? 8 : m.nwaves > 4 ? 4 : m.nwaves >> 1;
-    smem = (size_t)m.off_waves + (size_t)m.nwaves * m.wave_lds;
-}
-
-size_t mfma2_smem_bytes(int M, int N, uint32_t channels, uint32_t sample_bytes, uint32_t* waves_per_block) {
-    FirArgs a{};
-    a.epi.channels = channels; a.epi.sample_bytes = sample_bytes; a.epi.bits = 24;
-    Mfma2Args m{}; size_t smem = 0;
-    mfma2_geometry(a, M / 8, mfma2_pairs(M, N), m, smem);
-    if (waves_per_block) *waves_per_block = m.nwaves;
-    return smem;
-}
-
+// (which launch goes where and its geometry: d2d_route.cpp)
 template <int MB, int NPG, int CH, int EPI>
 static hipError_t launch_mfma2_t(Mfma2Args& m, size_t smem, uint32_t nwt_max, uint32_t nrows, hipStream_t s) {
     static KernelPrep prep;
@@ -788,14 +648,10 @@ hipError_t launch_fir_mfma2(const FirArgs& a, int M, int N, uint32_t max_nout, u
     const int MB = M / 8, NPG = mfma2_pairs(M, N);
     Mfma2Args m{};
     size_t smem = 0;
-    mfma2_geometry(a, MB, NPG, m, smem);
+    mfma2_launch_args(a, MB, NPG, N, m, smem);
     const uint32_t nrows = (nstreams / C) * m.ngroups;       // grid rows: one per (file, channel group)
-    if (a.pipelined == PIPE_FP6) {                           // the fp6 kernel has its own LDS layout (and M = 128 no two-group one at all)
-        m.npairs = mx_pairs(a, MB, N);
-        if (m.npairs > 1u) return launch_fir_mx(m, MB, N, max_nout, nstreams / C, s);     // one block row per file
-        if (MB == 16) m.gainq = (!a.to_scratch && (a.epi.gain != 1.0 || m.qsh != 0 || (a.epi.bits == 32 && a.epi.dither == 'F'))) ? 1u : 0u;
-        return launch_fir_mx(m, MB, N, max_nout, nrows, s);
-    }
+    // the fp6 kernel has its own LDS layout (and M = 128 no two-group one at all); several pairs per wave: one block row per file
+    if (a.pipelined == PIPE_FP6) return launch_fir_mx(m, MB, N, max_nout, m.npairs > 1u ? nstreams / C : nrows, s);
     if (smem > 160 * 1024) return hipErrorInvalidValue;
     const uint32_t nwt = (max_nout + (M2_TILE - 1)) / M2_TILE;
     // the epilogue flavour: the integers for the stage-A scratch, stereo 24-bit packed in registers, or anything via LDS

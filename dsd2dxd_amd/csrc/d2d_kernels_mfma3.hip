@@ -22,9 +22,10 @@
 //
 // Replaces: the per-block translate loop inside Rdsd2Pcm::do_conversion
 // (/root/reference/src/main.rs:345,429); the crate that holds it is absent from the reference.
-#include <vector>
+#include <array>
 
 #include "d2d_m3_kernel.h"
+#include "d2d_route.h"
 
 namespace d2d {
 
@@ -39,30 +40,20 @@ D2D_M3_UNIT_LIST(X)
 #undef X
 template hipError_t launch_m3_unit<0>(Mfma2Args& m, uint32_t nwt_max, uint32_t nrows, hipStream_t s);
 
-struct M3Row { int MB, NPG, nt[2]; hipError_t (*fn)(Mfma2Args&, uint32_t, uint32_t, hipStream_t); };
-static const std::vector<M3Row>& m3_rows() {
-    static const std::vector<M3Row> rows = [] {
-        std::vector<M3Row> v;
-#define X(unit, mb, npg, nt0, nt1) if constexpr (m3_unit_kept(mb, npg)) v.push_back({mb, npg, {nt0, nt1}, &launch_m3_unit<unit>});
-        D2D_M3_UNIT_LIST(X)
+// one launcher per unit number (null: a unit an A/B build leaves out); which unit serves a shape: d2d_route.cpp
+typedef hipError_t (*M3Launch)(Mfma2Args&, uint32_t, uint32_t, hipStream_t);
+static const std::array<M3Launch, D2D_M3_UNITS> m3_launchers = [] {
+    std::array<M3Launch, D2D_M3_UNITS> v{};
+#define X(unit, mb, npg, nt0, nt1) if constexpr (m3_unit_kept(mb, npg)) std::get<unit>(v) = &launch_m3_unit<unit>;
+    D2D_M3_UNIT_LIST(X)
 #undef X
-        return v;
-    }();
-    return rows;
-}
-// the row of a shape (one at most), and whether it serves frames with NT taps
-static const M3Row* m3_find(int MB, int NPG) {
-    for (const M3Row& r : m3_rows()) if (r.MB == MB && r.NPG == NPG) return &r;
-    return nullptr;
-}
-static bool m3_frames(const M3Row* r, int NT) { return r && NT > 0 && (r->nt[0] == NT || r->nt[1] == NT); }
-bool mfma3_scr_supported(int MB, int NPG) { return m3_find(MB, NPG) != nullptr; }
-bool mfma3_supported(int MB, int NPG, int NT) { return m3_frames(m3_find(MB, NPG), NT); }
+    return v;
+}();
 
 hipError_t launch_fir_mfma3(Mfma2Args& m, int MB, int NPG, int NT, uint32_t nwt_max, uint32_t nrows, hipStream_t s) {
-    const M3Row* r = m3_find(MB, NPG);
-    if (!r || (!m.f.to_scratch && !m3_frames(r, NT))) return hipErrorInvalidValue;
-    return r->fn(m, nwt_max, nrows, s);
+    const int u = m3_find(MB, NPG);
+    if (u < 0 || !m3_launchers[u] || (!m.f.to_scratch && !m3_frames(u, NT))) return hipErrorInvalidValue;
+    return m3_launchers[u](m, nwt_max, nrows, s);
 }
 
 #if D2D_M3_STAMPS

@@ -28,7 +28,10 @@
 //
 // Replaces: the per-block translate loop inside Rdsd2Pcm::do_conversion
 // (/root/reference/src/main.rs:345,429); the crate that holds it is absent from the reference.
+#include <array>
+
 #include "d2d_mx_kernel.h"
+#include "d2d_route.h"
 
 namespace d2d {
 
@@ -42,34 +45,20 @@ D2D_MX_UNIT_LIST(X)
 #undef X
 template hipError_t launch_mx_unit<0>(Mfma2Args& m, uint32_t max_nout, uint32_t nrows, hipStream_t s);
 
-struct MxRow { int MB, NT; MxFlavour fl; int npr; hipError_t (*fn)(Mfma2Args&, uint32_t, uint32_t, hipStream_t); };
-static const std::vector<MxRow>& mx_rows() {
-    static const std::vector<MxRow> rows = [] {
-        std::vector<MxRow> v;
-#define X(unit, mb, nt, fl, npr) if constexpr (mx_unit_kept(mb, nt)) v.push_back({mb, nt, fl, npr, &launch_mx_unit<unit>});
-        D2D_MX_UNIT_LIST(X)
+// one launcher per unit number (null: a unit an A/B build leaves out); which unit serves a launch: d2d_route.cpp
+typedef hipError_t (*MxLaunch)(Mfma2Args&, uint32_t, uint32_t, hipStream_t);
+static const std::array<MxLaunch, D2D_MX_UNITS> mx_launchers = [] {
+    std::array<MxLaunch, D2D_MX_UNITS> v{};
+#define X(unit, mb, nt, fl, npr) if constexpr (mx_unit_kept(mb, nt)) std::get<unit>(v) = &launch_mx_unit<unit>;
+    D2D_MX_UNIT_LIST(X)
 #undef X
-        return v;
-    }();
-    return rows;
-}
-static const MxRow* mx_find(int MB, int NT, MxFlavour fl, int npr) {
-    for (const MxRow& r : mx_rows()) if (r.MB == MB && r.NT == NT && r.fl == fl && r.npr == npr) return &r;
-    return nullptr;
-}
-bool mx_supported(int MB, int NT) { return mx_find(MB, NT, MX_INT, 1) != nullptr; }
-bool mx_pairs_supported(int MB, int NT, int npairs) { return npairs > 1 && mx_find(MB, NT, MX_INT, npairs) != nullptr; }
-bool mx_wide_supported(int MB, int NT) { return mx_find(MB, NT, MX_WIDE, 1) != nullptr; }
-bool mx_gain_supported(int MB, int NT) { return mx_find(MB, NT, MX_GAIN, 1) != nullptr; }
+    return v;
+}();
 
 hipError_t launch_fir_mx(Mfma2Args& m, int MB, int NT, uint32_t max_nout, uint32_t nrows, hipStream_t s) {
-    const MxRow* r = m.f.taps32 ? mx_find(MB, NT, MX_WIDE, 1)
-                   : m.npairs > 1 ? mx_find(MB, NT, MX_INT, (int)m.npairs)
-                   : m.gainq && !m.f.to_scratch ? mx_find(MB, NT, MX_GAIN, 1)
-                   : mx_find(MB, NT, MX_INT, 1);
-    return r ? r->fn(m, max_nout, nrows, s) : hipErrorInvalidValue;
+    const int u = mx_launch_unit(m, MB, NT);
+    return u >= 0 && mx_launchers[u] ? mx_launchers[u](m, max_nout, nrows, s) : hipErrorInvalidValue;
 }
-int mx_groups(int MB) { return mx_g(MB); }
 #if D2D_MX_STAMPS
 void mx_debug_stamps(unsigned long long out[8]) {
     (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(d2d_mx_stamps), sizeof(unsigned long long) * 8);

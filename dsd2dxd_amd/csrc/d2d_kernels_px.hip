@@ -23,7 +23,10 @@
 //
 // Replaces: the 48 kHz-family path inside Rdsd2Pcm::do_conversion (/root/reference/src/main.rs:345,429); the crate that holds it is
 // absent from the reference.
+#include <array>
+
 #include "d2d_px_kernel.h"
+#include "d2d_route.h"
 
 namespace d2d {
 
@@ -36,15 +39,15 @@ D2D_PX_UNIT_LIST(X)
 #undef X
 template hipError_t launch_px_unit<0>(PxArgs& a, uint32_t max_nout, uint32_t nfiles, hipStream_t s);
 
-struct PxRow { int Lp, Mp, NP, G; hipError_t (*fn)(PxArgs&, uint32_t, uint32_t, hipStream_t); };
-static const PxRow* px_find(const d2d_poly_def& p) {
-#define X(unit, lp, mp, np, g) {lp, mp, np, g, &launch_px_unit<unit>},
-    static const PxRow rows[] = {D2D_PX_UNIT_LIST(X)};
+// one launcher per unit number; which unit serves a table: d2d_route.cpp
+typedef hipError_t (*PxLaunch)(PxArgs&, uint32_t, uint32_t, hipStream_t);
+static const std::array<PxLaunch, D2D_PX_UNITS> px_launchers = [] {
+    std::array<PxLaunch, D2D_PX_UNITS> v{};
+#define X(unit, lp, mp, np, g) std::get<unit>(v) = &launch_px_unit<unit>;
+    D2D_PX_UNIT_LIST(X)
 #undef X
-    for (const PxRow& r : rows) if (p.Lp == r.Lp && p.Mp == r.Mp && p.NP == r.NP) return &r;
-    return nullptr;
-}
-bool px_supported(const d2d_poly_def& p) { return px_find(p) != nullptr; }
+    return v;
+}();
 
 // ---- the plain form: one output per lane, bit by bit ----
 constexpr int PXP_THREADS = 256;
@@ -116,8 +119,8 @@ hipError_t launch_fir_px(PxArgs& a, const d2d_poly_def& p, uint32_t max_nout, ui
     a.qmin_i = a.epi.bits == 32 ? 0 : -(1 << (a.epi.bits - 1));
     a.qmax_i = a.epi.bits == 32 ? 0 : (1 << (a.epi.bits - 1)) - 1;
     a.qsh = a.epi.bits == 20 ? 4u : 0u;
-    const PxRow* r = px_find(p);
-    return r ? r->fn(a, max_nout, nfiles, s) : hipErrorInvalidValue;
+    const int u = px_find(p);
+    return u >= 0 ? px_launchers[u](a, max_nout, nfiles, s) : hipErrorInvalidValue;
 }
 
 }  // namespace d2d

@@ -91,7 +91,6 @@ inline const char* launched_name(const char* base) {
 
 size_t lut_smem_bytes(const FirArgs& a, int MB);
 uint32_t lut_outputs_per_tile(int MB);
-const char* lut_kernel_name(int MB);
 hipError_t launch_fir_lut(const FirArgs& a, int MB, uint32_t max_tiles, uint32_t nstreams, hipStream_t s);
 hipError_t launch_resample2(Rs2Args& a, const d2d_resamp_def& r, uint32_t max_out, uint32_t nfiles, hipStream_t s);
 hipError_t launch_deinterleave(const StreamJob* jobs, uint32_t nfiles, uint32_t C, uint32_t streams_per_file, uint32_t max_L, hipStream_t s);

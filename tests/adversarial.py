@@ -221,7 +221,7 @@ def build_poly(name, T=64, seed=0, rot=(0, 1)):
 
 # ---- which table a conversion runs, and the tile of the kernel that serves it in production ----
 # T, outputs per tile of the production kernel for stereo frames:
-#   M = 8, 16        the int8 pipelined kernel: M2_TILE = 512 (d2d_mfma2_dev.h)
+#   M = 8, 16        the int8 pipelined kernel: M2_TILE = 512 (d2d_mfma.h)
 #   M = 32, 64, 128  the fp6 kernel: TILE = 32 PH G with PH = 6 phases and G = mx_g(MB) = 3 / 2 / 1 groups (d2d_mx.h, d2d_mx_kernel.h): 576 / 384 / 192
 #   tap_bits = 32    the fp6 kernel's seven-digit flavour: PH = 4, the same G: 384 / 256
 #   polyphase        d2d_fir_px_kernel: TILE = 160 G = 5 * 32 * groups, G from D2D_PX_UNIT_LIST (d2d_px.h)

@@ -42,7 +42,7 @@ def tile_of(kernel):
     if name == "d2d_fir_px_kernel":
         return 160 * a[3]                                    # TILE = 5 * 32 * G (d2d_px_kernel.h)
     if name in ("d2d_fir_mfma3_kernel", "d2d_fir_mfma2_kernel", "d2d_fir_mfma_kernel"):
-        return 512                                           # M2_TILE (d2d_mfma2_dev.h); the one-group kernel's tile of 256 divides it
+        return 512                                           # M2_TILE (d2d_mfma.h); the one-group kernel's tile of 256 divides it
     assert name in ("d2d_fir_lut_kernel", "d2d_poly_plain_kernel"), kernel
     return 64                                                # one output per lane: no tile structure
 

@@ -20,11 +20,14 @@ MX_UNITS=$(sed -n 's/^MX_UNITS = //p' $CS/Makefile); PX_UNITS=$(sed -n 's/^PX_UN
 COUNTS="-DD2D_MX_UNITS=$MX_UNITS -DD2D_PX_UNITS=$PX_UNITS -DD2D_M3_UNITS=$M3_UNITS"
 mx_unit_of() { grep -o "X([0-9]*, $1)" $CS/d2d_mx.h | sed 's/X(\([0-9]*\),.*/\1/'; }     # the unit of the row "MB, NT, flavour, NPR"
 mx_unit() { $HIPCC $FL -DD2D_MX_UNIT=$1 "${@:2}" -c $CS/d2d_mx_unit.hip -o $O/d2d_mx_unit$1.o; }
+DEV=       # the flag that leaves units out of a dispatcher: the route unit's lookups need it too, or they name units the dispatcher does not hold
 case $TARGET in
-  mx)      $HIPCC $FL $COUNTS -DD2D_MX_DEV=1 "$@" -c $CS/d2d_kernels_mx.hip -o $O/d2d_kernels_mx.o &
+  mx)      DEV=-DD2D_MX_DEV=1
+           $HIPCC $FL $COUNTS $DEV "$@" -c $CS/d2d_kernels_mx.hip -o $O/d2d_kernels_mx.o &
            mx_unit $(mx_unit_of "4, 560, MX_GAIN, 1") "$@"; wait ;;
   mxm)     mx_unit $(mx_unit_of "4, 560, MX_INT, 3") "$@" ;;
-  mfma3)   $HIPCC $FL $COUNTS -DD2D_M3_DEV=1 "$@" -c $CS/d2d_kernels_mfma3.hip -o $O/d2d_kernels_mfma3.o ;;
+  mfma3)   DEV=-DD2D_M3_DEV=1
+           $HIPCC $FL $COUNTS $DEV "$@" -c $CS/d2d_kernels_mfma3.hip -o $O/d2d_kernels_mfma3.o ;;
   px)      $HIPCC $FL $COUNTS "$@" -c $CS/d2d_kernels_px.hip -o $O/d2d_kernels_px.o &
            for i in $(seq 1 $((PX_UNITS - 1))); do $HIPCC $FL -DD2D_PX_UNIT=$i "$@" -c $CS/d2d_px_unit.hip -o $O/d2d_px_unit$i.o & done; wait ;;
   kernels) $HIPCC $FL "$@" -c $CS/d2d_kernels.hip -o $O/d2d_kernels.o ;;
@@ -32,9 +35,11 @@ case $TARGET in
 esac
 # (the engine sees the geometry macros too: groups per column name the kernel)
 $HIPCC $FL -x hip "$@" -c $CS/d2d_engine.cpp -o $O/d2d_engine.o
+# ... and so does the choice of the route (the lists of kept units, the groups per column)
+g++ -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I$CS -I$ROOT/filters $DEV "$@" -c $CS/d2d_route.cpp -o $O/d2d_route.o
 # the tree's objects, each replaced by the one just built where there is one
 OBJS=
-for n in d2d_kernels d2d_kernels_rs d2d_kernels_mfma d2d_kernels_mfma2 d2d_engine \
+for n in d2d_kernels d2d_kernels_rs d2d_kernels_mfma d2d_kernels_mfma2 d2d_engine d2d_tables d2d_route \
          d2d_kernels_mfma3 $(for i in $(seq 1 $((M3_UNITS - 1))); do echo d2d_m3_unit$i; done) \
          d2d_kernels_mx $(for i in $(seq 1 $((MX_UNITS - 1))); do echo d2d_mx_unit$i; done) \
          d2d_kernels_px $(for i in $(seq 1 $((PX_UNITS - 1))); do echo d2d_px_unit$i; done) \

@@ -4,15 +4,17 @@
     python tools/engine_matrix.py OUT.jsonl [--every N]      (the library: D2D_AMD_LIB, else the tree's)
 
 For every configuration of the sweep an engine is created and the line holds either the create error (code and text) or kernel_name() before
-any call, info(), frame_bytes, tables_bytes(), preroll_bytes(), slice_align_bytes(), the sha256 of the exported table blob (or the refusal),
-and after one translate of two 4096-byte blocks per channel of seeded random input the sha256 of the output, the frame count, the peaks and
-kernel_name() again.  A change of host code that must leave every create-time decision, table, job table and launch argument alone gives the
-same file with the library before and after it (`cmp`).  --every N keeps one configuration in N (a quick look)."""
+any call, info(), frame_bytes, tables_bytes(), preroll_bytes(), slice_align_bytes(), the sha256 of the exported table blob and the kernel,
+table_variant and fir_bytes of its header (or the refusal), and after one translate of two 4096-byte blocks per channel of seeded random
+input the sha256 of the output, the frame count, the peaks and kernel_name() again.  A change of host code that must leave every create-time
+decision, table, job table and launch argument alone gives the same file with the library before and after it (`cmp`).  --every N keeps
+one configuration in N (a quick look)."""
 import argparse
 import hashlib
 import itertools
 import json
 import os
+import struct
 import sys
 
 import numpy as np
@@ -57,7 +59,10 @@ def describe(cfg, data):
     try:
         e.tables_export_device(blob.data_ptr(), nb)
         torch.cuda.synchronize()
-        row["tables"] = hashlib.sha256(blob.cpu().numpy().tobytes()).hexdigest()
+        raw = blob.cpu().numpy().tobytes()
+        row["tables"] = hashlib.sha256(raw).hexdigest()
+        kernel, variant, fir_bytes = struct.unpack_from("<8xI20xI4xQ", raw)          # TableBlobHeader (d2d_internal.h)
+        row["header"] = dict(kernel=kernel, table_variant=variant, fir_bytes=fir_bytes)
     except d.D2DError as ex:
         row["tables"] = [ex.code, ex.message]
     pcm, frames = e.translate(data[:2 * 4096 * cfg["channels"]])
@@ -67,12 +72,16 @@ def describe(cfg, data):
     return row
 
 
+def call_buffer():
+    return np.random.default_rng(206).integers(0, 256, 2 * 4096 * 8, dtype=np.uint8)     # (any byte string is a call buffer in either layout)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("out")
     ap.add_argument("--every", type=int, default=1)
     args = ap.parse_args()
-    data = np.random.default_rng(206).integers(0, 256, 2 * 4096 * 8, dtype=np.uint8)     # (any byte string is a call buffer in either layout)
+    data = call_buffer()
     n = 0
     with open(args.out, "w") as f:
         for i, cfg in enumerate(configurations()):
