@@ -52,6 +52,24 @@ class Info(C.Structure):
                 ("kernel", C.c_uint32), ("abi_version", C.c_uint32), ("filter_name", C.c_char * 32)]
 
 
+class FlacResult(C.Structure):
+    _fields_ = [("bytes_out", C.c_uint64), ("min_frame_bytes", C.c_uint32), ("max_frame_bytes", C.c_uint32)]
+
+
+class FlacIO(C.Structure):
+    """d2d_flac_io: one file of a d2d_flac_encode_device call (DEVICE pointers; `result` device or pinned host)"""
+    _fields_ = [("pcm", C.c_void_p), ("frames", C.c_size_t), ("first_block", C.c_uint32), ("final", C.c_int32),
+                ("out", C.c_void_p), ("out_capacity_bytes", C.c_size_t), ("result", C.c_void_p),
+                ("blocks", C.c_size_t), ("frames_consumed", C.c_size_t)]
+
+
+class FlacStreamStats(C.Structure):
+    _fields_ = [("samples_per_channel", C.c_uint64), ("blocks", C.c_uint64),
+                ("min_frame_bytes", C.c_uint32), ("max_frame_bytes", C.c_uint32)]
+
+
+FLAC_BLOCK = 4096
+
 READ_FN = C.CFUNCTYPE(C.c_long, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t)
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_float)
@@ -62,7 +80,9 @@ EXPORTS = ["d2d_create", "d2d_create_error", "d2d_destroy", "d2d_reset", "d2d_la
            "d2d_peak", "d2d_peak_dbfs", "d2d_convert_stream", "d2d_tables_bytes",
            "d2d_tables_export_device", "d2d_tables_import_device", "d2d_get_info", "d2d_kernel_name",
            "d2d_profile_enable", "d2d_profile_read", "d2d_profile_read_all",
-           "d2d_seek", "d2d_tell", "d2d_preroll_bytes", "d2d_slice_align_bytes", "d2d_prime", "d2d_prime_batch_device"]
+           "d2d_seek", "d2d_tell", "d2d_preroll_bytes", "d2d_slice_align_bytes", "d2d_prime", "d2d_prime_batch_device",
+           "d2d_flac_bound_bytes", "d2d_flac_workspace_bytes", "d2d_flac_encode_device", "d2d_flac_error",
+           "d2d_flac_encode_host", "d2d_convert_stream_flac"]
 
 _lib = None
 
@@ -122,8 +142,52 @@ def lib():
     L.d2d_slice_align_bytes.restype = C.c_size_t
     L.d2d_prime.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.d2d_prime_batch_device.argtypes = [C.c_void_p, C.POINTER(FileIO), C.c_uint32, C.c_void_p]
+    L.d2d_flac_bound_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_size_t, C.c_int]
+    L.d2d_flac_bound_bytes.restype = C.c_size_t
+    L.d2d_flac_workspace_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_size_t, C.c_int]
+    L.d2d_flac_workspace_bytes.restype = C.c_size_t
+    L.d2d_flac_encode_device.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(FlacIO), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.d2d_flac_error.restype = C.c_char_p
+    L.d2d_flac_encode_host.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t,
+                                       C.POINTER(FlacResult), C.POINTER(C.c_size_t)]
+    L.d2d_convert_stream_flac.argtypes = [C.c_void_p, C.c_uint32, READ_FN, C.c_void_p, WRITE_FN, C.c_void_p, C.POINTER(C.c_int),
+                                          PROGRESS_FN, C.c_void_p, C.c_uint64, C.c_size_t, C.POINTER(FlacStreamStats)]
     _lib = L
     return L
+
+
+def _flac_check(rc):
+    if rc:
+        raise D2DError(rc, lib().d2d_flac_error().decode())
+
+
+def flac_bound_bytes(channels, bit_depth, frames, final):
+    return lib().d2d_flac_bound_bytes(channels, bit_depth, frames, int(bool(final)))
+
+
+def flac_workspace_bytes(channels, bit_depth, frames, final):
+    return lib().d2d_flac_workspace_bytes(channels, bit_depth, frames, int(bool(final)))
+
+
+def flac_encode_host(channels, bit_depth, pcm, first_block=0, final=True, capacity=None):
+    """d2d_flac_encode_host on a bytes-like of interleaved little-endian frames: the sink's own encoder, no device.
+    Returns (frame bytes, FlacResult, frames_consumed)."""
+    import numpy as np
+    buf = np.ascontiguousarray(np.frombuffer(pcm, dtype=np.uint8) if not isinstance(pcm, np.ndarray) else pcm.view(np.uint8).reshape(-1))
+    fb = channels * (2 if bit_depth == 16 else 3)
+    frames = buf.size // fb if fb else 0
+    cap = flac_bound_bytes(channels, bit_depth, frames, final) if capacity is None else capacity
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    res, used = FlacResult(), C.c_size_t()
+    _flac_check(lib().d2d_flac_encode_host(channels, bit_depth, buf.ctypes.data, frames, first_block, int(bool(final)),
+                                           out.ctypes.data, cap, C.byref(res), C.byref(used)))
+    return out[:res.bytes_out].tobytes(), res, used.value
+
+
+def flac_encode_device(channels, bit_depth, ios, workspace_ptr, workspace_bytes, stream=None):
+    """d2d_flac_encode_device: ios is a ctypes array of FlacIO with DEVICE pointers; asynchronous on `stream` (hipStream_t int)."""
+    _flac_check(lib().d2d_flac_encode_device(channels, bit_depth, ios, len(ios), C.c_void_p(workspace_ptr), workspace_bytes,
+                                             C.c_void_p(stream or 0)))
 
 
 class D2DError(Exception):
@@ -306,3 +370,29 @@ class Engine:
         cflag = cancel if cancel is not None else C.c_int(0)
         self._check(lib().d2d_convert_stream(self._h, keep["r"], None, keep["w"], None, C.byref(cflag),
                                              keep["p"], None, total_bytes_per_channel, chunk_bytes_per_channel))
+
+    def convert_stream_flac(self, read, write, total_bytes_per_channel=0, chunk_bytes_per_channel=1 << 22,
+                            cancel=None, progress=None):
+        """d2d_convert_stream_flac: as convert_stream, but write() receives FLAC frames (whole frames, in order); returns the
+        FlacStreamStats STREAMINFO needs.  Errors carry d2d_flac_error()'s message."""
+        def _read(_u, dst, cap):
+            data = read(cap)
+            if not data:
+                return 0
+            C.memmove(dst, data, len(data))
+            return len(data) // self.channels
+
+        def _write(_u, p, n):
+            write(C.string_at(p, n))
+            return 0
+
+        def _prog(_u, pct):
+            if progress:
+                progress(pct)
+
+        r, w, p = READ_FN(_read), WRITE_FN(_write), PROGRESS_FN(_prog)
+        cflag = cancel if cancel is not None else C.c_int(0)
+        stats = FlacStreamStats()
+        _flac_check(lib().d2d_convert_stream_flac(self._h, self.params.bit_depth, r, None, w, None, C.byref(cflag), p, None,
+                                                  total_bytes_per_channel, chunk_bytes_per_channel, C.byref(stats)))
+        return stats

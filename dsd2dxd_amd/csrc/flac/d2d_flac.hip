@@ -1,0 +1,525 @@
+// d2d_flac.hip -- FLAC frames on the GPU (gfx950): the kernels behind d2d_flac_encode_device, and d2d_convert_stream_flac on top
+// of the public calls.  The bitstream is the one flac_frame_enc.h defines; tests/test_gpu_flac.py compares them byte for byte.
+//
+//   flac_encode_kernel<CH>   one workgroup of 1024 threads per (file, block); thread t owns samples 4t .. 4t+3 of every channel.
+//     1. the block's PCM comes into LDS with 16-byte loads (4096 * frame_bytes is a multiple of 16; a short block's tail by bytes)
+//     2. residuals r = s[i] - 2 s[i-1] + s[i-2] stay in registers; sum |r| per channel is reduced over the workgroup (64-bit) and
+//        thread c derives k[c]
+//     3. code lengths, one exclusive scan per channel over the threads, channel c starting where channel c-1 ended: every bit
+//        position of the frame is known before a bit is placed
+//     4. the LDS that held the PCM is zeroed and becomes the frame image (big-endian 32-bit words); each code ORs in its stop bit and
+//        its k low bits (ds_or_b32), the unary zeros are the fill, so arrival order cannot matter
+//     5. CRC-16 in parallel: init 0 makes the CRC linear and blind to leading zeros, so the frame is treated as 1024 equal chunks
+//        with zeros in front, every thread runs the table over its chunk, and a tree combines  crc(A|B) = crc(A) x^(8 len B) + crc(B)
+//     6. the image goes to the block's workspace slot (16-byte stores), its size to the size table
+//   flac_pack_kernel        per file, 32 blocks per workgroup: sums the sizes in front of its blocks, copies the slots to `out`
+//                            contiguously; the first workgroup of a file writes the result record.
+// The two run one after the other on the caller's stream.  No workgroup waits on another: no look-back, no flags, no spinning.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+#include <vector>
+
+#include "d2d_flac_internal.h"
+
+using namespace d2dflac;
+
+namespace {
+
+constexpr int NT = 1024;          // threads of an encode workgroup
+constexpr int NW = NT / 64;
+constexpr int SPT = BS / NT;      // samples per thread and channel
+constexpr int MAXF = 16;          // files per launch: their descriptors ride in the kernel arguments
+constexpr int PT = 256;           // threads of a pack workgroup
+constexpr uint32_t PB = 32;       // blocks per pack workgroup
+
+struct FileDesc {
+    const uint8_t* pcm;
+    uint8_t* out;
+    d2d_flac_result* result;
+    uint32_t* sizes;              // workspace: one size per block
+    uint8_t* slots;               // workspace: one slot per block
+    uint32_t blocks, first_block, last_n, pad;      // last_n: samples of the last block (4096, or the short one)
+};
+struct FlacArgs {
+    FileDesc f[MAXF];
+    uint32_t depth, slot_bytes;
+};
+
+__device__ __forceinline__ uint32_t utf8_len(uint32_t v) { return v < 0x80 ? 1 : v < 0x800 ? 2 : v < 0x10000 ? 3 : v < 0x200000 ? 4 : v < 0x4000000 ? 5 : 6; }
+
+// `len` (1..32) bits of `val` at bit `pos` of the image, most significant bit first
+__device__ __forceinline__ void put_bits(uint32_t* img, uint32_t pos, uint32_t val, uint32_t len) {
+    const uint32_t w = pos >> 5, o = pos & 31;
+    const uint64_t v = (uint64_t)val << (64 - o - len);
+    const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
+    if (hi) atomicOr(&img[w], hi);
+    if (lo) atomicOr(&img[w + 1], lo);
+}
+
+// a * b in GF(2)[x] / (x^16 + x^15 + x^2 + 1)
+__device__ __forceinline__ uint32_t gf_mul(uint32_t a, uint32_t b) {
+    uint32_t r = 0;
+    for (int i = 15; i >= 0; --i) {
+        r <<= 1;
+        if (r & 0x10000u) r ^= 0x18005u;
+        if ((b >> i) & 1u) r ^= a;
+    }
+    return r;
+}
+__device__ __forceinline__ uint32_t gf_xpow(uint32_t e) {     // x^e
+    uint32_t r = 1, base = 2;
+    for (; e; e >>= 1) { if (e & 1u) r = gf_mul(r, base); base = gf_mul(base, base); }
+    return r;
+}
+
+template <int CH>
+__global__ __launch_bounds__(NT) void flac_encode_kernel(const FlacArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];          // the block's PCM, then the frame image
+    __shared__ unsigned long long s_wsum[NW][CH];
+    __shared__ uint32_t s_wtot[NW][CH];
+    __shared__ uint32_t s_k[CH];
+    __shared__ uint16_t s_crc_tab[256];
+    __shared__ uint16_t s_crc[NT];
+    __shared__ uint8_t s_hdr[16];
+
+    const FileDesc& fd = a.f[blockIdx.y];
+    const uint32_t b = blockIdx.x;
+    if (b >= fd.blocks) return;                                     // (the whole workgroup)
+    const uint32_t n = b + 1 == fd.blocks ? fd.last_n : BS;
+    const uint32_t depth = a.depth, sb = depth == 16 ? 2u : 3u, fb = CH * sb;
+    const uint32_t order = n > 2 ? 2u : 0u;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t frame_no = fd.first_block + b;
+    const uint32_t hdr_bytes = 4 + utf8_len(frame_no) + (n != BS ? 2u : 0u) + 1;
+
+    // 1. PCM -> LDS
+    {
+        const uint8_t* src = fd.pcm + (size_t)b * BS * fb;
+        const uint32_t nbytes = n * fb, nvec = nbytes >> 4;
+        for (uint32_t v = tid; v < nvec; v += NT) reinterpret_cast<uint4*>(smem)[v] = reinterpret_cast<const uint4*>(src)[v];
+        for (uint32_t j = (nvec << 4) + tid; j < nbytes; j += NT) smem[j] = src[j];
+    }
+    if (tid < 256) {                                                // the CRC-16 table (x^16 + x^15 + x^2 + 1)
+        uint32_t c = tid << 8;
+        for (int i = 0; i < 8; ++i) c = (c & 0x8000u) ? ((c << 1) ^ 0x8005u) & 0xFFFFu : (c << 1) & 0xFFFFu;
+        s_crc_tab[tid] = (uint16_t)c;
+    }
+    if (tid == 0) {                                                 // the frame header and its CRC-8 (x^8 + x^2 + x + 1)
+        uint32_t p = 0;
+        s_hdr[p++] = 0xFF; s_hdr[p++] = 0xF8;
+        s_hdr[p++] = n == BS ? 0xC0 : 0x70;
+        s_hdr[p++] = (uint8_t)(((CH - 1) << 4) | ((depth == 16 ? 4u : depth == 20 ? 5u : 6u) << 1));
+        if (frame_no < 0x80) s_hdr[p++] = (uint8_t)frame_no;
+        else {
+            const int m = (int)utf8_len(frame_no) - 1;
+            s_hdr[p++] = (uint8_t)(((0xFF00u >> (m + 1)) & 0xFFu) | (frame_no >> (6 * m)));
+            for (int i = m - 1; i >= 0; --i) s_hdr[p++] = (uint8_t)(0x80u | ((frame_no >> (6 * i)) & 0x3Fu));
+        }
+        if (n != BS) { s_hdr[p++] = (uint8_t)((n - 1) >> 8); s_hdr[p++] = (uint8_t)(n - 1); }
+        uint32_t c = 0;
+        for (uint32_t i = 0; i < p; ++i) {
+            c ^= s_hdr[i];
+            for (int k2 = 0; k2 < 8; ++k2) c = (c & 0x80u) ? ((c << 1) ^ 0x07u) & 0xFFu : (c << 1) & 0xFFu;
+        }
+        s_hdr[p] = (uint8_t)c;
+    }
+    __syncthreads();
+
+    // 2. samples -> residuals (warm-up and verbatim samples stay as they are), sum |r|
+    int32_t val[CH][SPT];
+    const uint32_t i0 = tid * SPT;
+    auto sample = [&](uint32_t i, uint32_t c) -> int32_t {
+        const uint8_t* q = smem + (i * CH + c) * sb;
+        int32_t v = sb == 2 ? (int32_t)(int16_t)(q[0] | (q[1] << 8)) : (int32_t)((uint32_t)(q[0] | (q[1] << 8) | (q[2] << 16)) << 8) >> 8;
+        return depth == 20 ? v >> 4 : v;
+    };
+    unsigned long long asum[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        int32_t s2 = i0 >= 2 && i0 - 2 < n ? sample(i0 - 2, c) : 0, s1 = i0 >= 1 && i0 - 1 < n ? sample(i0 - 1, c) : 0;
+        uint32_t acc = 0;
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) {
+            const uint32_t i = i0 + j;
+            const int32_t s0 = i < n ? sample(i, c) : 0;
+            int32_t v = s0;
+            if (i < n && i >= order && order == 2) {                // |r| <= 2^25: the sink's verbatim escape (30 bits) cannot fire
+                v = s0 - 2 * s1 + s2;
+                acc += (uint32_t)(v < 0 ? -v : v);
+            }
+            val[c][j] = v;
+            s2 = s1; s1 = s0;
+        }
+        unsigned long long t = acc;
+        for (int o = 32; o >= 1; o >>= 1) t += __shfl_xor(t, o, 64);
+        asum[c] = t;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < CH; ++c) s_wsum[wave][c] = asum[c];
+    }
+    __syncthreads();
+    if (tid < CH) {
+        unsigned long long sum = 0;
+        for (int w = 0; w < NW; ++w) sum += s_wsum[w][tid];
+        const unsigned long long mean = sum / (n > 2 ? n - 2 : 1);
+        uint32_t k = 0;
+        while (k < 30 && (1ull << k) < mean) ++k;
+        s_k[tid] = k;
+    }
+    __syncthreads();
+
+    // 3. code lengths and where every thread's bits begin
+    uint32_t kk[CH], start[CH];
+    uint32_t total_bits = hdr_bytes * 8;
+    {
+        uint32_t incl[CH], mine[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            const uint32_t k = s_k[c];
+            kk[c] = k;
+            uint32_t len = tid == 0 ? 8 + (order == 2 ? 11u : 0u) : 0;          // subframe header; residual header in front of sample 2
+#pragma unroll
+            for (int j = 0; j < SPT; ++j) {
+                const uint32_t i = i0 + j;
+                if (i >= n) continue;
+                if (i < 2 || order == 0) len += depth;
+                else {
+                    const int32_t r = val[c][j];
+                    const uint32_t u = r >= 0 ? (uint32_t)r << 1 : ((uint32_t)(-r) << 1) - 1;
+                    len += (u >> k) + 1 + k;
+                }
+            }
+            mine[c] = len;
+            uint32_t x = len;
+            for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(x, o, 64); if (lane >= (uint32_t)o) x += y; }
+            incl[c] = x;
+        }
+        if (lane == 63) {
+#pragma unroll
+            for (int c = 0; c < CH; ++c) s_wtot[wave][c] = incl[c];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            uint32_t before = 0, all = 0;
+            for (int w = 0; w < NW; ++w) { const uint32_t t = s_wtot[w][c]; all += t; if ((uint32_t)w < wave) before += t; }
+            start[c] = total_bits + before + incl[c] - mine[c];
+            total_bits += all;
+        }
+    }
+    const uint32_t data_bytes = (total_bits + 7) >> 3, frame_bytes = data_bytes + 2;
+    const uint32_t out_vecs = (frame_bytes + 15) >> 4;
+    // (frame_bytes <= slot_bytes by the bound of include/dsd2dxd_amd.h; a frame that broke it would be dropped whole, not written past the image)
+    if (frame_bytes > a.slot_bytes) { if (tid == 0) fd.sizes[b] = 0; return; }
+
+    // 4. the image: zero fill, then the bits that are one
+    uint32_t* img = reinterpret_cast<uint32_t*>(smem);
+    for (uint32_t w = tid; w < out_vecs * 4 + 4; w += NT) img[w] = 0;             // (every thread has passed the barriers behind its PCM reads)
+    __syncthreads();
+    if (tid < hdr_bytes && s_hdr[tid]) put_bits(img, tid * 8, s_hdr[tid], 8);
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        uint32_t p = start[c];
+        const uint32_t k = kk[c];
+        if (tid == 0) { put_bits(img, p, order == 2 ? 0x14u : 0x02u, 8); p += 8; }   // 0 001010 0: fixed order 2; 0 000001 0: verbatim
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) {
+            const uint32_t i = i0 + j;
+            if (i >= n) continue;
+            if (i == 2 && order == 2) { put_bits(img, p, (1u << 9) | k, 11); p += 11; }   // 01: 5-bit Rice parameters, 0000: one partition, k
+            if (i < 2 || order == 0) {
+                const uint32_t raw = (uint32_t)val[c][j] & ((1u << depth) - 1);
+                if (raw) put_bits(img, p, raw, depth);
+                p += depth;
+            } else {
+                const int32_t r = val[c][j];
+                const uint32_t u = r >= 0 ? (uint32_t)r << 1 : ((uint32_t)(-r) << 1) - 1;
+                const uint32_t q = u >> k;
+                put_bits(img, p + q, (1u << k) | (u & ((1u << k) - 1)), k + 1);
+                p += q + 1 + k;
+            }
+        }
+    }
+    __syncthreads();
+
+    // 5. CRC-16 over the data_bytes in front of it
+    auto image_byte = [&](uint32_t j) -> uint32_t { return (img[j >> 2] >> (24 - 8 * (j & 3))) & 0xFFu; };
+    {
+        const uint32_t L = (data_bytes + NT - 1) / NT, padz = NT * L - data_bytes;
+        uint32_t c = 0;
+        for (uint32_t v = tid * L; v < (tid + 1) * L; ++v)
+            if (v >= padz) c = ((c << 8) & 0xFFFFu) ^ s_crc_tab[(c >> 8) ^ image_byte(v - padz)];
+        s_crc[tid] = (uint16_t)c;
+        uint32_t m = gf_xpow(8 * L);
+        for (uint32_t stride = 1; stride < NT; stride <<= 1) {
+            __syncthreads();
+            if ((tid & (2 * stride - 1)) == 0) s_crc[tid] = (uint16_t)(gf_mul(s_crc[tid], m) ^ s_crc[tid + stride]);
+            m = gf_mul(m, m);
+        }
+        __syncthreads();
+        if (tid == 0 && s_crc[0]) put_bits(img, data_bytes * 8, s_crc[0], 16);
+    }
+    __syncthreads();
+
+    // 6. image -> slot
+    uint4* dst = reinterpret_cast<uint4*>(fd.slots + (size_t)b * a.slot_bytes);
+    for (uint32_t v = tid; v < out_vecs; v += NT) {
+        uint4 w = reinterpret_cast<const uint4*>(img)[v];
+        w.x = __builtin_bswap32(w.x); w.y = __builtin_bswap32(w.y); w.z = __builtin_bswap32(w.z); w.w = __builtin_bswap32(w.w);
+        dst[v] = w;
+    }
+    if (tid == 0) fd.sizes[b] = frame_bytes;
+}
+
+// sum, min and max of sizes[lo, hi) over the workgroup; every thread gets them
+__device__ void pack_reduce(const uint32_t* sizes, uint32_t lo, uint32_t hi, unsigned long long* red, unsigned long long& sum, uint32_t& mn, uint32_t& mx) {
+    unsigned long long s = 0; uint32_t a = 0xFFFFFFFFu, z = 0;
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += PT) { const uint32_t v = sizes[i]; s += v; a = min(a, v); z = max(z, v); }
+    for (int o = 32; o >= 1; o >>= 1) { s += __shfl_xor(s, o, 64); a = min(a, (uint32_t)__shfl_xor(a, o, 64)); z = max(z, (uint32_t)__shfl_xor(z, o, 64)); }
+    const uint32_t wave = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { red[wave * 3] = s; red[wave * 3 + 1] = a; red[wave * 3 + 2] = z; }
+    __syncthreads();
+    sum = 0; mn = 0xFFFFFFFFu; mx = 0;
+    for (int w = 0; w < PT / 64; ++w) { sum += red[w * 3]; mn = min(mn, (uint32_t)red[w * 3 + 1]); mx = max(mx, (uint32_t)red[w * 3 + 2]); }
+}
+
+__global__ __launch_bounds__(PT) void flac_pack_kernel(const FlacArgs a) {
+    __shared__ unsigned long long red[3 * PT / 64];
+    const FileDesc& fd = a.f[blockIdx.y];
+    const uint32_t b0 = blockIdx.x * PB, tid = threadIdx.x;
+    if (blockIdx.x != 0 && b0 >= fd.blocks) return;
+    unsigned long long off; uint32_t mn, mx;
+    if (blockIdx.x == 0) {                                          // the record: this workgroup starts at offset 0 anyway
+        pack_reduce(fd.sizes, 0, fd.blocks, red, off, mn, mx);
+        if (tid == 0) { d2d_flac_result r; r.bytes_out = off; r.min_frame_bytes = fd.blocks ? mn : 0; r.max_frame_bytes = mx; *fd.result = r; }
+        off = 0;
+    } else pack_reduce(fd.sizes, 0, b0, red, off, mn, mx);
+    const uint32_t b1 = min(b0 + PB, fd.blocks);
+    for (uint32_t b = b0; b < b1; ++b) {
+        const uint32_t size = fd.sizes[b];
+        const uint8_t* src = fd.slots + (size_t)b * a.slot_bytes;    // 16-byte aligned
+        uint8_t* dst = fd.out + off;
+        // bytes up to dst's next 4-byte boundary, whole words put together from two source words, the last bytes: exactly [off, off + size)
+        const uint32_t h = min((4u - (uint32_t)(off & 3u)) & 3u, size);
+        if (tid < h) dst[tid] = src[tid];
+        const uint32_t nw = (size - h) >> 2, sh = 8 * h;
+        const uint32_t* s32 = reinterpret_cast<const uint32_t*>(src);
+        uint32_t* d32 = reinterpret_cast<uint32_t*>(dst + h);
+        for (uint32_t m = tid; m < nw; m += PT) {
+            uint32_t w = s32[m];
+            if (h) w = (w >> sh) | (s32[m + 1] << (32 - sh));       // (word m + 1 begins below `size`: the code needs its first h bytes)
+            d32[m] = w;
+        }
+        for (uint32_t j = h + 4 * nw + tid; j < size; j += PT) dst[j] = src[j];
+        off += size;
+    }
+}
+
+size_t encode_lds_bytes(uint32_t ch, uint32_t depth) { return std::max<size_t>(slot_bytes(ch, depth) + 32, (size_t)BS * ch * sample_bytes(depth)); }
+
+template <int CH>
+hipError_t launch_encode(const FlacArgs& a, uint32_t max_blocks, uint32_t nf, hipStream_t s) {
+    // hipFuncSetAttribute acts on the current device: remembered per device, under a lock
+    static std::mutex mu;
+    static size_t allowed[64] = {};
+    const size_t lds = encode_lds_bytes(CH, a.depth);
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+    {
+        std::lock_guard<std::mutex> g(mu);
+        if (allowed[dev] < lds) {
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flac_encode_kernel<CH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+            allowed[dev] = lds;
+        }
+    }
+    hipLaunchKernelGGL(flac_encode_kernel<CH>, dim3(max_blocks, nf), dim3(NT), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_encode_ch(uint32_t ch, const FlacArgs& a, uint32_t max_blocks, uint32_t nf, hipStream_t s) {
+    switch (ch) {
+        case 1: return launch_encode<1>(a, max_blocks, nf, s);
+        case 2: return launch_encode<2>(a, max_blocks, nf, s);
+        case 3: return launch_encode<3>(a, max_blocks, nf, s);
+        case 4: return launch_encode<4>(a, max_blocks, nf, s);
+        case 5: return launch_encode<5>(a, max_blocks, nf, s);
+        case 6: return launch_encode<6>(a, max_blocks, nf, s);
+        case 7: return launch_encode<7>(a, max_blocks, nf, s);
+        default: return launch_encode<8>(a, max_blocks, nf, s);
+    }
+}
+
+int hip_fail(hipError_t e, const char* what) { return fail(D2D_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
+
+}  // namespace
+
+extern "C" {
+
+int d2d_flac_encode_device(uint32_t channels, uint32_t bit_depth, d2d_flac_io* io, uint32_t n_files,
+                           void* workspace, size_t workspace_bytes, void* hip_stream) {
+    // every check comes before the first device call
+    if (!depth_ok(bit_depth)) return fail(D2D_ERR_PARAM, "FLAC holds 16, 20 or 24-bit integers (Invalid bit depth)");
+    if (channels == 0 || channels > 8) return fail(D2D_ERR_PARAM, "FLAC holds 1 to 8 channels (Invalid channel count)");
+    if (!io || n_files == 0) return fail(D2D_ERR_PARAM, "no files");
+    size_t need = 0, any_blocks = 0;
+    for (uint32_t f = 0; f < n_files; ++f) {
+        const d2d_flac_io& x = io[f];
+        const size_t blocks = block_count(x.frames, x.final);
+        if ((uint64_t)x.first_block + blocks > (1ull << 31)) return fail(D2D_ERR_PARAM, "frame numbers are 31 bits: first_block + blocks exceeds 2^31");
+        if (!x.result) return fail(D2D_ERR_PARAM, "null result record");
+        if (((uintptr_t)x.pcm & 15) || ((uintptr_t)x.out & 15)) return fail(D2D_ERR_PARAM, "pcm and out device pointers must be 16-byte aligned");
+        if (blocks && (!x.pcm || !x.out)) return fail(D2D_ERR_PARAM, "pcm and out device pointers must be non-null");
+        if (x.out_capacity_bytes < d2d_flac_bound_bytes(channels, bit_depth, x.frames, x.final)) return fail(D2D_ERR_CAPACITY, "out buffer below d2d_flac_bound_bytes");
+        need += d2d_flac_workspace_bytes(channels, bit_depth, x.frames, x.final);
+        any_blocks += blocks;
+    }
+    if (any_blocks && (!workspace || ((uintptr_t)workspace & 15))) return fail(D2D_ERR_PARAM, "workspace must be a 16-byte aligned device pointer");
+    if (workspace_bytes < need) return fail(D2D_ERR_CAPACITY, "workspace below the sum of d2d_flac_workspace_bytes");
+
+    hipStream_t s = (hipStream_t)hip_stream;
+    const size_t slot = slot_bytes(channels, bit_depth);
+    uint8_t* ws = (uint8_t*)workspace;
+    for (uint32_t f0 = 0; f0 < n_files; f0 += MAXF) {
+        const uint32_t nf = std::min<uint32_t>(MAXF, n_files - f0);
+        FlacArgs a{};
+        a.depth = bit_depth; a.slot_bytes = (uint32_t)slot;
+        uint32_t max_blocks = 0;
+        for (uint32_t i = 0; i < nf; ++i) {
+            const d2d_flac_io& x = io[f0 + i];
+            const size_t blocks = block_count(x.frames, x.final);
+            FileDesc& d = a.f[i];
+            d.pcm = (const uint8_t*)x.pcm; d.out = (uint8_t*)x.out; d.result = x.result;
+            d.sizes = (uint32_t*)ws; d.slots = ws + align16(4 * blocks);
+            d.blocks = (uint32_t)blocks; d.first_block = x.first_block;
+            d.last_n = (x.final && x.frames % BS) ? (uint32_t)(x.frames % BS) : BS;
+            ws += d2d_flac_workspace_bytes(channels, bit_depth, x.frames, x.final);
+            max_blocks = std::max(max_blocks, d.blocks);
+        }
+        if (max_blocks) {
+            hipError_t e = launch_encode_ch(channels, a, max_blocks, nf, s);
+            if (e != hipSuccess) return hip_fail(e, "flac_encode_kernel");
+        }
+        hipLaunchKernelGGL(flac_pack_kernel, dim3(std::max(1u, (max_blocks + PB - 1) / PB), nf), dim3(PT), 0, s, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, "flac_pack_kernel");
+    }
+    for (uint32_t f = 0; f < n_files; ++f) {
+        io[f].blocks = block_count(io[f].frames, io[f].final);
+        io[f].frames_consumed = io[f].final ? io[f].frames : (io[f].frames / BS) * BS;
+    }
+    return D2D_OK;
+}
+
+}  // extern "C"
+
+// ---- the whole-stream driver ---------------------------------------------------------------------------------------------------
+
+namespace {
+
+struct DevBuf {
+    void* p = nullptr; size_t bytes = 0;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t n) { bytes = n; return hipMalloc(&p, std::max<size_t>(n, 16)); }
+};
+struct PinBuf {
+    void* p = nullptr;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t alloc(size_t n) { return hipHostMalloc(&p, std::max<size_t>(n, 16), hipHostMallocDefault); }
+};
+// All device work of the stream driver goes to the null stream: the engine remembers the stream of its last call (d2d_peak waits on
+// it), so it must not be one that ends with this function.  (The buffers' release waits for the device.)
+struct Stream { hipStream_t s = nullptr; };
+
+}  // namespace
+
+#define FLAC_HIP(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(e_, what); } while (0)
+
+extern "C" int d2d_convert_stream_flac(d2d_engine* e, uint32_t bit_depth, d2d_read_fn read, void* ru, d2d_write_fn write, void* wu,
+                                       const volatile int* cancel, d2d_progress_fn progress, void* pu,
+                                       uint64_t total, size_t chunk, d2d_flac_stream_stats* stats) {
+    if (!e) return fail(D2D_ERR_PARAM, "null engine");
+    if (!read) return fail(D2D_ERR_PARAM, "null read callback");
+    if (!stats) return fail(D2D_ERR_PARAM, "null stats");
+    if (!depth_ok(bit_depth)) return fail(D2D_ERR_PARAM, "FLAC holds 16, 20 or 24-bit integers (Invalid bit depth)");
+    const size_t fb = d2d_frame_bytes(e), sb = sample_bytes(bit_depth);
+    if (fb == 0 || fb % sb || fb / sb > 8) return fail(D2D_ERR_PARAM, "the engine's frames do not hold 1 to 8 channels of this bit depth");
+    const uint32_t ch = (uint32_t)(fb / sb);
+    if (chunk == 0) chunk = 1u << 22;
+    // the engine's device becomes this thread's current device (d2d_peak selects it and waits for the engine's pending work)
+    double peak0 = 0.0;
+    if (d2d_peak(e, 0, 0, &peak0) != D2D_OK) return fail(D2D_ERR_DEVICE, d2d_last_error(e));
+    *stats = d2d_flac_stream_stats{0, 0, 0, 0};
+
+    // frames one chunk can add: the engine's own count for a chunk from where it stands, and a margin for the rounding of later ones
+    const size_t chunk_frames = d2d_next_frames(e, 0, chunk) + 64, cap_frames = chunk_frames + BS;
+    const size_t out_cap = d2d_flac_bound_bytes(ch, bit_depth, cap_frames, 1), ws_cap = d2d_flac_workspace_bytes(ch, bit_depth, cap_frames, 1);
+    Stream st;
+    PinBuf h_in[2], h_out, h_res;
+    DevBuf d_in, d_new, d_pcm, d_out, d_ws;
+    FLAC_HIP(h_in[0].alloc(chunk * ch), "hipHostMalloc"); FLAC_HIP(h_in[1].alloc(chunk * ch), "hipHostMalloc");
+    FLAC_HIP(h_out.alloc(out_cap), "hipHostMalloc"); FLAC_HIP(h_res.alloc(sizeof(d2d_flac_result)), "hipHostMalloc");
+    FLAC_HIP(d_in.alloc(chunk * ch), "hipMalloc"); FLAC_HIP(d_new.alloc(chunk_frames * fb), "hipMalloc");
+    FLAC_HIP(d_pcm.alloc(cap_frames * fb), "hipMalloc"); FLAC_HIP(d_out.alloc(out_cap), "hipMalloc"); FLAC_HIP(d_ws.alloc(ws_cap), "hipMalloc");
+    d2d_flac_result* res = (d2d_flac_result*)h_res.p;
+
+    size_t carry = 0;                 // frames in front of d_pcm that no block has taken yet
+    uint64_t done = 0;
+    int cur = 0;
+    long got = read(ru, (uint8_t*)h_in[cur].p, chunk);
+    if (got < 0) return fail(D2D_ERR_IO, "read callback failed");
+    while (got > 0) {
+        if (cancel && *cancel) return fail(D2D_ERR_CANCELLED, "Conversion cancelled");
+        const size_t L = (size_t)got;
+        if (L > chunk) return fail(D2D_ERR_IO, "read callback returned more than it was asked for");
+        // upload and convert; the PCM lands in a buffer of its own (the translate call wants 16-byte alignment, the end of the carry
+        // has none) and is copied behind the carry on the same stream
+        d2d_file_io tio{};
+        tio.dsd = d_in.p; tio.bytes_per_channel = L; tio.pcm = d_new.p; tio.pcm_capacity_bytes = d_new.bytes;
+        FLAC_HIP(hipMemcpyAsync(d_in.p, h_in[cur].p, L * ch, hipMemcpyHostToDevice, st.s), "hipMemcpyAsync");
+        if (d2d_translate_batch_device(e, &tio, 1, st.s) != D2D_OK) return fail(D2D_ERR_DEVICE, d2d_last_error(e));
+        const size_t nf = tio.frames_out;
+        if (carry + nf > cap_frames) return fail(D2D_ERR_STATE, "a chunk produced more frames than planned");
+        if (nf) FLAC_HIP(hipMemcpyAsync((uint8_t*)d_pcm.p + carry * fb, d_new.p, nf * fb, hipMemcpyDeviceToDevice, st.s), "hipMemcpyAsync");
+        // the next chunk is read while the GPU works: the stream ends with this chunk if there is none
+        const long next = read(ru, (uint8_t*)h_in[cur ^ 1].p, chunk);
+        if (next < 0) return fail(D2D_ERR_IO, "read callback failed");
+        d2d_flac_io fio{};
+        fio.pcm = d_pcm.p; fio.frames = carry + nf; fio.first_block = (uint32_t)stats->blocks; fio.final = next == 0;
+        fio.out = d_out.p; fio.out_capacity_bytes = d_out.bytes; fio.result = res;
+        if (stats->blocks > 0xFFFFFFFFull) return fail(D2D_ERR_PARAM, "frame numbers are 31 bits");
+        const int rc = d2d_flac_encode_device(ch, bit_depth, &fio, 1, d_ws.p, d_ws.bytes, st.s);
+        if (rc != D2D_OK) return rc;
+        FLAC_HIP(hipStreamSynchronize(st.s), "hipStreamSynchronize");
+        const d2d_flac_result r = *res;
+        if (r.bytes_out) {
+            FLAC_HIP(hipMemcpy(h_out.p, d_out.p, r.bytes_out, hipMemcpyDeviceToHost), "hipMemcpy");
+            if (write && write(wu, h_out.p, r.bytes_out) != 0) return fail(D2D_ERR_IO, "write callback failed");
+        }
+        if (fio.blocks) {
+            stats->min_frame_bytes = stats->blocks ? std::min(stats->min_frame_bytes, r.min_frame_bytes) : r.min_frame_bytes;
+            stats->max_frame_bytes = std::max(stats->max_frame_bytes, r.max_frame_bytes);
+            stats->blocks += fio.blocks;
+            stats->samples_per_channel += fio.frames_consumed;
+        }
+        // the remainder moves to the front (it lies wholly behind its destination: a block was taken, or nothing moves)
+        carry = fio.frames - fio.frames_consumed;
+        if (carry && fio.frames_consumed)
+            FLAC_HIP(hipMemcpyAsync(d_pcm.p, (uint8_t*)d_pcm.p + fio.frames_consumed * fb, carry * fb, hipMemcpyDeviceToDevice, st.s), "hipMemcpyAsync");
+        done += (uint64_t)L;
+        if (progress && total) {
+            float pct = (float)(100.0 * (double)done / (double)total);
+            if (pct >= 100.0f) pct = 99.99f;       // exactly 100 is reserved for the end
+            progress(pu, pct);
+        }
+        got = next; cur ^= 1;
+    }
+    if (progress) progress(pu, 100.0f);
+    return D2D_OK;
+}

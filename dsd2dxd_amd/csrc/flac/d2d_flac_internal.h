@@ -1,0 +1,28 @@
+// d2d_flac_internal.h -- sizes and the error slot shared by the host and the device side of the FLAC entry points
+// (include/dsd2dxd_amd.h, "FLAC frames on the GPU").  Host code only.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "../../../include/dsd2dxd_amd.h"
+
+namespace d2dflac {
+
+constexpr uint32_t BS = D2D_FLAC_BLOCK;
+constexpr uint32_t MAX_HEADER_BYTES = 13;      // 4 fixed + 6 frame number + 2 block size + 1 CRC-8
+
+inline bool depth_ok(uint32_t d) { return d == 16 || d == 20 || d == 24; }
+inline uint32_t sample_bytes(uint32_t depth) { return depth == 16 ? 2 : 3; }
+// the header's bound: D2D_FLAC_FRAME_BOUND(n)
+inline size_t subframe_bits_bound(uint32_t depth, uint32_t n) { return 19 + 2 * (size_t)depth + 30 * (size_t)(n > 2 ? n - 2 : 0); }
+inline size_t frame_bound(uint32_t ch, uint32_t depth, uint32_t n) { return MAX_HEADER_BYTES + 2 + (ch * subframe_bits_bound(depth, n) + 7) / 8; }
+inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+inline size_t slot_bytes(uint32_t ch, uint32_t depth) { return align16(frame_bound(ch, depth, BS)); }
+inline size_t block_count(size_t frames, int final) { return frames / BS + ((final && frames % BS) ? 1 : 0); }
+
+// the message d2d_flac_error() returns (thread-local); returns `code`
+int fail(int code, const std::string& message);
+
+}  // namespace d2dflac

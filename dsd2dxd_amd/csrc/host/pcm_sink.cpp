@@ -1,6 +1,7 @@
 #include "pcm_sink.h"
 
 #include "id3_tag.h"
+#include "../flac/flac_frame_enc.h"
 
 #include <math.h>
 
@@ -189,89 +190,7 @@ struct Md5 {
     }
 };
 
-// FLAC with fixed-order-2 prediction and one Rice partition per subframe (valid, modest compression;
-// the reference uses the flac-codec crate, Cargo.lock:299-307).  Integer depths only.  Frames are
-// independent of each other, so a batch of them is encoded on as many threads and written in order.
-struct FlacFrameEnc {
-    std::vector<uint8_t> out;
-    std::vector<int32_t> res;
-    uint64_t bitacc = 0; int bitn = 0;
-    static const uint8_t* crc8_table() {
-        static uint8_t t[256]; static bool done = false;
-        if (!done) { for (int i = 0; i < 256; ++i) { uint8_t c = (uint8_t)i; for (int k = 0; k < 8; ++k) c = (uint8_t)((c & 0x80) ? (c << 1) ^ 0x07 : (c << 1)); t[i] = c; } done = true; }
-        return t;
-    }
-    static const uint16_t* crc16_table() {
-        static uint16_t t[256]; static bool done = false;
-        if (!done) { for (int i = 0; i < 256; ++i) { uint16_t c = (uint16_t)(i << 8); for (int k = 0; k < 8; ++k) c = (uint16_t)((c & 0x8000) ? (c << 1) ^ 0x8005 : (c << 1)); t[i] = c; } done = true; }
-        return t;
-    }
-    static uint8_t crc8(const uint8_t* p, size_t n) { const uint8_t* t = crc8_table(); uint8_t c = 0; for (size_t i = 0; i < n; ++i) c = t[c ^ p[i]]; return c; }
-    static uint16_t crc16(const uint8_t* p, size_t n) { const uint16_t* t = crc16_table(); uint16_t c = 0; for (size_t i = 0; i < n; ++i) c = (uint16_t)((c << 8) ^ t[(c >> 8) ^ p[i]]); return c; }
-    void bits_put(uint64_t v, int n) {
-        while (n > 0) {
-            int take = n > 32 ? 32 : n;
-            uint64_t part = (v >> (n - take)) & ((1ull << take) - 1);
-            bitacc = (bitacc << take) | part; bitn += take; n -= take;
-            while (bitn >= 8) { out.push_back((uint8_t)(bitacc >> (bitn - 8))); bitn -= 8; }
-        }
-    }
-    void bits_flush() { if (bitn) { out.push_back((uint8_t)(bitacc << (8 - bitn))); bitn = 0; } bitacc = 0; }
-    void put_utf8(uint32_t v) {
-        if (v < 0x80) { bits_put(v, 8); return; }
-        int n = v < 0x800 ? 1 : v < 0x10000 ? 2 : v < 0x200000 ? 3 : v < 0x4000000 ? 4 : 5;
-        bits_put(((0xFF00 >> (n + 1)) & 0xFF) | (v >> (6 * n)), 8);
-        for (int i = n - 1; i >= 0; --i) bits_put(0x80 | ((v >> (6 * i)) & 0x3F), 8);
-    }
-    // one frame of `n` interleaved samples starting at `buf`
-    void encode(const int32_t* buf, uint32_t n, uint32_t ch, uint32_t depth, uint32_t frame_no, uint32_t BS) {
-        out.clear(); bitn = 0; bitacc = 0;
-        bits_put(0xFFF8, 16);                                          // sync, fixed block size
-        bits_put(n == BS ? 0xC : 0x7, 4);                              // 4096, or 16-bit (n-1) at the end of the header
-        bits_put(0x0, 4);                                              // sample rate from STREAMINFO
-        bits_put(ch - 1, 4);                                           // independent channels
-        bits_put(depth == 16 ? 4 : depth == 20 ? 5 : 6, 3); bits_put(0, 1);
-        put_utf8(frame_no);
-        if (n != BS) bits_put(n - 1, 16);
-        bits_flush();
-        out.push_back(crc8(out.data(), out.size()));
-        res.resize(n);
-        for (uint32_t c = 0; c < ch; ++c) {
-            auto s = [&](uint32_t i) -> int64_t { return buf[(size_t)i * ch + c]; };
-            const uint32_t order = n > 2 ? 2 : 0;
-            uint64_t sum = 0;
-            bool fits = true;
-            for (uint32_t i = order; i < n; ++i) {
-                int64_t r = order == 2 ? s(i) - 2 * s(i - 1) + s(i - 2) : s(i);
-                if (r > 0x3FFFFFFF || r < -0x3FFFFFFF) fits = false;
-                res[i] = (int32_t)r; sum += (uint64_t)(r < 0 ? -r : r);
-            }
-            if (!fits || order == 0) {                                   // verbatim subframe
-                bits_put(0, 1); bits_put(1, 6); bits_put(0, 1);
-                for (uint32_t i = 0; i < n; ++i) bits_put((uint64_t)s(i) & ((1ull << depth) - 1), (int)depth);
-                continue;
-            }
-            bits_put(0, 1); bits_put(8 + order, 6); bits_put(0, 1);    // fixed predictor, no wasted bits
-            for (uint32_t i = 0; i < order; ++i) bits_put((uint64_t)s(i) & ((1ull << depth) - 1), (int)depth);
-            uint32_t k = 0;
-            const uint64_t mean = sum / (n - order ? n - order : 1);
-            while (k < 30 && (1ull << k) < mean) ++k;
-            bits_put(1, 2);                                             // residual coding method 1: 5-bit Rice parameters
-            bits_put(0, 4);                                             // partition order 0
-            bits_put(k, 5);
-            for (uint32_t i = order; i < n; ++i) {
-                uint32_t u = res[i] >= 0 ? (uint32_t)res[i] << 1 : (((uint32_t)(-(int64_t)res[i])) << 1) - 1;
-                uint32_t q = u >> k;
-                while (q >= 32) { bits_put(0, 32); q -= 32; }
-                bits_put(1, (int)q + 1);
-                if (k) bits_put(u & ((1u << k) - 1), (int)k);
-            }
-        }
-        bits_flush();
-        uint16_t c16 = crc16(out.data(), out.size());
-        out.push_back((uint8_t)(c16 >> 8)); out.push_back((uint8_t)c16);
-    }
-};
+// FlacFrameEnc, the frame encoder, lives in ../flac/flac_frame_enc.h: d2d_flac_encode_host runs the same code.
 
 struct FlacSink : PcmSink {
     FILE* f; uint32_t ch, rate, bits; uint64_t frames = 0; uint32_t frame_no = 0;
@@ -282,6 +201,7 @@ struct FlacSink : PcmSink {
     Md5 md5;                       // of the samples as little-endian whole-byte integers, interleaved (FLAC format, STREAMINFO)
     std::vector<FlacFrameEnc> encs;
     bool io_failed = false;
+    bool raw_frames = false;       // the frames came encoded (write_frames): no samples were seen, so there is no MD5
     uint32_t depth() const { return bits == 20 ? 20 : bits; }
     std::string begin() {
         // metadata: STREAMINFO (filled in at close), then the source's tag as VORBIS_COMMENT and PICTURE
@@ -366,6 +286,15 @@ struct FlacSink : PcmSink {
         if (buf.size() >= (size_t)BS * ch * 8) drain(false);
         return io_failed ? "short write" : "";
     }
+    std::string write_frames(const uint8_t* p, size_t nbytes) override {
+        raw_frames = true;
+        return fwrite(p, 1, nbytes, f) == nbytes ? "" : "short write";
+    }
+    void set_frame_stats(uint64_t samples, uint64_t blocks, uint32_t min_bytes, uint32_t max_bytes) override {
+        raw_frames = true;
+        frames = samples;
+        if (blocks) { min_fs = min_bytes; max_fs = max_bytes; }
+    }
     std::string close() override {
         drain(true);
         uint8_t si[34]; memset(si, 0, sizeof(si));
@@ -373,7 +302,7 @@ struct FlacSink : PcmSink {
         si[4] = min_fs >> 16; si[5] = min_fs >> 8; si[6] = (uint8_t)min_fs; si[7] = max_fs >> 16; si[8] = max_fs >> 8; si[9] = (uint8_t)max_fs;
         const uint64_t v = ((uint64_t)rate << 44) | ((uint64_t)(ch - 1) << 41) | ((uint64_t)(depth() - 1) << 36) | (frames & 0xFFFFFFFFFull);
         for (int i = 0; i < 8; ++i) si[10 + i] = (uint8_t)(v >> (56 - 8 * i));
-        md5.finish(si + 18);
+        if (!raw_frames) md5.finish(si + 18);                            // (16 zero bytes otherwise: "not computed")
         fseek(f, 8, SEEK_SET); fwrite(si, 1, 34, f);
         if (fclose(f) != 0 || io_failed) return "close failed";
         return "";

@@ -17,6 +17,11 @@ class PcmSink {
     virtual ~PcmSink() {}
     virtual std::string write(const uint8_t* frames, size_t bytes) = 0;   // "" or error
     virtual std::string close() = 0;
+    // The FLAC sink's raw-frame path (Rdsd2Pcm::set_gpu_flac): frames that d2d_convert_stream_flac encoded on the GPU are written as they
+    // come, and STREAMINFO is filled from the stream's stats at close().  Its MD5 field stays 16 zero bytes -- FLAC's "not computed" --
+    // because the samples never reach the host.  Every other sink refuses.
+    virtual std::string write_frames(const uint8_t*, size_t) { return "this sink takes PCM, not FLAC frames"; }
+    virtual void set_frame_stats(uint64_t /*samples_per_channel*/, uint64_t /*blocks*/, uint32_t /*min_frame_bytes*/, uint32_t /*max_frame_bytes*/) {}
 };
 
 // bit_depth 16/20/24 (integer, 20 in a 24-bit container) or 32 (float).  `id3` = the source's ID3v2

@@ -3,6 +3,7 @@
 #include <string.h>
 #include <sys/stat.h>
 
+#include <algorithm>
 #include <chrono>
 
 #include "../../../include/dsd2dxd_amd.h"
@@ -41,6 +42,7 @@ struct Rdsd2Pcm::Impl {
     DsdInfo info;
     bool level_only = false;
     size_t chunk = 4u << 20;
+    bool gpu_flac = false;
     std::string out_path;
     double dsp_s = 0.0, audio_s = 0.0;
     std::string tag_warning;
@@ -142,6 +144,7 @@ void Rdsd2Pcm::set_device(int device) { p_->prm.device = device; }
 void Rdsd2Pcm::set_seed(uint64_t seed) { p_->prm.seed = seed; }
 void Rdsd2Pcm::set_tap_bits(uint32_t bits) { p_->prm.tap_bits = bits; }
 void Rdsd2Pcm::set_chunk_bytes(size_t b) { if (b) p_->chunk = b; }
+void Rdsd2Pcm::set_gpu_flac(bool on) { p_->gpu_flac = on; }
 
 namespace {
 struct RunCtx {
@@ -161,6 +164,15 @@ int write_cb(void* u, const void* pcm, size_t bytes) {
     RunCtx* c = (RunCtx*)u;
     auto t0 = std::chrono::steady_clock::now();
     std::string e = c->sink ? c->sink->write((const uint8_t*)pcm, bytes) : "";
+    c->io_time += std::chrono::steady_clock::now() - t0;
+    if (!e.empty()) { c->io_error = e; return 1; }
+    if (c->cancel->load()) c->cancel_int = 1;
+    return 0;
+}
+int write_frames_cb(void* u, const void* frames, size_t bytes) {
+    RunCtx* c = (RunCtx*)u;
+    auto t0 = std::chrono::steady_clock::now();
+    std::string e = c->sink->write_frames((const uint8_t*)frames, bytes);
     c->io_time += std::chrono::steady_clock::now() - t0;
     if (!e.empty()) { c->io_error = e; return 1; }
     if (c->cancel->load()) c->cancel_int = 1;
@@ -214,10 +226,25 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
     if (d2d_create(&im.prm, 1, &e) != D2D_OK) throw std::runtime_error(d2d_create_error());
     RunCtx ctx; ctx.src = &src; ctx.sink = sink; ctx.cancel = &cancel; ctx.sender = &sender;
     auto t0 = std::chrono::steady_clock::now();
-    int rc = d2d_convert_stream(e, read_cb, &ctx, levels ? nullptr : write_cb, &ctx, &ctx.cancel_int,
+    const bool gpu_flac = !levels && im.gpu_flac && im.output == OutputType::Flac && sink;
+    int rc;
+    std::string msg;
+    if (gpu_flac) {
+        // the frames are encoded where the PCM is; the sink writes them as they come and takes STREAMINFO's figures from the stats
+        size_t chunk = im.chunk;
+        const size_t B = im.prm.fmt == D2D_FMT_PLANAR ? im.prm.block_size : 1;
+        if (B > 1) chunk = std::max(B, chunk / B * B);                  // whole planar blocks per read, as d2d_convert_stream cuts them
+        d2d_flac_stream_stats stats{};
+        rc = d2d_convert_stream_flac(e, im.prm.bit_depth, read_cb, &ctx, write_frames_cb, &ctx, &ctx.cancel_int,
+                                     progress_cb, &ctx, info.bytes_per_channel, chunk, &stats);
+        if (rc) msg = d2d_flac_error();
+        else sink->set_frame_stats(stats.samples_per_channel, stats.blocks, stats.min_frame_bytes, stats.max_frame_bytes);
+    } else {
+        rc = d2d_convert_stream(e, read_cb, &ctx, levels ? nullptr : write_cb, &ctx, &ctx.cancel_int,
                                 progress_cb, &ctx, info.bytes_per_channel, im.chunk);
+        if (rc) msg = d2d_last_error(e);
+    }
     auto total = std::chrono::steady_clock::now() - t0;
-    std::string msg = rc ? d2d_last_error(e) : "";
     float db = 0.f;
     if (!rc && levels) { if (d2d_peak_dbfs(e, 0, &db) != D2D_OK) msg = d2d_last_error(e); }
     const uint64_t bpc = info.bytes_per_channel;

@@ -20,8 +20,9 @@
 extern "C" {
 #endif
 
-#define D2D_ABI_VERSION 6   /* 3: the table blob header names the table variant; 4: d2d_params.tap_bits; 5: d2d_params.debug_flags (was reserved0);
-                             * 6: d2d_seek / d2d_tell / d2d_prime* and the two size queries (d2d_params unchanged) */
+#define D2D_ABI_VERSION 7   /* 3: the table blob header names the table variant; 4: d2d_params.tap_bits; 5: d2d_params.debug_flags (was reserved0);
+                             * 6: d2d_seek / d2d_tell / d2d_prime* and the two size queries (d2d_params unchanged);
+                             * 7: the d2d_flac_* entry points and d2d_convert_stream_flac (d2d_params unchanged) */
 
 /* status codes */
 enum {
@@ -239,6 +240,92 @@ int d2d_convert_stream(d2d_engine* e, d2d_read_fn read, void* read_user,
                        d2d_write_fn write, void* write_user,
                        const volatile int* cancel, d2d_progress_fn progress, void* progress_user,
                        uint64_t total_bytes_per_channel, size_t chunk_bytes_per_channel);
+
+/* ---- FLAC frames on the GPU (ABI 7) -------------------------------------------------------- */
+
+/* The frames FlacSink writes (csrc/flac/flac_frame_enc.h is the definition), produced where the PCM already is: fixed block size
+ * 4096, independent channels, fixed-order-2 prediction, one Rice partition per subframe (verbatim subframes for a last block of
+ * 1 or 2 samples), 16 / 20 / 24 bits, at most 8 channels.  The device and the host entry produce the same bytes.  The encoder's
+ * verbatim escape for residuals beyond 30 bits cannot fire at these depths (|s| <= 2^23 gives |r| <= 2^25), so it does not exist on
+ * the GPU.  None of these entry points takes an engine; samples are the interleaved little-endian frames the translate calls write
+ * (16-bit in 2 bytes, 24-bit in 3, 20-bit as the 3-byte container shifted right by 4).
+ *
+ * THE BOUND.  A frame of n samples per channel holds: a header of at most 13 bytes (2 sync/block-size-class, 1 block size and rate
+ * codes, 1 channels and sample size, at most 6 for a 31-bit frame number, 2 for n - 1 when n != 4096, 1 CRC-8; counted as 4 + 6 + 2
+ * + 1), `channels` subframes, zero bits up to a byte, and 2 bytes of CRC-16.  A subframe is 8 header bits, two warm-up samples of
+ * `depth` bits, 11 bits of residual header and the Rice codes.  k is the smallest value with 2^k >= mean = floor(sum / (n - 2)), so
+ * sum < (2^k + 1)(n - 2); with u_i <= 2 |r_i| the unary parts hold  sum(u_i >> k) <= 2 sum / 2^k < 2 (1 + 2^-k)(n - 2) <= 4 (n - 2)
+ * zeros, and every code adds a stop bit and k <= 25 low bits: under 30 (n - 2) bits.  So
+ *     subframe_bits(n)  <= 19 + 2 depth + 30 max(n - 2, 0)          (a verbatim subframe, n <= 2, is 8 + n depth)
+ *     frame_bytes(n)    <= D2D_FLAC_FRAME_BOUND(n) = 15 + ceil(channels * (19 + 2 depth + 30 max(n - 2, 0)) / 8)
+ *     d2d_flac_bound_bytes = floor(frames / 4096) * D2D_FLAC_FRAME_BOUND(4096) + (final and frames % 4096 ? D2D_FLAC_FRAME_BOUND(frames % 4096) : 0)
+ * Host arithmetic, no device; 0 for parameters the encoders refuse. */
+#define D2D_FLAC_BLOCK 4096u
+size_t d2d_flac_bound_bytes(uint32_t channels, uint32_t bit_depth, size_t frames, int final);
+/* Scratch one d2d_flac_encode_device call needs for one such file: a 4-byte size per block, rounded up to 16 bytes, and one slot of
+ * D2D_FLAC_FRAME_BOUND(4096) bytes, rounded up to 16, per block.  A call over several files needs the sum. */
+size_t d2d_flac_workspace_bytes(uint32_t channels, uint32_t bit_depth, size_t frames, int final);
+
+typedef struct d2d_flac_result {
+    uint64_t bytes_out;          /* frame bytes written to `out`                                 */
+    uint32_t min_frame_bytes;    /* smallest and largest frame of the call (STREAMINFO); 0 and 0 */
+    uint32_t max_frame_bytes;    /* when the call produced no block                              */
+} d2d_flac_result;
+
+typedef struct d2d_flac_io {
+    const void* pcm;             /* DEVICE pointer, 16-byte aligned: `frames` interleaved frames */
+    size_t      frames;
+    uint32_t    first_block;     /* frame number of the first block                              */
+    int32_t     final;           /* non-zero: the stream ends here, a short last block is coded  */
+    void*       out;             /* DEVICE pointer, 16-byte aligned                              */
+    size_t      out_capacity_bytes;   /* at least d2d_flac_bound_bytes(channels, depth, frames, final) */
+    d2d_flac_result* result;     /* memory the GPU can address (device or pinned host); valid once the stream has synchronised */
+    size_t      blocks;          /* written at return: floor(frames / 4096), plus the short one if final */
+    size_t      frames_consumed; /* written at return: 4096 * blocks, or all frames if final     */
+} d2d_flac_io;
+
+/* Encodes the whole blocks of `n_files` independent files (and, where `final`, the short last one) in two launches on `hip_stream`
+ * (a hipStream_t, NULL = the null stream): one workgroup per (file, block) writes its frame into a workspace slot, then a second
+ * kernel packs each file's slots into its `out`.  No workgroup waits for another; the kernel boundary is the only ordering.
+ * Asynchronous, like d2d_translate_batch_device: `blocks` and `frames_consumed` are known at return, the result records and the
+ * frames once the stream has synchronised.  The caller keeps the remainder of under 4096 frames in front of its next PCM.  A file
+ * with fewer than 4096 non-final frames yields 0 blocks and bytes_out = 0.  `workspace` is device memory, 16-byte aligned, of at
+ * least the sum of d2d_flac_workspace_bytes over the files.  Runs on the current device.
+ *
+ * Checked on the host before anything is launched: bit_depth not 16 / 20 / 24, channels 0 or above 8, first_block + blocks above
+ * 2^31, null or misaligned pointers -> D2D_ERR_PARAM; out_capacity_bytes below d2d_flac_bound_bytes, workspace too small ->
+ * D2D_ERR_CAPACITY.  d2d_flac_error() (thread-local) has the message.
+ *
+ * WHAT A CALL MAY TOUCH (tests/test_gpu_flac.py pins it): a successful call writes exactly the bytes [0, bytes_out) of each file's
+ * `out`, the result records, and bytes inside [workspace, workspace + workspace_bytes); no other byte.  A refused call writes
+ * nothing, `blocks` and `frames_consumed` included. */
+int d2d_flac_encode_device(uint32_t channels, uint32_t bit_depth, d2d_flac_io* io, uint32_t n_files,
+                           void* workspace, size_t workspace_bytes, void* hip_stream);
+const char* d2d_flac_error(void);
+
+/* The same frames from HOST memory with the sink's own encoder, no device: the reference the GPU tests compare against.  `pcm`
+ * needs no alignment.  Same checks and codes as the device entry (cap below the bound -> D2D_ERR_CAPACITY, nothing written). */
+int d2d_flac_encode_host(uint32_t channels, uint32_t bit_depth, const void* pcm, size_t frames, uint32_t first_block, int final,
+                         void* out, size_t out_capacity_bytes, d2d_flac_result* result, size_t* frames_consumed);
+
+/* d2d_convert_stream's twin: `write` receives FLAC frame bytes -- whole frames, in order -- instead of PCM, and `stats` what
+ * STREAMINFO needs.  Built on the public calls: each chunk is uploaded, converted by d2d_translate_batch_device into device PCM
+ * behind the carried remainder, encoded by d2d_flac_encode_device on the same stream, and only the frame bytes come back; `final` is
+ * raised on the chunk after which `read` returns 0.  `bit_depth` (16 / 20 / 24) is passed explicitly because d2d_frame_bytes cannot
+ * tell 20 from 24; it must be the engine's.  Single-file engines that convert all their channels (no channel subset); for planar
+ * input chunk_bytes_per_channel must be a multiple of the block size (0 = 4 MiB).  Cancel and progress as in d2d_convert_stream,
+ * exactly 100.0f last.  Single-buffered: upload, kernels and download of one chunk do not overlap the next chunk's.  On failure
+ * d2d_flac_error() has the message (the engine's own where an engine call failed). */
+typedef struct d2d_flac_stream_stats {
+    uint64_t samples_per_channel;
+    uint64_t blocks;
+    uint32_t min_frame_bytes;    /* 0 and 0 for an empty stream */
+    uint32_t max_frame_bytes;
+} d2d_flac_stream_stats;
+int d2d_convert_stream_flac(d2d_engine* e, uint32_t bit_depth, d2d_read_fn read, void* read_user,
+                            d2d_write_fn write, void* write_user,
+                            const volatile int* cancel, d2d_progress_fn progress, void* progress_user,
+                            uint64_t total_bytes_per_channel, size_t chunk_bytes_per_channel, d2d_flac_stream_stats* stats);
 
 /* ---- shared tables (multi-GPU) ------------------------------------------------------------ */
 

@@ -69,6 +69,11 @@ class Rdsd2Pcm {
     void set_seed(uint64_t seed);
     void set_tap_bits(uint32_t bits);     // 24 (default) or 32: d2d_params.tap_bits (include/dsd2dxd_amd.h); not a reference option
     void set_chunk_bytes(size_t bytes_per_channel);
+    // FLAC output only (ignored for every other output type); off by default.  On: the frames are encoded on the GPU
+    // (d2d_convert_stream_flac, include/dsd2dxd_amd.h) and only they cross the link.  The file is byte for byte the one the host
+    // encoder writes, except STREAMINFO's MD5 field, which is 16 zero bytes -- FLAC's "not computed" -- because the samples never
+    // reach the host.  Tags and pictures are written as before.  Not a reference option; the C mirror (rdsd2pcm_c.h) does not have it.
+    void set_gpu_flac(bool on);
 
     struct Impl;                              // opaque state (public only so the .cpp's helpers can name it)
 

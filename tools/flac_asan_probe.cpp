@@ -1,0 +1,66 @@
+// flac_asan_probe.cpp -- the host FLAC encoder (dsd2dxd_amd/csrc/flac/d2d_flac_host.cpp: d2d_flac_encode_host, i.e. the sink's
+// FlacFrameEnc) on the adversarial signals of tests/flac_ref.py, in heap buffers of exactly the declared sizes, for a sanitizer build:
+//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -o flac_asan_probe \
+//       tools/flac_asan_probe.cpp dsd2dxd_amd/csrc/flac/d2d_flac_host.cpp && ./flac_asan_probe
+// CPU only; prints one line per (channels, depth) with the bytes produced and an FNV-1a of them, and "ok" at the end.
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../include/dsd2dxd_amd.h"
+
+static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
+static uint32_t rng() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (uint32_t)(rng_state >> 16); }
+
+static int32_t sample(int sig, size_t i, uint32_t c, size_t frames, uint32_t depth) {
+    const int32_t hi = (1 << (depth - 1)) - 1, lo = -(1 << (depth - 1));
+    switch (sig) {
+        case 0: return 0;                                                  // digital silence
+        case 1: return (i + c) % 2 ? lo : hi;                              // alternating full scale
+        case 2: return i == (frames / 2 + 37 * c) % frames ? (c % 2 ? lo : hi) : 0;      // one spike in silence
+        case 3: return (int32_t)(rng() % (uint32_t)(hi - lo + 1)) + lo;    // uniform random
+        default: return (int32_t)lrint(hi * sin(2 * M_PI * 1000.0 * (double)i / 88200.0 + 0.7 * c));
+    }
+}
+
+int main() {
+    const size_t lengths[] = {2 * 4096 + 1000, 4096, 4097, 4098, 4099, 4095, 1, 2, 3, 0};
+    for (uint32_t ch : {1u, 2u, 3u, 8u})
+        for (uint32_t depth : {16u, 20u, 24u}) {
+            size_t total = 0; uint64_t h = 1469598103934665603ull;
+            for (int sig = 0; sig < 5; ++sig)
+                for (size_t frames : lengths)
+                    for (int final = 0; final < 2; ++final) {
+                        const uint32_t sb = depth == 16 ? 2 : 3;
+                        // exact-size heap buffers: one byte read or written outside them is a sanitizer report
+                        uint8_t* pcm = (uint8_t*)malloc(frames * ch * sb + (frames ? 0 : 1));
+                        for (size_t i = 0; i < frames; ++i)
+                            for (uint32_t c = 0; c < ch; ++c) {
+                                int32_t v = sample(sig, i, c, frames, depth);
+                                if (depth == 20) v = (int32_t)((uint32_t)v << 4) | (int32_t)(rng() & 15);
+                                uint8_t* q = pcm + (i * ch + c) * sb;
+                                q[0] = (uint8_t)v; q[1] = (uint8_t)(v >> 8); if (sb == 3) q[2] = (uint8_t)(v >> 16);
+                            }
+                        const size_t cap = d2d_flac_bound_bytes(ch, depth, frames, final);
+                        uint8_t* out = (uint8_t*)malloc(cap ? cap : 1);
+                        d2d_flac_result r; size_t used = 0;
+                        const uint32_t first = sig == 3 ? 0x7FFFFFFEu - (uint32_t)(frames / 4096) : (uint32_t)(0x7F * sig);
+                        if (d2d_flac_encode_host(ch, depth, pcm, frames, first, final, out, cap, &r, &used) != D2D_OK) {
+                            fprintf(stderr, "refused: %s\n", d2d_flac_error()); return 1;
+                        }
+                        if (r.bytes_out > cap || used > frames) { fprintf(stderr, "bound broken\n"); return 1; }
+                        for (size_t i = 0; i < r.bytes_out; ++i) h = (h ^ out[i]) * 1099511628211ull;
+                        total += r.bytes_out;
+                        if (cap && d2d_flac_encode_host(ch, depth, pcm, frames, first, final, out, cap - 1, &r, &used) != D2D_ERR_CAPACITY) {
+                            fprintf(stderr, "a capacity one byte short was accepted\n"); return 1;
+                        }
+                        free(pcm); free(out);
+                    }
+            printf("channels %u depth %u: %zu bytes, fnv %016llx\n", ch, depth, total, (unsigned long long)h);
+        }
+    printf("ok\n");
+    return 0;
+}

@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""What does encoding the bench batch's PCM to FLAC cost on the GPU, beside the 16 host threads the sink uses and beside the conversion?
+   tools/flac_probe.py [files] [seconds] [reps] [out.json]     (needs the GPU; defaults 64 files, 60 s each, 9 repetitions, bench_out/flac_probe.json)
+
+The PCM is what d2d_translate_batch_device writes for the bench shape (distinct DSD64 stereo files -> 24-bit 88.2 kHz, TPDF): real
+converter output.  GPU figure: device events around ONE d2d_flac_encode_device call over the whole batch (both kernels), after warm-ups,
+median of the repetitions; the conversion step is timed the same way on the same batch.  Baseline: d2d_flac_encode_host -- the sink's
+own encoder -- on the same PCM in host memory, one block per task on 16 threads, as FlacSink::drain spreads them; wall clock, best of
+two passes.  File 0's device frames are compared with the host's."""
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+import dsd2dxd_amd as d
+from bench import make_files, DSD64
+
+n_files = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 60.0
+reps = int(sys.argv[3]) if len(sys.argv) > 3 else 9
+out_path = sys.argv[4] if len(sys.argv) > 4 else os.path.join(ROOT, "bench_out", "flac_probe.json")
+blocks_in = max(1, int(round(seconds * DSD64 / 8 / 4096)))
+bpc = blocks_in * 4096
+CH, DEPTH, BS, THREADS = 2, 24, 4096, 16
+kw = dict(dsd_rate=1, output_rate=88200, channels=CH, fmt="P", endianness="L", block_size=4096, filter="E", bit_depth=DEPTH, dither="T", seed=206)
+assert torch.cuda.is_available(), "flac_probe.py measures on the GPU; there is no other path"
+dev = torch.device("cuda", 0)
+stream = torch.cuda.current_stream().cuda_stream
+L = d.lib()
+
+
+def timed(fn, before=None):
+    ms = []
+    for i in range(3 + reps):
+        if before:
+            before()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        if i >= 3:
+            ms.append(a.elapsed_time(b))
+    return statistics.median(ms), min(ms), max(ms)
+
+
+# ---- the conversion step: the batch's PCM, device-resident
+files = make_files(n_files, bpc, 1, n_files, 0, 16)
+eng = d.Engine(n_files=n_files, kernel=d.KERNEL_AUTO, device=0, **kw)
+frames, fb = eng.next_frames(bpc), eng.frame_bytes
+ins = [torch.from_numpy(b).to(dev) for b in files]
+row = (frames * fb + 31) // 16 * 16
+pcm = torch.empty((n_files, row), dtype=torch.uint8, device=dev)
+tio = (d.FileIO * n_files)()
+for f in range(n_files):
+    tio[f].dsd, tio[f].bytes_per_channel, tio[f].pcm, tio[f].pcm_capacity_bytes = ins[f].data_ptr(), bpc, pcm[f].data_ptr(), frames * fb
+conv = timed(lambda: eng.translate_batch_device(tio, stream), before=eng.reset)
+
+# ---- the encode call
+cap = d.flac_bound_bytes(CH, DEPTH, frames, True)
+cap16 = (cap + 15) // 16 * 16
+wsb = d.flac_workspace_bytes(CH, DEPTH, frames, True)
+out = torch.empty((n_files, cap16), dtype=torch.uint8, device=dev)
+ws = torch.empty(n_files * wsb, dtype=torch.uint8, device=dev)
+rec = torch.zeros(n_files * 16, dtype=torch.uint8, device=dev)
+fio = (d.FlacIO * n_files)()
+for f in range(n_files):
+    fio[f].pcm, fio[f].frames, fio[f].first_block, fio[f].final = pcm[f].data_ptr(), frames, 0, 1
+    fio[f].out, fio[f].out_capacity_bytes, fio[f].result = out[f].data_ptr(), cap, rec.data_ptr() + 16 * f
+enc = timed(lambda: d.flac_encode_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), stream))
+r = rec.cpu().numpy().view(np.uint64).reshape(n_files, 2)
+flac_bytes = int(r[:, 0].sum())
+nblocks = int(fio[0].blocks)
+
+# ---- the baseline: the sink's encoder on 16 threads, one block per task
+host_pcm = pcm[:, :frames * fb].cpu().numpy()
+slot = d.flac_bound_bytes(CH, DEPTH, BS, True)
+tls = {}
+
+
+def one_block(job):
+    f, b = job
+    import threading
+    st = tls.setdefault(threading.get_ident(), (np.empty(slot, dtype=np.uint8), d.FlacResult(), C.c_size_t()))
+    n = min(BS, frames - b * BS)
+    rc = L.d2d_flac_encode_host(CH, DEPTH, host_pcm[f].ctypes.data + b * BS * fb, n, b, 1, st[0].ctypes.data, slot, C.byref(st[1]), C.byref(st[2]))
+    assert rc == 0
+    return st[1].bytes_out
+
+
+jobs = [(f, b) for f in range(n_files) for b in range(nblocks)]
+host_s, host_bytes = [], 0
+with ThreadPoolExecutor(THREADS) as pool:
+    for _ in range(2):
+        t0 = time.perf_counter()
+        host_bytes = sum(pool.map(one_block, jobs, chunksize=64))
+        host_s.append(time.perf_counter() - t0)
+same_total = host_bytes == flac_bytes
+want0, _, _ = d.flac_encode_host(CH, DEPTH, host_pcm[0], first_block=0, final=True)
+same0 = out[0, :int(r[0, 0])].cpu().numpy().tobytes() == want0
+
+pcm_bytes = n_files * frames * fb
+res = dict(files=n_files, seconds_per_file=seconds, blocks_per_file=nblocks, frames_per_file=frames, pcm_bytes=pcm_bytes, flac_bytes=flac_bytes,
+           ratio=flac_bytes / pcm_bytes, gpu_encode_ms=dict(median=enc[0], min=enc[1], max=enc[2]), conversion_ms=dict(median=conv[0], min=conv[1], max=conv[2]),
+           host_16_threads_s=dict(best=min(host_s), passes=host_s), reps=reps, workspace_bytes=int(ws.numel()), crc="parallel (per-thread chunks, tree combine)",
+           file0_equals_host=bool(same0), total_bytes_equal_host=bool(same_total), kernel=eng.kernel_name())
+os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+with open(out_path, "w") as fh:
+    json.dump(res, fh, indent=1)
+samples = n_files * frames * CH
+print("batch: %d files x %d blocks (%d frames), PCM %.1f MB -> FLAC %.1f MB (ratio %.4f)" % (n_files, nblocks, frames, pcm_bytes / 1e6, flac_bytes / 1e6, flac_bytes / pcm_bytes))
+print("GPU encode (one d2d_flac_encode_device call, both kernels): median %.3f ms (min %.3f, max %.3f) = %.2f Gsamples/s" % (*enc, samples / enc[0] / 1e6))
+print("conversion step (d2d_translate_batch_device, %s):  median %.3f ms (min %.3f, max %.3f)" % (eng.kernel_name(), *conv))
+print("host, %d threads, one block per task: best %.3f s of %s = %.3f Gsamples/s" % (THREADS, min(host_s), ["%.3f" % s for s in host_s], samples / min(host_s) / 1e9))
+print("GPU encode / host: %.1fx;  encode / conversion: %.2fx;  file 0 equals the host encoding: %s;  total bytes equal: %s" %
+      (min(host_s) * 1e3 / enc[0], enc[0] / conv[0], same0, same_total))
+assert same0 and same_total
