@@ -213,6 +213,86 @@ def signal(name, frames, channels, depth, seed=0):
     raise ValueError(name)
 
 
+def _clip(s, depth):
+    return np.clip(s, -(1 << (depth - 1)), (1 << (depth - 1)) - 1).astype(np.int64)
+
+
+def noise(frames, channels, depth, amp_bits, seed):
+    """int64 (frames, channels): uniform noise in +/- 2^amp_bits, clipped to the depth.  amp_bits may be fractional (the amplitude is
+    rounded): the Rice parameter follows the amplitude, and whole steps alone leave some values of k out."""
+    amp = int(round(2.0 ** amp_bits))
+    return _clip(np.random.default_rng(seed).integers(-amp, amp + 1, size=(frames, channels), dtype=np.int64), depth)
+
+
+def residuals(s):
+    """the order-2 residuals of one channel (n > 2): r[i] = s[i] - 2 s[i-1] + s[i-2] for i = 2 .. n-1"""
+    s = np.asarray(s, dtype=np.int64)
+    return s[2:] - 2 * s[1:-1] + s[:-2]
+
+
+def rice_stats(s):
+    """(k, the longest unary run in bits) of one channel of one block, as every encoder here must choose and write them"""
+    if len(s) <= 2:
+        return None, 0
+    r = residuals(s)
+    k = rice_parameter(int(np.abs(r).sum()), len(r))
+    u = np.where(r >= 0, 2 * r, -2 * r - 1)
+    return k, int((u >> k).max())
+
+
+def tuned_sum(depth, n, target, seed):
+    """int64 (n,): one channel whose n - 2 order-2 residuals have sum |r| == target exactly: the mean that decides k sits where the
+    caller puts it.  Noise is scaled (by bisection) until the sum over all residuals but the last is just below the target; the last
+    sample, which r[n-1] alone depends on, makes up the difference."""
+    assert n >= 4 and target >= 0
+    u = np.random.default_rng(seed).uniform(-1.0, 1.0, n - 1)
+    top = float(1 << (depth - 3))                              # |s| <= 2^(depth-3): the last sample stays within the depth below
+
+    def part(a):
+        s = np.rint(u * a).astype(np.int64)
+        return s, int(np.abs(residuals(s)).sum())
+
+    assert part(top)[1] > target, "the target is beyond what noise of this depth reaches"
+    lo, hi = 0.0, top                                          # part(lo) <= target < part(hi)
+    for _ in range(80):
+        mid = 0.5 * (lo + hi)
+        if part(mid)[1] > target:
+            hi = mid
+        else:
+            lo = mid
+    s, p = part(lo)
+    d = target - p
+    assert 0 <= d <= 1 << (depth - 3), (d, target)
+    base = 2 * int(s[-1]) - int(s[-2])                         # the last sample that would make r[n-1] zero
+    last = base - d if base > 0 else base + d                  # |r[n-1]| = d, stepping towards zero
+    out = np.concatenate([s, [last]]).astype(np.int64)
+    assert -(1 << (depth - 1)) <= last < (1 << (depth - 1))
+    assert int(np.abs(residuals(out)).sum()) == target
+    return out
+
+
+def spike_at(frames, channels, depth, index, amp, floor_amp):
+    """int64 (frames, channels): silence (floor_amp = 0) or uniform +/- floor_amp noise, and one sample of height amp at `index` of
+    every channel: +amp in the even channels, -amp in the odd ones"""
+    if floor_amp:
+        s = np.random.default_rng(1000 * index + frames).integers(-floor_amp, floor_amp + 1, size=(frames, channels), dtype=np.int64)
+    else:
+        s = np.zeros((frames, channels), dtype=np.int64)
+    for c in range(channels):
+        s[index, c] = amp if c % 2 == 0 else -amp
+    return _clip(s, depth)
+
+
+def varying(frames, channels, depth, seed):
+    """int64 (frames, channels): noise whose amplitude is drawn anew for every block of 4096 (2^0 .. 2^(depth-2)), so that the frames
+    of one file differ in size by orders of magnitude"""
+    rng = np.random.default_rng(seed)
+    u = rng.uniform(-1.0, 1.0, size=(frames, channels))
+    bits = rng.integers(0, depth - 1, size=frames // BLOCK + 1)
+    amp = (1 << bits[np.arange(frames) // BLOCK]).astype(np.float64)
+    return _clip(np.rint(u * amp[:, None]), depth)
+
+
 def pack_pcm(samples, depth, seed=0):
     """interleaved little-endian frames as the translate calls write them: 16-bit in 2 bytes, 24-bit in 3, 20-bit in the upper 20 bits
     of a 3-byte container (the low nibble is filled with noise here: the encoders must shift it away)"""
