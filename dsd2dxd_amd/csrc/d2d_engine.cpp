@@ -125,10 +125,9 @@ struct EventPairs {
 // Everything a call's launches need that is fixed once d2d_create has made its choices.  batch_call copies what a launcher writes into and
 // fills in what belongs to the call (the shaper's ping-pong state and grid, the cascade's f64 line).
 struct LaunchState {
-    FirArgs fir{};             // the main table
-    FirArgs fir_lo{};          // 32-bit taps in two passes: the residual table, on the second half of the job table and of the scratch
-    FirArgs fir_m2{};          // MONO2: the pair kernel, on the half-call jobs behind the ordinary ones
-    PxArgs px{};
+    FirLaunch fir;             // the main table, or the composed polyphase pass
+    FirLaunch fir_lo;          // 32-bit taps in two passes: the residual table, on the second half of the job table and of the scratch
+    FirLaunch fir_m2;          // MONO2: the pair kernel, on the half-call jobs behind the ordinary ones
     Rs2Args rs{};
     NoiseShapeArgs ns{};
     size_t njobs = 0;          // job rows per slot (32-bit taps: the second pass's jobs behind the first's; MONO2: the half-call jobs)
@@ -278,24 +277,16 @@ static int clear_file_state(d2d_engine* e, uint32_t file) {
 // d2d_engine::launch, once the route is chosen and every table and the job table exist
 static void build_launch_state(d2d_engine* e) {
     LaunchState& l = e->launch;
-    l.fir = fir_args_static(e->p, e->fc, e->epi, e->route);
-    l.fir.jobs = e->d_jobs; l.fir.tables = e->d_fir_tables;
+    l.fir = fir_launch(e->p, e->fc, e->epi, e->route, PASS_MAIN);
+    l.fir.bind(e->d_jobs, e->d_fir_tables);
     if (e->route.fine) {
-        l.fir_lo = fir_args_static(e->p, e->fc, e->epi, e->route, &e->lo_def);
-        l.fir_lo.jobs = e->d_jobs + e->nstreams; l.fir_lo.tables = e->d_fir_tables_lo;
+        l.fir_lo = fir_launch(e->p, e->fc, e->epi, e->route, PASS_LO, &e->lo_def);
+        l.fir_lo.bind(e->d_jobs + e->nstreams, e->d_fir_tables_lo);
     }
     if (e->mono2_ok()) {
-        l.fir_m2 = l.fir;
-        l.fir_m2.jobs = e->d_jobs + e->nstreams; l.fir_m2.tables = e->d_fir_tables_m2;
-        l.fir_m2.epi.channels = 2; l.fir_m2.in_channels = 2;
-        l.fir_m2.B = 0x40000000u;     // (one "block" per half: the gather path's layout rule then reads half c at c * half)
-        l.fir_m2.pipelined = (uint32_t)e->route.mono2_pipe; l.fir_m2.mono2 = 1;
+        l.fir_m2 = fir_launch(e->p, e->fc, e->epi, e->route, PASS_MONO2);
+        l.fir_m2.bind(e->d_jobs + e->nstreams, e->d_fir_tables_m2);
     }
-    l.px.jobs = e->d_jobs; l.px.tables = e->d_fir_tables;
-    l.px.in_channels = e->Cin; l.px.B = e->route.B; l.px.keep = e->route.keep; l.px.msb = e->p.endianness == D2D_MSB_FIRST ? 1u : 0u;
-    l.px.to_scratch = e->noise_shape ? 1u : 0u;
-    l.px.il2 = e->route.il2 ? 1u : 0u;
-    l.px.epi = e->epi;
     l.rs.jobs = e->d_jobs; l.rs.tables = e->d_resamp;
     l.rs.S = e->S; l.rs.epi = e->epi;
     NoiseShapeArgs& ns = l.ns;
@@ -303,7 +294,7 @@ static void build_launch_state(d2d_engine* e) {
     ns.scale_bits = e->poly ? e->poly->S : e->S; ns.nstreams = e->nstreams; ns.epi = e->epi;
     ns.res = e->cascade() ? 1u : 0u;
     // the all-integer loop: the largest |y * 2^S| any output can reach (composed polyphase: its heaviest phase) leaves room for a few LSB
-    const uint64_t sa = e->poly ? max_phase_sum_abs(*e->poly) : l.fir.sum_abs_q;
+    const uint64_t sa = e->poly ? max_phase_sum_abs(*e->poly) : sum_abs_q(*e->fc.fir);
     ns.intq = (!(e->p.debug_flags & D2D_DBG_NO_INTQ) && sa + (1ull << 24) < (1ull << 31)) ? 1u : 0u;
     ns.general = (e->p.debug_flags & D2D_DBG_NS_GENERAL) ? 1u : 0u;
 }
@@ -633,16 +624,10 @@ static int enqueue_jobs(d2d_engine* e, const d2d_file_io* io, const CallPlan& pl
     return D2D_OK;
 }
 
-// one FIR pass of a single-filter engine over every stream
-static int launch_fir_pass(d2d_engine* e, const FirArgs& a, uint32_t max_nx, hipStream_t s) {
-    if (e->route.kernel == D2D_KERNEL_LUT) {
-        const uint32_t per_tile = lut_outputs_per_tile(e->Mb);
-        HIPCHK(e, launch_fir_lut(a, e->Mb, (max_nx + per_tile - 1) / per_tile, e->nstreams, s));
-    } else if (e->route.mfma_v2) {
-        HIPCHK(e, launch_fir_mfma2(a, e->M, e->N, max_nx, e->nstreams, s));
-    } else {
-        HIPCHK(e, launch_fir_mfma(a, e->mfma, max_nx, e->nstreams, s));
-    }
+// one FIR pass over every file: `max_nout` outputs per stream at the most
+static int launch_fir_pass(d2d_engine* e, const FirLaunch& p, uint32_t max_nout, hipStream_t s) {
+    static FirLauncher* const launchers[] = {launch_fir_lut, launch_fir_mfma, launch_fir_mfma2, launch_fir_mfma3, launch_fir_mx, launch_fir_px, launch_poly_plain};   // by FirFamily
+    HIPCHK(e, launchers[p.family](p, max_nout, e->n_files, s));
     return D2D_OK;
 }
 
@@ -656,14 +641,8 @@ static int launch_call(d2d_engine* e, const CallPlan& pl, hipStream_t s, const b
 
     EventPairs::Pair* pe = nullptr;
     if (e->profiling && max_nx) HIPCHK(e, e->prof.open(s, &pe));
-    if (e->poly) {
-        PxArgs px = l.px;
-        if (e->route.poly_plain) HIPCHK(e, launch_poly_plain(px, *e->poly, max_frames, e->nstreams, s));
-        else HIPCHK(e, launch_fir_px(px, *e->poly, max_frames, n_files, s));
-    } else if (pl.mono2) {
-        HIPCHK(e, launch_fir_mfma2(l.fir_m2, e->M, e->N, max_nx / 2, 2 * n_files, s));
-    } else if (max_nx) {
-        int rc = launch_fir_pass(e, l.fir, max_nx, s);
+    {   // (the composed polyphase pass makes the frames themselves; the mono pair converts the two halves of a call side by side)
+        int rc = e->poly ? launch_fir_pass(e, l.fir, max_frames, s) : pl.mono2 ? launch_fir_pass(e, l.fir_m2, max_nx / 2, s) : launch_fir_pass(e, l.fir, max_nx, s);
         if (rc) return rc;
     }
     if ((e->poly ? max_frames : max_nx) && d2d_last_launched_kernel) e->launched = d2d_last_launched_kernel;

@@ -19,6 +19,7 @@
 
 #include "d2d_device.h"
 #include "d2d_launch.h"
+#include "d2d_route.h"
 
 namespace d2d {
 
@@ -534,41 +535,34 @@ __global__ void d2d_xhist_kernel(const StreamJob* jobs, uint32_t P) {
 
 // ---- launchers -------------------------------------------------------------------------------
 
-size_t lut_smem_bytes(const FirArgs& a, int MB) {
-    const int LS = MB >= 8 ? MB : 8;
-    const size_t span = (size_t)((255 * LS + 8 * (a.nq + 1) + 16 + 15) & ~15);
-    return (size_t)a.ntab * 128 + 4 * sizeof(double) + span;
-}
-
+// (the arguments, the LDS bytes and the outputs per tile: d2d_route.cpp, lut_plan)
 template <int MB>
-static hipError_t launch_lut_t(const FirArgs& a, dim3 grid, hipStream_t s) {
-    const size_t smem = lut_smem_bytes(a, MB);
+static hipError_t launch_lut_t(const FirLaunch& p, dim3 grid, hipStream_t s) {
     static KernelPrep prep;
     hipError_t e = prep.max_dynamic_lds(reinterpret_cast<const void*>(&d2d_fir_lut_kernel<MB>), 160 * 1024);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(d2d_fir_lut_kernel<MB>, grid, dim3(LUT_THREADS), smem, s, a);
+    hipLaunchKernelGGL(d2d_fir_lut_kernel<MB>, grid, dim3(LUT_THREADS), p.lds, s, p.m.f);
     d2d_last_launched_kernel = launched_name<MB>("d2d_fir_lut_kernel");
     return hipGetLastError();
 }
 
-hipError_t launch_fir_lut(const FirArgs& a, int MB, uint32_t max_tiles, uint32_t nstreams, hipStream_t s) {
+hipError_t launch_fir_lut(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
+    const uint32_t nstreams = nfiles * p.rows_per_file, max_tiles = (max_nout + p.tile - 1) / p.tile;
     if (nstreams == 0 || max_tiles == 0) return hipSuccess;
     // enough blocks to fill 256 CUs a few times over, the rest by the in-kernel tile loop
     uint32_t gx = max_tiles;
     const uint32_t cap = (4096 + nstreams - 1) / nstreams;
     if (gx > cap) gx = cap < 1 ? 1 : cap;
     dim3 grid(gx, nstreams);
-    switch (MB) {
-        case 1: return launch_lut_t<1>(a, grid, s);
-        case 2: return launch_lut_t<2>(a, grid, s);
-        case 4: return launch_lut_t<4>(a, grid, s);
-        case 8: return launch_lut_t<8>(a, grid, s);
-        case 16: return launch_lut_t<16>(a, grid, s);
+    switch (p.unit) {
+        case 1: return launch_lut_t<1>(p, grid, s);
+        case 2: return launch_lut_t<2>(p, grid, s);
+        case 4: return launch_lut_t<4>(p, grid, s);
+        case 8: return launch_lut_t<8>(p, grid, s);
+        case 16: return launch_lut_t<16>(p, grid, s);
         default: return hipErrorInvalidValue;
     }
 }
-
-uint32_t lut_outputs_per_tile(int MB) { return LUT_THREADS * (MB >= 8 ? 1 : 8 / MB); }
 
 hipError_t launch_deinterleave(const StreamJob* jobs, uint32_t nfiles, uint32_t C, uint32_t spf, uint32_t max_L, hipStream_t s) {
     if (nfiles == 0 || max_L == 0) return hipSuccess;

@@ -581,39 +581,32 @@ __global__ __launch_bounds__(MFMA_MAX_THREADS, 3) void d2d_fir_mfma_kernel(MfmaA
 
 // ---- host side -------------------------------------------------------------------------------
 
-// (mfma_supported, mfma_geometry: d2d_route.cpp)
+// (mfma_supported, the arguments and the geometry: d2d_route.cpp, mfma_plan)
 
 template <int MB>
-static hipError_t launch_mfma_t(const MfmaArgs& m, size_t smem, uint32_t nwt_max, uint32_t nfiles, hipStream_t s) {
+static hipError_t launch_mfma_t(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
     static KernelPrep prep;
     int dev = 0;
     hipError_t e = prep.max_dynamic_lds(reinterpret_cast<const void*>(&d2d_fir_mfma_kernel<MB>), 160 * 1024, &dev);
     if (e != hipSuccess) return e;
     // every wave loops over its share of the wave-tiles: launch what is resident at once
+    const uint32_t nrows = nfiles * p.rows_per_file, nwt_max = (max_nout + p.tile - 1) / p.tile;
     uint32_t gx;
-    e = persistent_grid_x(&d2d_fir_mfma_kernel<MB>, prep, dev, m.nwaves, smem, nfiles, (nwt_max + m.nwaves - 1) / m.nwaves, &gx);
+    e = persistent_grid_x(&d2d_fir_mfma_kernel<MB>, prep, dev, p.nwaves, p.lds, nrows, (nwt_max + p.block_tiles - 1) / p.block_tiles, &gx);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((d2d_fir_mfma_kernel<MB>), dim3(gx, nfiles), dim3(64 * m.nwaves), smem, s, m);
+    hipLaunchKernelGGL((d2d_fir_mfma_kernel<MB>), dim3(gx, nrows), dim3(64 * p.nwaves), p.lds, s, p.m1);
     d2d_last_launched_kernel = launched_name<MB>("d2d_fir_mfma_kernel");
     return hipGetLastError();
 }
 
-hipError_t launch_fir_mfma(const FirArgs& a, const MfmaLayout& g, uint32_t max_nout, uint32_t nstreams, hipStream_t s) {
-    if (nstreams == 0 || max_nout == 0) return hipSuccess;
-    const uint32_t C = a.epi.channels;
-    const int MB = g.M / 8;
-    MfmaArgs m{};
-    size_t smem = 0;
-    mfma_geometry(a, g, m, smem);
-    const uint32_t nfiles = (nstreams / C) * m.ngroups;       // grid rows: one per (file, channel group)
-    if (smem > 160 * 1024) return hipErrorInvalidValue;
-    const uint32_t nwt = (max_nout + 255u) / 256u;
-    switch (MB) {
-        case 1: return launch_mfma_t<1>(m, smem, nwt, nfiles, s);
-        case 2: return launch_mfma_t<2>(m, smem, nwt, nfiles, s);
-        case 4: return launch_mfma_t<4>(m, smem, nwt, nfiles, s);
-        case 8: return launch_mfma_t<8>(m, smem, nwt, nfiles, s);
-        case 16: return launch_mfma_t<16>(m, smem, nwt, nfiles, s);
+hipError_t launch_fir_mfma(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
+    if (nfiles == 0 || max_nout == 0) return hipSuccess;
+    switch (p.unit) {
+        case 1: return launch_mfma_t<1>(p, max_nout, nfiles, s);
+        case 2: return launch_mfma_t<2>(p, max_nout, nfiles, s);
+        case 4: return launch_mfma_t<4>(p, max_nout, nfiles, s);
+        case 8: return launch_mfma_t<8>(p, max_nout, nfiles, s);
+        case 16: return launch_mfma_t<16>(p, max_nout, nfiles, s);
         default: return hipErrorInvalidValue;
     }
 }

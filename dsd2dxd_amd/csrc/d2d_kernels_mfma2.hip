@@ -597,9 +597,12 @@ __global__ __launch_bounds__(D2D_M2_THREADS) void d2d_fir_mfma2_kernel(Mfma2Args
 
 // ---- host side -------------------------------------------------------------------------------
 
-// (which launch goes where and its geometry: d2d_route.cpp)
+// (which launch goes where and its geometry: d2d_route.cpp, mfma2_plan)
 template <int MB, int NPG, int CH, int EPI>
-static hipError_t launch_mfma2_t(Mfma2Args& m, size_t smem, uint32_t nwt_max, uint32_t nrows, hipStream_t s) {
+static hipError_t launch_mfma2_t(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
+    Mfma2Args m = p.m;
+    size_t smem = p.lds;
+    const uint32_t nrows = nfiles * p.rows_per_file, nwt_max = (max_nout + p.tile - 1) / p.tile;
     static KernelPrep prep;
     int dev = 0;
     const void* fn = reinterpret_cast<const void*>(&d2d_fir_mfma2_kernel<MB, NPG, CH, EPI>);
@@ -642,31 +645,15 @@ static hipError_t launch_mfma2_t(Mfma2Args& m, size_t smem, uint32_t nwt_max, ui
     return hipGetLastError();
 }
 
-hipError_t launch_fir_mfma2(const FirArgs& a, int M, int N, uint32_t max_nout, uint32_t nstreams, hipStream_t s) {
-    if (nstreams == 0 || max_nout == 0) return hipSuccess;
-    const uint32_t C = a.epi.channels;
-    const int MB = M / 8, NPG = mfma2_pairs(M, N);
-    Mfma2Args m{};
-    size_t smem = 0;
-    mfma2_launch_args(a, MB, NPG, N, m, smem);
-    const uint32_t nrows = (nstreams / C) * m.ngroups;       // grid rows: one per (file, channel group)
-    // the fp6 kernel has its own LDS layout (and M = 128 no two-group one at all); several pairs per wave: one block row per file
-    if (a.pipelined == PIPE_FP6) return launch_fir_mx(m, MB, N, max_nout, m.npairs > 1u ? nstreams / C : nrows, s);
-    if (smem > 160 * 1024) return hipErrorInvalidValue;
-    const uint32_t nwt = (max_nout + (M2_TILE - 1)) / M2_TILE;
-    // the epilogue flavour: the integers for the stage-A scratch, stereo 24-bit packed in registers, or anything via LDS
-    const int epi = mfma2_epilogue(a, m);
-    // stereo 24-bit at 0 dB: the software-pipelined kernel (d2d_kernels_mfma3.hip), same results; the engine chose it (and its
-    // table variant) when it was created
-    if (a.pipelined) return launch_fir_mfma3(m, MB, NPG, N, nwt, nrows, s);
-#define X(mb, npg)                                                                                  \
-    if (MB == mb && NPG == npg) {                                                                   \
-        if (C == 1) return epi == 2 ? launch_mfma2_t<mb, npg, 1, 2>(m, smem, nwt, nrows, s) : launch_mfma2_t<mb, npg, 1, 0>(m, smem, nwt, nrows, s); \
-        return epi == 2 ? launch_mfma2_t<mb, npg, 2, 2>(m, smem, nwt, nrows, s)                      \
-             : epi == 1 ? launch_mfma2_t<mb, npg, 2, 1>(m, smem, nwt, nrows, s) : launch_mfma2_t<mb, npg, 2, 0>(m, smem, nwt, nrows, s); \
-    }
+hipError_t launch_fir_mfma2(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
+    if (nfiles == 0 || max_nout == 0) return hipSuccess;
+    if (p.unit < 0) return hipErrorInvalidValue;
+    const int MB = p.t[0], NPG = p.t[1];
+#define T(mb, npg, ch, epi) case (ch) * 4 + (epi): return launch_mfma2_t<mb, npg, ch, epi>(p, max_nout, nfiles, s);
+#define X(mb, npg) if (MB == mb && NPG == npg) switch (p.t[2] * 4 + p.t[3]) { T(mb, npg, 1, 2) T(mb, npg, 1, 0) T(mb, npg, 2, 2) T(mb, npg, 2, 1) T(mb, npg, 2, 0) default: break; }
     D2D_M2_SHAPES(X)
 #undef X
+#undef T
     return hipErrorInvalidValue;
 }
 

@@ -35,25 +35,23 @@ namespace d2d {
 #define X(unit, mb, npg, nt0, nt1) +1
 static_assert(D2D_M3_UNITS == 0 D2D_M3_UNIT_LIST(X), "the Makefile's M3_UNITS is not the length of D2D_M3_UNIT_LIST (d2d_m3.h)");
 #undef X
-#define X(unit, mb, npg, nt0, nt1) extern template hipError_t launch_m3_unit<unit>(Mfma2Args& m, uint32_t nwt_max, uint32_t nrows, hipStream_t s);
+#define X(unit, mb, npg, nt0, nt1) extern template hipError_t launch_m3_unit<unit>(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s);
 D2D_M3_UNIT_LIST(X)
 #undef X
-template hipError_t launch_m3_unit<0>(Mfma2Args& m, uint32_t nwt_max, uint32_t nrows, hipStream_t s);
+template hipError_t launch_m3_unit<0>(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s);
 
 // one launcher per unit number (null: a unit an A/B build leaves out); which unit serves a shape: d2d_route.cpp
-typedef hipError_t (*M3Launch)(Mfma2Args&, uint32_t, uint32_t, hipStream_t);
-static const std::array<M3Launch, D2D_M3_UNITS> m3_launchers = [] {
-    std::array<M3Launch, D2D_M3_UNITS> v{};
+static const std::array<FirLauncher*, D2D_M3_UNITS> m3_launchers = [] {
+    std::array<FirLauncher*, D2D_M3_UNITS> v{};
 #define X(unit, mb, npg, nt0, nt1) if constexpr (m3_unit_kept(mb, npg)) std::get<unit>(v) = &launch_m3_unit<unit>;
     D2D_M3_UNIT_LIST(X)
 #undef X
     return v;
 }();
 
-hipError_t launch_fir_mfma3(Mfma2Args& m, int MB, int NPG, int NT, uint32_t nwt_max, uint32_t nrows, hipStream_t s) {
-    const int u = m3_find(MB, NPG);
-    if (u < 0 || !m3_launchers[u] || (!m.f.to_scratch && !m3_frames(u, NT))) return hipErrorInvalidValue;
-    return m3_launchers[u](m, nwt_max, nrows, s);
+hipError_t launch_fir_mfma3(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
+    if (nfiles == 0 || max_nout == 0) return hipSuccess;
+    return p.unit >= 0 && m3_launchers[p.unit] ? m3_launchers[p.unit](p, max_nout, nfiles, s) : hipErrorInvalidValue;
 }
 
 #if D2D_M3_STAMPS

@@ -40,24 +40,23 @@ namespace d2d {
 #define X(unit, mb, nt, fl, npr) +1
 static_assert(D2D_MX_UNITS == 0 D2D_MX_UNIT_LIST(X), "the Makefile's MX_UNITS is not the length of D2D_MX_UNIT_LIST (d2d_mx.h)");
 #undef X
-#define X(unit, mb, nt, fl, npr) extern template hipError_t launch_mx_unit<unit>(Mfma2Args& m, uint32_t max_nout, uint32_t nrows, hipStream_t s);
+#define X(unit, mb, nt, fl, npr) extern template hipError_t launch_mx_unit<unit>(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s);
 D2D_MX_UNIT_LIST(X)
 #undef X
-template hipError_t launch_mx_unit<0>(Mfma2Args& m, uint32_t max_nout, uint32_t nrows, hipStream_t s);
+template hipError_t launch_mx_unit<0>(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s);
 
 // one launcher per unit number (null: a unit an A/B build leaves out); which unit serves a launch: d2d_route.cpp
-typedef hipError_t (*MxLaunch)(Mfma2Args&, uint32_t, uint32_t, hipStream_t);
-static const std::array<MxLaunch, D2D_MX_UNITS> mx_launchers = [] {
-    std::array<MxLaunch, D2D_MX_UNITS> v{};
+static const std::array<FirLauncher*, D2D_MX_UNITS> mx_launchers = [] {
+    std::array<FirLauncher*, D2D_MX_UNITS> v{};
 #define X(unit, mb, nt, fl, npr) if constexpr (mx_unit_kept(mb, nt)) std::get<unit>(v) = &launch_mx_unit<unit>;
     D2D_MX_UNIT_LIST(X)
 #undef X
     return v;
 }();
 
-hipError_t launch_fir_mx(Mfma2Args& m, int MB, int NT, uint32_t max_nout, uint32_t nrows, hipStream_t s) {
-    const int u = mx_launch_unit(m, MB, NT);
-    return u >= 0 && mx_launchers[u] ? mx_launchers[u](m, max_nout, nrows, s) : hipErrorInvalidValue;
+hipError_t launch_fir_mx(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
+    if (nfiles == 0 || max_nout == 0) return hipSuccess;
+    return p.unit >= 0 && mx_launchers[p.unit] ? mx_launchers[p.unit](p, max_nout, nfiles, s) : hipErrorInvalidValue;
 }
 #if D2D_MX_STAMPS
 void mx_debug_stamps(unsigned long long out[8]) {

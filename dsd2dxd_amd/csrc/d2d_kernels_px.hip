@@ -34,15 +34,14 @@ namespace d2d {
 #define X(unit, lp, mp, np, g) +1
 static_assert(D2D_PX_UNITS == 0 D2D_PX_UNIT_LIST(X), "the Makefile's PX_UNITS is not the length of D2D_PX_UNIT_LIST (d2d_px.h)");
 #undef X
-#define X(unit, lp, mp, np, g) extern template hipError_t launch_px_unit<unit>(PxArgs& a, uint32_t max_nout, uint32_t nfiles, hipStream_t s);
+#define X(unit, lp, mp, np, g) extern template hipError_t launch_px_unit<unit>(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s);
 D2D_PX_UNIT_LIST(X)
 #undef X
-template hipError_t launch_px_unit<0>(PxArgs& a, uint32_t max_nout, uint32_t nfiles, hipStream_t s);
+template hipError_t launch_px_unit<0>(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s);
 
 // one launcher per unit number; which unit serves a table: d2d_route.cpp
-typedef hipError_t (*PxLaunch)(PxArgs&, uint32_t, uint32_t, hipStream_t);
-static const std::array<PxLaunch, D2D_PX_UNITS> px_launchers = [] {
-    std::array<PxLaunch, D2D_PX_UNITS> v{};
+static const std::array<FirLauncher*, D2D_PX_UNITS> px_launchers = [] {
+    std::array<FirLauncher*, D2D_PX_UNITS> v{};
 #define X(unit, lp, mp, np, g) std::get<unit>(v) = &launch_px_unit<unit>;
     D2D_PX_UNIT_LIST(X)
 #undef X
@@ -50,7 +49,6 @@ static const std::array<PxLaunch, D2D_PX_UNITS> px_launchers = [] {
 }();
 
 // ---- the plain form: one output per lane, bit by bit ----
-constexpr int PXP_THREADS = 256;
 __global__ __launch_bounds__(PXP_THREADS) void d2d_poly_plain_kernel(PxArgs a, uint32_t span) {
     extern __shared__ __align__(16) unsigned char smem[];
     int32_t* tq = reinterpret_cast<int32_t*>(smem);                                  // Q[Lp][NP]
@@ -95,32 +93,23 @@ __global__ __launch_bounds__(PXP_THREADS) void d2d_poly_plain_kernel(PxArgs a, u
     if (!a.to_scratch) block_peak_max(pk, job.peak, red);
 }
 
-hipError_t launch_poly_plain(PxArgs& a, const d2d_poly_def& p, uint32_t max_nout, uint32_t nstreams, hipStream_t s) {
+// (the arguments, the span of a tile's windows and the LDS bytes: d2d_route.cpp, px_plan)
+hipError_t launch_poly_plain(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
+    const uint32_t nstreams = nfiles * p.rows_per_file;
     if (max_nout == 0 || nstreams == 0) return hipSuccess;
-    a.Lp = (uint32_t)p.Lp; a.Mp = (uint32_t)p.Mp; a.NP = (uint32_t)p.NP; a.D = p.D; a.S = p.S;
-    // bytes a tile's windows span: 255 outputs further on, the window itself, up to 15 bytes in front, 16 of slack
-    const uint32_t span = (uint32_t)((((uint64_t)255 * p.Mp / p.Lp + p.NP + 7) / 8 + 15 + 16 + 15) & ~(uint64_t)15);
-    const size_t smem = (((size_t)p.Lp * p.NP * 4 + 15) & ~(size_t)15) + 32 + span;
     static KernelPrep prep;
     hipError_t e = prep.max_dynamic_lds(reinterpret_cast<const void*>(&d2d_poly_plain_kernel), 160 * 1024);
     if (e != hipSuccess) return e;
-    const uint32_t ntiles = (max_nout + PXP_THREADS - 1) / PXP_THREADS;
+    const uint32_t ntiles = (max_nout + p.tile - 1) / p.tile;
     const uint32_t gx = std::min(ntiles, std::max(1u, 2048u / nstreams));
-    hipLaunchKernelGGL(d2d_poly_plain_kernel, dim3(gx, nstreams), dim3(PXP_THREADS), smem, s, a, span);
+    hipLaunchKernelGGL(d2d_poly_plain_kernel, dim3(gx, nstreams), dim3(PXP_THREADS), p.lds, s, p.px, p.px_span);
     d2d_last_launched_kernel = "d2d_poly_plain_kernel";
     return hipGetLastError();
 }
 
-hipError_t launch_fir_px(PxArgs& a, const d2d_poly_def& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
+hipError_t launch_fir_px(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
     if (max_nout == 0 || nfiles == 0) return hipSuccess;
-    a.Lp = (uint32_t)p.Lp; a.Mp = (uint32_t)p.Mp; a.NP = (uint32_t)p.NP; a.D = p.D; a.S = p.S;
-    a.dkind = a.epi.dither == 'T' ? 1u : (a.epi.dither == 'R' ? 2u : 0u);
-    a.fbits = p.S - ((int)a.epi.bits - 1);
-    a.qmin_i = a.epi.bits == 32 ? 0 : -(1 << (a.epi.bits - 1));
-    a.qmax_i = a.epi.bits == 32 ? 0 : (1 << (a.epi.bits - 1)) - 1;
-    a.qsh = a.epi.bits == 20 ? 4u : 0u;
-    const int u = px_find(p);
-    return u >= 0 ? px_launchers[u](a, max_nout, nfiles, s) : hipErrorInvalidValue;
+    return p.unit >= 0 ? px_launchers[p.unit](p, max_nout, nfiles, s) : hipErrorInvalidValue;
 }
 
 }  // namespace d2d

@@ -42,7 +42,7 @@ struct KernelPrep {
 // The grid of a persistent launch of the matrix-core FIR kernels: every wave loops over its share of the wave-tiles, so gx = what is resident
 // at once (blocks per CU from the occupancy query, cached per device in the kernel's own `prep`, under its lock) spread over the `nrows`
 // block rows, and no more than the `need` blocks that have a tile to start on.  (launch_mfma2_t keeps its own copy: it shrinks the block
-// inside the query and caches what the register file admitted.)
+// inside the query and caches what the register file admitted.)  `nwaves` and `smem` are the plan's: fixed per engine, so the cache holds.
 template <class Args>
 inline hipError_t persistent_grid_x(void (*kernel)(Args), KernelPrep& prep, int dev, uint32_t nwaves, size_t smem, uint32_t nrows, uint32_t need,
                                     uint32_t* gx_out) {
@@ -89,9 +89,11 @@ inline const char* launched_name(const char* base) {
     return it->second.c_str();       // (map nodes do not move)
 }
 
-size_t lut_smem_bytes(const FirArgs& a, int MB);
-uint32_t lut_outputs_per_tile(int MB);
-hipError_t launch_fir_lut(const FirArgs& a, int MB, uint32_t max_tiles, uint32_t nstreams, hipStream_t s);
+// The FIR launchers, one per FirFamily.  What they launch was planned when the engine was created (d2d_route.h: FirLaunch); they add what
+// depends on the device and the call: the LDS attribute, the occupancy, the grid for `max_nout` outputs of the longest of `nfiles` files.
+struct FirLaunch;
+typedef hipError_t FirLauncher(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s);
+FirLauncher launch_fir_lut, launch_fir_mfma, launch_fir_mfma2, launch_fir_mfma3, launch_fir_mx, launch_fir_px, launch_poly_plain;
 hipError_t launch_resample2(Rs2Args& a, const d2d_resamp_def& r, uint32_t max_out, uint32_t nfiles, hipStream_t s);
 hipError_t launch_deinterleave(const StreamJob* jobs, uint32_t nfiles, uint32_t C, uint32_t streams_per_file, uint32_t max_L, hipStream_t s);
 hipError_t launch_noise_shape(const NoiseShapeArgs& a, hipStream_t s);

@@ -5,10 +5,15 @@
 
 namespace d2d {
 
+#define D2D_M3_THREADS 512
+#ifndef D2D_M3_STAGED
+#define D2D_M3_STAGED 1     // M = 8: a full tile's frames go through LDS and leave as aligned 1-KiB rows (0: straight from registers, A/B builds)
+#endif
+
 // ---- the compiled kernels: ONE row per object ---------------------------------------------------------------------------------
 // X(unit, MB, NPG, NT0, NT1): MB = bytes per output (M / 8), NPG = pair steps of a group's window (mfma2_pairs(M, N) = (N + 7 M + 24 + 63) / 64).
 // Unit n is d2d_m3_unit.hip compiled with -DD2D_M3_UNIT=n (unit 0 rides in d2d_kernels_mfma3.hip, next to the dispatcher) and holds every
-// format of its row: launch_m3_formats in d2d_m3_kernel.h.  The dispatcher's table, launch_fir_mfma3, mfma3_supported and
+// format of its row: launch_m3_unit in d2d_m3_kernel.h.  The dispatcher's table, the launch plan (d2d_route.cpp: m3_plan), mfma3_supported and
 // mfma3_scr_supported all read this list and nothing else.  Adding a shape is one row here plus M3_UNITS in the Makefile (the
 // dispatcher's static_assert says so when the two disagree).
 //   every row   the exact integers for the scratch (the noise-shaping pass of the 44.1k-family filters, stage A of the 48k cascade)
@@ -28,10 +33,9 @@ constexpr bool m3_unit_kept(int MB, int NPG) { return MB == 1 && NPG == 4; }
 constexpr bool m3_unit_kept(int, int) { return true; }
 #endif
 
-struct Mfma2Args;
-template <int UNIT> hipError_t launch_m3_unit(Mfma2Args& m, uint32_t nwt_max, uint32_t nrows, hipStream_t s);   // d2d_m3_kernel.h; one explicit instantiation per object
+struct FirLaunch;
+template <int UNIT> hipError_t launch_m3_unit(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s);   // d2d_m3_kernel.h; one explicit instantiation per object
 bool mfma3_supported(int MB, int NPG, int NT);     // is a kernel compiled that serves frames for this shape and tap count?
 bool mfma3_scr_supported(int MB, int NPG);         // ... that writes the scratch for this shape?
-hipError_t launch_fir_mfma3(Mfma2Args& m, int MB, int NPG, int NT, uint32_t nwt_max, uint32_t nrows, hipStream_t s);
 
 }  // namespace d2d

@@ -5,13 +5,10 @@
 
 #include "d2d_m3.h"
 #include "d2d_mfma2_dev.h"
+#include "d2d_route.h"
 
 namespace d2d {
 
-#define D2D_M3_THREADS 512
-#ifndef D2D_M3_STAGED
-#define D2D_M3_STAGED 1     // M = 8: a full tile's frames go through LDS and leave as aligned 1-KiB rows (0: straight from registers, A/B builds)
-#endif
 
 #ifndef D2D_M3_ABL
 #define D2D_M3_ABL 0
@@ -761,75 +758,46 @@ __global__ __launch_bounds__(D2D_M3_THREADS) void d2d_fir_mfma3_kernel(Mfma2Args
     }
 }
 
+// (the instantiation, its arguments and the block's LDS layout: d2d_route.cpp, m3_plan)
 template <int MB, int NPG, int NT, int KIND, int SBY>
-static hipError_t launch_mfma3_t(Mfma2Args& m, uint32_t nwt_max, uint32_t nrows, hipStream_t s) {
+static hipError_t launch_mfma3_t(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
     static KernelPrep prep;
     int dev = 0;
     const void* fn = reinterpret_cast<const void*>(&d2d_fir_mfma3_kernel<MB, NPG, NT, KIND, SBY>);
     hipError_t e = prep.max_dynamic_lds(fn, 160 * 1024, &dev);
     if (e != hipSuccess) return e;
-    // LDS: the shared tap table, then two stream buffers per wave; eight waves per block = two per SIMD
-    m.off_waves = (uint32_t)(2 * NPG) * 1024u;
-    m.wave_lds = 2u * (uint32_t)m2_stream_bytes(MB, NPG);
-    m.off_out = m.wave_lds;
-    if (D2D_M3_STAGED && MB == 1 && SBY != 0) m.wave_lds += (uint32_t)M2_TILE * 2u * SBY;     // the tile's frames, staged for whole-line stores
-    const uint32_t wdbg = (m.f.dbg_flags >> 8) & 0xFFu;   // diagnostic override (d2d_params.debug_flags bits 8..15)
-    m.nwaves = wdbg ? wdbg : 8u;
-    if (m.nwaves < 1 || m.nwaves > 8) m.nwaves = 8;
-    while (m.nwaves > 1 && (size_t)m.off_waves + (size_t)m.nwaves * m.wave_lds > 160 * 1024) m.nwaves >>= 1;
-    const size_t smem = (size_t)m.off_waves + (size_t)m.nwaves * m.wave_lds;
-    if (smem > 160 * 1024) return hipErrorInvalidValue;
     // every wave loops over its share of the wave-tiles: launch what is resident at once
+    const uint32_t nrows = nfiles * p.rows_per_file, nwt_max = (max_nout + p.tile - 1) / p.tile;
     uint32_t gx;
-    e = persistent_grid_x(&d2d_fir_mfma3_kernel<MB, NPG, NT, KIND, SBY>, prep, dev, m.nwaves, smem, nrows, (nwt_max + m.nwaves - 1) / m.nwaves, &gx);
+    e = persistent_grid_x(&d2d_fir_mfma3_kernel<MB, NPG, NT, KIND, SBY>, prep, dev, p.nwaves, p.lds, nrows, (nwt_max + p.block_tiles - 1) / p.block_tiles, &gx);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((d2d_fir_mfma3_kernel<MB, NPG, NT, KIND, SBY>), dim3(gx, nrows), dim3(64 * m.nwaves), smem, s, m);
+    hipLaunchKernelGGL((d2d_fir_mfma3_kernel<MB, NPG, NT, KIND, SBY>), dim3(gx, nrows), dim3(64 * p.nwaves), p.lds, s, p.m);
     d2d_last_launched_kernel = launched_name<MB, NPG, NT, KIND, SBY>("d2d_fir_mfma3_kernel");
     return hipGetLastError();
 }
 
-// any level in dB (Mfma2Args::gainq): KIND + 4, compiled for the shapes this kernel serves by default (M = 8, 16)
-template <int MB, int NPG, int NT, int SBY>
-static hipError_t launch_mfma3_gain(Mfma2Args& m, uint32_t nwt_max, uint32_t nrows, hipStream_t s) {
-    if constexpr (MB < 4 && NT == 0 && SBY != 0) {
-        if constexpr (SBY != 4) {
-            if (m.dkind == 1) return launch_mfma3_t<MB, NPG, NT, 5, SBY>(m, nwt_max, nrows, s);
-            if (m.dkind == 2) return launch_mfma3_t<MB, NPG, NT, 6, SBY>(m, nwt_max, nrows, s);
-        } else {
-            if (m.f.epi.dither == 'F') return launch_mfma3_t<MB, NPG, NT, 7, SBY>(m, nwt_max, nrows, s);      // the float dither
-        }
-        return launch_mfma3_t<MB, NPG, NT, 4, SBY>(m, nwt_max, nrows, s);
-    } else return hipErrorInvalidValue;
-}
-
-// integer frames of SBY bytes per sample: the dither kinds at 0 dB, or the gain flavours
-template <int MB, int NPG, int SBY>
-static hipError_t launch_mfma3_kinds(Mfma2Args& m, uint32_t nwt_max, uint32_t nrows, hipStream_t s) {
-    if (m.gainq) return launch_mfma3_gain<MB, NPG, 0, SBY>(m, nwt_max, nrows, s);
-    if (m.dkind == 1) return launch_mfma3_t<MB, NPG, 0, 1, SBY>(m, nwt_max, nrows, s);
-    if (m.dkind == 2) return launch_mfma3_t<MB, NPG, 0, 2, SBY>(m, nwt_max, nrows, s);
-    return launch_mfma3_t<MB, NPG, 0, 0, SBY>(m, nwt_max, nrows, s);
-}
-
-// Every format of one shape: the exact integers for the scratch and, where the shape serves frames, 24-bit, 16-bit and float frames.
-template <int MB, int NPG, bool FRAMES>
-static hipError_t launch_m3_formats(Mfma2Args& m, uint32_t nwt_max, uint32_t nrows, hipStream_t s) {
-    if (m.f.to_scratch) return launch_mfma3_t<MB, NPG, 0, 0, 0>(m, nwt_max, nrows, s);
-    if constexpr (FRAMES) {
-        if (m.f.epi.sample_bytes == 4)         // float: no dither (the float dither 'F' stays with the two-group kernel, the gain flavour apart)
-            return m.gainq ? launch_mfma3_gain<MB, NPG, 0, 4>(m, nwt_max, nrows, s) : launch_mfma3_t<MB, NPG, 0, 0, 4>(m, nwt_max, nrows, s);
-        if (m.f.epi.sample_bytes != 3) return launch_mfma3_kinds<MB, NPG, 2>(m, nwt_max, nrows, s);
-        return launch_mfma3_kinds<MB, NPG, 3>(m, nwt_max, nrows, s);
-    } else return hipErrorInvalidValue;
-}
-
+// Every format of one shape, the plan's (KIND, SBY) to the instantiation: the exact integers for the scratch and, where the shape serves frames,
+// 24-bit, 16-bit and float frames at 0 dB (KIND 0-2; float: no dither) and for M = 8 and 16 at any level (KIND 4-7; 7: the float dither).
 template <int UNIT> struct M3Unit;
 #define X(unit, mb, npg, nt0, nt1) template <> struct M3Unit<unit> { static constexpr int MB = mb, NPG = npg; static constexpr bool FRAMES = nt0 != 0; };
 D2D_M3_UNIT_LIST(X)
 #undef X
-template <int UNIT> hipError_t launch_m3_unit(Mfma2Args& m, uint32_t nwt_max, uint32_t nrows, hipStream_t s) {
+template <int UNIT> hipError_t launch_m3_unit(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
     using U = M3Unit<UNIT>;
-    return launch_m3_formats<U::MB, U::NPG, U::FRAMES>(m, nwt_max, nrows, s);
+    constexpr int MB = U::MB, NPG = U::NPG;
+#define T(kind, sby) case (kind) * 8 + (sby): return launch_mfma3_t<MB, NPG, 0, kind, sby>(p, max_nout, nfiles, s);
+    const int ks = p.kind() * 8 + p.sby();
+    if (ks == 0) return launch_mfma3_t<MB, NPG, 0, 0, 0>(p, max_nout, nfiles, s);
+    if constexpr (U::FRAMES) switch (ks) {
+        T(0, 4) T(0, 2) T(1, 2) T(2, 2) T(0, 3) T(1, 3) T(2, 3)
+        default: break;
+    }
+    if constexpr (U::FRAMES && MB < 4) switch (ks) {
+        T(4, 4) T(7, 4) T(4, 2) T(5, 2) T(6, 2) T(4, 3) T(5, 3) T(6, 3)
+        default: break;
+    }
+#undef T
+    return hipErrorInvalidValue;
 }
 
 }  // namespace d2d

@@ -2,5 +2,5 @@
 #include "d2d_m3_kernel.h"
 
 namespace d2d {
-template hipError_t launch_m3_unit<D2D_M3_UNIT>(Mfma2Args& m, uint32_t nwt_max, uint32_t nrows, hipStream_t s);
+template hipError_t launch_m3_unit<D2D_M3_UNIT>(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s);
 }  // namespace d2d

@@ -1,4 +1,4 @@
-// d2d_mfma.h -- the int8-MFMA FIR kernels (d2d_kernels_mfma*.hip) as host and device both see them: launch arguments, staging geometry, launchers
+// d2d_mfma.h -- the int8-MFMA FIR kernels (d2d_kernels_mfma*.hip) as host and device both see them: launch arguments, staging geometry
 // (the tables: d2d_tables.h; which kernel serves an engine, and the arguments' values: d2d_route.h)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -36,7 +36,6 @@ struct MfmaArgs {
     uint32_t stagger;     // start offset between wave slots, in units of 1024 cycles
 };
 
-hipError_t launch_fir_mfma(const FirArgs& a, const MfmaLayout& g, uint32_t max_nout, uint32_t nstreams, hipStream_t s);
 void mfma_debug_stamps(unsigned long long out[8]);   // diagnostic (D2D_DBG=16)
 
 // second-generation kernel (d2d_kernels_mfma2.hip): two phase groups per matrix column; its pipelined variants (d2d_kernels_mfma3.hip,
@@ -80,7 +79,6 @@ __host__ __device__ constexpr int m2_stream_bytes(int MB, int NPG) {
 #define D2D_M2_SHAPES(X) X(4, 10) X(4, 12) X(4, 13) X(8, 19) X(8, 24) X(8, 25)
 
 void mfma2_debug_stamps(unsigned long long out[8]);   // diagnostic (make DIAG=1, D2D_DBG & 256)
-hipError_t launch_fir_mfma2(const FirArgs& a, int M, int N, uint32_t max_nout, uint32_t nstreams, hipStream_t s);
 void mfma3_debug_stamps(unsigned long long out[8]);  // diagnostic (make DIAG=1, D2D_DBG & 256): per-wave lifetimes of the pipelined kernel
 
 }  // namespace d2d

@@ -9,6 +9,9 @@
 namespace d2d {
 
 constexpr int MX_FRAG_BYTES = 1536;          // a tap fragment: 64 lanes x 16 bytes, then 64 lanes x 8 bytes (32 e2m3 codes per lane)
+#ifndef D2D_MX_THREADS
+#define D2D_MX_THREADS 512     // waves per block x 64: 512 = two waves per SIMD (256 registers each); 768 = three (168), an A/B build
+#endif
 
 // MB = bytes per output (M / 8), NT = taps, G = groups of PH phases per matrix column.  PH = 6 with the 24-bit taps' five base-32 digits (30 of the
 // 32 matrix rows), PH = 4 with the 32-bit taps' seven (28 rows; the one-pass form of tap_bits = 32, round 4)
@@ -65,11 +68,14 @@ __host__ __device__ constexpr int mx_g(int MB) { return MB == 4 ? D2D_MX_G4 : MB
 #endif
 __host__ __device__ constexpr bool mx_resident(int MB, int NT, int PH = 6) { return D2D_MX_RESIDENT && MB == 4 && mx_nf(MB, NT, PH) <= 12; }
 __host__ __device__ constexpr int mx_nres(int MB, int NT, int PH = 6) { return !mx_resident(MB, NT, PH) ? 0 : D2D_MX_NRES < mx_nf(MB, NT, PH) ? D2D_MX_NRES : mx_nf(MB, NT, PH); }
+// Fragments a wave of one instantiation keeps in registers: the stereo frame flavours of the M = 32 rows.  The scratch flavour, several pairs
+// per wave and the 32-bit taps read them from LDS like M = 64 and M = 128.
+__host__ __device__ constexpr int mx_nres_of(int MB, int NT, int SBY, int NPR, int ND) { return SBY != 0 && NPR == 1 && ND == 5 ? mx_nres(MB, NT) : 0; }
 
 // ---- the compiled kernels: ONE row per object --------------------------------------------------------------------------------
 // X(unit, MB, NT, flavour, NPR).  Unit n is d2d_mx_unit.hip compiled with -DD2D_MX_UNIT=n (unit 0 rides in d2d_kernels_mx.hip, next to the
-// dispatcher) and holds every sample format of its row: launch_mx_formats in d2d_mx_kernel.h.  The dispatcher's table, launch_fir_mx and
-// the mx_*_supported functions all read this list and nothing else.  Adding a shape is one row here plus MX_UNITS in the Makefile
+// dispatcher) and holds every sample format of its row: launch_mx_unit in d2d_mx_kernel.h.  The dispatcher's table, the launch plan
+// (d2d_route.cpp: mx_plan) and the mx_*_supported functions all read this list and nothing else.  Adding a shape is one row here plus MX_UNITS in the Makefile
 // (the dispatcher's static_assert says so when the two disagree).
 //   MX_INT   unit gain, all-integer requantiser (KIND 0-2: 24-bit, 16-bit, float frames); NPR = 1 also holds the exact integers for the scratch,
 //            NPR > 1 converts that many channel pairs per wave (planar multichannel frames: 2 quad, 3 a 5.1 stream, 4 a 7.1 / eight-channel stream)
@@ -92,14 +98,13 @@ constexpr bool mx_unit_kept(int MB, int NT) { return MB == 4 && NT == 560; }
 constexpr bool mx_unit_kept(int, int) { return true; }
 #endif
 
-struct Mfma2Args;
-template <int UNIT> hipError_t launch_mx_unit(Mfma2Args& m, uint32_t max_nout, uint32_t nrows, hipStream_t s);   // d2d_mx_kernel.h; one explicit instantiation per object
+struct FirLaunch;
+template <int UNIT> hipError_t launch_mx_unit(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s);   // d2d_mx_kernel.h; one explicit instantiation per object
 bool mx_supported(int MB, int NT);                 // is a kernel compiled for this shape?
 bool mx_pairs_supported(int MB, int NT, int npairs);   // ... for `npairs` channel pairs per wave (planar multichannel frames)?
 bool mx_gain_supported(int MB, int NT);            // ... and its gain flavours (frames at another level than 0 dB)?
 bool mx_wide_supported(int MB, int NT);            // ... the one-pass form of the 32-bit tap grid (seven digits, four phases per group)?
 int mx_groups(int MB);
 void mx_debug_stamps(unsigned long long out[8]);   // diagnostic (-DD2D_MX_STAMPS=1 builds)
-hipError_t launch_fir_mx(Mfma2Args& m, int MB, int NT, uint32_t max_nout, uint32_t nrows, hipStream_t s);
 
 }  // namespace d2d

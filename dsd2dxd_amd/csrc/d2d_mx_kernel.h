@@ -5,12 +5,10 @@
 
 #include "d2d_mfma2_dev.h"
 #include "d2d_mx.h"
+#include "d2d_route.h"
 
 namespace d2d {
 
-#ifndef D2D_MX_THREADS
-#define D2D_MX_THREADS 512     // waves per block x 64: 512 = two waves per SIMD (256 registers each); 768 = three (168), an A/B build
-#endif
 #ifndef D2D_MX_ABL
 #define D2D_MX_ABL 0
 #endif
@@ -56,10 +54,6 @@ __host__ __device__ constexpr uint32_t mx_pack_sel(int SBY, int o) {
     for (int j = 0; j < 4; ++j) { const int t = o + j; sel |= (uint32_t)(t < SBY ? t : 4 + (t - SBY)) << (8 * j); }
     return sel;
 }
-
-// Fragments a wave of this instantiation keeps in registers (d2d_mx.h: mx_resident): the stereo frame flavours of the M = 32 rows.  The
-// scratch flavour, several pairs per wave and the 32-bit taps read them from LDS like M = 64 and M = 128.
-__host__ __device__ constexpr int mx_nres_of(int MB, int NT, int SBY, int NPR, int ND) { return SBY != 0 && NPR == 1 && ND == 5 ? mx_nres(MB, NT) : 0; }
 
 // KIND: 0 no dither, 1 triangular, 2 rectangular (unit gain, all-integer requantiser); 4, 5, 6: the same dithers at any level in dB (the
 // f64 requantiser of the definition inside the pipelined epilogue, no careful path).  Stereo; SBY = bytes per sample: 3 (24-bit packed frames), 2 (16-bit),
@@ -1109,65 +1103,41 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
     }
 }
 
+// (the instantiation, its arguments and the block's LDS layout: d2d_route.cpp, mx_plan)
 template <int MB, int NT, int G, int KIND, int SBY, int NPR = 1, int ND = 5>
-static hipError_t launch_mx_t(Mfma2Args& m, uint32_t max_nout, uint32_t nrows, hipStream_t s) {
+static hipError_t launch_mx_t(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
     static KernelPrep prep;
     int dev = 0;
-    constexpr int PH = ND == 7 ? 4 : 6;
     const void* fn = reinterpret_cast<const void*>(&d2d_fir_mx_kernel<MB, NT, G, KIND, SBY, NPR, ND>);
     hipError_t e = prep.max_dynamic_lds(fn, 160 * 1024, &dev);
     if (e != hipSuccess) return e;
-    constexpr uint32_t TILE = 32u * (uint32_t)PH * G;
-    // LDS: the shared tap table, then per wave two stream buffers and the output slice; eight waves per block = two per SIMD
-    m.off_waves = mx_nres_of(MB, NT, SBY, NPR, ND) == mx_nf(MB, NT, PH) ? 0u : (uint32_t)mx_nf(MB, NT, PH) * MX_FRAG_BYTES;    // (no table where every fragment is resident)
-    m.off_out = 2u * (uint32_t)mx_stream_bytes(MB, NT, G, PH);
-    m.wave_lds = m.off_out + 2u * (uint32_t)NPR * TILE * 4u; // the slice: a row of TILE dwords per channel (the scratch flavour too: its integers leave as rows of the slice)
-    const uint32_t wdbg = (m.f.dbg_flags >> 8) & 0xFFu;   // diagnostic override (d2d_params.debug_flags bits 8..15)
-    uint32_t nwaves = wdbg ? wdbg : (uint32_t)(D2D_MX_THREADS / 64);
-    if (nwaves < 1 || nwaves > D2D_MX_THREADS / 64) nwaves = D2D_MX_THREADS / 64;
-    while (nwaves > 1 && (size_t)m.off_waves + (size_t)nwaves * m.wave_lds > 160 * 1024) { if (NPR > 1) --nwaves; else nwaves >>= 1; }
-    const bool coop = SBY == 0 && m.f.coop;                 // a block = all channel pairs of a file on one tile: one wave per pair, one grid row per file
-    if (coop) { nwaves = m.f.epi.channels / 2u; nrows /= m.ngroups; }
-    m.nwaves = nwaves;
-    const size_t smem = (size_t)m.off_waves + (size_t)m.nwaves * m.wave_lds;
-    if (smem > 160 * 1024) return hipErrorInvalidValue;
     // every wave loops over its share of the wave-tiles: launch what is resident at once
-    const uint32_t nwt_max = (max_nout + TILE - 1) / TILE;
+    const uint32_t nrows = nfiles * p.rows_per_file, nwt_max = (max_nout + p.tile - 1) / p.tile;
     uint32_t gx;
-    e = persistent_grid_x(&d2d_fir_mx_kernel<MB, NT, G, KIND, SBY, NPR, ND>, prep, dev, m.nwaves, smem, nrows, coop ? nwt_max : (nwt_max + m.nwaves - 1) / m.nwaves, &gx);
+    e = persistent_grid_x(&d2d_fir_mx_kernel<MB, NT, G, KIND, SBY, NPR, ND>, prep, dev, p.nwaves, p.lds, nrows, (nwt_max + p.block_tiles - 1) / p.block_tiles, &gx);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((d2d_fir_mx_kernel<MB, NT, G, KIND, SBY, NPR, ND>), dim3(gx, nrows), dim3(64 * m.nwaves), smem, s, m);
+    hipLaunchKernelGGL((d2d_fir_mx_kernel<MB, NT, G, KIND, SBY, NPR, ND>), dim3(gx, nrows), dim3(64 * p.nwaves), p.lds, s, p.m);
     d2d_last_launched_kernel = launched_name<MB, NT, G, KIND, SBY, NPR, ND>("d2d_fir_mx_kernel");     // (all seven arguments: the way rocprofv3 prints the instantiation)
     return hipGetLastError();
 }
 
-// Every sample format of one (shape, pairs, digits, requantiser): the integer flavour's KIND 0-2, or GAIN's KIND 4-7 (7: float frames with the float dither);
-// the exact integers for the scratch only where a wave converts one pair at unit gain.
-template <int MB, int NT, int NPR, int ND, bool GAIN>
-static hipError_t launch_mx_formats(Mfma2Args& m, uint32_t max_nout, uint32_t nrows, hipStream_t s) {
-    constexpr int G = mx_g(MB), K = GAIN ? 4 : 0;       // (wide: the groups per column of the 24-bit form -- twelve outputs at M = 32, eight at M = 64)
-    if constexpr (!GAIN && NPR == 1) { if (m.f.to_scratch) return launch_mx_t<MB, NT, G, 0, 0>(m, max_nout, nrows, s); }
-    if (m.f.epi.sample_bytes == 4) {
-        if constexpr (GAIN) { if (m.f.epi.dither == 'F') return launch_mx_t<MB, NT, G, 7, 4, NPR, ND>(m, max_nout, nrows, s); }
-        return launch_mx_t<MB, NT, G, K, 4, NPR, ND>(m, max_nout, nrows, s);
-    }
-    if (m.f.epi.sample_bytes == 2) {
-        if (m.dkind == 1) return launch_mx_t<MB, NT, G, K + 1, 2, NPR, ND>(m, max_nout, nrows, s);
-        if (m.dkind == 2) return launch_mx_t<MB, NT, G, K + 2, 2, NPR, ND>(m, max_nout, nrows, s);
-        return launch_mx_t<MB, NT, G, K, 2, NPR, ND>(m, max_nout, nrows, s);
-    }
-    if (m.dkind == 1) return launch_mx_t<MB, NT, G, K + 1, 3, NPR, ND>(m, max_nout, nrows, s);
-    if (m.dkind == 2) return launch_mx_t<MB, NT, G, K + 2, 3, NPR, ND>(m, max_nout, nrows, s);
-    return launch_mx_t<MB, NT, G, K, 3, NPR, ND>(m, max_nout, nrows, s);
-}
-
+// Every sample format of one row of the unit list: the plan's (KIND, SBY) to the instantiation.  The integer flavour holds KIND 0-2, the gain and
+// wide ones KIND 4-7 (7: float frames with the float dither); the exact integers for the scratch only where a wave converts one pair at unit gain.
 template <int UNIT> struct MxUnit;
 #define X(unit, mb, nt, fl, npr) template <> struct MxUnit<unit> { static constexpr int MB = mb, NT = nt, NPR = npr; static constexpr MxFlavour FL = fl; };
 D2D_MX_UNIT_LIST(X)
 #undef X
-template <int UNIT> hipError_t launch_mx_unit(Mfma2Args& m, uint32_t max_nout, uint32_t nrows, hipStream_t s) {
+template <int UNIT> hipError_t launch_mx_unit(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
     using U = MxUnit<UNIT>;
-    return launch_mx_formats<U::MB, U::NT, U::NPR, U::FL == MX_WIDE ? 7 : 5, U::FL != MX_INT>(m, max_nout, nrows, s);
+    constexpr int MB = U::MB, NT = U::NT, NPR = U::NPR, G = mx_g(MB), ND = U::FL == MX_WIDE ? 7 : 5, K = U::FL != MX_INT ? 4 : 0;
+#define T(kind, sby) case (kind) * 8 + (sby): return launch_mx_t<MB, NT, G, kind, sby, NPR, ND>(p, max_nout, nfiles, s);
+    switch (p.kind() * 8 + p.sby()) {
+        T(K, 4) T(K, 2) T(K + 1, 2) T(K + 2, 2) T(K, 3) T(K + 1, 3) T(K + 2, 3)
+        case 7 * 8 + 4: if constexpr (K == 4) return launch_mx_t<MB, NT, G, 7, 4, NPR, ND>(p, max_nout, nfiles, s); else break;
+        case 0: if constexpr (K == 0 && NPR == 1) return launch_mx_t<MB, NT, G, 0, 0>(p, max_nout, nfiles, s); else break;
+    }
+#undef T
+    return hipErrorInvalidValue;
 }
 
 }  // namespace d2d

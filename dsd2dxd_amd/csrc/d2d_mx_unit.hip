@@ -2,5 +2,5 @@
 #include "d2d_mx_kernel.h"
 
 namespace d2d {
-template hipError_t launch_mx_unit<D2D_MX_UNIT>(Mfma2Args& m, uint32_t max_nout, uint32_t nrows, hipStream_t s);
+template hipError_t launch_mx_unit<D2D_MX_UNIT>(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s);
 }  // namespace d2d

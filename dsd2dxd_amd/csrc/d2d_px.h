@@ -21,6 +21,7 @@ constexpr int PX_FRAG_BYTES = 1536;          // a tap fragment: 64 lanes x 16 by
 #define D2D_PX_THREADS 512     // waves per block x 64: 512 = two waves per SIMD; 768 = three (at most 168 registers), an A/B build
 #endif
 constexpr int PX_THREADS = D2D_PX_THREADS;
+constexpr int PXP_THREADS = 256;             // the plain kernel's block: one output per lane
 
 // first bit (relative to the column's first output) of output o's window: floor(o Mp / Lp)
 __host__ __device__ constexpr int px_q(int LP, int MP, int o) { return (int)(((long long)o * MP) / LP); }
@@ -93,13 +94,14 @@ struct PxArgs {
 // ---- the compiled matrix-core kernels: ONE row per object ------------------------------------------------------------------------
 // X(unit, LP, MP, NP, G): the (Lp, Mp, NP) of a generated table (filters/filter_tables.inc: D2D_POLYS; tests/test_poly48k.py fails when a table
 // has no row here) and the groups per column it is compiled with.  Unit n is d2d_px_unit.hip compiled with -DD2D_PX_UNIT=n (unit 0 rides in
-// d2d_kernels_px.hip, next to the plain kernel and the dispatcher) and holds every KIND of its row.  launch_fir_px, px_supported and px_groups
-// read this list and nothing else.  Adding a shape is one row here plus PX_UNITS in the Makefile (the dispatcher's static_assert says so
+// d2d_kernels_px.hip, next to the plain kernel and the dispatcher) and holds every KIND of its row.  The launch plan (d2d_route.cpp: px_plan),
+// px_supported and px_groups read this list and nothing else.  Adding a shape is one row here plus PX_UNITS in the Makefile (the dispatcher's static_assert says so
 // when the two disagree).
 #define D2D_PX_UNIT_LIST(X)                                                                  \
     X(0, 5, 147, 751, 3)  X(1, 10, 147, 375, 4) X(2, 20, 147, 269, 4) X(3, 5, 294, 1501, 2)  \
     X(4, 5, 147, 771, 3)  X(5, 10, 147, 539, 4) X(6, 5, 294, 1541, 2) X(7, 5, 147, 1079, 3)
-template <int UNIT> hipError_t launch_px_unit(PxArgs& a, uint32_t max_nout, uint32_t nfiles, hipStream_t s);   // d2d_px_kernel.h; one explicit instantiation per object
+struct FirLaunch;
+template <int UNIT> hipError_t launch_px_unit(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s);   // d2d_px_kernel.h; one explicit instantiation per object
 
 bool px_supported(const d2d_poly_def& p);                                   // is a matrix-core kernel compiled for this table?
 inline int px_groups(const d2d_poly_def& p) {      // groups per column a table is compiled with (0: no row)
@@ -108,7 +110,5 @@ inline int px_groups(const d2d_poly_def& p) {      // groups per column a table 
 #undef X
     return 0;
 }
-hipError_t launch_fir_px(PxArgs& a, const d2d_poly_def& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s);
-hipError_t launch_poly_plain(PxArgs& a, const d2d_poly_def& p, uint32_t max_nout, uint32_t nstreams, hipStream_t s);
 
 }  // namespace d2d

@@ -8,6 +8,7 @@
 
 #include "d2d_mfma2_dev.h"
 #include "d2d_px.h"
+#include "d2d_route.h"
 
 namespace d2d {
 
@@ -524,54 +525,36 @@ __global__ __launch_bounds__(PX_THREADS) void d2d_fir_px_kernel(PxArgs a) {
     }
 }
 
+// (the instantiation, its arguments and the block's LDS layout: d2d_route.cpp, px_plan)
 template <int LP, int MP, int NP, int G, int KIND>
-static hipError_t launch_px_t(PxArgs& a, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
+static hipError_t launch_px_t(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
     static KernelPrep prep;
     int dev = 0;
     const void* fn = reinterpret_cast<const void*>(&d2d_fir_px_kernel<LP, MP, NP, G, KIND>);
     hipError_t e = prep.max_dynamic_lds(fn, 160 * 1024, &dev);
     if (e != hipSuccess) return e;
-    constexpr uint32_t TILE = 160u * G;
-    const uint32_t C = a.epi.channels;
-    a.cw = C == 1 ? 1u : 2u;
-    a.ngroups = (C + a.cw - 1) / a.cw;
-    a.off_waves = (uint32_t)px_nslot(LP, MP, NP, G) * PX_FRAG_BYTES;
-    a.off_out = a.cw * (uint32_t)px_stream_bytes(LP, MP, NP, G);
-    a.wave_lds = a.off_out + a.cw * TILE * 4u + 256u;                // (+ 64 dwords nobody reads: where the pipelined epilogue puts half 1's third slot)
-    uint32_t nwaves = PX_THREADS / 64;
-    while (nwaves > 1 && (size_t)a.off_waves + (size_t)nwaves * a.wave_lds > 160 * 1024) --nwaves;
-    a.nwaves = nwaves;
-    const size_t smem = (size_t)a.off_waves + (size_t)nwaves * a.wave_lds;
-    if (smem > 160 * 1024) return hipErrorInvalidValue;
     int ncu = 0;
     if ((e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-    const uint32_t nrows = nfiles * a.ngroups;
-    const uint32_t ntiles = max_nout / TILE + 2;                     // (a call's outputs may straddle one tile more than their count fills)
+    const uint32_t nrows = nfiles * p.rows_per_file;
+    const uint32_t ntiles = max_nout / p.tile + 2;                   // (a call's outputs may straddle one tile more than their count fills)
     uint32_t gx = std::max(1u, (uint32_t)ncu / std::max(1u, nrows));
-    gx = std::min(gx, (ntiles + nwaves - 1) / nwaves);
-    hipLaunchKernelGGL((d2d_fir_px_kernel<LP, MP, NP, G, KIND>), dim3(gx, nrows), dim3(64 * nwaves), smem, s, a);
+    gx = std::min(gx, (ntiles + p.block_tiles - 1) / p.block_tiles);
+    hipLaunchKernelGGL((d2d_fir_px_kernel<LP, MP, NP, G, KIND>), dim3(gx, nrows), dim3(64 * p.nwaves), p.lds, s, p.px);
     d2d_last_launched_kernel = launched_name<LP, MP, NP, G, KIND>("d2d_fir_px_kernel");
     return hipGetLastError();
 }
 
 // every KIND of one table shape
-template <int LP, int MP, int NP, int G>
-static hipError_t launch_px_kinds(PxArgs& a, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
-    if (a.to_scratch) return launch_px_t<LP, MP, NP, G, 4>(a, max_nout, nfiles, s);
-    const bool intq = a.epi.gain == 1.0 && (a.epi.bits == 24 || a.epi.bits == 16) && a.epi.dither != 'F';
-    if (!intq) return launch_px_t<LP, MP, NP, G, 3>(a, max_nout, nfiles, s);
-    if (a.dkind == 1) return launch_px_t<LP, MP, NP, G, 1>(a, max_nout, nfiles, s);
-    if (a.dkind == 2) return launch_px_t<LP, MP, NP, G, 2>(a, max_nout, nfiles, s);
-    return launch_px_t<LP, MP, NP, G, 0>(a, max_nout, nfiles, s);
-}
-
 template <int UNIT> struct PxUnit;
 #define X(unit, lp, mp, np, g) template <> struct PxUnit<unit> { static constexpr int LP = lp, MP = mp, NP = np, G = g; };
 D2D_PX_UNIT_LIST(X)
 #undef X
-template <int UNIT> hipError_t launch_px_unit(PxArgs& a, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
+template <int UNIT> hipError_t launch_px_unit(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
     using U = PxUnit<UNIT>;
-    return launch_px_kinds<U::LP, U::MP, U::NP, U::G>(a, max_nout, nfiles, s);
+#define T(kind) case kind: return launch_px_t<U::LP, U::MP, U::NP, U::G, kind>(p, max_nout, nfiles, s);
+    switch (p.kind()) { T(0) T(1) T(2) T(3) T(4) }
+#undef T
+    return hipErrorInvalidValue;
 }
 
 }  // namespace d2d

@@ -2,5 +2,5 @@
 #include "d2d_px_kernel.h"
 
 namespace d2d {
-template hipError_t launch_px_unit<D2D_PX_UNIT>(PxArgs& a, uint32_t max_nout, uint32_t nfiles, hipStream_t s);
+template hipError_t launch_px_unit<D2D_PX_UNIT>(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s);
 }  // namespace d2d

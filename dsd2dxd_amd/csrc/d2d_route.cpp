@@ -56,6 +56,12 @@ bool mfma2_supported(int M, int N) {
     return false;
 }
 
+// the waves of a block before LDS has its say: the diagnostic override (d2d_params.debug_flags bits 8..15) or `most`
+static uint32_t waves_asked(const FirArgs& a, uint32_t most) {
+    const uint32_t wdbg = (a.dbg_flags >> 8) & 0xFFu;
+    return wdbg < 1 || wdbg > most ? most : wdbg;
+}
+
 // ---- the one-group kernel's geometry ---------------------------------------------------------------------------------------------
 void mfma_geometry(const FirArgs& a, const MfmaLayout& g, MfmaArgs& m, size_t& smem) {
     // channels per block: all of a mono/stereo file, one pair of a multichannel one
@@ -90,9 +96,7 @@ void mfma_geometry(const FirArgs& a, const MfmaLayout& g, MfmaArgs& m, size_t& s
     { static const char* e = getenv("D2D_DBG"); m.dbg = e ? (uint32_t)atoi(e) : 0u; }          // (make DIAG=1 builds only: never the shipped library)
     { static const char* e = getenv("D2D_STAGGER"); m.stagger = e ? (uint32_t)atoi(e) : 0u; }
 #endif
-    const uint32_t wdbg = (a.dbg_flags >> 8) & 0xFFu;      // diagnostic override (d2d_params.debug_flags bits 8..15)
-    m.nwaves = wdbg ? wdbg : 12u;
-    if (m.nwaves < 1 || m.nwaves > 12) m.nwaves = 12;
+    m.nwaves = waves_asked(a, 12);
     // largest block that fits the CU's LDS, keeping the waves evenly spread over the four SIMDs
     while (m.nwaves > 1 && (size_t)m.off_waves + (size_t)m.nwaves * m.wave_lds > 160 * 1024)
         m.nwaves = m.nwaves > 8 ? 8 : m.nwaves > 4 ? 4 : m.nwaves >> 1;
@@ -123,11 +127,11 @@ static bool mfma3_eligible(const FirArgs& a, const Mfma2Args& m, int MB, int NPG
     // the exact integers for the stage-A scratch: every channel pair of an even channel count
     if (a.to_scratch) return a.epi.channels >= 2 && a.epi.channels % 2 == 0 && !m.wide && a.scale_bits >= 18 && a.scale_bits <= 30 &&
                              a.sum_abs_q != 0 && a.sum_abs_q < (1ull << 31) && mfma3_scr_supported(MB, NPG);
-    const bool frames_ok = !a.to_scratch && a.epi.channels == 2 && (a.epi.sample_bytes == 3 || a.epi.sample_bytes == 2) && m.qsh == 0 && !m.wide;
+    const bool frames_ok = a.epi.channels == 2 && (a.epi.sample_bytes == 3 || a.epi.sample_bytes == 2) && m.qsh == 0 && !m.wide;
     const bool shape_ok = a.scale_bits >= 18 && a.scale_bits <= 30 && mfma3_supported(MB, NPG, NT);
     // ... or 32-bit float at 0 dB without the float dither: the sample is (float)v * 2^-S
     const bool noint = (a.dbg_flags & D2D_DBG_NO_INTQ) != 0;
-    const bool float_ok = !noint && !a.to_scratch && a.epi.channels == 2 && a.epi.bits == 32 && a.epi.dither != 'F' && a.epi.gain == 1.0 && !m.wide &&
+    const bool float_ok = !noint && a.epi.channels == 2 && a.epi.bits == 32 && a.epi.dither != 'F' && a.epi.gain == 1.0 && !m.wide &&
                           a.sum_abs_q != 0 && a.sum_abs_q < (1ull << 31);
     // (M = 8 float frames too since the pipelined kernel stages that shape's frames through LDS: 4.18 against 4.50 ms on the one-group kernel)
     if (float_ok && shape_ok) return true;
@@ -144,9 +148,14 @@ static uint32_t mx_pairs(const FirArgs& a, int MB, int N) {
     return mx_pairs_supported(MB, N, (int)(C / 2u)) ? C / 2u : 1u;
 }
 
-// the same conversions as mfma3_eligible, shape apart (the caller checks mx_supported and the engine mx_exact)
+// the tables whose digit sums the fp6 kernel recombines exactly, with v = sum q s in an int32
+static bool mx_range_ok(const FirArgs& a) {
+    return a.scale_bits >= 20 && a.scale_bits <= 30 && a.sum_abs_q != 0 && a.sum_abs_q < (1ull << 31) && a.mx_exact;
+}
+
+// the same conversions as mfma3_eligible, shape apart (the caller checks mx_supported)
 static bool mx_eligible(const FirArgs& a, const Mfma2Args& m, int MB, int N) {
-    const bool range_ok = a.scale_bits >= 20 && a.scale_bits <= 30 && a.sum_abs_q != 0 && a.sum_abs_q < (1ull << 31) && a.mx_exact;
+    const bool range_ok = mx_range_ok(a);
     if (a.to_scratch) return a.epi.channels >= 2 && a.epi.channels % 2 == 0 && range_ok;
     const bool noint = (a.dbg_flags & D2D_DBG_NO_INTQ) != 0;
     const bool stereo = (a.epi.channels == 2 || mx_pairs(a, MB, N) > 1u) && m.qsh == 0;       // (or whole frames of several pairs)
@@ -166,8 +175,7 @@ int mfma2_pipelined(const FirArgs& a, int M, int N) {
     // (S = 30: no biased accumulators, and the int8 kernels' limb-sum bound `wide` does not apply)
     if (MB == 16) {
         const bool noint16 = (a.dbg_flags & D2D_DBG_NO_INTQ) != 0;
-        const bool range_ok = a.scale_bits >= 20 && a.scale_bits <= 30 && a.sum_abs_q != 0 && a.sum_abs_q < (1ull << 31) && a.mx_exact;
-        if (nomx || !mx_supported(MB, N) || !range_ok || noint16) return PIPE_NONE;
+        if (nomx || !mx_supported(MB, N) || !mx_range_ok(a) || noint16) return PIPE_NONE;
         if (a.to_scratch) return a.epi.channels >= 2 && a.epi.channels % 2 == 0 ? PIPE_FP6 : PIPE_NONE;
         const bool depth_ok = a.epi.bits == 32 ? true : ((a.epi.bits == 24 || a.epi.bits == 20 || a.epi.bits == 16) && m.fbits > 0 && m.fbits <= 16 && a.epi.dither != 'F');
         const bool mp = mx_pairs(a, MB, N) > 1u;
@@ -178,8 +186,8 @@ int mfma2_pipelined(const FirArgs& a, int M, int N) {
     }
     // the fp6 x fp4 kernel (d2d_kernels_mx.hip) serves what the pipelined int8 kernel serves at M = 32 and 64
     if (!nomx && mx_supported(MB, N) && mx_eligible(a, m, MB, N)) return PIPE_FP6;
-    // ... and stereo frames at another level than 0 dB (its gain flavours)
-    if (!nomx && m.gainq && mx_gain_supported(MB, N) && a.mx_exact && a.scale_bits >= 20 && a.scale_bits <= 30 && (a.epi.bits == 32 || a.epi.sample_bytes == 2 || a.epi.sample_bytes == 3)) return PIPE_FP6;
+    // ... and stereo frames at another level than 0 dB (its gain flavours; gainq has tested sum_abs_q already)
+    if (!nomx && m.gainq && mx_gain_supported(MB, N) && mx_range_ok(a) && (a.epi.bits == 32 || a.epi.sample_bytes == 2 || a.epi.sample_bytes == 3)) return PIPE_FP6;
     if (!mfma2_supported(M, N) && !mfma3_supported(MB, NPG, N) && !(a.to_scratch && mfma3_scr_supported(MB, NPG))) return PIPE_NONE;
     if (!mfma3_eligible(a, m, MB, NPG, N)) return PIPE_NONE;
     return PIPE_INT8;
@@ -216,9 +224,7 @@ void mfma2_geometry(const FirArgs& a, int MB, int NPG, Mfma2Args& m, size_t& sme
 #if D2D_DIAG
     { static const char* e = getenv("D2D_DBG"); m.dbg = e ? (uint32_t)atoi(e) : 0u; }     // (make DIAG=1 builds only: never the shipped library)
 #endif
-    const uint32_t wdbg = (a.dbg_flags >> 8) & 0xFFu;      // diagnostic override (d2d_params.debug_flags bits 8..15)
-    m.nwaves = wdbg ? wdbg : 12u;
-    if (m.nwaves < 1 || m.nwaves > 12) m.nwaves = 12;
+    m.nwaves = waves_asked(a, 12);
     // largest block that fits the CU's LDS, keeping the waves evenly spread over the four SIMDs
     while (m.nwaves > 1 && (size_t)m.off_waves + (size_t)m.nwaves * m.wave_lds > 160 * 1024)
         m.nwaves = m.nwaves > 8 ? 8 : m.nwaves > 4 ? 4 : m.nwaves >> 1;
@@ -232,21 +238,6 @@ size_t mfma2_smem_bytes(int M, int N, uint32_t channels, uint32_t sample_bytes, 
     mfma2_geometry(a, M / 8, mfma2_pairs(M, N), m, smem);
     if (waves_per_block) *waves_per_block = m.nwaves;
     return smem;
-}
-
-void mfma2_launch_args(const FirArgs& a, int MB, int NPG, int N, Mfma2Args& m, size_t& smem) {
-    mfma2_geometry(a, MB, NPG, m, smem);
-    if (a.pipelined != PIPE_FP6) return;                     // the fp6 kernel has its own LDS layout (and M = 128 no two-group one at all)
-    m.npairs = mx_pairs(a, MB, N);
-    if (m.npairs > 1u) return;                               // (one block row per file)
-    if (MB == 16) m.gainq = (!a.to_scratch && (a.epi.gain != 1.0 || m.qsh != 0 || (a.epi.bits == 32 && a.epi.dither == 'F'))) ? 1u : 0u;
-}
-
-int mx_launch_unit(const Mfma2Args& m, int MB, int NT) {
-    return m.f.taps32 ? mx_find(MB, NT, MX_WIDE, 1)
-         : m.npairs > 1 ? mx_find(MB, NT, MX_INT, (int)m.npairs)
-         : m.gainq && !m.f.to_scratch ? mx_find(MB, NT, MX_GAIN, 1)
-         : mx_find(MB, NT, MX_INT, 1);
 }
 
 // ---- the route -------------------------------------------------------------------------------------------------------------------
@@ -415,6 +406,191 @@ std::string route_kernel_name(const FirRoute& r, const FilterChoice& fc, const E
                num(scr ? 0u : epi.sample_bytes) + ">";
     }
     return "d2d_fir_mfma2_kernel<" + num(Mb) + ", " + num(mfma2_pairs(M, N)) + ", " + num(epi.channels == 1 ? 1 : 2) + ">";
+}
+
+// ---- the launch plans ------------------------------------------------------------------------------------------------------------
+// One builder per kernel family.  Each chooses the instantiation from the arguments (the unit lists' comments say which ones an object holds),
+// fills the kernel's argument struct and lays out the block's LDS.  A plan whose `unit` stays -1 is one no compiled kernel serves.
+
+constexpr size_t LDS_BYTES = 160 * 1024;
+
+static void instantiation(FirLaunch& l, int family, std::initializer_list<int> targs) {
+    static const char* const KERNEL[] = {"d2d_fir_lut_kernel", "d2d_fir_mfma_kernel", "d2d_fir_mfma2_kernel", "d2d_fir_mfma3_kernel",
+                                         "d2d_fir_mx_kernel", "d2d_fir_px_kernel", "d2d_poly_plain_kernel"};
+    l.family = family;
+    l.nt = 0;
+    l.name = KERNEL[family];
+    for (int v : targs) { l.name += (l.nt ? ", " : "<") + std::to_string(v); l.t[l.nt++] = v; }
+    if (l.nt) l.name += ">";
+}
+
+// the requantiser's flavour of the pipelined kernels' frames: the dither kinds of the all-integer one (0 none, 1 triangular, 2 rectangular),
+// + 4 with the f64 one (`gain`), whose 7 is float frames with the float dither
+static int pipe_kind(const Mfma2Args& m, bool gain) {
+    if (gain && m.f.epi.sample_bytes == 4) return m.f.epi.dither == 'F' ? 7 : 4;
+    return (gain ? 4 : 0) + (m.f.epi.sample_bytes == 4 ? 0 : m.dkind == 1 ? 1 : m.dkind == 2 ? 2 : 0);
+}
+
+static FirLaunch lut_plan(const FirArgs& a, int MB) {
+    FirLaunch l;
+    instantiation(l, FIR_LUT, {MB});
+    l.m.f = a;
+    const int LS = MB >= 8 ? MB : 8;
+    const size_t span = (size_t)((255 * LS + 8 * (a.nq + 1) + 16 + 15) & ~15);
+    l.lds = (size_t)a.ntab * 128 + 4 * sizeof(double) + span;
+    l.nwaves = LUT_THREADS / 64;
+    l.tile = (uint32_t)(LUT_THREADS * (MB >= 8 ? 1 : 8 / MB));
+    l.block_tiles = 1;
+    l.rows_per_file = a.epi.channels;
+    if (MB == 1 || MB == 2 || MB == 4 || MB == 8 || MB == 16) l.unit = MB;
+    return l;
+}
+
+static FirLaunch mfma_plan(const FirArgs& a, const MfmaLayout& g) {
+    FirLaunch l;
+    const int MB = g.M / 8;
+    instantiation(l, FIR_MFMA, {MB});
+    mfma_geometry(a, g, l.m1, l.lds);
+    l.nwaves = l.block_tiles = l.m1.nwaves;
+    l.tile = 256;
+    l.rows_per_file = l.m1.ngroups;       // one row per (file, channel group)
+    if (mfma_supported(g.M, g.N) && l.lds <= LDS_BYTES) l.unit = MB;
+    return l;
+}
+
+// the fp6 kernel: `l.m` holds the two-group geometry's arguments; the LDS layout is the kernel's own
+static void mx_plan(FirLaunch& l, int MB, int NT) {
+    Mfma2Args& m = l.m;
+    const FirArgs& a = m.f;
+    m.npairs = mx_pairs(a, MB, NT);
+    // M = 128 has no other kernel whose conditions gainq would have to respect: every frame format that is not the all-integer requantiser's
+    if (MB == 16 && m.npairs == 1) m.gainq = (!a.to_scratch && (a.epi.gain != 1.0 || m.qsh != 0 || (a.epi.bits == 32 && a.epi.dither == 'F'))) ? 1u : 0u;
+    const MxFlavour fl = a.taps32 ? MX_WIDE : m.npairs == 1 && m.gainq && !a.to_scratch ? MX_GAIN : MX_INT;
+    const int NPR = a.taps32 ? 1 : (int)m.npairs, ND = fl == MX_WIDE ? 7 : 5, PH = ND == 7 ? 4 : 6, G = mx_g(MB);
+    // the exact integers for the scratch only where a wave converts one pair at unit gain
+    const bool scr = a.to_scratch && fl == MX_INT && NPR == 1;
+    const int KIND = scr ? 0 : pipe_kind(m, fl != MX_INT), SBY = scr ? 0 : (int)a.epi.sample_bytes;
+    instantiation(l, FIR_MX, {MB, NT, G, KIND, SBY, NPR, ND});     // (all seven arguments: the way rocprofv3 prints the instantiation)
+    l.tile = 32u * (uint32_t)PH * (uint32_t)G;
+    // LDS: the shared tap table, then per wave two stream buffers and the output slice; eight waves per block = two per SIMD
+    m.off_waves = mx_nres_of(MB, NT, SBY, NPR, ND) == mx_nf(MB, NT, PH) ? 0u : (uint32_t)mx_nf(MB, NT, PH) * MX_FRAG_BYTES;    // (no table where every fragment is resident)
+    m.off_out = 2u * (uint32_t)mx_stream_bytes(MB, NT, G, PH);
+    m.wave_lds = m.off_out + 2u * (uint32_t)NPR * l.tile * 4u;   // the slice: a row of `tile` dwords per channel (the scratch flavour too: its integers leave as rows of the slice)
+    uint32_t nwaves = waves_asked(a, D2D_MX_THREADS / 64);
+    while (nwaves > 1 && (size_t)m.off_waves + (size_t)nwaves * m.wave_lds > LDS_BYTES) { if (NPR > 1) --nwaves; else nwaves >>= 1; }
+    const bool coop = SBY == 0 && a.coop;                   // a block = all channel pairs of a file on one tile: one wave per pair, one grid row per file
+    if (coop) nwaves = a.epi.channels / 2u;
+    m.nwaves = l.nwaves = nwaves;
+    l.block_tiles = coop ? 1u : nwaves;
+    if (coop || NPR > 1) l.rows_per_file = 1;               // (several pairs per wave: whole frames from one wave)
+    l.lds = (size_t)m.off_waves + (size_t)nwaves * m.wave_lds;
+    l.unit = l.lds <= LDS_BYTES ? mx_find(MB, NT, fl, NPR) : -1;
+}
+
+// the pipelined int8 kernel, on the two-group geometry's arguments likewise
+static void m3_plan(FirLaunch& l, int MB, int NPG, int NT) {
+    Mfma2Args& m = l.m;
+    const FirArgs& a = m.f;
+    const bool scr = a.to_scratch != 0;
+    const int KIND = scr ? 0 : pipe_kind(m, m.gainq != 0), SBY = scr ? 0 : a.epi.sample_bytes == 4 ? 4 : a.epi.sample_bytes == 3 ? 3 : 2;
+    instantiation(l, FIR_M3, {MB, NPG, 0, KIND, SBY});
+    l.tile = M2_TILE;
+    // LDS: the shared tap table, then two stream buffers per wave; eight waves per block = two per SIMD
+    m.off_waves = (uint32_t)(2 * NPG) * 1024u;
+    m.wave_lds = 2u * (uint32_t)m2_stream_bytes(MB, NPG);
+    m.off_out = m.wave_lds;
+    if (D2D_M3_STAGED && MB == 1 && SBY != 0) m.wave_lds += (uint32_t)M2_TILE * 2u * (uint32_t)SBY;     // the tile's frames, staged for whole-line stores
+    m.nwaves = waves_asked(a, 8);
+    while (m.nwaves > 1 && (size_t)m.off_waves + (size_t)m.nwaves * m.wave_lds > LDS_BYTES) m.nwaves >>= 1;
+    l.nwaves = l.block_tiles = m.nwaves;
+    l.lds = (size_t)m.off_waves + (size_t)m.nwaves * m.wave_lds;
+    // every unit holds the scratch flavour; frames where its row names the tap count, their gain flavours for M = 8 and 16
+    const int u = m3_find(MB, NPG);
+    if (l.lds <= LDS_BYTES && (scr || (m3_frames(u, NT) && (KIND < 4 || MB < 4)))) l.unit = u;
+}
+
+// a shape of the two-group geometry: the two-group kernel itself or the pipelined kernel the engine built its table for (FirArgs::pipelined)
+static FirLaunch mfma2_plan(const FirArgs& a, int M, int N) {
+    FirLaunch l;
+    const int MB = M / 8, NPG = mfma2_pairs(M, N);
+    mfma2_geometry(a, MB, NPG, l.m, l.lds);
+    l.rows_per_file = l.m.ngroups;        // one row per (file, channel group)
+    if (a.pipelined == PIPE_FP6) { mx_plan(l, MB, N); return l; }      // (M = 128 has no two-group kernel at all)
+    const bool fits = l.lds <= LDS_BYTES;
+    if (a.pipelined) {
+        m3_plan(l, MB, NPG, N);
+    } else {
+        // the epilogue flavour: the integers for the stage-A scratch, stereo 24-bit packed in registers, or anything via LDS
+        instantiation(l, FIR_MFMA2, {MB, NPG, a.epi.channels == 1 ? 1 : 2, mfma2_epilogue(a, l.m)});
+        l.nwaves = l.block_tiles = l.m.nwaves;
+        l.tile = M2_TILE;
+        int row = 0;
+#define X(mb, npg) if (MB == mb && NPG == npg) l.unit = row; ++row;
+        D2D_M2_SHAPES(X)
+#undef X
+    }
+    if (!fits) l.unit = -1;
+    return l;
+}
+
+static FirLaunch px_plan(const d2d_params& p, const d2d_poly_def& pd, const Epilogue& epi, const FirRoute& r) {
+    FirLaunch l;
+    PxArgs& a = l.px;
+    a.in_channels = p.channels; a.B = r.B; a.keep = r.keep; a.msb = p.endianness == D2D_MSB_FIRST ? 1u : 0u;
+    a.to_scratch = epi.dither == 'N' ? 1u : 0u;
+    a.il2 = r.il2 ? 1u : 0u;
+    a.epi = epi;
+    a.Lp = (uint32_t)pd.Lp; a.Mp = (uint32_t)pd.Mp; a.NP = (uint32_t)pd.NP; a.D = pd.D; a.S = pd.S;
+    const uint32_t C = epi.channels;
+    if (r.poly_plain) {
+        instantiation(l, FIR_PX_PLAIN, {});
+        // bytes a tile's windows span: 255 outputs further on, the window itself, up to 15 bytes in front, 16 of slack
+        l.px_span = (uint32_t)((((uint64_t)(PXP_THREADS - 1) * pd.Mp / pd.Lp + pd.NP + 7) / 8 + 15 + 16 + 15) & ~(uint64_t)15);
+        l.lds = (((size_t)pd.Lp * pd.NP * 4 + 15) & ~(size_t)15) + 32 + l.px_span;
+        l.nwaves = PXP_THREADS / 64;
+        l.tile = PXP_THREADS;
+        l.block_tiles = 1;
+        l.rows_per_file = C;
+        l.unit = 0;
+        return l;
+    }
+    a.dkind = epi.dither == 'T' ? 1u : (epi.dither == 'R' ? 2u : 0u);
+    a.fbits = pd.S - ((int)epi.bits - 1);
+    a.qmin_i = epi.bits == 32 ? 0 : -(1 << (epi.bits - 1));
+    a.qmax_i = epi.bits == 32 ? 0 : (1 << (epi.bits - 1)) - 1;
+    a.qsh = epi.bits == 20 ? 4u : 0u;
+    // KIND: the integers for the noise shaper (4), the f64 requantiser (3), or the all-integer one's dither kind
+    const bool intq = epi.gain == 1.0 && (epi.bits == 24 || epi.bits == 16) && epi.dither != 'F';
+    const int LP = pd.Lp, MP = pd.Mp, NP = pd.NP, G = px_groups(pd);
+    instantiation(l, FIR_PX, {LP, MP, NP, G, a.to_scratch ? 4 : !intq ? 3 : (int)a.dkind});
+    if (G == 0) return l;                 // (no row for the table)
+    l.tile = 160u * (uint32_t)G;
+    a.cw = C == 1 ? 1u : 2u;
+    a.ngroups = (C + a.cw - 1) / a.cw;
+    a.off_waves = (uint32_t)px_nslot(LP, MP, NP, G) * PX_FRAG_BYTES;
+    a.off_out = a.cw * (uint32_t)px_stream_bytes(LP, MP, NP, G);
+    a.wave_lds = a.off_out + a.cw * l.tile * 4u + 256u;                // (+ 64 dwords nobody reads: where the pipelined epilogue puts half 1's third slot)
+    a.nwaves = PX_THREADS / 64;
+    while (a.nwaves > 1 && (size_t)a.off_waves + (size_t)a.nwaves * a.wave_lds > LDS_BYTES) --a.nwaves;
+    l.nwaves = l.block_tiles = a.nwaves;
+    l.rows_per_file = a.ngroups;
+    l.lds = (size_t)a.off_waves + (size_t)a.nwaves * a.wave_lds;
+    if (l.lds <= LDS_BYTES) l.unit = px_find(pd);
+    return l;
+}
+
+FirLaunch fir_launch(const d2d_params& p, const FilterChoice& fc, const Epilogue& epi, const FirRoute& r, FirPass pass, const d2d_filter_def* lo) {
+    if (r.poly) return px_plan(p, *fc.poly, epi, r);
+    const int M = fc.fir->M, N = fc.fir->ntaps;
+    FirArgs a = fir_args_static(p, fc, epi, r, pass == PASS_LO ? lo : nullptr);
+    if (pass == PASS_MONO2) {
+        a.epi.channels = 2; a.in_channels = 2;
+        a.B = 0x40000000u;     // (one "block" per half: the gather path's layout rule then reads half c at c * half)
+        a.pipelined = (uint32_t)r.mono2_pipe; a.mono2 = 1;
+        return mfma2_plan(a, M, N);
+    }
+    if (r.kernel == D2D_KERNEL_LUT) return lut_plan(a, M / 8);
+    return r.mfma_v2 ? mfma2_plan(a, M, N) : mfma_plan(a, mfma_layout(M, N));
 }
 
 }  // namespace d2d

@@ -1,7 +1,7 @@
 // d2d_route.h -- which kernel, which tap-table layout and which staging serve an engine, decided once (choose_route), and everything those
-// decisions read: the lookups in the lists of compiled kernels, the matrix-core kernels' launch geometry, the FIR launch arguments.  The unit
-// (d2d_route.cpp) calls no HIP function: tools/route_probe.cpp builds from it and d2d_tables.cpp with g++ alone and prints the route of every
-// configuration, which tests/golden/route_predicates.json and tests/golden/route_matrix.json pin (tests/test_route_cpu.py).
+// decisions read: the lookups in the lists of compiled kernels, and the plan of every FIR launch an engine can make (fir_launch: the instantiation,
+// its arguments and its geometry).  The unit (d2d_route.cpp) calls no HIP function: tools/route_probe.cpp builds from it and d2d_tables.cpp with
+// g++ alone and prints the route and the launches of every configuration, which tests/golden/route_*.json pin (tests/test_route_cpu.py).
 #pragma once
 #include <string>
 
@@ -27,9 +27,6 @@ size_t mfma2_smem_bytes(int M, int N, uint32_t channels, uint32_t sample_bytes, 
 int mfma2_epilogue(const FirArgs& a, const Mfma2Args& m);
 // does this launch shape go to a software-pipelined kernel?  Fixed per engine: decides the table variant.  A PipeKind.
 int mfma2_pipelined(const FirArgs& a, int M, int N);
-// the arguments of a two-group launch as the kernel that serves it wants them (launch_fir_mfma2)
-void mfma2_launch_args(const FirArgs& a, int MB, int NPG, int N, Mfma2Args& m, size_t& smem);
-int mx_launch_unit(const Mfma2Args& m, int MB, int NT);      // the fp6 kernel's unit for a launch (launch_fir_mx), or -1
 
 // ---- the route of an engine ----
 struct FirRoute {
@@ -65,5 +62,42 @@ uint32_t route_table_variant(const FirRoute& r);
 FirArgs fir_args_static(const d2d_params& p, const FilterChoice& fc, const Epilogue& epi, const FirRoute& r, const d2d_filter_def* lo = nullptr);
 // the FIR kernel the dispatch will choose, spelled the way rocprofv3 prints it (d2d_kernel_name before the first call)
 std::string route_kernel_name(const FirRoute& r, const FilterChoice& fc, const Epilogue& epi);
+
+// ---- the plan of a FIR launch: everything about it that no call changes, made once when the engine is created ----
+enum FirFamily : int {
+    FIR_LUT,                   // d2d_fir_lut_kernel<MB>
+    FIR_MFMA,                  // d2d_fir_mfma_kernel<MB>                                  the one-group matrix-core kernel
+    FIR_MFMA2,                 // d2d_fir_mfma2_kernel<MB, NPG, CH, EPI>                   the two-group one
+    FIR_M3,                    // d2d_fir_mfma3_kernel<MB, NPG, NT, KIND, SBY>             pipelined, int8
+    FIR_MX,                    // d2d_fir_mx_kernel<MB, NT, G, KIND, SBY, NPR, ND>         pipelined, fp6 x fp4
+    FIR_PX,                    // d2d_fir_px_kernel<LP, MP, NP, G, KIND>                   the composed polyphase filter
+    FIR_PX_PLAIN,              // d2d_poly_plain_kernel                                    ... bit by bit
+};
+struct FirLaunch {
+    int family = FIR_LUT;
+    // the object that holds the instantiation: the row of D2D_M3_UNIT_LIST / D2D_MX_UNIT_LIST / D2D_PX_UNIT_LIST or of D2D_M2_SHAPES, MB for
+    // the LUT and one-group kernels, 0 for the plain one.  -1: no compiled kernel serves these arguments, the launcher returns hipErrorInvalidValue
+    int unit = -1;
+    int nt = 0, t[7] = {};     // the template arguments, in the order rocprofv3 prints them (the family's comment above)
+    int kind() const { return family == FIR_PX ? t[4] : t[3]; }      // KIND, and for FIR_MFMA2 its EPI
+    int sby() const { return t[4]; }                                  // SBY of the two pipelined kernels
+    // the kernel's argument struct, whole; `jobs` and `tables` are the engine's (bind).  One of the three per family: m1 FIR_MFMA; px the two
+    // polyphase kernels; m everything else (FIR_LUT passes m.f)
+    MfmaArgs m1{};
+    Mfma2Args m{};
+    PxArgs px{};
+    uint32_t px_span = 0;      // FIR_PX_PLAIN: bytes a tile's windows span (the kernel's second argument)
+    size_t lds = 0;            // dynamic LDS bytes of a block
+    uint32_t nwaves = 0;       // waves per block (FIR_MFMA2: what is asked for, the register file may admit fewer)
+    uint32_t tile = 0;         // outputs per wave-tile (FIR_LUT, FIR_PX_PLAIN: per block)
+    uint32_t block_tiles = 0;  // wave-tiles a block works on at a time: its waves, or one where the waves of a block share a tile (FirArgs::coop)
+    uint32_t rows_per_file = 0;   // grid rows per file: channel groups, or one (coop, several pairs per wave), or streams (FIR_LUT, FIR_PX_PLAIN)
+    std::string name;          // the kernel, spelled the way rocprofv3 prints it
+    void bind(const StreamJob* jobs, const void* tables) { m1.f.jobs = m.f.jobs = px.jobs = jobs; m1.f.tables = m.f.tables = px.tables = tables; }
+};
+// The launches of an engine: its main pass (the composed polyphase pass where route.poly), the residual table's pass (route.fine; `lo` its
+// filter) and the mono pair (route.mono2_pipe), on jobs of two "channels" per file.
+enum FirPass { PASS_MAIN, PASS_LO, PASS_MONO2 };
+FirLaunch fir_launch(const d2d_params& p, const FilterChoice& fc, const Epilogue& epi, const FirRoute& r, FirPass pass, const d2d_filter_def* lo = nullptr);
 
 }  // namespace d2d

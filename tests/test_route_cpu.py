@@ -1,4 +1,4 @@
-"""Which kernel, table layout and staging serve an engine: dsd2dxd_amd/csrc/d2d_route.cpp on the CPU, pinned by two goldens.
+"""Which kernel, table layout, staging and launch serve an engine: dsd2dxd_amd/csrc/d2d_route.cpp on the CPU, pinned by goldens.
 
 tools/route_probe.cpp is built from that unit and d2d_tables.cpp with g++ alone.  Both goldens were recorded from the commit before the route
 moved into one unit (profiles/route_refactor_check.md), so a condition that changes shows here, next to its cause, and not as a slower kernel
@@ -11,8 +11,12 @@ that a GPU parity test happens to name:
                                        mfma_pipe_lo, mono2_pipe, the launch geometry, the fp6 unit), one digest per rate and filter.  The
                                        parent had no place to read them from, so this one was recorded from the moved code, once its
                                        engine_matrix output had compared equal to the parent's on the GPU: it pins what is, for later changes
-Where the name predicted before the first call differs from the kernel that was then launched, the golden keeps both and this test asserts
-the prediction: d2d_kernel_name's text moved unchanged."""
+  tests/golden/route_launches.json     the launch plans of those configurations (`route_probe launches -`: family, unit, LDS bytes, waves, tile,
+                                       rows per file and kernel name of every pass), one digest per rate and filter; recorded from the code that
+                                       first had plans, once its engine_matrix output had compared equal to its parent's on the GPU
+                                       (profiles/launch_plan_check.md): a pin for later changes too
+Where the name predicted before the first call differs from the kernel that was then launched, the golden keeps both; this test asserts the
+prediction against route_kernel_name (d2d_kernel_name's text moved unchanged) and the launched name against the plan's."""
 import hashlib
 import json
 import os
@@ -60,6 +64,23 @@ def routes(probe, matrix):
     lines = [l.split("\t", 1) for l in _run(probe, "-", stdin="\n".join(keys) + "\n")]
     assert [k for k, _ in lines] == keys
     return dict(lines)
+
+
+@pytest.fixture(scope="module")
+def launches(probe, matrix):
+    """key -> the rest of the probe's `launches` line, for every configuration of the golden"""
+    keys = [k for g in matrix for k in g["configurations"]]
+    lines = [l.split("\t", 1) for l in _run(probe, "launches", "-", stdin="\n".join(keys) + "\n")]
+    assert [k for k, _ in lines] == keys
+    return dict(lines)
+
+
+def _digests(lines_by_key):
+    """the probe's lines as one "<lines> <first 16 hex digits of their sha256>" per rate and filter"""
+    blocks = {}
+    for k, rest in lines_by_key.items():
+        blocks.setdefault(":".join(k.split(":")[:3]), []).append(k + "\t" + rest)
+    return {k: "%d %s" % (len(b), hashlib.sha256("\n".join(b).encode()).hexdigest()[:16]) for k, b in blocks.items()}
 
 
 def _fields(rest):
@@ -128,10 +149,41 @@ def test_every_route_equals_what_the_gpu_reported(routes, matrix):
 
 def test_every_route_field_equals_the_golden(routes):
     """the whole line of every configuration of the sweep, staging and launch geometry included, as one digest per rate and filter"""
-    blocks = {}
-    for k, rest in routes.items():
-        blocks.setdefault(":".join(k.split(":")[:3]), []).append(k + "\t" + rest)
-    probed = {k: "%d %s" % (len(b), hashlib.sha256("\n".join(b).encode()).hexdigest()[:16]) for k, b in blocks.items()}
+    probed = _digests(routes)
     with open(os.path.join(ROOT, "tests", "golden", "route_fields.json")) as f:
+        golden = json.load(f)
+    assert probed == golden, [(k, probed.get(k), golden.get(k)) for k in sorted(set(probed) | set(golden)) if probed.get(k) != golden.get(k)]
+
+
+def test_every_launch_plan_names_the_kernel_the_gpu_launched(routes, launches, matrix):
+    """kernel_name_after of every creatable configuration of the sweep is the name of the plan its call took: the mono pair's where the engine has
+    one, else the main pass's.  The sweep's one call feeds a fresh engine 8192 bytes per channel.  plan_call (d2d_engine.cpp) sends it through
+    the pair when the halves (4096 bytes) are whole 16-byte chunks, whole outputs (M / 8 is 1, 2, 4, 8 or 16 bytes per output), no shorter than
+    the history `keep`, and the outputs (8192 / (M / 8)) are even in number and end below 2^32: all but `keep` hold by arithmetic, `keep` is
+    asserted here."""
+    bad, creatable = [], 0
+    for g in matrix:
+        if "create_error" in g["outcome"]:
+            continue
+        for k in g["configurations"]:
+            creatable += 1
+            status, *passes = launches[k].split("\t")
+            plans = {p.split(" ", 1)[0]: _fields(p.split(" ", 1)[1]) for p in passes}
+            assert status == "ok" and "main" in plans, (k, launches[k])
+            got = _fields(routes[k])
+            assert ("m2" in plans) == (got["mono2_pipe"] != "0") and ("lo" in plans) == (got["fine"] == "1"), (k, launches[k])
+            if "m2" in plans:
+                assert int(got["keep"]) <= 4096, (k, got["keep"])
+            plan = plans["m2" if "m2" in plans else "main"]
+            if plan["name"] != g["outcome"]["kernel_name_after"] or int(plan["unit"]) < 0:
+                bad.append((k, plan, g["outcome"]["kernel_name_after"]))
+    assert creatable == 16720
+    assert not bad, (len(bad), bad[:3])
+
+
+def test_every_launch_plan_equals_the_golden(launches):
+    """family, unit, LDS bytes, waves, tile, rows per file and name of every pass of every configuration of the sweep"""
+    probed = _digests(launches)
+    with open(os.path.join(ROOT, "tests", "golden", "route_launches.json")) as f:
         golden = json.load(f)
     assert probed == golden, [(k, probed.get(k), golden.get(k)) for k in sorted(set(probed) | set(golden)) if probed.get(k) != golden.get(k)]

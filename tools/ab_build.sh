@@ -35,7 +35,7 @@ case $TARGET in
 esac
 # (the engine sees the geometry macros too: groups per column name the kernel)
 $HIPCC $FL -x hip "$@" -c $CS/d2d_engine.cpp -o $O/d2d_engine.o
-# ... and so does the choice of the route (the lists of kept units, the groups per column)
+# ... and so do the choice of the route and the launch plans (the lists of kept units, the groups per column, the threads per block, the resident fragments)
 g++ -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I$CS -I$ROOT/filters $DEV "$@" -c $CS/d2d_route.cpp -o $O/d2d_route.o
 # the tree's objects, each replaced by the one just built where there is one
 OBJS=

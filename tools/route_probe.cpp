@@ -13,6 +13,9 @@
 //                              pass's launch geometry and the fp6 unit, or error=<code>:<text>.  The key is
 //                              <dsd_rate>:<output_rate>:<filter>:<channels><fmt><depth><dither>:<level>:<tap_bits>:<kernel>:<debug flags>
 //   route_probe -              the same lines for the keys on standard input, one per line
+//   route_probe launches -     for those keys the launch plans of the engine (d2d_route.h: fir_launch), "<key>\t<pass> <field>=<value> ...[\t<pass> ...]":
+//                              the passes it has (main; lo: the residual table's; m2: the mono pair), each with the plan's family, unit, LDS bytes,
+//                              waves per block, outputs per wave-tile, wave-tiles per block, grid rows per file and the kernel's name
 #include <math.h>
 #include <stdio.h>
 
@@ -113,7 +116,13 @@ static const Rate RATE_MATRIX[] = {       // tests/test_gpu_parity.py: RATE_MATR
     {8, 96000, 'E'},
 };
 
-static void route_line(const Rate& rt, uint32_t ch, char fmt, uint32_t bits, char dither, double level, uint32_t tap_bits, uint32_t kernel, uint32_t dbg) {
+static void launch_field(const char* pass, const FirLaunch& l) {
+    printf("\t%s family=%d unit=%d lds=%zu nwaves=%u tile=%u block_tiles=%u rows=%u name=%s", pass, l.family, l.unit, l.lds, l.nwaves, l.tile, l.block_tiles,
+           l.rows_per_file, l.name.c_str());
+}
+
+static void route_line(const Rate& rt, uint32_t ch, char fmt, uint32_t bits, char dither, double level, uint32_t tap_bits, uint32_t kernel, uint32_t dbg,
+                       bool launches = false) {
     d2d_params p{};
     p.struct_size = sizeof(p);
     p.dsd_rate = rt.dsd_rate; p.output_rate = rt.output_rate; p.filter = (uint32_t)rt.filter; p.channels = ch;
@@ -125,6 +134,18 @@ static void route_line(const Rate& rt, uint32_t ch, char fmt, uint32_t bits, cha
     if (rc == D2D_OK) rc = choose_route(p, fc, r, err);
     if (rc != D2D_OK) { printf("error=%d:%s\n", rc, err.c_str()); return; }
     const Epilogue epi = epilogue_of(p);
+    if (launches) {
+        printf("ok");
+        launch_field("main", fir_launch(p, fc, epi, r, PASS_MAIN));
+        if (r.fine) {
+            std::vector<int32_t> half;
+            const d2d_filter_def lo = residual_def(*fc.fir, half);
+            launch_field("lo", fir_launch(p, fc, epi, r, PASS_LO, &lo));
+        }
+        if (r.mono2_pipe != PIPE_NONE) launch_field("m2", fir_launch(p, fc, epi, r, PASS_MONO2));
+        printf("\n");
+        return;
+    }
     printf("kernel=%u poly=%d poly_plain=%d mfma_v2=%d mfma_pipe=%d mfma_pipe_lo=%d fine=%d taps32=%d deinterleave=%d il2=%d coop=%d B=%u keep=%u mono2_pipe=%d "
            "table_variant=%u variant=%u", r.kernel, r.poly, r.poly_plain, r.mfma_v2, r.mfma_pipe, r.mfma_pipe_lo, r.fine, r.taps32, r.deinterleave, r.il2,
            r.coop, r.B, r.keep, r.mono2_pipe, r.table_variant, route_table_variant(r));
@@ -133,10 +154,13 @@ static void route_line(const Rate& rt, uint32_t ch, char fmt, uint32_t bits, cha
         const FirArgs a = fir_args_static(p, fc, epi, r);
         size_t smem = 0;
         if (r.mfma_v2) {
+            // (the LDS bytes and the waves of the two-group geometry, whichever kernel serves; what the fp6 kernel's plan makes of gainq and the pairs)
             Mfma2Args m{};
-            mfma2_launch_args(a, f.M / 8, mfma2_pairs(f.M, f.ntaps), f.ntaps, m, smem);
-            printf(" lds=%zu nwaves=%u ngroups=%u intq=%u gainq=%u wide=%u epilogue=%d npairs=%u mx_unit=%d", smem, m.nwaves, m.ngroups, m.intq, m.gainq, m.wide,
-                   mfma2_epilogue(a, m), m.npairs, r.mfma_pipe == PIPE_FP6 ? mx_launch_unit(m, f.M / 8, f.ntaps) : -1);
+            mfma2_geometry(a, f.M / 8, mfma2_pairs(f.M, f.ntaps), m, smem);
+            const FirLaunch l = fir_launch(p, fc, epi, r, PASS_MAIN);
+            const bool mx = l.family == FIR_MX;
+            printf(" lds=%zu nwaves=%u ngroups=%u intq=%u gainq=%u wide=%u epilogue=%d npairs=%u mx_unit=%d", smem, m.nwaves, m.ngroups, m.intq, mx ? l.m.gainq : m.gainq,
+                   m.wide, mfma2_epilogue(a, m), mx ? l.m.npairs : m.npairs, mx ? l.unit : -1);
         } else {
             MfmaArgs m{};
             mfma_geometry(a, mfma_layout(f.M, f.ntaps), m, smem);
@@ -165,13 +189,14 @@ int main(int argc, char** argv) {
     if (argc > 1 && std::string(argv[1]) == "predicates") { predicates(); return 0; }
 #ifndef ROUTE_PROBE_PREDICATES_ONLY
     if (argc == 1) { routes(); return 0; }
-    if (std::string(argv[1]) == "-") {
+    const bool launches = std::string(argv[1]) == "launches";
+    if (std::string(argv[launches && argc > 2 ? 2 : 1]) == "-") {
         Rate rt; unsigned ch, bits, tap_bits, kernel, dbg; int level; char fmt, dither;
         while (scanf("%u:%u:%c:%u%c%u%c:%d:%u:%u:%u", &rt.dsd_rate, &rt.output_rate, &rt.filter, &ch, &fmt, &bits, &dither, &level, &tap_bits, &kernel, &dbg) == 11)
-            route_line(rt, ch, fmt, bits, dither, level, tap_bits, kernel, dbg);
+            route_line(rt, ch, fmt, bits, dither, level, tap_bits, kernel, dbg, launches);
         return 0;
     }
 #endif
-    fprintf(stderr, "usage: route_probe [predicates]\n");
+    fprintf(stderr, "usage: route_probe [predicates | - | launches -]\n");
     return 2;
 }
