@@ -252,6 +252,14 @@ static int validate(const d2d_params& p, std::string& err) {
 // what a stream that has not started yet holds as history
 static uint8_t idle_byte(const d2d_engine* e) { return e->p.endianness == D2D_MSB_FIRST ? IDLE_BYTE : (uint8_t)0x96; }  // 0x69 bit-reversed
 
+// The fills of create, d2d_reset and d2d_seek are null-stream hipMemsets.  The next call runs on a hipStreamNonBlocking stream (own_stream, or
+// a caller's), which the null stream does not order, and a hipMemset of device memory may return before the fill has run: every path that
+// fills ends here, so that the fills are ordered before whatever stream the next call uses.
+static int fills_done(d2d_engine* e) {
+    HIPCHK(e, hipDeviceSynchronize());
+    return D2D_OK;
+}
+
 static int reset_state(d2d_engine* e) {
     HIPCHK(e, hipSetDevice(e->p.device));
     for (int b = 0; b < 2; ++b) HIPCHK(e, hipMemset(e->d_hist[b], idle_byte(e), e->d_hist[b].bytes));
@@ -260,7 +268,7 @@ static int reset_state(d2d_engine* e) {
     for (int i = 0; i < 2; ++i) if (e->d_ns[i]) HIPCHK(e, hipMemset(e->d_ns[i], 0, e->d_ns[i].bytes));
     for (auto& f : e->files) f = FileState{};
     e->hist_cur = 0;
-    return D2D_OK;
+    return fills_done(e);
 }
 
 // one file back to the device state of a fresh engine, in both ping-pong buffers; the other files' rows stay
@@ -452,8 +460,8 @@ int d2d_seek(d2d_engine* e, uint32_t file, uint64_t pos) {
     HIPCHK(e, hipSetDevice(e->p.device));
     HIPCHK(e, hipDeviceSynchronize());
     int rc = clear_file_state(e, file);
+    if (!rc) rc = fills_done(e);
     if (rc) return rc;
-    HIPCHK(e, hipDeviceSynchronize());      // (the fills are ordered before whatever stream the next call uses)
     FileState& st = e->files[file];
     st.pos = pos;
     st.nfir = pos / (uint64_t)e->Mb;
