@@ -69,6 +69,7 @@ class FlacStreamStats(C.Structure):
 
 
 FLAC_BLOCK = 4096
+FLAC_EFFORT_FIXED2, FLAC_EFFORT_SEARCH = 0, 1      # D2D_FLAC_EFFORT_*
 
 READ_FN = C.CFUNCTYPE(C.c_long, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t)
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -82,7 +83,8 @@ EXPORTS = ["d2d_create", "d2d_create_error", "d2d_destroy", "d2d_reset", "d2d_la
            "d2d_profile_enable", "d2d_profile_read", "d2d_profile_read_all",
            "d2d_seek", "d2d_tell", "d2d_preroll_bytes", "d2d_slice_align_bytes", "d2d_prime", "d2d_prime_batch_device",
            "d2d_flac_bound_bytes", "d2d_flac_workspace_bytes", "d2d_flac_encode_device", "d2d_flac_error",
-           "d2d_flac_encode_host", "d2d_convert_stream_flac"]
+           "d2d_flac_encode_host", "d2d_convert_stream_flac",
+           "d2d_flac_encode_device_effort", "d2d_flac_encode_host_effort", "d2d_convert_stream_flac_effort"]
 
 _lib = None
 
@@ -152,6 +154,13 @@ def lib():
                                        C.POINTER(FlacResult), C.POINTER(C.c_size_t)]
     L.d2d_convert_stream_flac.argtypes = [C.c_void_p, C.c_uint32, READ_FN, C.c_void_p, WRITE_FN, C.c_void_p, C.POINTER(C.c_int),
                                           PROGRESS_FN, C.c_void_p, C.c_uint64, C.c_size_t, C.POINTER(FlacStreamStats)]
+    L.d2d_flac_encode_device_effort.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(FlacIO), C.c_uint32, C.c_void_p, C.c_size_t,
+                                                C.c_void_p]
+    L.d2d_flac_encode_host_effort.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_void_p,
+                                              C.c_size_t, C.POINTER(FlacResult), C.POINTER(C.c_size_t)]
+    L.d2d_convert_stream_flac_effort.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, READ_FN, C.c_void_p, WRITE_FN, C.c_void_p,
+                                                 C.POINTER(C.c_int), PROGRESS_FN, C.c_void_p, C.c_uint64, C.c_size_t,
+                                                 C.POINTER(FlacStreamStats)]
     _lib = L
     return L
 
@@ -169,8 +178,8 @@ def flac_workspace_bytes(channels, bit_depth, frames, final):
     return lib().d2d_flac_workspace_bytes(channels, bit_depth, frames, int(bool(final)))
 
 
-def flac_encode_host(channels, bit_depth, pcm, first_block=0, final=True, capacity=None):
-    """d2d_flac_encode_host on a bytes-like of interleaved little-endian frames: the sink's own encoder, no device.
+def flac_encode_host(channels, bit_depth, pcm, first_block=0, final=True, capacity=None, effort=0):
+    """d2d_flac_encode_host_effort on a bytes-like of interleaved little-endian frames: the sink's own encoder, no device.
     Returns (frame bytes, FlacResult, frames_consumed)."""
     import numpy as np
     buf = np.ascontiguousarray(np.frombuffer(pcm, dtype=np.uint8) if not isinstance(pcm, np.ndarray) else pcm.view(np.uint8).reshape(-1))
@@ -179,15 +188,15 @@ def flac_encode_host(channels, bit_depth, pcm, first_block=0, final=True, capaci
     cap = flac_bound_bytes(channels, bit_depth, frames, final) if capacity is None else capacity
     out = np.zeros(max(cap, 1), dtype=np.uint8)
     res, used = FlacResult(), C.c_size_t()
-    _flac_check(lib().d2d_flac_encode_host(channels, bit_depth, buf.ctypes.data, frames, first_block, int(bool(final)),
-                                           out.ctypes.data, cap, C.byref(res), C.byref(used)))
+    _flac_check(lib().d2d_flac_encode_host_effort(channels, bit_depth, effort, buf.ctypes.data, frames, first_block, int(bool(final)),
+                                                  out.ctypes.data, cap, C.byref(res), C.byref(used)))
     return out[:res.bytes_out].tobytes(), res, used.value
 
 
-def flac_encode_device(channels, bit_depth, ios, workspace_ptr, workspace_bytes, stream=None):
-    """d2d_flac_encode_device: ios is a ctypes array of FlacIO with DEVICE pointers; asynchronous on `stream` (hipStream_t int)."""
-    _flac_check(lib().d2d_flac_encode_device(channels, bit_depth, ios, len(ios), C.c_void_p(workspace_ptr), workspace_bytes,
-                                             C.c_void_p(stream or 0)))
+def flac_encode_device(channels, bit_depth, ios, workspace_ptr, workspace_bytes, stream=None, effort=0):
+    """d2d_flac_encode_device_effort: ios is a ctypes array of FlacIO with DEVICE pointers; asynchronous on `stream` (hipStream_t int)."""
+    _flac_check(lib().d2d_flac_encode_device_effort(channels, bit_depth, effort, ios, len(ios), C.c_void_p(workspace_ptr), workspace_bytes,
+                                                    C.c_void_p(stream or 0)))
 
 
 class D2DError(Exception):
@@ -372,8 +381,8 @@ class Engine:
                                              keep["p"], None, total_bytes_per_channel, chunk_bytes_per_channel))
 
     def convert_stream_flac(self, read, write, total_bytes_per_channel=0, chunk_bytes_per_channel=1 << 22,
-                            cancel=None, progress=None):
-        """d2d_convert_stream_flac: as convert_stream, but write() receives FLAC frames (whole frames, in order); returns the
+                            cancel=None, progress=None, effort=0):
+        """d2d_convert_stream_flac_effort: as convert_stream, but write() receives FLAC frames (whole frames, in order); returns the
         FlacStreamStats STREAMINFO needs.  Errors carry d2d_flac_error()'s message."""
         def _read(_u, dst, cap):
             data = read(cap)
@@ -393,6 +402,6 @@ class Engine:
         r, w, p = READ_FN(_read), WRITE_FN(_write), PROGRESS_FN(_prog)
         cflag = cancel if cancel is not None else C.c_int(0)
         stats = FlacStreamStats()
-        _flac_check(lib().d2d_convert_stream_flac(self._h, self.params.bit_depth, r, None, w, None, C.byref(cflag), p, None,
-                                                  total_bytes_per_channel, chunk_bytes_per_channel, C.byref(stats)))
+        _flac_check(lib().d2d_convert_stream_flac_effort(self._h, self.params.bit_depth, effort, r, None, w, None, C.byref(cflag), p, None,
+                                                         total_bytes_per_channel, chunk_bytes_per_channel, C.byref(stats)))
         return stats

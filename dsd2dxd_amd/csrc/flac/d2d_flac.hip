@@ -1,7 +1,8 @@
 // d2d_flac.hip -- FLAC frames on the GPU (gfx950): the kernels behind d2d_flac_encode_device, and d2d_convert_stream_flac on top
-// of the public calls.  The bitstream is the one flac_frame_enc.h defines; tests/test_gpu_flac.py compares them byte for byte.
+// of the public calls.  The bitstream is the one flac_frame_enc.h defines, at both efforts; tests/test_gpu_flac.py (effort 0) and
+// tests/test_gpu_flac_search.py (effort 1) compare them byte for byte.
 //
-//   flac_encode_kernel<CH>   one workgroup of 1024 threads per (file, block); thread t owns samples 4t .. 4t+3 of every channel.
+//   flac_encode_kernel<CH>   effort 0: one workgroup of 1024 threads per (file, block); thread t owns samples 4t .. 4t+3 of every channel.
 //     1. the block's PCM comes into LDS with 16-byte loads (4096 * frame_bytes is a multiple of 16; a short block's tail by bytes)
 //     2. residuals r = s[i] - 2 s[i-1] + s[i-2] stay in registers; sum |r| per channel is reduced over the workgroup (64-bit) and
 //        thread c derives k[c]
@@ -12,6 +13,7 @@
 //     5. CRC-16 in parallel: init 0 makes the CRC linear and blind to leading zeros, so the frame is treated as 1024 equal chunks
 //        with zeros in front, every thread runs the table over its chunk, and a tree combines  crc(A|B) = crc(A) x^(8 len B) + crc(B)
 //     6. the image goes to the block's workspace slot (16-byte stores), its size to the size table
+//   flac_search_kernel<CH>   effort 1: the same workgroup and steps 3 to 6, with the search in front of them (described at the kernel)
 //   flac_pack_kernel        per file, 32 blocks per workgroup: sums the sizes in front of its blocks, copies the slots to `out`
 //                            contiguously; the first workgroup of a file writes the result record.
 // The two run one after the other on the caller's stream.  No workgroup waits on another: no look-back, no flags, no spinning.
@@ -74,6 +76,66 @@ __device__ __forceinline__ uint32_t gf_xpow(uint32_t e) {     // x^e
     return r;
 }
 
+// the CRC-16 table (x^16 + x^15 + x^2 + 1)
+__device__ __forceinline__ void build_crc_tab(uint16_t* s_crc_tab, uint32_t tid) {
+    if (tid < 256) {
+        uint32_t c = tid << 8;
+        for (int i = 0; i < 8; ++i) c = (c & 0x8000u) ? ((c << 1) ^ 0x8005u) & 0xFFFFu : (c << 1) & 0xFFFFu;
+        s_crc_tab[tid] = (uint16_t)c;
+    }
+}
+
+// the frame header and its CRC-8 (x^8 + x^2 + x + 1); `assignment` is the channel-assignment nibble.  One thread.
+__device__ __forceinline__ void build_header(uint8_t* s_hdr, uint32_t n, uint32_t assignment, uint32_t depth, uint32_t frame_no) {
+    uint32_t p = 0;
+    s_hdr[p++] = 0xFF; s_hdr[p++] = 0xF8;
+    s_hdr[p++] = n == BS ? 0xC0 : 0x70;
+    s_hdr[p++] = (uint8_t)((assignment << 4) | ((depth == 16 ? 4u : depth == 20 ? 5u : 6u) << 1));
+    if (frame_no < 0x80) s_hdr[p++] = (uint8_t)frame_no;
+    else {
+        const int m = (int)utf8_len(frame_no) - 1;
+        s_hdr[p++] = (uint8_t)(((0xFF00u >> (m + 1)) & 0xFFu) | (frame_no >> (6 * m)));
+        for (int i = m - 1; i >= 0; --i) s_hdr[p++] = (uint8_t)(0x80u | ((frame_no >> (6 * i)) & 0x3Fu));
+    }
+    if (n != BS) { s_hdr[p++] = (uint8_t)((n - 1) >> 8); s_hdr[p++] = (uint8_t)(n - 1); }
+    uint32_t c = 0;
+    for (uint32_t i = 0; i < p; ++i) {
+        c ^= s_hdr[i];
+        for (int k2 = 0; k2 < 8; ++k2) c = (c & 0x80u) ? ((c << 1) ^ 0x07u) & 0xFFu : (c << 1) & 0xFFu;
+    }
+    s_hdr[p] = (uint8_t)c;
+}
+
+// CRC-16 of the image's first data_bytes, placed behind them.  The whole workgroup, all bits of the image placed and a barrier passed;
+// ends with a barrier.
+__device__ __forceinline__ void frame_crc16(uint32_t* img, uint32_t data_bytes, const uint16_t* s_crc_tab, uint16_t* s_crc, uint32_t tid) {
+    auto image_byte = [&](uint32_t j) -> uint32_t { return (img[j >> 2] >> (24 - 8 * (j & 3))) & 0xFFu; };
+    const uint32_t L = (data_bytes + NT - 1) / NT, padz = NT * L - data_bytes;
+    uint32_t c = 0;
+    for (uint32_t v = tid * L; v < (tid + 1) * L; ++v)
+        if (v >= padz) c = ((c << 8) & 0xFFFFu) ^ s_crc_tab[(c >> 8) ^ image_byte(v - padz)];
+    s_crc[tid] = (uint16_t)c;
+    uint32_t m = gf_xpow(8 * L);
+    for (uint32_t stride = 1; stride < NT; stride <<= 1) {
+        __syncthreads();
+        if ((tid & (2 * stride - 1)) == 0) s_crc[tid] = (uint16_t)(gf_mul(s_crc[tid], m) ^ s_crc[tid + stride]);
+        m = gf_mul(m, m);
+    }
+    __syncthreads();
+    if (tid == 0 && s_crc[0]) put_bits(img, data_bytes * 8, s_crc[0], 16);
+    __syncthreads();
+}
+
+// the image (big-endian words) to its 16-byte aligned slot
+__device__ __forceinline__ void store_frame(const uint32_t* img, uint8_t* slot, uint32_t out_vecs, uint32_t tid) {
+    uint4* dst = reinterpret_cast<uint4*>(slot);
+    for (uint32_t v = tid; v < out_vecs; v += NT) {
+        uint4 w = reinterpret_cast<const uint4*>(img)[v];
+        w.x = __builtin_bswap32(w.x); w.y = __builtin_bswap32(w.y); w.z = __builtin_bswap32(w.z); w.w = __builtin_bswap32(w.w);
+        dst[v] = w;
+    }
+}
+
 template <int CH>
 __global__ __launch_bounds__(NT) void flac_encode_kernel(const FlacArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];          // the block's PCM, then the frame image
@@ -101,30 +163,8 @@ __global__ __launch_bounds__(NT) void flac_encode_kernel(const FlacArgs a) {
         for (uint32_t v = tid; v < nvec; v += NT) reinterpret_cast<uint4*>(smem)[v] = reinterpret_cast<const uint4*>(src)[v];
         for (uint32_t j = (nvec << 4) + tid; j < nbytes; j += NT) smem[j] = src[j];
     }
-    if (tid < 256) {                                                // the CRC-16 table (x^16 + x^15 + x^2 + 1)
-        uint32_t c = tid << 8;
-        for (int i = 0; i < 8; ++i) c = (c & 0x8000u) ? ((c << 1) ^ 0x8005u) & 0xFFFFu : (c << 1) & 0xFFFFu;
-        s_crc_tab[tid] = (uint16_t)c;
-    }
-    if (tid == 0) {                                                 // the frame header and its CRC-8 (x^8 + x^2 + x + 1)
-        uint32_t p = 0;
-        s_hdr[p++] = 0xFF; s_hdr[p++] = 0xF8;
-        s_hdr[p++] = n == BS ? 0xC0 : 0x70;
-        s_hdr[p++] = (uint8_t)(((CH - 1) << 4) | ((depth == 16 ? 4u : depth == 20 ? 5u : 6u) << 1));
-        if (frame_no < 0x80) s_hdr[p++] = (uint8_t)frame_no;
-        else {
-            const int m = (int)utf8_len(frame_no) - 1;
-            s_hdr[p++] = (uint8_t)(((0xFF00u >> (m + 1)) & 0xFFu) | (frame_no >> (6 * m)));
-            for (int i = m - 1; i >= 0; --i) s_hdr[p++] = (uint8_t)(0x80u | ((frame_no >> (6 * i)) & 0x3Fu));
-        }
-        if (n != BS) { s_hdr[p++] = (uint8_t)((n - 1) >> 8); s_hdr[p++] = (uint8_t)(n - 1); }
-        uint32_t c = 0;
-        for (uint32_t i = 0; i < p; ++i) {
-            c ^= s_hdr[i];
-            for (int k2 = 0; k2 < 8; ++k2) c = (c & 0x80u) ? ((c << 1) ^ 0x07u) & 0xFFu : (c << 1) & 0xFFu;
-        }
-        s_hdr[p] = (uint8_t)c;
-    }
+    build_crc_tab(s_crc_tab, tid);
+    if (tid == 0) build_header(s_hdr, n, CH - 1, depth, frame_no);
     __syncthreads();
 
     // 2. samples -> residuals (warm-up and verbatim samples stay as they are), sum |r|
@@ -245,32 +285,385 @@ __global__ __launch_bounds__(NT) void flac_encode_kernel(const FlacArgs a) {
     }
     __syncthreads();
 
-    // 5. CRC-16 over the data_bytes in front of it
-    auto image_byte = [&](uint32_t j) -> uint32_t { return (img[j >> 2] >> (24 - 8 * (j & 3))) & 0xFFu; };
-    {
-        const uint32_t L = (data_bytes + NT - 1) / NT, padz = NT * L - data_bytes;
-        uint32_t c = 0;
-        for (uint32_t v = tid * L; v < (tid + 1) * L; ++v)
-            if (v >= padz) c = ((c << 8) & 0xFFFFu) ^ s_crc_tab[(c >> 8) ^ image_byte(v - padz)];
-        s_crc[tid] = (uint16_t)c;
-        uint32_t m = gf_xpow(8 * L);
-        for (uint32_t stride = 1; stride < NT; stride <<= 1) {
-            __syncthreads();
-            if ((tid & (2 * stride - 1)) == 0) s_crc[tid] = (uint16_t)(gf_mul(s_crc[tid], m) ^ s_crc[tid + stride]);
-            m = gf_mul(m, m);
+    // 5. CRC-16 over the data_bytes in front of it; 6. image -> slot
+    frame_crc16(img, data_bytes, s_crc_tab, s_crc, tid);
+    store_frame(img, fd.slots + (size_t)b * a.slot_bytes, out_vecs, tid);
+    if (tid == 0) fd.sizes[b] = frame_bytes;
+}
+
+// ---- effort 1: the search of flac_frame_enc.h -------------------------------------------------------------------------------
+
+constexpr int NP = 64;            // Rice partitions of a whole block at the finest partition order, 6: 64 samples, 16 lanes each
+
+__device__ __forceinline__ uint32_t zigzag(int32_t r) { return r >= 0 ? (uint32_t)r << 1 : ((uint32_t)(-r) << 1) - 1; }
+__device__ __forceinline__ uint32_t rice_k(unsigned long long sum, uint32_t count) {
+    const unsigned long long mean = sum / (count ? count : 1);
+    uint32_t k = 0;
+    while (k < 30 && (1ull << k) < mean) ++k;
+    return k;
+}
+// The block's PCM into LDS as planar 32-bit samples, pcm[c * BS + i]: thread t unpacks its frames 4t .. 4t+3, which are CH * SB
+// whole dwords of the source (the block begins 16-byte aligned), and writes one 16-byte vector per channel.  A short block's last,
+// partial group goes byte by byte, so that nothing behind the n frames is read.  Samples from n on stay unwritten.
+template <int CH, int SB>
+__device__ __forceinline__ void load_planar_sb(int32_t* pcm, const uint8_t* src, uint32_t n, uint32_t depth, uint32_t tid) {
+    constexpr int ND = CH * SB;                                     // dwords of four frames
+    const uint32_t i0 = tid * SPT;
+    if (i0 >= n) return;
+    uint32_t w[ND];
+    if (i0 + SPT <= n) {
+#pragma unroll
+        for (int d = 0; d < ND; ++d) w[d] = reinterpret_cast<const uint32_t*>(src)[tid * ND + d];
+    } else {
+        const uint32_t have = (n - i0) * CH * SB;
+#pragma unroll
+        for (int d = 0; d < ND; ++d) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) if ((uint32_t)(4 * d + k) < have) v |= (uint32_t)src[(size_t)tid * ND * 4 + 4 * d + k] << (8 * k);
+            w[d] = v;
+        }
+    }
+    auto byte = [&](int k) -> uint32_t { return (w[k >> 2] >> (8 * (k & 3))) & 0xFFu; };
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        int32_t v[SPT];
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) {
+            const int k = (j * CH + c) * SB;
+            v[j] = SB == 2 ? (int32_t)(int16_t)(byte(k) | (byte(k + 1) << 8)) : (int32_t)((byte(k) | (byte(k + 1) << 8) | (byte(k + 2) << 16)) << 8) >> 8;
+            if (depth == 20) v[j] >>= 4;
+        }
+        *reinterpret_cast<int4*>(pcm + c * BS + i0) = make_int4(v[0], v[1], v[2], v[3]);
+    }
+}
+template <int CH>
+__device__ __forceinline__ void load_planar(int32_t* pcm, const uint8_t* src, uint32_t n, uint32_t depth, uint32_t tid) {
+    if (depth == 16) load_planar_sb<CH, 2>(pcm, src, n, depth, tid);
+    else load_planar_sb<CH, 3>(pcm, src, n, depth, tid);
+}
+// x[w] = sample i0 - 4 + w of candidate signal sg, 0 outside [0, n): a thread's four samples behind their four predecessors.
+// sg is a channel, or for two channels 2 = mid, 3 = side.
+template <int CH>
+__device__ __forceinline__ void load_window(int32_t (&x)[8], const int32_t* pcm, uint32_t i0, uint32_t n, uint32_t sg) {
+    const int32_t* q = pcm + (CH == 2 && sg >= 2 ? 0u : sg) * BS + i0;
+    const int4 z = make_int4(0, 0, 0, 0);
+    const int4 lo = i0 ? *reinterpret_cast<const int4*>(q - 4) : z, hi = *reinterpret_cast<const int4*>(q);
+    x[0] = lo.x; x[1] = lo.y; x[2] = lo.z; x[3] = lo.w; x[4] = hi.x; x[5] = hi.y; x[6] = hi.z; x[7] = hi.w;
+    if (CH == 2 && sg >= 2) {
+        const int4 rlo = i0 ? *reinterpret_cast<const int4*>(q + BS - 4) : z, rhi = *reinterpret_cast<const int4*>(q + BS);
+        const int32_t r[8] = {rlo.x, rlo.y, rlo.z, rlo.w, rhi.x, rhi.y, rhi.z, rhi.w};
+#pragma unroll
+        for (int w = 0; w < 8; ++w) x[w] = sg == 2 ? (x[w] + r[w]) >> 1 : x[w] - r[w];
+    }
+#pragma unroll
+    for (int w = 4; w < 8; ++w) if (i0 + w - 4 >= n) x[w] = 0;      // (what lies before i0 lies below n, or nothing here is used)
+}
+// one more difference over the window: residuals of order o from those of order o - 1, in x[o ..]
+__device__ __forceinline__ void difference(int32_t (&x)[8], int o) {
+#pragma unroll
+    for (int w = 7; w >= 1; --w) if (w >= o) x[w] -= x[w - 1];
+}
+// Sums across lanes without LDS traffic: four DPP adds leave the sum of each row of 16 lanes in all its lanes (lane ^ 1, lane ^ 2 by
+// quad permutes, then the half row and the row mirrored); four lane reads add the rows of a wave into a wave-uniform value.  Every
+// lane of the wave must be active.
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_move(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true); }
+__device__ __forceinline__ uint32_t row_sum(uint32_t v) {
+    v += dpp_move<0xB1>(v);                                          // quad_perm [1, 0, 3, 2]
+    v += dpp_move<0x4E>(v);                                          // quad_perm [2, 3, 0, 1]
+    v += dpp_move<0x141>(v);                                         // row_half_mirror
+    v += dpp_move<0x140>(v);                                         // row_mirror
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+    v = row_sum(v);
+    return (uint32_t)(__builtin_amdgcn_readlane((int)v, 0) + __builtin_amdgcn_readlane((int)v, 16) + __builtin_amdgcn_readlane((int)v, 32) +
+                      __builtin_amdgcn_readlane((int)v, 48));
+}
+// ... of 64-bit values below 2^48 as two 32-bit sums of 24-bit halves: neither can overflow over 64 lanes
+__device__ __forceinline__ unsigned long long row_sum(unsigned long long v) {
+    return ((unsigned long long)row_sum((uint32_t)(v >> 24)) << 24) + row_sum((uint32_t)v & 0xFFFFFFu);
+}
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+    return ((unsigned long long)wave_sum((uint32_t)(v >> 24)) << 24) + wave_sum((uint32_t)v & 0xFFFFFFu);
+}
+// v[i] summed over the workgroup, in every thread; N sums share the two barriers.  32-bit sums must fit 32 bits, 64-bit sums 48.
+template <int N, typename T>
+__device__ __forceinline__ void wg_sum(T (&v)[N], unsigned long long* s_red, uint32_t lane, uint32_t wave) {
+    T* red = reinterpret_cast<T*>(s_red);
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = wave_sum(v[i]);
+    __syncthreads();                                                 // (the readers of the last use are through)
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) red[wave * N + i] = v[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = row_sum(red[(lane & (NW - 1)) * N + i]);      // 16 lanes hold the 16 waves' sums
+}
+
+//   flac_search_kernel<CH>   the same workgroup, with the decisions of effort 1 between "PCM in LDS" and "place bits".  Candidate
+//   signals (the channels; for two channels also mid and side) go through (a) to (c) one at a time, so that one signal's five
+//   residual sets are all the registers hold:
+//     (a) sum |r_o| for o = 0 .. 4, one five-wide 64-bit reduction; threads 0 .. 4 derive the five k; the code lengths under them,
+//         one five-wide reduction; every thread picks the order from the five exact costs
+//     (b) sum |r| of the chosen order per finest partition (n >> pmax samples): for a whole block 16 lanes, one DPP row sum; for
+//         a short block whatever the samples fall into, by LDS adds.  Threads 0 .. 126 add them up to the partitions of every order
+//         p <= pmax and derive their k: the table s_kt
+//     (c) every thread's code lengths under each p's k, one seven-wide reduction; every thread picks the partition order; the chosen
+//         order's k row is kept per signal
+//     (d) two channels: the assignment from the four signals' costs
+//     (e) per subframe the chosen signal's residuals again, now kept; lengths with the residual header in front of sample `order` and
+//         a 5-bit k in front of every partition's first residual; then the scan, the image, the CRC and the slot as at effort 0.
+//   A frame of fewer than 16 samples takes the same path with the choices forced to effort 0's.
+template <int CH>
+__global__ __launch_bounds__(NT) void flac_search_kernel(const FlacArgs a) {
+    constexpr int NSIG = CH == 2 ? 4 : CH;
+    extern __shared__ __align__(16) unsigned char smem[];          // the block's PCM as planar 32-bit samples, then the frame image
+    __shared__ unsigned long long s_red[NW * 8];
+    __shared__ unsigned long long s_psum[NP];
+    __shared__ uint32_t s_wtot[NW][CH];
+    __shared__ uint32_t s_ko[5];
+    __shared__ uint32_t s_sel[NSIG][3];                             // order, partition order, cost of each signal
+    __shared__ uint8_t s_kt[2 * NP];                                // k of partition j at partition order p: s_kt[2^p - 1 + j]
+    __shared__ uint8_t s_ksel[NSIG][NP];                            // ... the chosen order's row
+    __shared__ uint16_t s_crc_tab[256];
+    __shared__ uint16_t s_crc[NT];
+    __shared__ uint8_t s_hdr[16];
+
+    const FileDesc& fd = a.f[blockIdx.y];
+    const uint32_t b = blockIdx.x;
+    if (b >= fd.blocks) return;                                     // (the whole workgroup)
+    const uint32_t n = b + 1 == fd.blocks ? fd.last_n : BS;
+    const uint32_t depth = a.depth, sb = depth == 16 ? 2u : 3u, fb = CH * sb;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t frame_no = fd.first_block + b;
+    const uint32_t hdr_bytes = 4 + utf8_len(frame_no) + (n != BS ? 2u : 0u) + 1;
+    const bool searched = n >= 16;
+    // the largest p <= 6 with n % 2^p == 0 and (n >> p) >= 16; the finest partitions and where this thread's samples lie in them
+    const uint32_t pmax = searched ? min(6u, min((uint32_t)__ffs(n) - 1u, 27u - (uint32_t)__clz(n))) : 0u;
+    const uint32_t fsz = n >> pmax, i0 = tid * SPT, pj0 = i0 / fsz, rem0 = i0 - pj0 * fsz;
+
+    int32_t* pcm = reinterpret_cast<int32_t*>(smem);
+    load_planar<CH>(pcm, fd.pcm + (size_t)b * BS * fb, n, depth, tid);
+    build_crc_tab(s_crc_tab, tid);
+    __syncthreads();
+
+#pragma unroll 1
+    for (uint32_t sg = 0; sg < (uint32_t)NSIG; ++sg) {
+        const uint32_t bits = CH == 2 && sg == 3 ? depth + 1 : depth;
+        if (tid < NP) s_psum[tid] = 0;                              // (read last before the barriers of the previous round's sums)
+        // (a) the five residual sets as u = zigzag(r); |r| = (u + 1) >> 1
+        uint32_t u[5][SPT];
+        unsigned long long asum[5];
+        {
+            int32_t x[8];
+            load_window<CH>(x, pcm, i0, n, sg);
+#pragma unroll
+            for (int o = 0; o < 5; ++o) {
+                if (o) difference(x, o);
+                uint32_t acc = 0;                                   // |r_4| <= 2^28: four of them fit
+#pragma unroll
+                for (int j = 0; j < SPT; ++j) {
+                    u[o][j] = zigzag(x[4 + j]);
+                    if (i0 + j < n && i0 + j >= (uint32_t)o) acc += (u[o][j] + 1) >> 1;
+                }
+                asum[o] = acc;
+            }
+        }
+        wg_sum<5>(asum, s_red, lane, wave);
+        if (tid < 5) s_ko[tid] = rice_k(tid == 0 ? asum[0] : tid == 1 ? asum[1] : tid == 2 ? asum[2] : tid == 3 ? asum[3] : asum[4], n > tid ? n - tid : 1);
+        __syncthreads();
+        uint32_t len[5];
+#pragma unroll
+        for (int o = 0; o < 5; ++o) {
+            const uint32_t k = s_ko[o];
+            len[o] = 0;
+#pragma unroll
+            for (int j = 0; j < SPT; ++j)
+                if (i0 + j < n && i0 + j >= (uint32_t)o) len[o] += (u[o][j] >> k) + 1 + k;
+        }
+        wg_sum<5>(len, s_red, lane, wave);
+        uint32_t order = 0, cost = 0;
+#pragma unroll
+        for (int o = 0; o < 5; ++o) {                               // the smallest order wins a tie
+            const uint32_t c = 8 + o * bits + 6 + 5 + len[o];
+            if (o == 0 || c < cost) { order = o; cost = c; }
+        }
+        if (!searched) order = n > 2 ? 2u : n;                      // effort 0's frame: order 2, or verbatim (every sample a warm-up)
+
+        // (b) sum |r| per finest partition, then k for every partition of every order
+        uint32_t uo[SPT];
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) uo[j] = order == 0 ? u[0][j] : order == 1 ? u[1][j] : order == 2 ? u[2][j] : order == 3 ? u[3][j] : u[4][j];
+        if (n == BS) {                                              // 16 lanes hold one partition
+            unsigned long long t = 0;
+#pragma unroll
+            for (int j = 0; j < SPT; ++j) if (i0 + j >= order) t += (uo[j] + 1) >> 1;
+            t = row_sum(t);
+            if ((lane & 15u) == 0) s_psum[tid >> 4] = t;
+        } else {
+            unsigned long long run = 0;
+            uint32_t pj = pj0, rem = rem0;
+#pragma unroll
+            for (int j = 0; j < SPT; ++j) {
+                if (i0 + j < n && i0 + j >= order) run += (uo[j] + 1) >> 1;
+                const bool ends = j == SPT - 1 || rem + 1 == fsz;
+                if (ends && run) { atomicAdd(&s_psum[pj], run); run = 0; }     // (run != 0 only below n: pj < 2^pmax)
+                if (++rem == fsz) { rem = 0; ++pj; }
+            }
         }
         __syncthreads();
-        if (tid == 0 && s_crc[0]) put_bits(img, data_bytes * 8, s_crc[0], 16);
+        if (tid < 2 * NP - 1) {
+            const uint32_t p = 31u - (uint32_t)__clz(tid + 1), j = tid + 1 - (1u << p);
+            if (p <= pmax) {
+                const uint32_t span = 1u << (pmax - p);
+                unsigned long long sum = 0;
+                for (uint32_t t = 0; t < span; ++t) sum += s_psum[j * span + t];
+                s_kt[tid] = (uint8_t)rice_k(sum, (n >> p) - (j == 0 ? order : 0u));
+            }
+        }
+        __syncthreads();
+
+        // (c) the cost of every partition order
+        uint32_t plen[7];
+#pragma unroll
+        for (int p = 0; p < 7; ++p) plen[p] = 0;
+        {
+            uint32_t pj = pj0, rem = rem0;
+#pragma unroll
+            for (int j = 0; j < SPT; ++j) {
+                if (i0 + j < n && i0 + j >= order) {
+#pragma unroll
+                    for (int p = 0; p < 7; ++p)
+                        if ((uint32_t)p <= pmax) { const uint32_t k = s_kt[(1u << p) - 1 + (pj >> (pmax - p))]; plen[p] += (uo[j] >> k) + 1 + k; }
+                }
+                if (++rem == fsz) { rem = 0; ++pj; }
+            }
+        }
+        wg_sum<7>(plen, s_red, lane, wave);
+        uint32_t porder = 0;
+#pragma unroll
+        for (int p = 0; p < 7; ++p) {                               // the smallest partition order wins a tie
+            const uint32_t c = 8 + order * bits + 6 + (5u << p) + plen[p];
+            if (p == 0) cost = c;
+            else if ((uint32_t)p <= pmax && c < cost) { porder = p; cost = c; }
+        }
+        if (tid == 0) { s_sel[sg][0] = order; s_sel[sg][1] = porder; s_sel[sg][2] = cost; }
+        if (tid < (1u << porder)) s_ksel[sg][tid] = s_kt[(1u << porder) - 1 + tid];
     }
     __syncthreads();
 
-    // 6. image -> slot
-    uint4* dst = reinterpret_cast<uint4*>(fd.slots + (size_t)b * a.slot_bytes);
-    for (uint32_t v = tid; v < out_vecs; v += NT) {
-        uint4 w = reinterpret_cast<const uint4*>(img)[v];
-        w.x = __builtin_bswap32(w.x); w.y = __builtin_bswap32(w.y); w.z = __builtin_bswap32(w.z); w.w = __builtin_bswap32(w.w);
-        dst[v] = w;
+    // (d) the channel assignment: independent, left/side, side/right, mid/side; ties in this order
+    uint32_t mode = 0;
+    if (CH == 2 && searched) {
+        const uint32_t L = s_sel[0][2], R = s_sel[1][2], M = s_sel[NSIG > 2 ? 2 : 0][2], S = s_sel[NSIG > 3 ? 3 : 0][2];
+        uint32_t total = L + R;
+        if (L + S < total) { total = L + S; mode = 1; }
+        if (S + R < total) { total = S + R; mode = 2; }
+        if (M + S < total) { total = M + S; mode = 3; }
     }
+    if (tid == 0) build_header(s_hdr, n, mode == 0 ? CH - 1 : 7 + mode, depth, frame_no);
+    auto subframe_signal = [&](int c) -> uint32_t {
+        if (CH != 2) return (uint32_t)c;
+        return c == 0 ? (mode == 2 ? 3u : mode == 3 ? 2u : 0u) : (mode == 0 || mode == 2 ? 1u : 3u);
+    };
+
+    // (e) the chosen residuals (warm-up samples as they are), code lengths, and where every thread's bits begin
+    int32_t val[CH][SPT];
+    uint32_t start[CH];
+    uint32_t total_bits = hdr_bytes * 8;
+    {
+        uint32_t incl[CH], mine[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            const uint32_t sg = subframe_signal(c), order = s_sel[sg][0], sh = pmax - s_sel[sg][1];
+            const uint32_t bits = CH == 2 && sg == 3 ? depth + 1 : depth;
+            int32_t x[8];
+            load_window<CH>(x, pcm, i0, n, sg);
+            int32_t raw[SPT];
+#pragma unroll
+            for (int j = 0; j < SPT; ++j) raw[j] = x[4 + j];
+#pragma unroll
+            for (int o = 1; o < 5; ++o) if ((uint32_t)o <= order) difference(x, o);
+            uint32_t len = tid == 0 ? 8 : 0;                        // the subframe header
+            uint32_t pj = pj0, rem = rem0;
+#pragma unroll
+            for (int j = 0; j < SPT; ++j) {
+                const uint32_t i = i0 + j;
+                val[c][j] = i < order ? raw[j] : x[4 + j];
+                if (i < n) {
+                    if (i < order) len += bits;
+                    else {
+                        if (i == order) len += 6;                   // 01 pppp
+                        if (i == order || (rem == 0 && (pj & ((1u << sh) - 1)) == 0)) len += 5;     // a partition's first residual: kkkkk
+                        const uint32_t k = s_ksel[sg][pj >> sh];
+                        len += (zigzag(val[c][j]) >> k) + 1 + k;
+                    }
+                }
+                if (++rem == fsz) { rem = 0; ++pj; }
+            }
+            mine[c] = len;
+            uint32_t y = len;
+            for (int o = 1; o < 64; o <<= 1) { const uint32_t z = __shfl_up(y, o, 64); if (lane >= (uint32_t)o) y += z; }
+            incl[c] = y;
+        }
+        if (lane == 63) {
+#pragma unroll
+            for (int c = 0; c < CH; ++c) s_wtot[wave][c] = incl[c];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            uint32_t all = s_wtot[lane & (NW - 1)][c], before = (lane & (NW - 1)) < wave ? all : 0;      // 16 lanes hold the 16 waves' totals
+            for (int o = NW / 2; o >= 1; o >>= 1) { all += __shfl_xor(all, o, 64); before += __shfl_xor(before, o, 64); }
+            start[c] = total_bits + before + incl[c] - mine[c];
+            total_bits += all;
+        }
+    }
+    const uint32_t data_bytes = (total_bits + 7) >> 3, frame_bytes = data_bytes + 2;
+    const uint32_t out_vecs = (frame_bytes + 15) >> 4;
+    // (an effort-1 frame is no longer than the effort-0 frame, so the bound of include/dsd2dxd_amd.h holds; as there, a frame that broke it would be dropped whole)
+    if (frame_bytes > a.slot_bytes) { if (tid == 0) fd.sizes[b] = 0; return; }
+
+    // the image: zero fill, then the bits that are one
+    uint32_t* img = reinterpret_cast<uint32_t*>(smem);
+    for (uint32_t w = tid; w < out_vecs * 4 + 4; w += NT) img[w] = 0;             // (every thread has passed the barrier behind its PCM reads)
+    __syncthreads();
+    if (tid < hdr_bytes && s_hdr[tid]) put_bits(img, tid * 8, s_hdr[tid], 8);
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        const uint32_t sg = subframe_signal(c), order = s_sel[sg][0], porder = s_sel[sg][1], sh = pmax - porder;
+        const uint32_t bits = CH == 2 && sg == 3 ? depth + 1 : depth;
+        uint32_t p = start[c];
+        if (tid == 0) { put_bits(img, p, n > 2 ? (8u | order) << 1 : 0x02u, 8); p += 8; }   // 0 001ooo 0: fixed order ooo; 0 000001 0: verbatim
+        uint32_t pj = pj0, rem = rem0;
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) {
+            const uint32_t i = i0 + j;
+            if (i < n) {
+                if (i < order) {
+                    const uint32_t raw = (uint32_t)val[c][j] & (0xFFFFFFFFu >> (32 - bits));
+                    if (raw) put_bits(img, p, raw, bits);
+                    p += bits;
+                } else {
+                    const uint32_t k = s_ksel[sg][pj >> sh];
+                    if (i == order) { put_bits(img, p, (1u << 4) | porder, 6); p += 6; }          // 01: 5-bit Rice parameters, pppp
+                    if (i == order || (rem == 0 && (pj & ((1u << sh) - 1)) == 0)) { if (k) put_bits(img, p, k, 5); p += 5; }
+                    const uint32_t v = zigzag(val[c][j]), q = v >> k;
+                    put_bits(img, p + q, (1u << k) | (v & ((1u << k) - 1)), k + 1);
+                    p += q + 1 + k;
+                }
+            }
+            if (++rem == fsz) { rem = 0; ++pj; }
+        }
+    }
+    __syncthreads();
+
+    frame_crc16(img, data_bytes, s_crc_tab, s_crc, tid);
+    store_frame(img, fd.slots + (size_t)b * a.slot_bytes, out_vecs, tid);
     if (tid == 0) fd.sizes[b] = frame_bytes;
 }
 
@@ -319,14 +712,16 @@ __global__ __launch_bounds__(PT) void flac_pack_kernel(const FlacArgs a) {
     }
 }
 
-size_t encode_lds_bytes(uint32_t ch, uint32_t depth) { return std::max<size_t>(slot_bytes(ch, depth) + 32, (size_t)BS * ch * sample_bytes(depth)); }
+// the frame image over the block's PCM: packed as it comes at effort 0, planar 32-bit samples at effort 1
+size_t encode_lds_bytes(uint32_t ch, uint32_t depth, int effort) { return std::max<size_t>(slot_bytes(ch, depth) + 32, (size_t)BS * ch * (effort ? 4 : sample_bytes(depth))); }
 
-template <int CH>
+template <int CH, int EFFORT>
 hipError_t launch_encode(const FlacArgs& a, uint32_t max_blocks, uint32_t nf, hipStream_t s) {
+    const auto kernel = EFFORT == 0 ? &flac_encode_kernel<CH> : &flac_search_kernel<CH>;
     // hipFuncSetAttribute acts on the current device: remembered per device, under a lock
     static std::mutex mu;
     static size_t allowed[64] = {};
-    const size_t lds = encode_lds_bytes(CH, a.depth);
+    const size_t lds = encode_lds_bytes(CH, a.depth, EFFORT);
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -334,25 +729,26 @@ hipError_t launch_encode(const FlacArgs& a, uint32_t max_blocks, uint32_t nf, hi
     {
         std::lock_guard<std::mutex> g(mu);
         if (allowed[dev] < lds) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flac_encode_kernel<CH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return e;
             allowed[dev] = lds;
         }
     }
-    hipLaunchKernelGGL(flac_encode_kernel<CH>, dim3(max_blocks, nf), dim3(NT), lds, s, a);
+    hipLaunchKernelGGL(kernel, dim3(max_blocks, nf), dim3(NT), lds, s, a);
     return hipGetLastError();
 }
 
+template <int EFFORT>
 hipError_t launch_encode_ch(uint32_t ch, const FlacArgs& a, uint32_t max_blocks, uint32_t nf, hipStream_t s) {
     switch (ch) {
-        case 1: return launch_encode<1>(a, max_blocks, nf, s);
-        case 2: return launch_encode<2>(a, max_blocks, nf, s);
-        case 3: return launch_encode<3>(a, max_blocks, nf, s);
-        case 4: return launch_encode<4>(a, max_blocks, nf, s);
-        case 5: return launch_encode<5>(a, max_blocks, nf, s);
-        case 6: return launch_encode<6>(a, max_blocks, nf, s);
-        case 7: return launch_encode<7>(a, max_blocks, nf, s);
-        default: return launch_encode<8>(a, max_blocks, nf, s);
+        case 1: return launch_encode<1, EFFORT>(a, max_blocks, nf, s);
+        case 2: return launch_encode<2, EFFORT>(a, max_blocks, nf, s);
+        case 3: return launch_encode<3, EFFORT>(a, max_blocks, nf, s);
+        case 4: return launch_encode<4, EFFORT>(a, max_blocks, nf, s);
+        case 5: return launch_encode<5, EFFORT>(a, max_blocks, nf, s);
+        case 6: return launch_encode<6, EFFORT>(a, max_blocks, nf, s);
+        case 7: return launch_encode<7, EFFORT>(a, max_blocks, nf, s);
+        default: return launch_encode<8, EFFORT>(a, max_blocks, nf, s);
     }
 }
 
@@ -364,7 +760,13 @@ extern "C" {
 
 int d2d_flac_encode_device(uint32_t channels, uint32_t bit_depth, d2d_flac_io* io, uint32_t n_files,
                            void* workspace, size_t workspace_bytes, void* hip_stream) {
+    return d2d_flac_encode_device_effort(channels, bit_depth, D2D_FLAC_EFFORT_FIXED2, io, n_files, workspace, workspace_bytes, hip_stream);
+}
+
+int d2d_flac_encode_device_effort(uint32_t channels, uint32_t bit_depth, uint32_t effort, d2d_flac_io* io, uint32_t n_files,
+                                  void* workspace, size_t workspace_bytes, void* hip_stream) {
     // every check comes before the first device call
+    if (!effort_ok(effort)) return fail(D2D_ERR_PARAM, "unknown FLAC effort: 0 (fixed order 2) or 1 (search)");
     if (!depth_ok(bit_depth)) return fail(D2D_ERR_PARAM, "FLAC holds 16, 20 or 24-bit integers (Invalid bit depth)");
     if (channels == 0 || channels > 8) return fail(D2D_ERR_PARAM, "FLAC holds 1 to 8 channels (Invalid channel count)");
     if (!io || n_files == 0) return fail(D2D_ERR_PARAM, "no files");
@@ -403,8 +805,8 @@ int d2d_flac_encode_device(uint32_t channels, uint32_t bit_depth, d2d_flac_io* i
             max_blocks = std::max(max_blocks, d.blocks);
         }
         if (max_blocks) {
-            hipError_t e = launch_encode_ch(channels, a, max_blocks, nf, s);
-            if (e != hipSuccess) return hip_fail(e, "flac_encode_kernel");
+            hipError_t e = effort == D2D_FLAC_EFFORT_SEARCH ? launch_encode_ch<1>(channels, a, max_blocks, nf, s) : launch_encode_ch<0>(channels, a, max_blocks, nf, s);
+            if (e != hipSuccess) return hip_fail(e, effort == D2D_FLAC_EFFORT_SEARCH ? "flac_search_kernel" : "flac_encode_kernel");
         }
         hipLaunchKernelGGL(flac_pack_kernel, dim3(std::max(1u, (max_blocks + PB - 1) / PB), nf), dim3(PT), 0, s, a);
         hipError_t e = hipGetLastError();
@@ -444,6 +846,13 @@ struct Stream { hipStream_t s = nullptr; };
 extern "C" int d2d_convert_stream_flac(d2d_engine* e, uint32_t bit_depth, d2d_read_fn read, void* ru, d2d_write_fn write, void* wu,
                                        const volatile int* cancel, d2d_progress_fn progress, void* pu,
                                        uint64_t total, size_t chunk, d2d_flac_stream_stats* stats) {
+    return d2d_convert_stream_flac_effort(e, bit_depth, D2D_FLAC_EFFORT_FIXED2, read, ru, write, wu, cancel, progress, pu, total, chunk, stats);
+}
+
+extern "C" int d2d_convert_stream_flac_effort(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
+                                              d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
+                                              uint64_t total, size_t chunk, d2d_flac_stream_stats* stats) {
+    if (!effort_ok(effort)) return fail(D2D_ERR_PARAM, "unknown FLAC effort: 0 (fixed order 2) or 1 (search)");
     if (!e) return fail(D2D_ERR_PARAM, "null engine");
     if (!read) return fail(D2D_ERR_PARAM, "null read callback");
     if (!stats) return fail(D2D_ERR_PARAM, "null stats");
@@ -494,7 +903,7 @@ extern "C" int d2d_convert_stream_flac(d2d_engine* e, uint32_t bit_depth, d2d_re
         fio.pcm = d_pcm.p; fio.frames = carry + nf; fio.first_block = (uint32_t)stats->blocks; fio.final = next == 0;
         fio.out = d_out.p; fio.out_capacity_bytes = d_out.bytes; fio.result = res;
         if (stats->blocks > 0xFFFFFFFFull) return fail(D2D_ERR_PARAM, "frame numbers are 31 bits");
-        const int rc = d2d_flac_encode_device(ch, bit_depth, &fio, 1, d_ws.p, d_ws.bytes, st.s);
+        const int rc = d2d_flac_encode_device_effort(ch, bit_depth, effort, &fio, 1, d_ws.p, d_ws.bytes, st.s);
         if (rc != D2D_OK) return rc;
         FLAC_HIP(hipStreamSynchronize(st.s), "hipStreamSynchronize");
         const d2d_flac_result r = *res;

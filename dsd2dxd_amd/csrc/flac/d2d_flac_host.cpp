@@ -35,6 +35,12 @@ size_t d2d_flac_workspace_bytes(uint32_t channels, uint32_t bit_depth, size_t fr
 
 int d2d_flac_encode_host(uint32_t channels, uint32_t bit_depth, const void* pcm, size_t frames, uint32_t first_block, int final,
                          void* out, size_t out_capacity_bytes, d2d_flac_result* result, size_t* frames_consumed) {
+    return d2d_flac_encode_host_effort(channels, bit_depth, D2D_FLAC_EFFORT_FIXED2, pcm, frames, first_block, final, out, out_capacity_bytes, result, frames_consumed);
+}
+
+int d2d_flac_encode_host_effort(uint32_t channels, uint32_t bit_depth, uint32_t effort, const void* pcm, size_t frames, uint32_t first_block,
+                                int final, void* out, size_t out_capacity_bytes, d2d_flac_result* result, size_t* frames_consumed) {
+    if (!effort_ok(effort)) return fail(D2D_ERR_PARAM, "unknown FLAC effort: 0 (fixed order 2) or 1 (search)");
     if (!depth_ok(bit_depth)) return fail(D2D_ERR_PARAM, "FLAC holds 16, 20 or 24-bit integers (Invalid bit depth)");
     if (channels == 0 || channels > 8) return fail(D2D_ERR_PARAM, "FLAC holds 1 to 8 channels (Invalid channel count)");
     if (!result) return fail(D2D_ERR_PARAM, "null result record");
@@ -56,7 +62,7 @@ int d2d_flac_encode_host(uint32_t channels, uint32_t bit_depth, const void* pcm,
             if (bit_depth == 20) v >>= 4;
             buf[i] = v;
         }
-        enc.encode(buf.data(), n, channels, bit_depth, first_block + (uint32_t)b, BS);
+        enc.encode(buf.data(), n, channels, bit_depth, first_block + (uint32_t)b, BS, effort);
         const uint32_t fs = (uint32_t)enc.out.size();
         memcpy(o + r.bytes_out, enc.out.data(), fs);
         r.bytes_out += fs;

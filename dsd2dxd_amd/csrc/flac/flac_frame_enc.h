@@ -9,9 +9,30 @@
 
 namespace d2dhost {
 
-// FLAC with fixed-order-2 prediction and one Rice partition per subframe (valid, modest compression;
-// the reference uses the flac-codec crate, Cargo.lock:299-307).  Integer depths only.  Frames are
-// independent of each other, so a batch of them is encoded on as many threads and written in order.
+// Integer depths only.  Frames are independent of each other, so a batch of them is encoded on as many threads and written in
+// order.  (The reference uses the flac-codec crate, Cargo.lock:299-307.)  Two efforts, both with fixed block size:
+//
+// EFFORT 0: fixed-order-2 prediction, one Rice partition per subframe, independent channels (valid, modest compression).
+//
+// EFFORT 1: searched fixed predictors, partitioned Rice and stereo modes.  Every cost is an exact bit count and every tie has a
+// fixed winner, so the host, the GPU and the Python restatement of the tests agree on every byte.  For a frame of n samples per
+// channel, ch channels, depth d (header, CRCs and padding as at effort 0):
+//   1. n < 16: the frame is the effort-0 frame.
+//   2. Candidate signals: each channel at b = d bits; for ch == 2 also M = (L + R) >> 1 (arithmetic, floor) at b = d and
+//      S = L - R at b = d + 1.
+//   3. Residuals r_0 = x, r_o(i) = r_{o-1}(i) - r_{o-1}(i-1) for i >= o, o = 0 .. 4.  |x| <= 2^24 gives |r_4| <= 2^28: residuals
+//      and u = zigzag(r) fit 32 bits, and no verbatim or escape-coded partition exists.
+//   4. cost(o, p) = 8 + o b + 2 + 4 + sum over the 2^p partitions of (5 + sum of ((u >> k) + 1 + k)); partition j holds the
+//      residuals with i in [j (n >> p), (j + 1)(n >> p)) and i >= o; its k is effort 0's rule on that partition: the smallest k
+//      with 2^k >= floor(sum |r| / count), at most 30, written with the 5-bit method `01`.
+//   5. Predictor order: the o in 0 .. 4 with the least cost(o, 0); the smallest o wins a tie.
+//   6. Partition order: for that o, the p in 0 .. pmax with the least cost(o, p); the smallest p wins a tie.  pmax is the largest
+//      p <= 6 with n % 2^p == 0 and (n >> p) >= 16.
+//   7. ch == 2: the least of L + R (nibble 0001: L, R), L + S (1000: L, S), S + R (1001: S, R), M + S (1010: M, S); ties go to the
+//      earlier one.  The sample-size code stays d's; the side subframe has d + 1-bit warm-up samples.  Other counts: independent.
+//   8. Subframe: 0, 001ooo, 0; o warm-up samples of b bits; 01, pppp; per partition kkkkk and its codes.
+// (o = 2, p = 0) and the independent assignment are always candidates and the costs are exact, so an effort-1 frame is never
+// longer than the effort-0 frame of the same samples: THE BOUND of include/dsd2dxd_amd.h holds for both.
 struct FlacFrameEnc {
     std::vector<uint8_t> out;
     std::vector<int32_t> res;
@@ -38,18 +59,131 @@ struct FlacFrameEnc {
         bits_put(((0xFF00 >> (n + 1)) & 0xFF) | (v >> (6 * n)), 8);
         for (int i = n - 1; i >= 0; --i) bits_put(0x80 | ((v >> (6 * i)) & 0x3F), 8);
     }
-    // one frame of `n` interleaved samples starting at `buf`
-    void encode(const int32_t* buf, uint32_t n, uint32_t ch, uint32_t depth, uint32_t frame_no, uint32_t BS) {
+    // the frame header with its CRC-8; `assignment` is the channel-assignment nibble
+    void begin_frame(uint32_t n, uint32_t assignment, uint32_t depth, uint32_t frame_no, uint32_t BS) {
         out.clear(); bitn = 0; bitacc = 0;
         bits_put(0xFFF8, 16);                                          // sync, fixed block size
         bits_put(n == BS ? 0xC : 0x7, 4);                              // 4096, or 16-bit (n-1) at the end of the header
         bits_put(0x0, 4);                                              // sample rate from STREAMINFO
-        bits_put(ch - 1, 4);                                           // independent channels
+        bits_put(assignment, 4);
         bits_put(depth == 16 ? 4 : depth == 20 ? 5 : 6, 3); bits_put(0, 1);
         put_utf8(frame_no);
         if (n != BS) bits_put(n - 1, 16);
         bits_flush();
         out.push_back(crc8(out.data(), out.size()));
+    }
+    // zero bits to the next byte, then the CRC-16 of the frame
+    void end_frame() {
+        bits_flush();
+        uint16_t c16 = crc16(out.data(), out.size());
+        out.push_back((uint8_t)(c16 >> 8)); out.push_back((uint8_t)c16);
+    }
+
+    // ---- effort 1: the search (see the head of this file) --------------------------------------------------------------------
+    // the smallest k with 2^k >= floor(sum / count), at most 30: effort 0's rule, here per partition
+    static uint32_t rice_k(uint64_t sum, uint32_t count) {
+        const uint64_t mean = sum / (count ? count : 1);
+        uint32_t k = 0;
+        while (k < 30 && (1ull << k) < mean) ++k;
+        return k;
+    }
+    static uint32_t zigzag(int32_t r) { return r >= 0 ? (uint32_t)r << 1 : (((uint32_t)(-(int64_t)r)) << 1) - 1; }
+    // the largest p <= 6 with n % 2^p == 0 and (n >> p) >= 16
+    static uint32_t search_pmax(uint32_t n) {
+        uint32_t p = 0;
+        while (p < 6 && n % (2u << p) == 0 && (n >> (p + 1)) >= 16) ++p;
+        return p;
+    }
+    // cost(o, p) of a signal of b bits whose order-o residuals are r[o .. n); ks (may be null) receives the 2^p parameters
+    static uint32_t search_cost(const int32_t* r, uint32_t n, uint32_t o, uint32_t p, uint32_t b, uint8_t* ks) {
+        uint32_t cost = 8 + o * b + 2 + 4;
+        const uint32_t psz = n >> p;
+        for (uint32_t j = 0; j < (1u << p); ++j) {
+            const uint32_t lo = j * psz > o ? j * psz : o, hi = (j + 1) * psz;
+            uint64_t sum = 0;
+            for (uint32_t i = lo; i < hi; ++i) sum += (uint64_t)(r[i] < 0 ? -(int64_t)r[i] : (int64_t)r[i]);
+            const uint32_t k = rice_k(sum, hi - lo);
+            cost += 5;
+            for (uint32_t i = lo; i < hi; ++i) cost += (zigzag(r[i]) >> k) + 1 + k;
+            if (ks) ks[j] = (uint8_t)k;
+        }
+        return cost;
+    }
+    struct Plan {                               // what the search chose for one candidate signal
+        uint32_t order = 0, porder = 0, bits = 0, cost = 0;
+        uint8_t k[64];
+        std::vector<int32_t> x, r;              // the signal, and its residuals at `order` (valid from index `order`)
+    };
+    Plan plans[4];
+    std::vector<int32_t> rs[5];
+    void search(Plan& pl, uint32_t n, uint32_t b) {
+        pl.bits = b;
+        rs[0] = pl.x;
+        for (uint32_t o = 1; o <= 4; ++o) {
+            rs[o].resize(n);
+            for (uint32_t i = o; i < n; ++i) rs[o][i] = rs[o - 1][i] - rs[o - 1][i - 1];
+        }
+        uint32_t best = 0, cost = 0;
+        for (uint32_t o = 0; o <= 4; ++o) {                            // the smallest order wins a tie
+            const uint32_t c = search_cost(rs[o].data(), n, o, 0, b, nullptr);
+            if (o == 0 || c < cost) { best = o; cost = c; }
+        }
+        pl.order = best; pl.r = rs[best]; pl.porder = 0;
+        const uint32_t pmax = search_pmax(n);
+        for (uint32_t p = 1; p <= pmax; ++p) {                         // the smallest partition order wins a tie
+            const uint32_t c = search_cost(pl.r.data(), n, best, p, b, nullptr);
+            if (c < cost) { pl.porder = p; cost = c; }
+        }
+        pl.cost = search_cost(pl.r.data(), n, best, pl.porder, b, pl.k);
+    }
+    void put_subframe(const Plan& pl, uint32_t n) {
+        bits_put(0, 1); bits_put(8 + pl.order, 6); bits_put(0, 1);
+        for (uint32_t i = 0; i < pl.order; ++i) bits_put((uint64_t)(int64_t)pl.x[i] & ((1ull << pl.bits) - 1), (int)pl.bits);
+        bits_put(1, 2); bits_put(pl.porder, 4);
+        const uint32_t psz = n >> pl.porder;
+        for (uint32_t j = 0; j < (1u << pl.porder); ++j) {
+            const uint32_t k = pl.k[j];
+            bits_put(k, 5);
+            for (uint32_t i = j * psz > pl.order ? j * psz : pl.order; i < (j + 1) * psz; ++i) {
+                const uint32_t u = zigzag(pl.r[i]);
+                uint32_t q = u >> k;
+                while (q >= 32) { bits_put(0, 32); q -= 32; }
+                bits_put(1, (int)q + 1);
+                if (k) bits_put(u & ((1u << k) - 1), (int)k);
+            }
+        }
+    }
+    void encode_search(const int32_t* buf, uint32_t n, uint32_t ch, uint32_t depth, uint32_t frame_no, uint32_t BS) {
+        uint32_t first = 0, second = 1, nibble = ch - 1;
+        if (ch == 2) {
+            for (Plan& pl : plans) pl.x.resize(n);
+            for (uint32_t i = 0; i < n; ++i) {
+                const int32_t l = buf[(size_t)i * 2], r = buf[(size_t)i * 2 + 1];
+                plans[0].x[i] = l; plans[1].x[i] = r; plans[2].x[i] = (l + r) >> 1; plans[3].x[i] = l - r;
+            }
+            for (uint32_t s = 0; s < 4; ++s) search(plans[s], n, s == 3 ? depth + 1 : depth);
+            const uint32_t L = plans[0].cost, R = plans[1].cost, M = plans[2].cost, S = plans[3].cost;
+            uint32_t total = L + R;                                     // ties go to the earlier mode
+            if (L + S < total) { total = L + S; first = 0; second = 3; nibble = 0x8; }
+            if (S + R < total) { total = S + R; first = 3; second = 1; nibble = 0x9; }
+            if (M + S < total) { total = M + S; first = 2; second = 3; nibble = 0xA; }
+        }
+        begin_frame(n, nibble, depth, frame_no, BS);
+        if (ch == 2) { put_subframe(plans[first], n); put_subframe(plans[second], n); }
+        else for (uint32_t c = 0; c < ch; ++c) {
+            Plan& pl = plans[0];
+            pl.x.resize(n);
+            for (uint32_t i = 0; i < n; ++i) pl.x[i] = buf[(size_t)i * ch + c];
+            search(pl, n, depth);
+            put_subframe(pl, n);
+        }
+        end_frame();
+    }
+
+    // one frame of `n` interleaved samples starting at `buf`; effort 0 = fixed order 2, 1 = the search
+    void encode(const int32_t* buf, uint32_t n, uint32_t ch, uint32_t depth, uint32_t frame_no, uint32_t BS, uint32_t effort = 0) {
+        if (effort != 0 && n >= 16) { encode_search(buf, n, ch, depth, frame_no, BS); return; }
+        begin_frame(n, ch - 1, depth, frame_no, BS);                   // independent channels
         res.resize(n);
         for (uint32_t c = 0; c < ch; ++c) {
             auto s = [&](uint32_t i) -> int64_t { return buf[(size_t)i * ch + c]; };
@@ -82,9 +216,7 @@ struct FlacFrameEnc {
                 if (k) bits_put(u & ((1u << k) - 1), (int)k);
             }
         }
-        bits_flush();
-        uint16_t c16 = crc16(out.data(), out.size());
-        out.push_back((uint8_t)(c16 >> 8)); out.push_back((uint8_t)c16);
+        end_frame();
     }
 };
 

@@ -202,6 +202,8 @@ struct FlacSink : PcmSink {
     std::vector<FlacFrameEnc> encs;
     bool io_failed = false;
     bool raw_frames = false;       // the frames came encoded (write_frames): no samples were seen, so there is no MD5
+    uint32_t effort = 0;           // flac_frame_enc.h: 0 = fixed order 2, 1 = the search
+    void set_flac_effort(uint32_t e) override { effort = e; }
     uint32_t depth() const { return bits == 20 ? 20 : bits; }
     std::string begin() {
         // metadata: STREAMINFO (filled in at close), then the source's tag as VORBIS_COMMENT and PICTURE
@@ -258,8 +260,8 @@ struct FlacSink : PcmSink {
             const size_t nb = std::min(encs.size(), jobs.size() - j0);
             std::vector<std::thread> th;
             for (size_t j = 1; j < nb; ++j)
-                th.emplace_back([&, j] { encs[j].encode(buf.data() + jobs[j0 + j].first, jobs[j0 + j].second, ch, depth(), frame_no + (uint32_t)j, BS); });
-            encs[0].encode(buf.data() + jobs[j0].first, jobs[j0].second, ch, depth(), frame_no, BS);
+                th.emplace_back([&, j] { encs[j].encode(buf.data() + jobs[j0 + j].first, jobs[j0 + j].second, ch, depth(), frame_no + (uint32_t)j, BS, effort); });
+            encs[0].encode(buf.data() + jobs[j0].first, jobs[j0].second, ch, depth(), frame_no, BS, effort);
             for (auto& t : th) t.join();
             for (size_t j = 0; j < nb; ++j) {
                 const std::vector<uint8_t>& o = encs[j].out;

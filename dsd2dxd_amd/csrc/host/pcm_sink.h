@@ -22,6 +22,8 @@ class PcmSink {
     // because the samples never reach the host.  Every other sink refuses.
     virtual std::string write_frames(const uint8_t*, size_t) { return "this sink takes PCM, not FLAC frames"; }
     virtual void set_frame_stats(uint64_t /*samples_per_channel*/, uint64_t /*blocks*/, uint32_t /*min_frame_bytes*/, uint32_t /*max_frame_bytes*/) {}
+    // The FLAC sink's encoder effort (D2D_FLAC_EFFORT_* of include/dsd2dxd_amd.h; 0 unless set), before the first write.  Other sinks ignore it.
+    virtual void set_flac_effort(uint32_t /*effort*/) {}
 };
 
 // bit_depth 16/20/24 (integer, 20 in a 24-bit container) or 32 (float).  `id3` = the source's ID3v2

@@ -43,6 +43,7 @@ struct Rdsd2Pcm::Impl {
     bool level_only = false;
     size_t chunk = 4u << 20;
     bool gpu_flac = false;
+    uint32_t flac_effort = D2D_FLAC_EFFORT_FIXED2;
     std::string out_path;
     double dsp_s = 0.0, audio_s = 0.0;
     std::string tag_warning;
@@ -145,6 +146,10 @@ void Rdsd2Pcm::set_seed(uint64_t seed) { p_->prm.seed = seed; }
 void Rdsd2Pcm::set_tap_bits(uint32_t bits) { p_->prm.tap_bits = bits; }
 void Rdsd2Pcm::set_chunk_bytes(size_t b) { if (b) p_->chunk = b; }
 void Rdsd2Pcm::set_gpu_flac(bool on) { p_->gpu_flac = on; }
+void Rdsd2Pcm::set_flac_effort(int effort) {
+    if (effort != D2D_FLAC_EFFORT_FIXED2 && effort != D2D_FLAC_EFFORT_SEARCH) throw std::runtime_error("Invalid FLAC effort; must be 0 or 1");
+    p_->flac_effort = (uint32_t)effort;
+}
 
 namespace {
 struct RunCtx {
@@ -220,6 +225,7 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
         }
         err = open_sink((d2dhost::OutputType)(int)im.output, im.out_path, im.prm.channels, im.prm.output_rate, im.prm.bit_depth, &sink, &tag);
         if (!err.empty()) throw std::runtime_error(err);
+        sink->set_flac_effort(im.flac_effort);
     }
     std::unique_ptr<PcmSink> sink_guard(sink);
     d2d_engine* e = nullptr;
@@ -235,8 +241,8 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
         const size_t B = im.prm.fmt == D2D_FMT_PLANAR ? im.prm.block_size : 1;
         if (B > 1) chunk = std::max(B, chunk / B * B);                  // whole planar blocks per read, as d2d_convert_stream cuts them
         d2d_flac_stream_stats stats{};
-        rc = d2d_convert_stream_flac(e, im.prm.bit_depth, read_cb, &ctx, write_frames_cb, &ctx, &ctx.cancel_int,
-                                     progress_cb, &ctx, info.bytes_per_channel, chunk, &stats);
+        rc = d2d_convert_stream_flac_effort(e, im.prm.bit_depth, im.flac_effort, read_cb, &ctx, write_frames_cb, &ctx, &ctx.cancel_int,
+                                            progress_cb, &ctx, info.bytes_per_channel, chunk, &stats);
         if (rc) msg = d2d_flac_error();
         else sink->set_frame_stats(stats.samples_per_channel, stats.blocks, stats.min_frame_bytes, stats.max_frame_bytes);
     } else {

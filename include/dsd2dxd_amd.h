@@ -20,9 +20,10 @@
 extern "C" {
 #endif
 
-#define D2D_ABI_VERSION 7   /* 3: the table blob header names the table variant; 4: d2d_params.tap_bits; 5: d2d_params.debug_flags (was reserved0);
+#define D2D_ABI_VERSION 8   /* 3: the table blob header names the table variant; 4: d2d_params.tap_bits; 5: d2d_params.debug_flags (was reserved0);
                              * 6: d2d_seek / d2d_tell / d2d_prime* and the two size queries (d2d_params unchanged);
-                             * 7: the d2d_flac_* entry points and d2d_convert_stream_flac (d2d_params unchanged) */
+                             * 7: the d2d_flac_* entry points and d2d_convert_stream_flac (d2d_params unchanged);
+                             * 8: the FLAC efforts: d2d_flac_encode_device_effort / _host_effort, d2d_convert_stream_flac_effort (d2d_params unchanged) */
 
 /* status codes */
 enum {
@@ -259,8 +260,19 @@ int d2d_convert_stream(d2d_engine* e, d2d_read_fn read, void* read_user,
  *     subframe_bits(n)  <= 19 + 2 depth + 30 max(n - 2, 0)          (a verbatim subframe, n <= 2, is 8 + n depth)
  *     frame_bytes(n)    <= D2D_FLAC_FRAME_BOUND(n) = 15 + ceil(channels * (19 + 2 depth + 30 max(n - 2, 0)) / 8)
  *     d2d_flac_bound_bytes = floor(frames / 4096) * D2D_FLAC_FRAME_BOUND(4096) + (final and frames % 4096 ? D2D_FLAC_FRAME_BOUND(frames % 4096) : 0)
- * Host arithmetic, no device; 0 for parameters the encoders refuse. */
+ * Host arithmetic, no device; 0 for parameters the encoders refuse.
+ *
+ * EFFORTS (ABI 8).  Everything above describes effort 0, which every entry point without `effort` in its name means.  Effort 1 is
+ * the search that csrc/flac/flac_frame_enc.h defines: per subframe the fixed predictor order 0 .. 4 with the least exact cost at one
+ * partition (the smallest order wins a tie), then the Rice partition order 0 .. pmax with the least exact cost (the smallest wins a
+ * tie; pmax the largest p <= 6 with n % 2^p == 0 and (n >> p) >= 16), each partition's k by the rule above; for two channels the
+ * least of independent, left/side, side/right and mid/side (ties in that order), the side channel one bit wider.  Frames of fewer
+ * than 16 samples are the effort-0 frames.  THE BOUND DOES NOT CHANGE: (order 2, one partition) and the independent assignment are
+ * always candidates and the costs are exact bit counts, so an effort-1 frame is never longer than the effort-0 frame of the same
+ * samples; the argument for k (under 30 bits per residual) holds per partition, and |S| <= 2^24 gives |r_4| <= 2^28, so no escape
+ * exists here either.  D2D_FLAC_FRAME_BOUND, d2d_flac_bound_bytes, d2d_flac_workspace_bytes and the slots serve both efforts. */
 #define D2D_FLAC_BLOCK 4096u
+enum { D2D_FLAC_EFFORT_FIXED2 = 0, D2D_FLAC_EFFORT_SEARCH = 1 };
 size_t d2d_flac_bound_bytes(uint32_t channels, uint32_t bit_depth, size_t frames, int final);
 /* Scratch one d2d_flac_encode_device call needs for one such file: a 4-byte size per block, rounded up to 16 bytes, and one slot of
  * D2D_FLAC_FRAME_BOUND(4096) bytes, rounded up to 16, per block.  A call over several files needs the sum. */
@@ -301,12 +313,18 @@ typedef struct d2d_flac_io {
  * nothing, `blocks` and `frames_consumed` included. */
 int d2d_flac_encode_device(uint32_t channels, uint32_t bit_depth, d2d_flac_io* io, uint32_t n_files,
                            void* workspace, size_t workspace_bytes, void* hip_stream);
+/* The same call at a chosen effort (D2D_FLAC_EFFORT_*; d2d_flac_encode_device is effort 0).  An unknown effort -> D2D_ERR_PARAM,
+ * checked with the rest before any device call.  Sizes, workspace and what a call may touch are those of effort 0. */
+int d2d_flac_encode_device_effort(uint32_t channels, uint32_t bit_depth, uint32_t effort, d2d_flac_io* io, uint32_t n_files,
+                                  void* workspace, size_t workspace_bytes, void* hip_stream);
 const char* d2d_flac_error(void);
 
 /* The same frames from HOST memory with the sink's own encoder, no device: the reference the GPU tests compare against.  `pcm`
  * needs no alignment.  Same checks and codes as the device entry (cap below the bound -> D2D_ERR_CAPACITY, nothing written). */
 int d2d_flac_encode_host(uint32_t channels, uint32_t bit_depth, const void* pcm, size_t frames, uint32_t first_block, int final,
                          void* out, size_t out_capacity_bytes, d2d_flac_result* result, size_t* frames_consumed);
+int d2d_flac_encode_host_effort(uint32_t channels, uint32_t bit_depth, uint32_t effort, const void* pcm, size_t frames, uint32_t first_block,
+                                int final, void* out, size_t out_capacity_bytes, d2d_flac_result* result, size_t* frames_consumed);
 
 /* d2d_convert_stream's twin: `write` receives FLAC frame bytes -- whole frames, in order -- instead of PCM, and `stats` what
  * STREAMINFO needs.  Built on the public calls: each chunk is uploaded, converted by d2d_translate_batch_device into device PCM
@@ -326,6 +344,10 @@ int d2d_convert_stream_flac(d2d_engine* e, uint32_t bit_depth, d2d_read_fn read,
                             d2d_write_fn write, void* write_user,
                             const volatile int* cancel, d2d_progress_fn progress, void* progress_user,
                             uint64_t total_bytes_per_channel, size_t chunk_bytes_per_channel, d2d_flac_stream_stats* stats);
+int d2d_convert_stream_flac_effort(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* read_user,
+                                   d2d_write_fn write, void* write_user,
+                                   const volatile int* cancel, d2d_progress_fn progress, void* progress_user,
+                                   uint64_t total_bytes_per_channel, size_t chunk_bytes_per_channel, d2d_flac_stream_stats* stats);
 
 /* ---- shared tables (multi-GPU) ------------------------------------------------------------ */
 

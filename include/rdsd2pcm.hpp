@@ -74,6 +74,10 @@ class Rdsd2Pcm {
     // encoder writes, except STREAMINFO's MD5 field, which is 16 zero bytes -- FLAC's "not computed" -- because the samples never
     // reach the host.  Tags and pictures are written as before.  Not a reference option; the C mirror (rdsd2pcm_c.h) does not have it.
     void set_gpu_flac(bool on);
+    // FLAC output only; 0 by default.  The encoder effort, D2D_FLAC_EFFORT_* of include/dsd2dxd_amd.h: 0 = fixed order 2, one Rice
+    // partition, independent channels; 1 = searched fixed predictors, partitioned Rice and stereo modes.  It applies to the host sink
+    // and to the set_gpu_flac path alike, which write the same frames at either effort.  Any other value throws.
+    void set_flac_effort(int effort);
 
     struct Impl;                              // opaque state (public only so the .cpp's helpers can name it)
 

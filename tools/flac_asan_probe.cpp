@@ -1,8 +1,11 @@
-// flac_asan_probe.cpp -- the host FLAC encoder (dsd2dxd_amd/csrc/flac/d2d_flac_host.cpp: d2d_flac_encode_host, i.e. the sink's
-// FlacFrameEnc) on the adversarial signals of tests/flac_ref.py, in heap buffers of exactly the declared sizes, for a sanitizer build:
+// flac_asan_probe.cpp -- the host FLAC encoder (dsd2dxd_amd/csrc/flac/d2d_flac_host.cpp: d2d_flac_encode_host_effort, i.e. the sink's
+// FlacFrameEnc) at both efforts on the adversarial signals of tests/flac_ref.py, in heap buffers of exactly the declared sizes, for a
+// sanitizer build:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -o flac_asan_probe \
 //       tools/flac_asan_probe.cpp dsd2dxd_amd/csrc/flac/d2d_flac_host.cpp && ./flac_asan_probe
-// CPU only; prints one line per (channels, depth) with the bytes produced and an FNV-1a of them, and "ok" at the end.
+// CPU only; prints one line per (channels, depth) and effort with the bytes produced and an FNV-1a of them, and "ok" at the end.
+// Effort 1 also runs the lengths at which the search changes its partition range (16, 17, 32, 1024) and must never produce more bytes
+// than effort 0.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -12,7 +15,7 @@
 
 #include "../include/dsd2dxd_amd.h"
 
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
+static uint64_t rng_state = 0x9E3779B97F4A7C15ull, extra_state = 0xD1B54A32D192ED03ull;
 static uint32_t rng() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (uint32_t)(rng_state >> 16); }
 
 static int32_t sample(int sig, size_t i, uint32_t c, size_t frames, uint32_t depth) {
@@ -27,16 +30,20 @@ static int32_t sample(int sig, size_t i, uint32_t c, size_t frames, uint32_t dep
 }
 
 int main() {
-    const size_t lengths[] = {2 * 4096 + 1000, 4096, 4097, 4098, 4099, 4095, 1, 2, 3, 0};
+    const size_t lengths[] = {2 * 4096 + 1000, 4096, 4097, 4098, 4099, 4095, 1, 2, 3, 0, 16, 17, 32, 1024};
+    const size_t n_effort0 = 10;                                               // effort 0 runs the first ten, as it always has
     for (uint32_t ch : {1u, 2u, 3u, 8u})
         for (uint32_t depth : {16u, 20u, 24u}) {
-            size_t total = 0; uint64_t h = 1469598103934665603ull;
+            size_t total[2] = {0, 0}; uint64_t h[2] = {1469598103934665603ull, 1469598103934665603ull};
             for (int sig = 0; sig < 5; ++sig)
-                for (size_t frames : lengths)
+                for (size_t li = 0; li < sizeof(lengths) / sizeof(lengths[0]); ++li)
                     for (int final = 0; final < 2; ++final) {
+                        const size_t frames = lengths[li];
                         const uint32_t sb = depth == 16 ? 2 : 3;
                         // exact-size heap buffers: one byte read or written outside them is a sanitizer report
                         uint8_t* pcm = (uint8_t*)malloc(frames * ch * sb + (frames ? 0 : 1));
+                        const uint64_t main_state = rng_state;                 // the added lengths draw from a stream of their own
+                        if (li >= n_effort0) rng_state = extra_state;
                         for (size_t i = 0; i < frames; ++i)
                             for (uint32_t c = 0; c < ch; ++c) {
                                 int32_t v = sample(sig, i, c, frames, depth);
@@ -44,22 +51,31 @@ int main() {
                                 uint8_t* q = pcm + (i * ch + c) * sb;
                                 q[0] = (uint8_t)v; q[1] = (uint8_t)(v >> 8); if (sb == 3) q[2] = (uint8_t)(v >> 16);
                             }
+                        if (li >= n_effort0) { extra_state = rng_state; rng_state = main_state; }
                         const size_t cap = d2d_flac_bound_bytes(ch, depth, frames, final);
                         uint8_t* out = (uint8_t*)malloc(cap ? cap : 1);
-                        d2d_flac_result r; size_t used = 0;
                         const uint32_t first = sig == 3 ? 0x7FFFFFFEu - (uint32_t)(frames / 4096) : (uint32_t)(0x7F * sig);
-                        if (d2d_flac_encode_host(ch, depth, pcm, frames, first, final, out, cap, &r, &used) != D2D_OK) {
-                            fprintf(stderr, "refused: %s\n", d2d_flac_error()); return 1;
-                        }
-                        if (r.bytes_out > cap || used > frames) { fprintf(stderr, "bound broken\n"); return 1; }
-                        for (size_t i = 0; i < r.bytes_out; ++i) h = (h ^ out[i]) * 1099511628211ull;
-                        total += r.bytes_out;
-                        if (cap && d2d_flac_encode_host(ch, depth, pcm, frames, first, final, out, cap - 1, &r, &used) != D2D_ERR_CAPACITY) {
-                            fprintf(stderr, "a capacity one byte short was accepted\n"); return 1;
+                        uint64_t bytes0 = 0;
+                        for (uint32_t effort = 0; effort < 2; ++effort) {
+                            d2d_flac_result r; size_t used = 0;
+                            if (d2d_flac_encode_host_effort(ch, depth, effort, pcm, frames, first, final, out, cap, &r, &used) != D2D_OK) {
+                                fprintf(stderr, "refused: %s\n", d2d_flac_error()); return 1;
+                            }
+                            if (r.bytes_out > cap || used > frames) { fprintf(stderr, "bound broken\n"); return 1; }
+                            if (effort == 0) bytes0 = r.bytes_out;
+                            else if (r.bytes_out > bytes0) { fprintf(stderr, "effort 1 is longer than effort 0\n"); return 1; }
+                            if (effort == 1 || li < n_effort0) {
+                                for (size_t i = 0; i < r.bytes_out; ++i) h[effort] = (h[effort] ^ out[i]) * 1099511628211ull;
+                                total[effort] += r.bytes_out;
+                            }
+                            if (cap && d2d_flac_encode_host_effort(ch, depth, effort, pcm, frames, first, final, out, cap - 1, &r, &used) != D2D_ERR_CAPACITY) {
+                                fprintf(stderr, "a capacity one byte short was accepted\n"); return 1;
+                            }
                         }
                         free(pcm); free(out);
                     }
-            printf("channels %u depth %u: %zu bytes, fnv %016llx\n", ch, depth, total, (unsigned long long)h);
+            printf("channels %u depth %u: %zu bytes, fnv %016llx\n", ch, depth, total[0], (unsigned long long)h[0]);
+            printf("channels %u depth %u effort 1: %zu bytes, fnv %016llx\n", ch, depth, total[1], (unsigned long long)h[1]);
         }
     printf("ok\n");
     return 0;

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """What does encoding the bench batch's PCM to FLAC cost on the GPU, beside the 16 host threads the sink uses and beside the conversion?
-   tools/flac_probe.py [files] [seconds] [reps] [out.json]     (needs the GPU; defaults 64 files, 60 s each, 9 repetitions, bench_out/flac_probe.json)
+   tools/flac_probe.py [--effort N] [files] [seconds] [reps] [out.json]
+   (needs the GPU; defaults effort 0, 64 files, 60 s each, 9 repetitions, bench_out/flac_probe.json)
 
 The PCM is what d2d_translate_batch_device writes for the bench shape (distinct DSD64 stereo files -> 24-bit 88.2 kHz, TPDF): real
 converter output.  GPU figure: device events around ONE d2d_flac_encode_device call over the whole batch (both kernels), after warm-ups,
 median of the repetitions; the conversion step is timed the same way on the same batch.  Baseline: d2d_flac_encode_host -- the sink's
 own encoder -- on the same PCM in host memory, one block per task on 16 threads, as FlacSink::drain spreads them; wall clock, best of
-two passes.  File 0's device frames are compared with the host's."""
+two passes.  File 0's device frames are compared with the host's.  With --effort 1 (the search, D2D_FLAC_EFFORT_SEARCH) both sides run
+at that effort, and the effort-0 call is timed beside it on the same buffers for the size ratio."""
 import ctypes as C
 import json
 import os
@@ -22,10 +24,16 @@ import torch
 import dsd2dxd_amd as d
 from bench import make_files, DSD64
 
-n_files = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 60.0
-reps = int(sys.argv[3]) if len(sys.argv) > 3 else 9
-out_path = sys.argv[4] if len(sys.argv) > 4 else os.path.join(ROOT, "bench_out", "flac_probe.json")
+argv = sys.argv[1:]
+effort = 0
+if "--effort" in argv:
+    at = argv.index("--effort")
+    effort = int(argv[at + 1])
+    del argv[at:at + 2]
+n_files = int(argv[0]) if len(argv) > 0 else 64
+seconds = float(argv[1]) if len(argv) > 1 else 60.0
+reps = int(argv[2]) if len(argv) > 2 else 9
+out_path = argv[3] if len(argv) > 3 else os.path.join(ROOT, "bench_out", "flac_probe.json")
 blocks_in = max(1, int(round(seconds * DSD64 / 8 / 4096)))
 bpc = blocks_in * 4096
 CH, DEPTH, BS, THREADS = 2, 24, 4096, 16
@@ -74,7 +82,11 @@ fio = (d.FlacIO * n_files)()
 for f in range(n_files):
     fio[f].pcm, fio[f].frames, fio[f].first_block, fio[f].final = pcm[f].data_ptr(), frames, 0, 1
     fio[f].out, fio[f].out_capacity_bytes, fio[f].result = out[f].data_ptr(), cap, rec.data_ptr() + 16 * f
-enc = timed(lambda: d.flac_encode_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), stream))
+enc0, bytes0 = None, None
+if effort:                                                      # effort 0 on the same buffers first: its time and its bytes
+    enc0 = timed(lambda: d.flac_encode_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), stream))
+    bytes0 = int(rec.cpu().numpy().view(np.uint64).reshape(n_files, 2)[:, 0].sum())
+enc = timed(lambda: d.flac_encode_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), stream, effort=effort))
 r = rec.cpu().numpy().view(np.uint64).reshape(n_files, 2)
 flac_bytes = int(r[:, 0].sum())
 nblocks = int(fio[0].blocks)
@@ -90,7 +102,7 @@ def one_block(job):
     import threading
     st = tls.setdefault(threading.get_ident(), (np.empty(slot, dtype=np.uint8), d.FlacResult(), C.c_size_t()))
     n = min(BS, frames - b * BS)
-    rc = L.d2d_flac_encode_host(CH, DEPTH, host_pcm[f].ctypes.data + b * BS * fb, n, b, 1, st[0].ctypes.data, slot, C.byref(st[1]), C.byref(st[2]))
+    rc = L.d2d_flac_encode_host_effort(CH, DEPTH, effort, host_pcm[f].ctypes.data + b * BS * fb, n, b, 1, st[0].ctypes.data, slot, C.byref(st[1]), C.byref(st[2]))
     assert rc == 0
     return st[1].bytes_out
 
@@ -103,19 +115,24 @@ with ThreadPoolExecutor(THREADS) as pool:
         host_bytes = sum(pool.map(one_block, jobs, chunksize=64))
         host_s.append(time.perf_counter() - t0)
 same_total = host_bytes == flac_bytes
-want0, _, _ = d.flac_encode_host(CH, DEPTH, host_pcm[0], first_block=0, final=True)
+want0, _, _ = d.flac_encode_host(CH, DEPTH, host_pcm[0], first_block=0, final=True, effort=effort)
 same0 = out[0, :int(r[0, 0])].cpu().numpy().tobytes() == want0
 
 pcm_bytes = n_files * frames * fb
-res = dict(files=n_files, seconds_per_file=seconds, blocks_per_file=nblocks, frames_per_file=frames, pcm_bytes=pcm_bytes, flac_bytes=flac_bytes,
+res = dict(effort=effort, files=n_files, seconds_per_file=seconds, blocks_per_file=nblocks, frames_per_file=frames, pcm_bytes=pcm_bytes, flac_bytes=flac_bytes,
            ratio=flac_bytes / pcm_bytes, gpu_encode_ms=dict(median=enc[0], min=enc[1], max=enc[2]), conversion_ms=dict(median=conv[0], min=conv[1], max=conv[2]),
            host_16_threads_s=dict(best=min(host_s), passes=host_s), reps=reps, workspace_bytes=int(ws.numel()), crc="parallel (per-thread chunks, tree combine)",
            file0_equals_host=bool(same0), total_bytes_equal_host=bool(same_total), kernel=eng.kernel_name())
+if effort:
+    res.update(effort0_gpu_encode_ms=dict(median=enc0[0], min=enc0[1], max=enc0[2]), effort0_flac_bytes=bytes0, size_over_effort0=flac_bytes / bytes0)
 os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
 with open(out_path, "w") as fh:
     json.dump(res, fh, indent=1)
 samples = n_files * frames * CH
 print("batch: %d files x %d blocks (%d frames), PCM %.1f MB -> FLAC %.1f MB (ratio %.4f)" % (n_files, nblocks, frames, pcm_bytes / 1e6, flac_bytes / 1e6, flac_bytes / pcm_bytes))
+print("effort %d" % effort)
+if effort:
+    print("effort 0 on the same buffers: median %.3f ms (min %.3f, max %.3f), %.1f MB; effort %d / effort 0 bytes: %.4f" % (*enc0, bytes0 / 1e6, effort, flac_bytes / bytes0))
 print("GPU encode (one d2d_flac_encode_device call, both kernels): median %.3f ms (min %.3f, max %.3f) = %.2f Gsamples/s" % (*enc, samples / enc[0] / 1e6))
 print("conversion step (d2d_translate_batch_device, %s):  median %.3f ms (min %.3f, max %.3f)" % (eng.kernel_name(), *conv))
 print("host, %d threads, one block per task: best %.3f s of %s = %.3f Gsamples/s" % (THREADS, min(host_s), ["%.3f" % s for s in host_s], samples / min(host_s) / 1e9))
