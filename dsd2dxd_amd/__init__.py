@@ -7,4 +7,4 @@ drive it through; there is no Python or CPU implementation of the conversion beh
 from ._capi import (D2DError, Engine, FileIO, Params, lib, library_path, build_library,  # noqa: F401
                     KERNEL_AUTO, KERNEL_LUT, KERNEL_MFMA,
                     DBG_NO_MX, DBG_NO_GAINQ, DBG_NO_COOP, DBG_HOST_STAGED, DBG_NO_PIPE, DBG_MFMA_V1, DBG_NO_INTQ, DBG_NS_GENERAL, DBG_TAPS32_2PASS, dbg_waves,
-                    FLAC_BLOCK, FLAC_EFFORT_FIXED2, FLAC_EFFORT_SEARCH, FlacIO, FlacResult, FlacStreamStats, flac_bound_bytes, flac_workspace_bytes, flac_encode_host, flac_encode_device)
+                    FLAC_BLOCK, FLAC_EFFORT_FIXED2, FLAC_EFFORT_SEARCH, FLAC_EFFORT_LPC, FlacIO, FlacResult, FlacStreamStats, flac_bound_bytes, flac_workspace_bytes, flac_encode_host, flac_encode_device)

@@ -69,7 +69,7 @@ class FlacStreamStats(C.Structure):
 
 
 FLAC_BLOCK = 4096
-FLAC_EFFORT_FIXED2, FLAC_EFFORT_SEARCH = 0, 1      # D2D_FLAC_EFFORT_*
+FLAC_EFFORT_FIXED2, FLAC_EFFORT_SEARCH, FLAC_EFFORT_LPC = 0, 1, 12      # D2D_FLAC_EFFORT_*
 
 READ_FN = C.CFUNCTYPE(C.c_long, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t)
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)

@@ -1,6 +1,6 @@
 // d2d_flac.hip -- FLAC frames on the GPU (gfx950): the kernels behind d2d_flac_encode_device, and d2d_convert_stream_flac on top
-// of the public calls.  The bitstream is the one flac_frame_enc.h defines, at both efforts; tests/test_gpu_flac.py (effort 0) and
-// tests/test_gpu_flac_search.py (effort 1) compare them byte for byte.
+// of the public calls.  The bitstream is the one flac_frame_enc.h defines, at every effort; tests/test_gpu_flac.py (effort 0),
+// tests/test_gpu_flac_search.py (effort 1) and tests/test_gpu_flac_lpc.py (effort 12) compare them byte for byte.
 //
 //   flac_encode_kernel<CH>   effort 0: one workgroup of 1024 threads per (file, block); thread t owns samples 4t .. 4t+3 of every channel.
 //     1. the block's PCM comes into LDS with 16-byte loads (4096 * frame_bytes is a multiple of 16; a short block's tail by bytes)
@@ -13,7 +13,8 @@
 //     5. CRC-16 in parallel: init 0 makes the CRC linear and blind to leading zeros, so the frame is treated as 1024 equal chunks
 //        with zeros in front, every thread runs the table over its chunk, and a tree combines  crc(A|B) = crc(A) x^(8 len B) + crc(B)
 //     6. the image goes to the block's workspace slot (16-byte stores), its size to the size table
-//   flac_search_kernel<CH>   effort 1: the same workgroup and steps 3 to 6, with the search in front of them (described at the kernel)
+//   flac_search_kernel<CH, LPC>   efforts 1 and 12: the same workgroup and steps 3 to 6, with the search in front of them (described at
+//                            the kernel); LPC = true adds effort 12's linear predictors and changes nothing of the LPC = false code
 //   flac_pack_kernel        per file, 32 blocks per workgroup: sums the sizes in front of its blocks, copies the slots to `out`
 //                            contiguously; the first workgroup of a file writes the result record.
 // The two run one after the other on the caller's stream.  No workgroup waits on another: no look-back, no flags, no spinning.
@@ -24,6 +25,7 @@
 #include <vector>
 
 #include "d2d_flac_internal.h"
+#include "flac_lpc.h"
 
 using namespace d2dflac;
 
@@ -404,7 +406,44 @@ __device__ __forceinline__ void wg_sum(T (&v)[N], unsigned long long* s_red, uin
     for (int i = 0; i < N; ++i) v[i] = row_sum(red[(lane & (NW - 1)) * N + i]);      // 16 lanes hold the 16 waves' sums
 }
 
-//   flac_search_kernel<CH>   the same workgroup, with the decisions of effort 1 between "PCM in LDS" and "place bits".  Candidate
+// ---- effort 12: what the LPC flavour of the search kernel adds ----------------------------------------------------------------
+// x[w] = sample i0 - 12 + w of candidate signal sg, 0 outside [0, n): a thread's four samples behind their twelve predecessors
+template <int CH>
+__device__ __forceinline__ void load_window16(int32_t (&x)[16], const int32_t* pcm, uint32_t i0, uint32_t n, uint32_t sg) {
+    const int32_t* q = pcm + (CH == 2 && sg >= 2 ? 0u : sg) * BS + i0;
+    const int4 z = make_int4(0, 0, 0, 0);
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+        const bool in = i0 + 4 * v >= 12;                           // (i0 is a multiple of 4: a vector lies wholly in front of sample 0 or not at all)
+        int4 l = in ? *reinterpret_cast<const int4*>(q + 4 * v - 12) : z;
+        if (CH == 2 && sg >= 2) {
+            const int4 r = in ? *reinterpret_cast<const int4*>(q + BS + 4 * v - 12) : z;
+            if (sg == 2) l = make_int4((l.x + r.x) >> 1, (l.y + r.y) >> 1, (l.z + r.z) >> 1, (l.w + r.w) >> 1);
+            else l = make_int4(l.x - r.x, l.y - r.y, l.z - r.z, l.w - r.w);
+        }
+        x[4 * v] = l.x; x[4 * v + 1] = l.y; x[4 * v + 2] = l.z; x[4 * v + 3] = l.w;
+    }
+#pragma unroll
+    for (int w = 12; w < 16; ++w) if (i0 + w - 12 >= n) x[w] = 0;   // (what lies before i0 lies below n, or nothing here is used)
+}
+// the four residuals of a thread's samples under 12 coefficients (a lower order's are zero from its order on)
+__device__ __forceinline__ void lpc_residuals4(int32_t (&r)[SPT], const int32_t (&x)[16], const int32_t* s_q, int32_t shift) {
+    int32_t q[d2dlpc::MAX_ORDER], rev[16];
+#pragma unroll
+    for (int j = 0; j < d2dlpc::MAX_ORDER; ++j) q[j] = s_q[j];
+#pragma unroll
+    for (int w = 0; w < 16; ++w) rev[w] = x[15 - w];                // rev[4 - j + m] = x(i0 + j - 1 - m)
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) r[j] = d2dlpc::lpc_residual<d2dlpc::MAX_ORDER>(x[12 + j], &rev[4 - j], q, shift);
+}
+// a signed 64-bit sum over the wave, exact for |total| < 2^62, as three 32-bit sums of 22-bit limbs (the top one signed)
+__device__ __forceinline__ long long wave_sum_i64(long long v) {
+    const uint32_t lo = wave_sum((uint32_t)v & 0x3FFFFFu), mid = wave_sum((uint32_t)(v >> 22) & 0x3FFFFFu);
+    const int32_t hi = (int32_t)wave_sum((uint32_t)(int32_t)(v >> 44));
+    return (long long)(((unsigned long long)(long long)hi << 44) + ((unsigned long long)mid << 22) + lo);
+}
+
+//   flac_search_kernel<CH, LPC>   the same workgroup, with the decisions of effort 1 between "PCM in LDS" and "place bits".  Candidate
 //   signals (the channels; for two channels also mid and side) go through (a) to (c) one at a time, so that one signal's five
 //   residual sets are all the registers hold:
 //     (a) sum |r_o| for o = 0 .. 4, one five-wide 64-bit reduction; threads 0 .. 4 derive the five k; the code lengths under them,
@@ -418,7 +457,14 @@ __device__ __forceinline__ void wg_sum(T (&v)[N], unsigned long long* s_red, uin
 //     (e) per subframe the chosen signal's residuals again, now kept; lengths with the residual header in front of sample `order` and
 //         a 5-bit k in front of every partition's first residual; then the scan, the image, the CRC and the slot as at effort 0.
 //   A frame of fewer than 16 samples takes the same path with the choices forced to effort 0's.
-template <int CH>
+//   LPC (effort 12, rules 9 to 19 of flac_frame_enc.h; frames of 64 samples and more): behind (c) a signal goes through
+//     (f) y = the windowed signal into an LDS plane of its own behind the PCM; every thread's part of R(0 .. 12) from its four y and
+//         their twelve predecessors, 64-bit; three-limb wave sums, then 64-bit LDS adds: exact, whatever the order of arrival
+//     (g) thread 0 runs flac_lpc.h from R to the quantised coefficients of orders 4, 8 and 12; the others wait at the barrier
+//     (h) the three residual sets by 64-bit multiply-adds from the PCM plane, their k and their costs at one partition as in (a)
+//     (i) (b) and (c) once more for the best order; the signal keeps its effort-1 plan unless this one is strictly cheaper
+//   and (e) forms an LPC subframe's residuals and header from the kept coefficients.
+template <int CH, bool LPC>
 __global__ __launch_bounds__(NT) void flac_search_kernel(const FlacArgs a) {
     constexpr int NSIG = CH == 2 ? 4 : CH;
     extern __shared__ __align__(16) unsigned char smem[];          // the block's PCM as planar 32-bit samples, then the frame image
@@ -429,6 +475,9 @@ __global__ __launch_bounds__(NT) void flac_search_kernel(const FlacArgs a) {
     __shared__ uint32_t s_sel[NSIG][3];                             // order, partition order, cost of each signal
     __shared__ uint8_t s_kt[2 * NP];                                // k of partition j at partition order p: s_kt[2^p - 1 + j]
     __shared__ uint8_t s_ksel[NSIG][NP];                            // ... the chosen order's row
+    __shared__ unsigned long long s_R[LPC ? d2dlpc::MAX_ORDER + 1 : 1];
+    __shared__ int32_t s_co[LPC ? d2dlpc::CANDIDATES * d2dlpc::MAX_ORDER + d2dlpc::CANDIDATES + 1 : 1];   // q, the shifts, the valid bits
+    __shared__ int32_t s_lq[LPC ? NSIG : 1][d2dlpc::MAX_ORDER + 2];  // a signal's kept coefficients (zero from its order on), shift, and whether its plan is LPC
     __shared__ uint16_t s_crc_tab[256];
     __shared__ uint16_t s_crc[NT];
     __shared__ uint8_t s_hdr[16];
@@ -447,6 +496,7 @@ __global__ __launch_bounds__(NT) void flac_search_kernel(const FlacArgs a) {
     const uint32_t fsz = n >> pmax, i0 = tid * SPT, pj0 = i0 / fsz, rem0 = i0 - pj0 * fsz;
 
     int32_t* pcm = reinterpret_cast<int32_t*>(smem);
+    int32_t* yplane = pcm + CH * BS;                                // (LPC only: the launch asks for it)
     load_planar<CH>(pcm, fd.pcm + (size_t)b * BS * fb, n, depth, tid);
     build_crc_tab(s_crc_tab, tid);
     __syncthreads();
@@ -494,10 +544,116 @@ __global__ __launch_bounds__(NT) void flac_search_kernel(const FlacArgs a) {
         }
         if (!searched) order = n > 2 ? 2u : n;                      // effort 0's frame: order 2, or verbatim (every sample a warm-up)
 
-        // (b) sum |r| per finest partition, then k for every partition of every order
         uint32_t uo[SPT];
 #pragma unroll
         for (int j = 0; j < SPT; ++j) uo[j] = order == 0 ? u[0][j] : order == 1 ? u[1][j] : order == 2 ? u[2][j] : order == 3 ? u[3][j] : u[4][j];
+        uint32_t hdrbits = 8 + order * bits + 6;                    // in front of the partitions: subframe header, warm-up, 01 pppp
+        uint32_t cost1 = 0, lbest = 0;
+        // pass 0: (b) and (c) for the fixed order; LPC only, pass 1: (f) to (h), then (b) and (c) again for the best LPC order.
+        // (The loop's body keeps effort 1's indentation: with LPC = false it is effort 1's code, run once.)
+#pragma unroll 1
+        for (int pass = 0; pass < (LPC ? 2 : 1); ++pass) {
+        if (LPC && pass == 1) {
+            if (n < d2dlpc::MIN_FRAME) break;
+            if (tid < NP) s_psum[tid] = 0;                          // (read last before the barriers of pass 0's sums)
+            // (f) the windowed signal, its autocorrelation
+            {
+                int32_t xw[16];
+                load_window16<CH>(xw, pcm, i0, n, sg);
+                const uint32_t ws = d2dlpc::lpc_window_shift(n);
+                int32_t y[SPT];
+#pragma unroll
+                for (int j = 0; j < SPT; ++j) y[j] = i0 + j < n ? d2dlpc::lpc_window(xw[12 + j], i0 + j, n, ws) : 0;
+                *reinterpret_cast<int4*>(yplane + i0) = make_int4(y[0], y[1], y[2], y[3]);
+            }
+            if (tid <= (uint32_t)d2dlpc::MAX_ORDER) s_R[tid] = 0;
+            __syncthreads();
+            {
+                int32_t yw[16];
+                const int4 z = make_int4(0, 0, 0, 0);
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    const int4 l = i0 + 4 * v >= 12 ? *reinterpret_cast<const int4*>(yplane + i0 + 4 * v - 12) : z;
+                    yw[4 * v] = l.x; yw[4 * v + 1] = l.y; yw[4 * v + 2] = l.z; yw[4 * v + 3] = l.w;
+                }
+#pragma unroll
+                for (int l = 0; l <= d2dlpc::MAX_ORDER; ++l) {
+                    long long part = 0;                             // |y| <= 2^24: a thread's part stays below 2^50, a wave's below 2^56
+#pragma unroll
+                    for (int j = 0; j < SPT; ++j) part += (long long)yw[12 + j] * yw[12 + j - l];
+                    part = wave_sum_i64(part);
+                    if (lane == 0) atomicAdd(&s_R[l], (unsigned long long)part);
+                }
+            }
+            __syncthreads();
+            // (g) from R to coefficients: one lane
+            if (tid == 0) {
+                int64_t R[d2dlpc::MAX_ORDER + 1];
+#pragma unroll
+                for (int l = 0; l <= d2dlpc::MAX_ORDER; ++l) R[l] = (int64_t)s_R[l];
+                d2dlpc::LpcCoefs co;
+                d2dlpc::lpc_coefficients(R, co);
+#pragma unroll
+                for (int c = 0; c < d2dlpc::CANDIDATES; ++c) {
+                    if (!(co.valid >> c & 1u)) continue;
+#pragma unroll
+                    for (int j = 0; j < d2dlpc::MAX_ORDER; ++j) s_co[c * d2dlpc::MAX_ORDER + j] = j < 4 * (c + 1) ? co.q[c][j] : 0;
+                    s_co[d2dlpc::CANDIDATES * d2dlpc::MAX_ORDER + c] = co.shift[c];
+                }
+                s_co[d2dlpc::CANDIDATES * (d2dlpc::MAX_ORDER + 1)] = (int32_t)co.valid;
+            }
+            __syncthreads();
+            const uint32_t valid = (uint32_t)s_co[d2dlpc::CANDIDATES * (d2dlpc::MAX_ORDER + 1)];
+            if (!valid) break;
+            // (h) the residuals of the three orders, their costs at one partition
+            int32_t xw[16];
+            load_window16<CH>(xw, pcm, i0, n, sg);
+            uint32_t ul[d2dlpc::CANDIDATES][SPT];
+            unsigned long long lsum[d2dlpc::CANDIDATES];
+#pragma unroll
+            for (int c = 0; c < d2dlpc::CANDIDATES; ++c) {
+                unsigned long long acc = 0;                         // |r| < 2^30
+                if (valid >> c & 1u) {
+                    int32_t r[SPT];
+                    lpc_residuals4(r, xw, &s_co[c * d2dlpc::MAX_ORDER], s_co[d2dlpc::CANDIDATES * d2dlpc::MAX_ORDER + c]);
+#pragma unroll
+                    for (int j = 0; j < SPT; ++j) {
+                        ul[c][j] = zigzag(r[j]);
+                        if (i0 + j < n && i0 + j >= 4u * (c + 1)) acc += (ul[c][j] + 1) >> 1;
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < SPT; ++j) ul[c][j] = 0;
+                }
+                lsum[c] = acc;
+            }
+            wg_sum<d2dlpc::CANDIDATES>(lsum, s_red, lane, wave);
+            if (tid < (uint32_t)d2dlpc::CANDIDATES) s_ko[tid] = rice_k(tid == 0 ? lsum[0] : tid == 1 ? lsum[1] : lsum[2], n - 4 * (tid + 1));
+            __syncthreads();
+            uint32_t llen[d2dlpc::CANDIDATES];
+#pragma unroll
+            for (int c = 0; c < d2dlpc::CANDIDATES; ++c) {
+                const uint32_t k = s_ko[c];
+                llen[c] = 0;
+#pragma unroll
+                for (int j = 0; j < SPT; ++j)
+                    if (i0 + j < n && i0 + j >= 4u * (c + 1)) llen[c] += (ul[c][j] >> k) + 1 + k;
+            }
+            wg_sum<d2dlpc::CANDIDATES>(llen, s_red, lane, wave);
+            bool any = false;
+            uint32_t lcost = 0;
+#pragma unroll
+            for (int c = 0; c < d2dlpc::CANDIDATES; ++c) {         // the smaller order wins a tie
+                const uint32_t P = 4 * (c + 1), cc = 8 + P * bits + 9 + 14 * P + 6 + 5 + llen[c];
+                if ((valid >> c & 1u) && (!any || cc < lcost)) { any = true; lbest = c; lcost = cc; }
+            }
+            order = 4 * (lbest + 1);
+            hdrbits = 8 + order * bits + 9 + 14 * order + 6;
+#pragma unroll
+            for (int j = 0; j < SPT; ++j) uo[j] = lbest == 0 ? ul[0][j] : lbest == 1 ? ul[1][j] : ul[2][j];
+        }
+
+        // (b) sum |r| per finest partition, then k for every partition of every order
         if (n == BS) {                                              // 16 lanes hold one partition
             unsigned long long t = 0;
 #pragma unroll
@@ -547,12 +703,19 @@ __global__ __launch_bounds__(NT) void flac_search_kernel(const FlacArgs a) {
         uint32_t porder = 0;
 #pragma unroll
         for (int p = 0; p < 7; ++p) {                               // the smallest partition order wins a tie
-            const uint32_t c = 8 + order * bits + 6 + (5u << p) + plen[p];
+            const uint32_t c = hdrbits + (5u << p) + plen[p];
             if (p == 0) cost = c;
             else if ((uint32_t)p <= pmax && c < cost) { porder = p; cost = c; }
         }
+        if (LPC && pass == 1) {                                     // (i) the LPC plan only where it is strictly cheaper
+            if (!(cost < cost1)) break;
+            if (tid < (uint32_t)d2dlpc::MAX_ORDER) s_lq[sg][tid] = s_co[lbest * d2dlpc::MAX_ORDER + tid];
+            if (tid == 0) { s_lq[sg][d2dlpc::MAX_ORDER] = s_co[d2dlpc::CANDIDATES * d2dlpc::MAX_ORDER + lbest]; s_lq[sg][d2dlpc::MAX_ORDER + 1] = 1; }
+        } else if (LPC && tid == 0) s_lq[sg][d2dlpc::MAX_ORDER + 1] = 0;
+        cost1 = cost;
         if (tid == 0) { s_sel[sg][0] = order; s_sel[sg][1] = porder; s_sel[sg][2] = cost; }
         if (tid < (1u << porder)) s_ksel[sg][tid] = s_kt[(1u << porder) - 1 + tid];
+        }
     }
     __syncthreads();
 
@@ -582,12 +745,21 @@ __global__ __launch_bounds__(NT) void flac_search_kernel(const FlacArgs a) {
             const uint32_t sg = subframe_signal(c), order = s_sel[sg][0], sh = pmax - s_sel[sg][1];
             const uint32_t bits = CH == 2 && sg == 3 ? depth + 1 : depth;
             int32_t x[8];
-            load_window<CH>(x, pcm, i0, n, sg);
             int32_t raw[SPT];
+            const bool lp = LPC && s_lq[LPC ? sg : 0][d2dlpc::MAX_ORDER + 1];
+            if (LPC && lp) {
+                int32_t xw[16], r[SPT];
+                load_window16<CH>(xw, pcm, i0, n, sg);
+                lpc_residuals4(r, xw, s_lq[sg], s_lq[sg][d2dlpc::MAX_ORDER]);
+#pragma unroll
+                for (int j = 0; j < SPT; ++j) { raw[j] = xw[12 + j]; x[4 + j] = r[j]; }
+            } else {
+            load_window<CH>(x, pcm, i0, n, sg);
 #pragma unroll
             for (int j = 0; j < SPT; ++j) raw[j] = x[4 + j];
 #pragma unroll
             for (int o = 1; o < 5; ++o) if ((uint32_t)o <= order) difference(x, o);
+            }
             uint32_t len = tid == 0 ? 8 : 0;                        // the subframe header
             uint32_t pj = pj0, rem = rem0;
 #pragma unroll
@@ -598,6 +770,7 @@ __global__ __launch_bounds__(NT) void flac_search_kernel(const FlacArgs a) {
                     if (i < order) len += bits;
                     else {
                         if (i == order) len += 6;                   // 01 pppp
+                        if (LPC && lp && i == order) len += 9 + 14 * order;     // 1101 sssss and the coefficients
                         if (i == order || (rem == 0 && (pj & ((1u << sh) - 1)) == 0)) len += 5;     // a partition's first residual: kkkkk
                         const uint32_t k = s_ksel[sg][pj >> sh];
                         len += (zigzag(val[c][j]) >> k) + 1 + k;
@@ -638,6 +811,9 @@ __global__ __launch_bounds__(NT) void flac_search_kernel(const FlacArgs a) {
         const uint32_t sg = subframe_signal(c), order = s_sel[sg][0], porder = s_sel[sg][1], sh = pmax - porder;
         const uint32_t bits = CH == 2 && sg == 3 ? depth + 1 : depth;
         uint32_t p = start[c];
+        const bool lp = LPC && s_lq[LPC ? sg : 0][d2dlpc::MAX_ORDER + 1];
+        if (LPC && lp) { if (tid == 0) { put_bits(img, p, (0x20u | (order - 1)) << 1, 8); p += 8; } }   // 0 1ppppp 0: LPC order ppppp + 1
+        else
         if (tid == 0) { put_bits(img, p, n > 2 ? (8u | order) << 1 : 0x02u, 8); p += 8; }   // 0 001ooo 0: fixed order ooo; 0 000001 0: verbatim
         uint32_t pj = pj0, rem = rem0;
 #pragma unroll
@@ -650,6 +826,10 @@ __global__ __launch_bounds__(NT) void flac_search_kernel(const FlacArgs a) {
                     p += bits;
                 } else {
                     const uint32_t k = s_ksel[sg][pj >> sh];
+                    if (LPC && lp && i == order) {                  // 1101: 14-bit coefficients; their shift; the coefficients
+                        put_bits(img, p, ((uint32_t)(d2dlpc::PRECISION - 1) << 5) | (uint32_t)s_lq[sg][d2dlpc::MAX_ORDER], 9); p += 9;
+                        for (uint32_t m = 0; m < order; ++m) { put_bits(img, p, (uint32_t)s_lq[sg][m] & 0x3FFFu, d2dlpc::PRECISION); p += d2dlpc::PRECISION; }
+                    }
                     if (i == order) { put_bits(img, p, (1u << 4) | porder, 6); p += 6; }          // 01: 5-bit Rice parameters, pppp
                     if (i == order || (rem == 0 && (pj & ((1u << sh) - 1)) == 0)) { if (k) put_bits(img, p, k, 5); p += 5; }
                     const uint32_t v = zigzag(val[c][j]), q = v >> k;
@@ -712,12 +892,15 @@ __global__ __launch_bounds__(PT) void flac_pack_kernel(const FlacArgs a) {
     }
 }
 
-// the frame image over the block's PCM: packed as it comes at effort 0, planar 32-bit samples at effort 1
-size_t encode_lds_bytes(uint32_t ch, uint32_t depth, int effort) { return std::max<size_t>(slot_bytes(ch, depth) + 32, (size_t)BS * ch * (effort ? 4 : sample_bytes(depth))); }
+// the frame image over the block's PCM: packed as it comes at effort 0, planar 32-bit samples in the search kernel, whose LPC flavour
+// (`effort` 2 here) keeps the windowed signal's plane behind them
+size_t encode_lds_bytes(uint32_t ch, uint32_t depth, int effort) {
+    return std::max<size_t>(slot_bytes(ch, depth) + 32, (size_t)BS * ch * (effort ? 4 : sample_bytes(depth)) + (effort == 2 ? (size_t)BS * 4 : 0));
+}
 
 template <int CH, int EFFORT>
 hipError_t launch_encode(const FlacArgs& a, uint32_t max_blocks, uint32_t nf, hipStream_t s) {
-    const auto kernel = EFFORT == 0 ? &flac_encode_kernel<CH> : &flac_search_kernel<CH>;
+    const auto kernel = EFFORT == 0 ? &flac_encode_kernel<CH> : EFFORT == 1 ? &flac_search_kernel<CH, false> : &flac_search_kernel<CH, true>;
     // hipFuncSetAttribute acts on the current device: remembered per device, under a lock
     static std::mutex mu;
     static size_t allowed[64] = {};
@@ -766,7 +949,7 @@ int d2d_flac_encode_device(uint32_t channels, uint32_t bit_depth, d2d_flac_io* i
 int d2d_flac_encode_device_effort(uint32_t channels, uint32_t bit_depth, uint32_t effort, d2d_flac_io* io, uint32_t n_files,
                                   void* workspace, size_t workspace_bytes, void* hip_stream) {
     // every check comes before the first device call
-    if (!effort_ok(effort)) return fail(D2D_ERR_PARAM, "unknown FLAC effort: 0 (fixed order 2) or 1 (search)");
+    if (!effort_ok(effort)) return fail(D2D_ERR_PARAM, EFFORT_MESSAGE);
     if (!depth_ok(bit_depth)) return fail(D2D_ERR_PARAM, "FLAC holds 16, 20 or 24-bit integers (Invalid bit depth)");
     if (channels == 0 || channels > 8) return fail(D2D_ERR_PARAM, "FLAC holds 1 to 8 channels (Invalid channel count)");
     if (!io || n_files == 0) return fail(D2D_ERR_PARAM, "no files");
@@ -805,8 +988,9 @@ int d2d_flac_encode_device_effort(uint32_t channels, uint32_t bit_depth, uint32_
             max_blocks = std::max(max_blocks, d.blocks);
         }
         if (max_blocks) {
-            hipError_t e = effort == D2D_FLAC_EFFORT_SEARCH ? launch_encode_ch<1>(channels, a, max_blocks, nf, s) : launch_encode_ch<0>(channels, a, max_blocks, nf, s);
-            if (e != hipSuccess) return hip_fail(e, effort == D2D_FLAC_EFFORT_SEARCH ? "flac_search_kernel" : "flac_encode_kernel");
+            hipError_t e = effort == D2D_FLAC_EFFORT_LPC ? launch_encode_ch<2>(channels, a, max_blocks, nf, s)
+                         : effort == D2D_FLAC_EFFORT_SEARCH ? launch_encode_ch<1>(channels, a, max_blocks, nf, s) : launch_encode_ch<0>(channels, a, max_blocks, nf, s);
+            if (e != hipSuccess) return hip_fail(e, effort == D2D_FLAC_EFFORT_FIXED2 ? "flac_encode_kernel" : "flac_search_kernel");
         }
         hipLaunchKernelGGL(flac_pack_kernel, dim3(std::max(1u, (max_blocks + PB - 1) / PB), nf), dim3(PT), 0, s, a);
         hipError_t e = hipGetLastError();
@@ -852,7 +1036,7 @@ extern "C" int d2d_convert_stream_flac(d2d_engine* e, uint32_t bit_depth, d2d_re
 extern "C" int d2d_convert_stream_flac_effort(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
                                               d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
                                               uint64_t total, size_t chunk, d2d_flac_stream_stats* stats) {
-    if (!effort_ok(effort)) return fail(D2D_ERR_PARAM, "unknown FLAC effort: 0 (fixed order 2) or 1 (search)");
+    if (!effort_ok(effort)) return fail(D2D_ERR_PARAM, EFFORT_MESSAGE);
     if (!e) return fail(D2D_ERR_PARAM, "null engine");
     if (!read) return fail(D2D_ERR_PARAM, "null read callback");
     if (!stats) return fail(D2D_ERR_PARAM, "null stats");

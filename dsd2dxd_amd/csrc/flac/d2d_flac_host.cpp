@@ -40,7 +40,7 @@ int d2d_flac_encode_host(uint32_t channels, uint32_t bit_depth, const void* pcm,
 
 int d2d_flac_encode_host_effort(uint32_t channels, uint32_t bit_depth, uint32_t effort, const void* pcm, size_t frames, uint32_t first_block,
                                 int final, void* out, size_t out_capacity_bytes, d2d_flac_result* result, size_t* frames_consumed) {
-    if (!effort_ok(effort)) return fail(D2D_ERR_PARAM, "unknown FLAC effort: 0 (fixed order 2) or 1 (search)");
+    if (!effort_ok(effort)) return fail(D2D_ERR_PARAM, EFFORT_MESSAGE);
     if (!depth_ok(bit_depth)) return fail(D2D_ERR_PARAM, "FLAC holds 16, 20 or 24-bit integers (Invalid bit depth)");
     if (channels == 0 || channels > 8) return fail(D2D_ERR_PARAM, "FLAC holds 1 to 8 channels (Invalid channel count)");
     if (!result) return fail(D2D_ERR_PARAM, "null result record");

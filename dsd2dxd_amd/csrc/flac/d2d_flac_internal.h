@@ -14,7 +14,8 @@ constexpr uint32_t BS = D2D_FLAC_BLOCK;
 constexpr uint32_t MAX_HEADER_BYTES = 13;      // 4 fixed + 6 frame number + 2 block size + 1 CRC-8
 
 inline bool depth_ok(uint32_t d) { return d == 16 || d == 20 || d == 24; }
-inline bool effort_ok(uint32_t e) { return e == D2D_FLAC_EFFORT_FIXED2 || e == D2D_FLAC_EFFORT_SEARCH; }
+inline bool effort_ok(uint32_t e) { return e == D2D_FLAC_EFFORT_FIXED2 || e == D2D_FLAC_EFFORT_SEARCH || e == D2D_FLAC_EFFORT_LPC; }
+constexpr const char* EFFORT_MESSAGE = "unknown FLAC effort: 0 (fixed order 2), 1 (search) or 12 (search with LPC)";
 inline uint32_t sample_bytes(uint32_t depth) { return depth == 16 ? 2 : 3; }
 // the header's bound: D2D_FLAC_FRAME_BOUND(n)
 inline size_t subframe_bits_bound(uint32_t depth, uint32_t n) { return 19 + 2 * (size_t)depth + 30 * (size_t)(n > 2 ? n - 2 : 0); }

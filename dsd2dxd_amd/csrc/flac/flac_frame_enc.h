@@ -7,10 +7,12 @@
 
 #include <vector>
 
+#include "flac_lpc.h"
+
 namespace d2dhost {
 
 // Integer depths only.  Frames are independent of each other, so a batch of them is encoded on as many threads and written in
-// order.  (The reference uses the flac-codec crate, Cargo.lock:299-307.)  Two efforts, both with fixed block size:
+// order.  (The reference uses the flac-codec crate, Cargo.lock:299-307.)  Three efforts, all with fixed block size:
 //
 // EFFORT 0: fixed-order-2 prediction, one Rice partition per subframe, independent channels (valid, modest compression).
 //
@@ -33,6 +35,32 @@ namespace d2dhost {
 //   8. Subframe: 0, 001ooo, 0; o warm-up samples of b bits; 01, pppp; per partition kkkkk and its codes.
 // (o = 2, p = 0) and the independent assignment are always candidates and the costs are exact, so an effort-1 frame is never
 // longer than the effort-0 frame of the same samples: THE BOUND of include/dsd2dxd_amd.h holds for both.
+//
+// EFFORT 12: effort 1, and per candidate signal linear predictors of order 4, 8 and 12 (the value is the highest order searched).
+// The autocorrelation is exact integer arithmetic; what is floating point (rule 13) is one serial f64 routine, flac_lpc.h, compiled
+// from one source for the host and the GPU.  For a frame of n samples per channel and each candidate signal x of b bits (rule 2):
+//   9. n < 64: the frame is the effort-1 frame (below 16 samples the effort-0 frame).
+//  10. The effort-1 plan: rules 3 to 6 on x give (o1, p1, cost1).
+//  11. Window: w(i) = (i + 1)(n - i); s = the bit length of floor((n + 1) / 2) floor((n + 2) / 2), the window's maximum;
+//      y(i) = (x(i) w(i)) >> s, a 64-bit product and an arithmetic shift, so |y| <= |x| <= 2^24.
+//  12. Autocorrelation: R(l) = sum over i = l .. n-1 of y(i) y(i - l), l = 0 .. 12: exact in signed 64 bits (|R| <= 2^60), so the
+//      order of summation does not matter.
+//  13. From R to coefficients, in IEEE f64, one operation per operation written, no fused multiply-add.  R(0) == 0: no LPC
+//      candidates.  err = (double)R(0); for m = 1 .. 12: acc = (double)R(m); for j = 1 .. m-1: acc = acc - a[j] (double)R(m - j);
+//      k = acc / err; a'[j] = a[j] - k a[m - j] for j < m, a'[m] = k; err = err (1.0 - k k); the first time !(err > 0) (NaN too) the
+//      recursion stops for good, and that m is not reached.  For each m in {4, 8, 12} reached: a candidate needs every |a[j]| < 2^13
+//      (a lesser bound would make the shift negative; anything not finite ends here) and cmax = max |a[j]| > 0; e = the smallest
+//      integer with cmax < 2^e; sh = min(15, 13 - e); error feedback from t = 0, for j = 1 .. m: t = t + a[j] 2^sh,
+//      q[j] = clamp(floor(t + 0.5), -8192, 8191), t = t - q[j].  The candidate is dropped when sum |q[j]| > 62 * 2^sh; for those that
+//      remain |prediction| <= 62 * 2^24 and every residual has |r| < 2^30: no per-sample range check exists.
+//  14. Residuals: r(i) = x(i) - ((sum over j = 1 .. P of q[j] x(i - j)) >> sh) for i >= P; a 64-bit sum, an arithmetic shift.
+//  15. cost_lpc(P, p) = 8 + P b + 4 + 5 + 14 P + 2 + 4 + the partition terms of rule 4 with o = P.
+//  16. The LPC plan: the P with the least cost_lpc(P, 0), the smaller P at a tie; for it the partition order by rule 6: cost2.
+//  17. The signal's plan is the LPC plan only if cost2 < cost1, else the effort-1 plan.  Both partition searches come first, so an
+//      effort-12 frame is never longer than the effort-1 frame of the same samples: THE BOUND, the workspace and the slots stand.
+//  18. Stereo: rule 7 on the four signals' final costs.
+//  19. LPC subframe: 0, 1ppppp (P - 1), 0; P warm-up samples of b bits; 1101 (precision 14, less one); sh in 5 bits; P coefficients
+//      of 14 bits, two's complement, q[1] first; then 01, pppp and the partitions as in rule 8.
 struct FlacFrameEnc {
     std::vector<uint8_t> out;
     std::vector<int32_t> res;
@@ -111,13 +139,15 @@ struct FlacFrameEnc {
     }
     struct Plan {                               // what the search chose for one candidate signal
         uint32_t order = 0, porder = 0, bits = 0, cost = 0;
+        bool lpc = false;                       // effort 12: `order` is an LPC order, with these coefficients
+        int32_t q[d2dlpc::MAX_ORDER] = {}, shift = 0;
         uint8_t k[64];
         std::vector<int32_t> x, r;              // the signal, and its residuals at `order` (valid from index `order`)
     };
     Plan plans[4];
     std::vector<int32_t> rs[5];
     void search(Plan& pl, uint32_t n, uint32_t b) {
-        pl.bits = b;
+        pl.bits = b; pl.lpc = false;
         rs[0] = pl.x;
         for (uint32_t o = 1; o <= 4; ++o) {
             rs[o].resize(n);
@@ -136,9 +166,56 @@ struct FlacFrameEnc {
         }
         pl.cost = search_cost(pl.r.data(), n, best, pl.porder, b, pl.k);
     }
+    // ---- effort 12: rules 11 to 17 for one signal whose effort-1 plan `pl` holds ------------------------------------------------
+    std::vector<int32_t> win, lres[d2dlpc::CANDIDATES];
+    void search_lpc(Plan& pl, uint32_t n, uint32_t b) {
+        using namespace d2dlpc;
+        const uint32_t s = lpc_window_shift(n);
+        win.resize(n);
+        for (uint32_t i = 0; i < n; ++i) win[i] = lpc_window(pl.x[i], i, n, s);
+        int64_t R[MAX_ORDER + 1];
+        for (uint32_t l = 0; l <= (uint32_t)MAX_ORDER; ++l) {
+            int64_t sum = 0;
+            for (uint32_t i = l; i < n; ++i) sum += (int64_t)win[i] * win[i - l];
+            R[l] = sum;
+        }
+        LpcCoefs co;
+        lpc_coefficients(R, co);
+        int best = -1; uint32_t cost = 0;
+        for (int c = 0; c < CANDIDATES; ++c) {                         // the smaller order wins a tie
+            if (!(co.valid >> c & 1u)) continue;
+            const uint32_t P = 4 * (c + 1);
+            std::vector<int32_t>& r = lres[c];
+            r.resize(n);
+            int32_t before[MAX_ORDER];
+            for (uint32_t i = P; i < n; ++i) {
+                for (uint32_t j = 0; j < P; ++j) before[j] = pl.x[i - 1 - j];
+                r[i] = P == 4 ? lpc_residual<4>(pl.x[i], before, co.q[c], co.shift[c]) : P == 8 ? lpc_residual<8>(pl.x[i], before, co.q[c], co.shift[c])
+                                                                                         : lpc_residual<12>(pl.x[i], before, co.q[c], co.shift[c]);
+            }
+            const uint32_t cc = 9 + 14 * P + search_cost(r.data(), n, P, 0, b, nullptr);
+            if (best < 0 || cc < cost) { best = c; cost = cc; }
+        }
+        if (best < 0) return;
+        const uint32_t P = 4 * (best + 1), pmax = search_pmax(n);
+        uint32_t porder = 0;
+        for (uint32_t p = 1; p <= pmax; ++p) {                         // the smallest partition order wins a tie
+            const uint32_t cc = 9 + 14 * P + search_cost(lres[best].data(), n, P, p, b, nullptr);
+            if (cc < cost) { porder = p; cost = cc; }
+        }
+        if (!(cost < pl.cost)) return;                                 // rule 17: the effort-1 plan stays unless LPC is strictly cheaper
+        pl.lpc = true; pl.order = P; pl.porder = porder; pl.shift = co.shift[best];
+        for (uint32_t j = 0; j < P; ++j) pl.q[j] = co.q[best][j];
+        pl.r = lres[best];
+        pl.cost = 9 + 14 * P + search_cost(pl.r.data(), n, P, porder, b, pl.k);
+    }
     void put_subframe(const Plan& pl, uint32_t n) {
-        bits_put(0, 1); bits_put(8 + pl.order, 6); bits_put(0, 1);
+        bits_put(0, 1); bits_put(pl.lpc ? 32 + pl.order - 1 : 8 + pl.order, 6); bits_put(0, 1);
         for (uint32_t i = 0; i < pl.order; ++i) bits_put((uint64_t)(int64_t)pl.x[i] & ((1ull << pl.bits) - 1), (int)pl.bits);
+        if (pl.lpc) {
+            bits_put(d2dlpc::PRECISION - 1, 4); bits_put((uint64_t)pl.shift, 5);
+            for (uint32_t j = 0; j < pl.order; ++j) bits_put((uint64_t)(int64_t)pl.q[j] & 0x3FFF, d2dlpc::PRECISION);
+        }
         bits_put(1, 2); bits_put(pl.porder, 4);
         const uint32_t psz = n >> pl.porder;
         for (uint32_t j = 0; j < (1u << pl.porder); ++j) {
@@ -153,7 +230,7 @@ struct FlacFrameEnc {
             }
         }
     }
-    void encode_search(const int32_t* buf, uint32_t n, uint32_t ch, uint32_t depth, uint32_t frame_no, uint32_t BS) {
+    void encode_search(const int32_t* buf, uint32_t n, uint32_t ch, uint32_t depth, uint32_t frame_no, uint32_t BS, bool lpc = false) {
         uint32_t first = 0, second = 1, nibble = ch - 1;
         if (ch == 2) {
             for (Plan& pl : plans) pl.x.resize(n);
@@ -161,7 +238,10 @@ struct FlacFrameEnc {
                 const int32_t l = buf[(size_t)i * 2], r = buf[(size_t)i * 2 + 1];
                 plans[0].x[i] = l; plans[1].x[i] = r; plans[2].x[i] = (l + r) >> 1; plans[3].x[i] = l - r;
             }
-            for (uint32_t s = 0; s < 4; ++s) search(plans[s], n, s == 3 ? depth + 1 : depth);
+            for (uint32_t s = 0; s < 4; ++s) {
+                search(plans[s], n, s == 3 ? depth + 1 : depth);
+                if (lpc) search_lpc(plans[s], n, s == 3 ? depth + 1 : depth);
+            }
             const uint32_t L = plans[0].cost, R = plans[1].cost, M = plans[2].cost, S = plans[3].cost;
             uint32_t total = L + R;                                     // ties go to the earlier mode
             if (L + S < total) { total = L + S; first = 0; second = 3; nibble = 0x8; }
@@ -175,14 +255,15 @@ struct FlacFrameEnc {
             pl.x.resize(n);
             for (uint32_t i = 0; i < n; ++i) pl.x[i] = buf[(size_t)i * ch + c];
             search(pl, n, depth);
+            if (lpc) search_lpc(pl, n, depth);
             put_subframe(pl, n);
         }
         end_frame();
     }
 
-    // one frame of `n` interleaved samples starting at `buf`; effort 0 = fixed order 2, 1 = the search
+    // one frame of `n` interleaved samples starting at `buf`; effort 0 = fixed order 2, 1 = the search, 12 = the search with LPC
     void encode(const int32_t* buf, uint32_t n, uint32_t ch, uint32_t depth, uint32_t frame_no, uint32_t BS, uint32_t effort = 0) {
-        if (effort != 0 && n >= 16) { encode_search(buf, n, ch, depth, frame_no, BS); return; }
+        if (effort != 0 && n >= 16) { encode_search(buf, n, ch, depth, frame_no, BS, effort == 12 && n >= d2dlpc::MIN_FRAME); return; }
         begin_frame(n, ch - 1, depth, frame_no, BS);                   // independent channels
         res.resize(n);
         for (uint32_t c = 0; c < ch; ++c) {

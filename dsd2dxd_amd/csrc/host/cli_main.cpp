@@ -111,7 +111,7 @@ int main(int argc, char** argv) {
         else if (a == "--seed") seed = strtoull(val(), 0, 10);
         else if (a == "--tap-bits") tap_bits = (uint32_t)strtoul(val(), 0, 10);
         else if (a == "--gpu-flac") gpu_flac = true;               // -o f only: encode the frames on the GPU (Rdsd2Pcm::set_gpu_flac)
-        else if (a == "--flac-effort") flac_effort = atoi(val());  // -o f only: 0 (default) or 1, the search (Rdsd2Pcm::set_flac_effort)
+        else if (a == "--flac-effort") flac_effort = atoi(val());  // -o f only: 0 (default), 1, the search, or 12, the search with LPC (Rdsd2Pcm::set_flac_effort)
         else files.push_back(a);
     }
     if (files.empty()) files.push_back("-");

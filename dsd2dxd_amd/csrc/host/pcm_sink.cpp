@@ -202,7 +202,7 @@ struct FlacSink : PcmSink {
     std::vector<FlacFrameEnc> encs;
     bool io_failed = false;
     bool raw_frames = false;       // the frames came encoded (write_frames): no samples were seen, so there is no MD5
-    uint32_t effort = 0;           // flac_frame_enc.h: 0 = fixed order 2, 1 = the search
+    uint32_t effort = 0;           // flac_frame_enc.h: 0 = fixed order 2, 1 = the search, 12 = the search with LPC
     void set_flac_effort(uint32_t e) override { effort = e; }
     uint32_t depth() const { return bits == 20 ? 20 : bits; }
     std::string begin() {

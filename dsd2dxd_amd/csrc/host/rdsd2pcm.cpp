@@ -147,7 +147,7 @@ void Rdsd2Pcm::set_tap_bits(uint32_t bits) { p_->prm.tap_bits = bits; }
 void Rdsd2Pcm::set_chunk_bytes(size_t b) { if (b) p_->chunk = b; }
 void Rdsd2Pcm::set_gpu_flac(bool on) { p_->gpu_flac = on; }
 void Rdsd2Pcm::set_flac_effort(int effort) {
-    if (effort != D2D_FLAC_EFFORT_FIXED2 && effort != D2D_FLAC_EFFORT_SEARCH) throw std::runtime_error("Invalid FLAC effort; must be 0 or 1");
+    if (effort != D2D_FLAC_EFFORT_FIXED2 && effort != D2D_FLAC_EFFORT_SEARCH && effort != D2D_FLAC_EFFORT_LPC) throw std::runtime_error("Invalid FLAC effort; must be 0, 1 or 12");
     p_->flac_effort = (uint32_t)effort;
 }
 

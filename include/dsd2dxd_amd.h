@@ -20,10 +20,11 @@
 extern "C" {
 #endif
 
-#define D2D_ABI_VERSION 8   /* 3: the table blob header names the table variant; 4: d2d_params.tap_bits; 5: d2d_params.debug_flags (was reserved0);
+#define D2D_ABI_VERSION 9   /* 3: the table blob header names the table variant; 4: d2d_params.tap_bits; 5: d2d_params.debug_flags (was reserved0);
                              * 6: d2d_seek / d2d_tell / d2d_prime* and the two size queries (d2d_params unchanged);
                              * 7: the d2d_flac_* entry points and d2d_convert_stream_flac (d2d_params unchanged);
-                             * 8: the FLAC efforts: d2d_flac_encode_device_effort / _host_effort, d2d_convert_stream_flac_effort (d2d_params unchanged) */
+                             * 8: the FLAC efforts: d2d_flac_encode_device_effort / _host_effort, d2d_convert_stream_flac_effort (d2d_params unchanged);
+                             * 9: FLAC effort 12, D2D_FLAC_EFFORT_LPC, through the same entry points (d2d_params unchanged) */
 
 /* status codes */
 enum {
@@ -270,9 +271,17 @@ int d2d_convert_stream(d2d_engine* e, d2d_read_fn read, void* read_user,
  * than 16 samples are the effort-0 frames.  THE BOUND DOES NOT CHANGE: (order 2, one partition) and the independent assignment are
  * always candidates and the costs are exact bit counts, so an effort-1 frame is never longer than the effort-0 frame of the same
  * samples; the argument for k (under 30 bits per residual) holds per partition, and |S| <= 2^24 gives |r_4| <= 2^28, so no escape
- * exists here either.  D2D_FLAC_FRAME_BOUND, d2d_flac_bound_bytes, d2d_flac_workspace_bytes and the slots serve both efforts. */
+ * exists here either.  D2D_FLAC_FRAME_BOUND, d2d_flac_bound_bytes, d2d_flac_workspace_bytes and the slots serve every effort.
+ *
+ * Effort 12 (ABI 9; the value is the highest LPC order searched) adds linear predictors of order 4, 8 and 12 with 14-bit
+ * coefficients to effort 1, per candidate signal, by rules 9 to 19 of csrc/flac/flac_frame_enc.h: an exact integer autocorrelation of
+ * the windowed signal, one serial f64 routine from it to the quantised coefficients (csrc/flac/flac_lpc.h, the same source on the host
+ * and on the GPU), exact costs.  A signal takes its LPC plan only where that is strictly cheaper than its effort-1 plan after both
+ * partition searches, so an effort-12 frame is never longer than the effort-1 frame of the same samples and THE BOUND STANDS; every
+ * residual stays below 2^30 in magnitude.  Frames of fewer than 64 samples are the effort-1 frames.  The values 2 .. 11 and everything
+ * above 12 are unknown efforts. */
 #define D2D_FLAC_BLOCK 4096u
-enum { D2D_FLAC_EFFORT_FIXED2 = 0, D2D_FLAC_EFFORT_SEARCH = 1 };
+enum { D2D_FLAC_EFFORT_FIXED2 = 0, D2D_FLAC_EFFORT_SEARCH = 1, D2D_FLAC_EFFORT_LPC = 12 };
 size_t d2d_flac_bound_bytes(uint32_t channels, uint32_t bit_depth, size_t frames, int final);
 /* Scratch one d2d_flac_encode_device call needs for one such file: a 4-byte size per block, rounded up to 16 bytes, and one slot of
  * D2D_FLAC_FRAME_BOUND(4096) bytes, rounded up to 16, per block.  A call over several files needs the sum. */

@@ -75,8 +75,9 @@ class Rdsd2Pcm {
     // reach the host.  Tags and pictures are written as before.  Not a reference option; the C mirror (rdsd2pcm_c.h) does not have it.
     void set_gpu_flac(bool on);
     // FLAC output only; 0 by default.  The encoder effort, D2D_FLAC_EFFORT_* of include/dsd2dxd_amd.h: 0 = fixed order 2, one Rice
-    // partition, independent channels; 1 = searched fixed predictors, partitioned Rice and stereo modes.  It applies to the host sink
-    // and to the set_gpu_flac path alike, which write the same frames at either effort.  Any other value throws.
+    // partition, independent channels; 1 = searched fixed predictors, partitioned Rice and stereo modes; 12 = that search with LPC
+    // predictors of order 4, 8 and 12.  It applies to the host sink and to the set_gpu_flac path alike, which write the same frames
+    // at every effort.  Any other value throws.
     void set_flac_effort(int effort);
 
     struct Impl;                              // opaque state (public only so the .cpp's helpers can name it)

@@ -8,7 +8,9 @@ converter output.  GPU figure: device events around ONE d2d_flac_encode_device c
 median of the repetitions; the conversion step is timed the same way on the same batch.  Baseline: d2d_flac_encode_host -- the sink's
 own encoder -- on the same PCM in host memory, one block per task on 16 threads, as FlacSink::drain spreads them; wall clock, best of
 two passes.  File 0's device frames are compared with the host's.  With --effort 1 (the search, D2D_FLAC_EFFORT_SEARCH) both sides run
-at that effort, and the effort-0 call is timed beside it on the same buffers for the size ratio."""
+at that effort, and the effort-0 call is timed beside it on the same buffers for the size ratio.  With --effort 12 (the search with
+LPC, D2D_FLAC_EFFORT_LPC) the call timed beside it is effort 1's, in the same session on the same buffers: bytes and time are stated
+over effort 1's, and no file may come out longer than at effort 1."""
 import ctypes as C
 import json
 import os
@@ -82,10 +84,12 @@ fio = (d.FlacIO * n_files)()
 for f in range(n_files):
     fio[f].pcm, fio[f].frames, fio[f].first_block, fio[f].final = pcm[f].data_ptr(), frames, 0, 1
     fio[f].out, fio[f].out_capacity_bytes, fio[f].result = out[f].data_ptr(), cap, rec.data_ptr() + 16 * f
-enc0, bytes0 = None, None
-if effort:                                                      # effort 0 on the same buffers first: its time and its bytes
-    enc0 = timed(lambda: d.flac_encode_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), stream))
-    bytes0 = int(rec.cpu().numpy().view(np.uint64).reshape(n_files, 2)[:, 0].sum())
+enc0, bytes0, per_file0 = None, None, None
+base = 1 if effort == d.FLAC_EFFORT_LPC else 0                  # the effort this one is held against
+if effort:                                                      # the base effort on the same buffers first: its time and its bytes
+    enc0 = timed(lambda: d.flac_encode_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), stream, effort=base))
+    per_file0 = rec.cpu().numpy().view(np.uint64).reshape(n_files, 2)[:, 0].copy()
+    bytes0 = int(per_file0.sum())
 enc = timed(lambda: d.flac_encode_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), stream, effort=effort))
 r = rec.cpu().numpy().view(np.uint64).reshape(n_files, 2)
 flac_bytes = int(r[:, 0].sum())
@@ -124,7 +128,9 @@ res = dict(effort=effort, files=n_files, seconds_per_file=seconds, blocks_per_fi
            host_16_threads_s=dict(best=min(host_s), passes=host_s), reps=reps, workspace_bytes=int(ws.numel()), crc="parallel (per-thread chunks, tree combine)",
            file0_equals_host=bool(same0), total_bytes_equal_host=bool(same_total), kernel=eng.kernel_name())
 if effort:
-    res.update(effort0_gpu_encode_ms=dict(median=enc0[0], min=enc0[1], max=enc0[2]), effort0_flac_bytes=bytes0, size_over_effort0=flac_bytes / bytes0)
+    res.update({"base_effort": base, "effort%d_gpu_encode_ms" % base: dict(median=enc0[0], min=enc0[1], max=enc0[2]), "effort%d_flac_bytes" % base: bytes0,
+                "size_over_effort%d" % base: flac_bytes / bytes0, "time_over_effort%d" % base: enc[0] / enc0[0],
+                "worst_file_size_over_effort%d" % base: float((r[:, 0] / per_file0).max())})
 os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
 with open(out_path, "w") as fh:
     json.dump(res, fh, indent=1)
@@ -132,10 +138,12 @@ samples = n_files * frames * CH
 print("batch: %d files x %d blocks (%d frames), PCM %.1f MB -> FLAC %.1f MB (ratio %.4f)" % (n_files, nblocks, frames, pcm_bytes / 1e6, flac_bytes / 1e6, flac_bytes / pcm_bytes))
 print("effort %d" % effort)
 if effort:
-    print("effort 0 on the same buffers: median %.3f ms (min %.3f, max %.3f), %.1f MB; effort %d / effort 0 bytes: %.4f" % (*enc0, bytes0 / 1e6, effort, flac_bytes / bytes0))
+    print("effort %d on the same buffers: median %.3f ms (min %.3f, max %.3f), %.1f MB; effort %d / effort %d bytes: %.4f (worst file %.4f), time: %.2fx" %
+          (base, *enc0, bytes0 / 1e6, effort, base, flac_bytes / bytes0, float((r[:, 0] / per_file0).max()), enc[0] / enc0[0]))
 print("GPU encode (one d2d_flac_encode_device call, both kernels): median %.3f ms (min %.3f, max %.3f) = %.2f Gsamples/s" % (*enc, samples / enc[0] / 1e6))
 print("conversion step (d2d_translate_batch_device, %s):  median %.3f ms (min %.3f, max %.3f)" % (eng.kernel_name(), *conv))
 print("host, %d threads, one block per task: best %.3f s of %s = %.3f Gsamples/s" % (THREADS, min(host_s), ["%.3f" % s for s in host_s], samples / min(host_s) / 1e9))
 print("GPU encode / host: %.1fx;  encode / conversion: %.2fx;  file 0 equals the host encoding: %s;  total bytes equal: %s" %
       (min(host_s) * 1e3 / enc[0], enc[0] / conv[0], same0, same_total))
 assert same0 and same_total
+assert not effort or (r[:, 0] <= per_file0).all(), "a file came out longer than at the base effort"
