@@ -1,7 +1,9 @@
-// d2d_flac.hip -- FLAC frames on the GPU (gfx950): the kernels behind d2d_flac_encode_device, and d2d_convert_stream_flac on top
-// of the public calls.  The bitstream is the one flac_frame_enc.h defines, at every effort; tests/test_gpu_flac.py (effort 0),
-// tests/test_gpu_flac_search.py (effort 1) and tests/test_gpu_flac_lpc.py (effort 12) compare them byte for byte.
-//
+// d2d_flac.hip -- FLAC frames on the GPU (gfx950): the kernels behind d2d_flac_encode_device (the whole-stream driver on top of the
+// public calls is d2d_flac_stream.cpp).  The bitstream is the one flac_frame_enc.h defines, at every effort; tests/test_gpu_flac.py
+// (effort 0), tests/test_gpu_flac_search.py (effort 1) and tests/test_gpu_flac_lpc.py (effort 12) compare them byte for byte.  The
+// rules' small arithmetic (Rice parameter, zigzag, pmax, header bit counts, the LPC routine) is flac_lpc.h, the host encoder's copy.
+// Both encode kernels are a front of their own (PCM in LDS, the decisions, every thread's code lengths) and one emit path:
+// block_context in front of everything, then scan_starts, begin_image, put_bits / put_rice and finish_frame (steps 3 to 6 below).
 //   flac_encode_kernel<CH>   effort 0: one workgroup of 1024 threads per (file, block); thread t owns samples 4t .. 4t+3 of every channel.
 //     1. the block's PCM comes into LDS with 16-byte loads (4096 * frame_bytes is a multiple of 16; a short block's tail by bytes)
 //     2. residuals r = s[i] - 2 s[i-1] + s[i-2] stay in registers; sum |r| per channel is reduced over the workgroup (64-bit) and
@@ -28,6 +30,7 @@
 #include "flac_lpc.h"
 
 using namespace d2dflac;
+using namespace d2drice;
 
 namespace {
 
@@ -138,25 +141,97 @@ __device__ __forceinline__ void store_frame(const uint32_t* img, uint8_t* slot, 
     }
 }
 
+// ---- what both encode kernels share: the block's context in front, the emit path behind -------------------------------------
+
+// What a workgroup knows of its block before it reads a sample.  Passed by value: every field is uniform or a function of the thread.
+struct Block {
+    uint32_t n, depth;                              // samples per channel, their bits
+    uint32_t tid, lane, wave, i0;                   // this thread; its first sample
+    uint32_t frame_no, hdr_bytes;
+    uint32_t pmax, fsz, pj0, rem0;                  // the search: rule 6's pmax; a finest partition's samples, n >> pmax; i0 = pj0 * fsz + rem0
+};
+__device__ __forceinline__ Block block_context(const FileDesc& fd, uint32_t b, uint32_t depth) {
+    Block B;
+    B.n = b + 1 == fd.blocks ? fd.last_n : BS; B.depth = depth;
+    B.tid = threadIdx.x; B.lane = B.tid & 63u; B.wave = B.tid >> 6; B.i0 = B.tid * SPT;
+    B.frame_no = fd.first_block + b;
+    B.hdr_bytes = 4 + utf8_len(B.frame_no) + (B.n != BS ? 2u : 0u) + 1;
+    B.pmax = search_pmax(B.n);                      // (0 for an unsearched frame, n < 16)
+    B.fsz = B.n >> B.pmax; B.pj0 = B.i0 / B.fsz; B.rem0 = B.i0 - B.pj0 * B.fsz;
+    return B;
+}
+
+template <int CH>
+struct EmitLds {                                    // the emit path's static LDS
+    uint32_t wtot[NW][CH];
+    uint16_t crc_tab[256], crc[NT];
+    uint8_t hdr[16];
+};
+
+// Step 3: where this thread's bits of every channel begin, from its code lengths mine[c]: an inclusive scan over the wave's lanes, the
+// 16 waves' totals through LDS into 16 lanes; channel 0 starts at first_bit.  Returns the bits behind the last channel.  One barrier.
+template <int CH>
+__device__ __forceinline__ uint32_t scan_starts(uint32_t (&start)[CH], const uint32_t (&mine)[CH], uint32_t first_bit, uint32_t (*s_wtot)[CH], const Block B) {
+    uint32_t incl[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        uint32_t x = mine[c];
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(x, o, 64); if (B.lane >= (uint32_t)o) x += y; }
+        incl[c] = x;
+    }
+    if (B.lane == 63) {
+#pragma unroll
+        for (int c = 0; c < CH; ++c) s_wtot[B.wave][c] = incl[c];
+    }
+    __syncthreads();
+    uint32_t total_bits = first_bit;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        uint32_t all = s_wtot[B.lane & (NW - 1)][c], before = (B.lane & (NW - 1)) < B.wave ? all : 0;
+        for (int o = NW / 2; o >= 1; o >>= 1) { all += __shfl_xor(all, o, 64); before += __shfl_xor(before, o, 64); }
+        start[c] = total_bits + before + incl[c] - mine[c];
+        total_bits += all;
+    }
+    return total_bits;
+}
+// Step 4's beginning: the LDS behind `img` zeroed for a frame of data_bytes and its CRC-16, the header bytes placed.  Every thread must
+// have passed a barrier behind its last read of what lay there.  False, for the whole workgroup, for a frame beyond the slot: the bound of
+// include/dsd2dxd_amd.h says there is none at any effort; one that broke it is dropped whole, size 0, not written past the image.
+__device__ __forceinline__ bool begin_image(uint32_t* img, uint32_t data_bytes, uint32_t slot_bytes, uint32_t* size, const uint8_t* s_hdr, const Block B) {
+    if (data_bytes + 2 > slot_bytes) { if (B.tid == 0) *size = 0; return false; }
+    for (uint32_t w = B.tid; w < ((data_bytes + 2 + 15) >> 4) * 4 + 4; w += NT) img[w] = 0;
+    __syncthreads();
+    if (B.tid < B.hdr_bytes && s_hdr[B.tid]) put_bits(img, B.tid * 8, s_hdr[B.tid], 8);
+    return true;
+}
+// the Rice code of u under k at bit p: q = u >> k zeros (the fill), the stop bit, k low bits; returns the bit behind it
+__device__ __forceinline__ uint32_t put_rice(uint32_t* img, uint32_t p, uint32_t u, uint32_t k) {
+    const uint32_t q = u >> k;
+    put_bits(img, p + q, (1u << k) | (u & ((1u << k) - 1)), k + 1);
+    return p + q + 1 + k;
+}
+// Steps 5 and 6, once every thread has placed its bits: the CRC-16 behind the data bytes, the image to the slot, the frame's size
+template <int CH>
+__device__ __forceinline__ void finish_frame(uint32_t* img, uint32_t data_bytes, EmitLds<CH>& s, uint8_t* slot, uint32_t* size, uint32_t tid) {
+    __syncthreads();
+    frame_crc16(img, data_bytes, s.crc_tab, s.crc, tid);
+    store_frame(img, slot, (data_bytes + 2 + 15) >> 4, tid);
+    if (tid == 0) *size = data_bytes + 2;
+}
+
 template <int CH>
 __global__ __launch_bounds__(NT) void flac_encode_kernel(const FlacArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];          // the block's PCM, then the frame image
     __shared__ unsigned long long s_wsum[NW][CH];
-    __shared__ uint32_t s_wtot[NW][CH];
     __shared__ uint32_t s_k[CH];
-    __shared__ uint16_t s_crc_tab[256];
-    __shared__ uint16_t s_crc[NT];
-    __shared__ uint8_t s_hdr[16];
+    __shared__ EmitLds<CH> s_emit;
 
     const FileDesc& fd = a.f[blockIdx.y];
     const uint32_t b = blockIdx.x;
     if (b >= fd.blocks) return;                                     // (the whole workgroup)
-    const uint32_t n = b + 1 == fd.blocks ? fd.last_n : BS;
-    const uint32_t depth = a.depth, sb = depth == 16 ? 2u : 3u, fb = CH * sb;
-    const uint32_t order = n > 2 ? 2u : 0u;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t frame_no = fd.first_block + b;
-    const uint32_t hdr_bytes = 4 + utf8_len(frame_no) + (n != BS ? 2u : 0u) + 1;
+    const Block B = block_context(fd, b, a.depth);
+    const uint32_t n = B.n, depth = B.depth, tid = B.tid, i0 = B.i0, sb = depth == 16 ? 2u : 3u, fb = CH * sb;
+    const bool fixed2 = n > 2;                                      // else the verbatim subframe: every sample a warm-up
 
     // 1. PCM -> LDS
     {
@@ -165,13 +240,12 @@ __global__ __launch_bounds__(NT) void flac_encode_kernel(const FlacArgs a) {
         for (uint32_t v = tid; v < nvec; v += NT) reinterpret_cast<uint4*>(smem)[v] = reinterpret_cast<const uint4*>(src)[v];
         for (uint32_t j = (nvec << 4) + tid; j < nbytes; j += NT) smem[j] = src[j];
     }
-    build_crc_tab(s_crc_tab, tid);
-    if (tid == 0) build_header(s_hdr, n, CH - 1, depth, frame_no);
+    build_crc_tab(s_emit.crc_tab, tid);
+    if (tid == 0) build_header(s_emit.hdr, n, CH - 1, depth, B.frame_no);
     __syncthreads();
 
     // 2. samples -> residuals (warm-up and verbatim samples stay as they are), sum |r|
     int32_t val[CH][SPT];
-    const uint32_t i0 = tid * SPT;
     auto sample = [&](uint32_t i, uint32_t c) -> int32_t {
         const uint8_t* q = smem + (i * CH + c) * sb;
         int32_t v = sb == 2 ? (int32_t)(int16_t)(q[0] | (q[1] << 8)) : (int32_t)((uint32_t)(q[0] | (q[1] << 8) | (q[2] << 16)) << 8) >> 8;
@@ -187,7 +261,7 @@ __global__ __launch_bounds__(NT) void flac_encode_kernel(const FlacArgs a) {
             const uint32_t i = i0 + j;
             const int32_t s0 = i < n ? sample(i, c) : 0;
             int32_t v = s0;
-            if (i < n && i >= order && order == 2) {                // |r| <= 2^25: the sink's verbatim escape (30 bits) cannot fire
+            if (i < n && i >= 2) {                                  // |r| <= 2^25
                 v = s0 - 2 * s1 + s2;
                 acc += (uint32_t)(v < 0 ? -v : v);
             }
@@ -198,112 +272,59 @@ __global__ __launch_bounds__(NT) void flac_encode_kernel(const FlacArgs a) {
         for (int o = 32; o >= 1; o >>= 1) t += __shfl_xor(t, o, 64);
         asum[c] = t;
     }
-    if (lane == 0) {
+    if (B.lane == 0) {
 #pragma unroll
-        for (int c = 0; c < CH; ++c) s_wsum[wave][c] = asum[c];
+        for (int c = 0; c < CH; ++c) s_wsum[B.wave][c] = asum[c];
     }
     __syncthreads();
     if (tid < CH) {
         unsigned long long sum = 0;
         for (int w = 0; w < NW; ++w) sum += s_wsum[w][tid];
-        const unsigned long long mean = sum / (n > 2 ? n - 2 : 1);
-        uint32_t k = 0;
-        while (k < 30 && (1ull << k) < mean) ++k;
-        s_k[tid] = k;
+        s_k[tid] = rice_k(sum, fixed2 ? n - 2 : 1);
     }
     __syncthreads();
 
-    // 3. code lengths and where every thread's bits begin
-    uint32_t kk[CH], start[CH];
-    uint32_t total_bits = hdr_bytes * 8;
-    {
-        uint32_t incl[CH], mine[CH];
+    // 3. code lengths (thread 0 holds whatever is no residual) and where every thread's bits begin
+    uint32_t kk[CH], mine[CH], start[CH];
 #pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            const uint32_t k = s_k[c];
-            kk[c] = k;
-            uint32_t len = tid == 0 ? 8 + (order == 2 ? 11u : 0u) : 0;          // subframe header; residual header in front of sample 2
+    for (int c = 0; c < CH; ++c) {
+        kk[c] = s_k[c];
+        uint32_t len = tid != 0 ? 0 : fixed2 ? fixed_header_bits(2, depth) + PARAM_BITS : SUBFRAME_BITS + n * depth;
 #pragma unroll
-            for (int j = 0; j < SPT; ++j) {
-                const uint32_t i = i0 + j;
-                if (i >= n) continue;
-                if (i < 2 || order == 0) len += depth;
-                else {
-                    const int32_t r = val[c][j];
-                    const uint32_t u = r >= 0 ? (uint32_t)r << 1 : ((uint32_t)(-r) << 1) - 1;
-                    len += (u >> k) + 1 + k;
-                }
-            }
-            mine[c] = len;
-            uint32_t x = len;
-            for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(x, o, 64); if (lane >= (uint32_t)o) x += y; }
-            incl[c] = x;
-        }
-        if (lane == 63) {
-#pragma unroll
-            for (int c = 0; c < CH; ++c) s_wtot[wave][c] = incl[c];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            uint32_t before = 0, all = 0;
-            for (int w = 0; w < NW; ++w) { const uint32_t t = s_wtot[w][c]; all += t; if ((uint32_t)w < wave) before += t; }
-            start[c] = total_bits + before + incl[c] - mine[c];
-            total_bits += all;
-        }
+        for (int j = 0; j < SPT; ++j)
+            if (i0 + j < n && i0 + j >= 2) len += (zigzag(val[c][j]) >> kk[c]) + 1 + kk[c];
+        mine[c] = len;
     }
-    const uint32_t data_bytes = (total_bits + 7) >> 3, frame_bytes = data_bytes + 2;
-    const uint32_t out_vecs = (frame_bytes + 15) >> 4;
-    // (frame_bytes <= slot_bytes by the bound of include/dsd2dxd_amd.h; a frame that broke it would be dropped whole, not written past the image)
-    if (frame_bytes > a.slot_bytes) { if (tid == 0) fd.sizes[b] = 0; return; }
+    const uint32_t data_bytes = (scan_starts<CH>(start, mine, B.hdr_bytes * 8, s_emit.wtot, B) + 7) >> 3;
 
     // 4. the image: zero fill, then the bits that are one
     uint32_t* img = reinterpret_cast<uint32_t*>(smem);
-    for (uint32_t w = tid; w < out_vecs * 4 + 4; w += NT) img[w] = 0;             // (every thread has passed the barriers behind its PCM reads)
-    __syncthreads();
-    if (tid < hdr_bytes && s_hdr[tid]) put_bits(img, tid * 8, s_hdr[tid], 8);
+    if (!begin_image(img, data_bytes, a.slot_bytes, &fd.sizes[b], s_emit.hdr, B)) return;
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
         uint32_t p = start[c];
-        const uint32_t k = kk[c];
-        if (tid == 0) { put_bits(img, p, order == 2 ? 0x14u : 0x02u, 8); p += 8; }   // 0 001010 0: fixed order 2; 0 000001 0: verbatim
+        if (tid == 0) { put_bits(img, p, fixed2 ? 0x14u : 0x02u, SUBFRAME_BITS); p += SUBFRAME_BITS; }   // 0 001010 0: fixed order 2; 0 000001 0: verbatim
 #pragma unroll
         for (int j = 0; j < SPT; ++j) {
             const uint32_t i = i0 + j;
             if (i >= n) continue;
-            if (i == 2 && order == 2) { put_bits(img, p, (1u << 9) | k, 11); p += 11; }   // 01: 5-bit Rice parameters, 0000: one partition, k
-            if (i < 2 || order == 0) {
+            if (i == 2) { put_bits(img, p, (1u << 9) | kk[c], METHOD_BITS + PARAM_BITS); p += METHOD_BITS + PARAM_BITS; }   // 01: 5-bit Rice parameters, 0000: one partition, k
+            if (i < 2) {
                 const uint32_t raw = (uint32_t)val[c][j] & ((1u << depth) - 1);
                 if (raw) put_bits(img, p, raw, depth);
                 p += depth;
-            } else {
-                const int32_t r = val[c][j];
-                const uint32_t u = r >= 0 ? (uint32_t)r << 1 : ((uint32_t)(-r) << 1) - 1;
-                const uint32_t q = u >> k;
-                put_bits(img, p + q, (1u << k) | (u & ((1u << k) - 1)), k + 1);
-                p += q + 1 + k;
-            }
+            } else p = put_rice(img, p, zigzag(val[c][j]), kk[c]);
         }
     }
-    __syncthreads();
 
     // 5. CRC-16 over the data_bytes in front of it; 6. image -> slot
-    frame_crc16(img, data_bytes, s_crc_tab, s_crc, tid);
-    store_frame(img, fd.slots + (size_t)b * a.slot_bytes, out_vecs, tid);
-    if (tid == 0) fd.sizes[b] = frame_bytes;
+    finish_frame(img, data_bytes, s_emit, fd.slots + (size_t)b * a.slot_bytes, &fd.sizes[b], tid);
 }
 
 // ---- effort 1: the search of flac_frame_enc.h -------------------------------------------------------------------------------
 
 constexpr int NP = 64;            // Rice partitions of a whole block at the finest partition order, 6: 64 samples, 16 lanes each
 
-__device__ __forceinline__ uint32_t zigzag(int32_t r) { return r >= 0 ? (uint32_t)r << 1 : ((uint32_t)(-r) << 1) - 1; }
-__device__ __forceinline__ uint32_t rice_k(unsigned long long sum, uint32_t count) {
-    const unsigned long long mean = sum / (count ? count : 1);
-    uint32_t k = 0;
-    while (k < 30 && (1ull << k) < mean) ++k;
-    return k;
-}
 // The block's PCM into LDS as planar 32-bit samples, pcm[c * BS + i]: thread t unpacks its frames 4t .. 4t+3, which are CH * SB
 // whole dwords of the source (the block begins 16-byte aligned), and writes one 16-byte vector per channel.  A short block's last,
 // partial group goes byte by byte, so that nothing behind the n frames is read.  Samples from n on stay unwritten.
@@ -443,278 +464,282 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {
     return (long long)(((unsigned long long)(long long)hi << 44) + ((unsigned long long)mid << 22) + lo);
 }
 
+// ---- the stages of the search kernel (the letters are those of its head comment) ------------------------------------------------
+
+// row `which` of u, without indexing registers by a variable
+template <int N>
+__device__ __forceinline__ void pick(uint32_t (&out)[SPT], const uint32_t (&u)[N][SPT], uint32_t which) {
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+        out[j] = u[0][j];
+#pragma unroll
+        for (int s = 1; s < N; ++s) if (which == (uint32_t)s) out[j] = u[s][j];
+    }
+}
+// (a) and (h), the part they share: N residual sets of this thread's four samples as u = zigzag(r), set s coded from sample
+// FIRST + STEP s on; len[s] = the exact length of its codes under one k, that of its sum |r| = sum (u + 1) >> 1: one N-wide 64-bit
+// reduction (|r| < 2^30: below 2^48), threads 0 .. N-1 derive the N k, one N-wide reduction of the lengths.
+template <int N, int FIRST, int STEP>
+__device__ __forceinline__ void rice_costs(uint32_t (&len)[N], const uint32_t (&u)[N][SPT], const Block B, uint32_t* s_ko, unsigned long long* s_red) {
+    auto coded = [&](int s, int j) -> bool { return B.i0 + j < B.n && B.i0 + j >= (uint32_t)(FIRST + STEP * s); };
+    unsigned long long sum[N];
+#pragma unroll
+    for (int s = 0; s < N; ++s) {
+        sum[s] = 0;
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) if (coded(s, j)) sum[s] += (u[s][j] + 1) >> 1;
+    }
+    wg_sum<N>(sum, s_red, B.lane, B.wave);
+    if (B.tid < (uint32_t)N) {
+        unsigned long long mine = sum[0];
+#pragma unroll
+        for (int s = 1; s < N; ++s) if (B.tid == (uint32_t)s) mine = sum[s];
+        const uint32_t first = FIRST + STEP * B.tid;
+        s_ko[B.tid] = rice_k(mine, B.n > first ? B.n - first : 1);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < N; ++s) {
+        const uint32_t k = s_ko[s];
+        len[s] = 0;
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) if (coded(s, j)) len[s] += (u[s][j] >> k) + 1 + k;
+    }
+    wg_sum<N>(len, s_red, B.lane, B.wave);
+}
+// (a) for signal sg of `bits` bits: the fixed order with the least exact cost at one partition, the smallest at a tie (rule 5); an
+// unsearched frame (n < 16) gets effort 0's: order 2, or verbatim (every sample a warm-up).  uo = that order's residuals.
+template <int CH>
+__device__ __forceinline__ uint32_t fixed_order(uint32_t (&uo)[SPT], uint32_t bits, const int32_t* pcm, const Block B, uint32_t sg, uint32_t* s_ko, unsigned long long* s_red) {
+    uint32_t u[5][SPT], len[5], order = 0, cost = 0;
+    int32_t x[8];
+    load_window<CH>(x, pcm, B.i0, B.n, sg);
+#pragma unroll
+    for (int o = 0; o < 5; ++o) {
+        if (o) difference(x, o);
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) u[o][j] = zigzag(x[4 + j]);
+    }
+    rice_costs<5, 0, 1>(len, u, B, s_ko, s_red);
+#pragma unroll
+    for (int o = 0; o < 5; ++o) {
+        const uint32_t c = fixed_header_bits(o, bits) + PARAM_BITS + len[o];
+        if (o == 0 || c < cost) { order = o; cost = c; }
+    }
+    if (B.n < 16) order = B.n > 2 ? 2u : B.n;
+    pick<5>(uo, u, order);
+    return order;
+}
+// (h): the candidate of `valid` (not 0) with the least exact cost at one partition, the smaller order at a tie (rule 16); its
+// residuals, 64-bit multiply-adds from the PCM plane, in uo
+template <int CH>
+__device__ __forceinline__ uint32_t lpc_order(uint32_t (&uo)[SPT], uint32_t bits, uint32_t valid, const d2dlpc::LpcCoefs& s_cand, const int32_t* pcm, const Block B,
+                                              uint32_t sg, uint32_t* s_ko, unsigned long long* s_red) {
+    using namespace d2dlpc;
+    uint32_t u[CANDIDATES][SPT], len[CANDIDATES], best = 0, cost = 0;
+    int32_t xw[16];
+    load_window16<CH>(xw, pcm, B.i0, B.n, sg);
+#pragma unroll
+    for (int c = 0; c < CANDIDATES; ++c) {                          // (a candidate that does not exist: zeros, its cost unused)
+        int32_t r[SPT] = {0, 0, 0, 0};
+        if (valid >> c & 1u) lpc_residuals4(r, xw, s_cand.q[c], s_cand.shift[c]);
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) u[c][j] = zigzag(r[j]);
+    }
+    rice_costs<CANDIDATES, 4, 4>(len, u, B, s_ko, s_red);
+    bool any = false;
+#pragma unroll
+    for (int c = 0; c < CANDIDATES; ++c) {
+        const uint32_t cc = lpc_header_bits(4 * (c + 1), bits) + PARAM_BITS + len[c];
+        if ((valid >> c & 1u) && (!any || cc < cost)) { any = true; best = c; cost = cc; }
+    }
+    pick<CANDIDATES>(uo, u, best);
+    return best;
+}
+// (b) and (c) for one residual set uo of predictor order `order` with hdrbits in front of its partitions: the partition order and
+// the subframe's exact cost.  s_psum must be zero, a barrier passed since; s_kt keeps the k of every partition of every order.
+struct Partitions { uint32_t porder, cost; };
+__device__ __forceinline__ Partitions partition_search(const uint32_t (&uo)[SPT], uint32_t order, uint32_t hdrbits, const Block B,
+                                                       unsigned long long* s_psum, uint8_t* s_kt, unsigned long long* s_red) {
+    const uint32_t n = B.n, i0 = B.i0, tid = B.tid;
+    // (b) sum |r| per finest partition, then k for every partition of every order
+    if (n == BS) {                                                  // 16 lanes hold one partition
+        unsigned long long t = 0;
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) if (i0 + j >= order) t += (uo[j] + 1) >> 1;
+        t = row_sum(t);
+        if ((B.lane & 15u) == 0) s_psum[tid >> 4] = t;
+    } else {
+        unsigned long long run = 0;
+        uint32_t pj = B.pj0, rem = B.rem0;
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) {
+            if (i0 + j < n && i0 + j >= order) run += (uo[j] + 1) >> 1;
+            const bool ends = j == SPT - 1 || rem + 1 == B.fsz;
+            if (ends && run) { atomicAdd(&s_psum[pj], run); run = 0; }         // (run != 0 only below n: pj < 2^pmax)
+            if (++rem == B.fsz) { rem = 0; ++pj; }
+        }
+    }
+    __syncthreads();
+    if (tid < 2 * NP - 1) {
+        const uint32_t p = 31u - (uint32_t)__clz(tid + 1), j = tid + 1 - (1u << p);
+        if (p <= B.pmax) {
+            const uint32_t span = 1u << (B.pmax - p);
+            unsigned long long sum = 0;
+            for (uint32_t t = 0; t < span; ++t) sum += s_psum[j * span + t];
+            s_kt[tid] = (uint8_t)rice_k(sum, (n >> p) - (j == 0 ? order : 0u));
+        }
+    }
+    __syncthreads();
+
+    // (c) the cost of every partition order
+    uint32_t plen[7];
+#pragma unroll
+    for (int p = 0; p < 7; ++p) plen[p] = 0;
+    uint32_t pj = B.pj0, rem = B.rem0;
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+        if (i0 + j < n && i0 + j >= order) {
+#pragma unroll
+            for (int p = 0; p < 7; ++p)
+                if ((uint32_t)p <= B.pmax) { const uint32_t k = s_kt[(1u << p) - 1 + (pj >> (B.pmax - p))]; plen[p] += (uo[j] >> k) + 1 + k; }
+        }
+        if (++rem == B.fsz) { rem = 0; ++pj; }
+    }
+    wg_sum<7>(plen, s_red, B.lane, B.wave);
+    Partitions best = {0, hdrbits + PARAM_BITS + plen[0]};
+#pragma unroll
+    for (int p = 1; p < 7; ++p) {                                   // the smallest partition order wins a tie
+        const uint32_t c = hdrbits + (PARAM_BITS << p) + plen[p];
+        if ((uint32_t)p <= B.pmax && c < best.cost) { best.porder = p; best.cost = c; }
+    }
+    return best;
+}
+// (f) and (g) for signal sg: the windowed signal into yplane; R(0 .. 12) from every thread's four y and their twelve predecessors by
+// three-limb wave sums and 64-bit LDS adds (exact, whatever the order of arrival); thread 0 runs flac_lpc.h from R to the candidates in
+// s_cand (coefficients zero from their order on), the others wait at the barrier.  Returns the valid mask.
+template <int CH>
+__device__ __forceinline__ uint32_t lpc_candidates(d2dlpc::LpcCoefs& s_cand, unsigned long long* s_R, int32_t* yplane, const int32_t* pcm, const Block B, uint32_t sg) {
+    using namespace d2dlpc;
+    const uint32_t n = B.n, i0 = B.i0;
+    {
+        int32_t xw[16];
+        load_window16<CH>(xw, pcm, i0, n, sg);
+        const uint32_t ws = lpc_window_shift(n);
+        int32_t y[SPT];
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) y[j] = i0 + j < n ? lpc_window(xw[12 + j], i0 + j, n, ws) : 0;
+        *reinterpret_cast<int4*>(yplane + i0) = make_int4(y[0], y[1], y[2], y[3]);
+    }
+    if (B.tid <= (uint32_t)MAX_ORDER) s_R[B.tid] = 0;
+    __syncthreads();
+    {
+        int32_t yw[16];
+        const int4 z = make_int4(0, 0, 0, 0);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int4 l = i0 + 4 * v >= 12 ? *reinterpret_cast<const int4*>(yplane + i0 + 4 * v - 12) : z;
+            yw[4 * v] = l.x; yw[4 * v + 1] = l.y; yw[4 * v + 2] = l.z; yw[4 * v + 3] = l.w;
+        }
+#pragma unroll
+        for (int l = 0; l <= MAX_ORDER; ++l) {
+            long long part = 0;                                     // |y| <= 2^24: a thread's part stays below 2^50, a wave's below 2^56
+#pragma unroll
+            for (int j = 0; j < SPT; ++j) part += (long long)yw[12 + j] * yw[12 + j - l];
+            part = wave_sum_i64(part);
+            if (B.lane == 0) atomicAdd(&s_R[l], (unsigned long long)part);
+        }
+    }
+    __syncthreads();
+    if (B.tid == 0) {
+        int64_t R[MAX_ORDER + 1];
+#pragma unroll
+        for (int l = 0; l <= MAX_ORDER; ++l) R[l] = (int64_t)s_R[l];
+        LpcCoefs co;
+        lpc_coefficients(R, co);
+#pragma unroll
+        for (int c = 0; c < CANDIDATES; ++c) {
+            if (!(co.valid >> c & 1u)) continue;
+#pragma unroll
+            for (int j = 0; j < MAX_ORDER; ++j) s_cand.q[c][j] = j < 4 * (c + 1) ? co.q[c][j] : 0;
+            s_cand.shift[c] = co.shift[c];
+        }
+        s_cand.valid = co.valid;
+    }
+    __syncthreads();
+    return s_cand.valid;
+}
+
 //   flac_search_kernel<CH, LPC>   the same workgroup, with the decisions of effort 1 between "PCM in LDS" and "place bits".  Candidate
-//   signals (the channels; for two channels also mid and side) go through (a) to (c) one at a time, so that one signal's five
+//   signals (the channels; for two channels also mid and side) go through their stages one at a time, so that one signal's five
 //   residual sets are all the registers hold:
-//     (a) sum |r_o| for o = 0 .. 4, one five-wide 64-bit reduction; threads 0 .. 4 derive the five k; the code lengths under them,
-//         one five-wide reduction; every thread picks the order from the five exact costs
-//     (b) sum |r| of the chosen order per finest partition (n >> pmax samples): for a whole block 16 lanes, one DPP row sum; for
-//         a short block whatever the samples fall into, by LDS adds.  Threads 0 .. 126 add them up to the partitions of every order
-//         p <= pmax and derive their k: the table s_kt
-//     (c) every thread's code lengths under each p's k, one seven-wide reduction; every thread picks the partition order; the chosen
-//         order's k row is kept per signal
+//     (a) fixed_order, (b) and (c) partition_search: the signal's effort-1 plan; the chosen partition order's k row is kept per signal
+//     LPC (effort 12, rules 9 to 19 of flac_frame_enc.h; frames of 64 samples and more): (f) and (g) lpc_candidates, (h) lpc_order,
+//     (i) partition_search once more; the signal keeps its effort-1 plan unless this one is strictly cheaper
 //     (d) two channels: the assignment from the four signals' costs
-//     (e) per subframe the chosen signal's residuals again, now kept; lengths with the residual header in front of sample `order` and
-//         a 5-bit k in front of every partition's first residual; then the scan, the image, the CRC and the slot as at effort 0.
+//     (e) per subframe the chosen signal's residuals again (an LPC subframe's from the kept coefficients), now kept; lengths with the
+//         residual header in front of sample `order` and a 5-bit k in front of every partition's first residual; then the emit path.
 //   A frame of fewer than 16 samples takes the same path with the choices forced to effort 0's.
-//   LPC (effort 12, rules 9 to 19 of flac_frame_enc.h; frames of 64 samples and more): behind (c) a signal goes through
-//     (f) y = the windowed signal into an LDS plane of its own behind the PCM; every thread's part of R(0 .. 12) from its four y and
-//         their twelve predecessors, 64-bit; three-limb wave sums, then 64-bit LDS adds: exact, whatever the order of arrival
-//     (g) thread 0 runs flac_lpc.h from R to the quantised coefficients of orders 4, 8 and 12; the others wait at the barrier
-//     (h) the three residual sets by 64-bit multiply-adds from the PCM plane, their k and their costs at one partition as in (a)
-//     (i) (b) and (c) once more for the best order; the signal keeps its effort-1 plan unless this one is strictly cheaper
-//   and (e) forms an LPC subframe's residuals and header from the kept coefficients.
+struct Plan { uint32_t order, porder, cost; };                      // what (a) to (c), or (f) to (i), chose for a signal
+struct KeptLpc { int32_t q[d2dlpc::MAX_ORDER], shift; uint32_t lpc; };      // a signal's coefficients (zero from its order on), and whether its plan is LPC
+
 template <int CH, bool LPC>
 __global__ __launch_bounds__(NT) void flac_search_kernel(const FlacArgs a) {
+    using namespace d2dlpc;
     constexpr int NSIG = CH == 2 ? 4 : CH;
     extern __shared__ __align__(16) unsigned char smem[];          // the block's PCM as planar 32-bit samples, then the frame image
     __shared__ unsigned long long s_red[NW * 8];
     __shared__ unsigned long long s_psum[NP];
-    __shared__ uint32_t s_wtot[NW][CH];
     __shared__ uint32_t s_ko[5];
-    __shared__ uint32_t s_sel[NSIG][3];                             // order, partition order, cost of each signal
+    __shared__ Plan s_plan[NSIG];
     __shared__ uint8_t s_kt[2 * NP];                                // k of partition j at partition order p: s_kt[2^p - 1 + j]
     __shared__ uint8_t s_ksel[NSIG][NP];                            // ... the chosen order's row
-    __shared__ unsigned long long s_R[LPC ? d2dlpc::MAX_ORDER + 1 : 1];
-    __shared__ int32_t s_co[LPC ? d2dlpc::CANDIDATES * d2dlpc::MAX_ORDER + d2dlpc::CANDIDATES + 1 : 1];   // q, the shifts, the valid bits
-    __shared__ int32_t s_lq[LPC ? NSIG : 1][d2dlpc::MAX_ORDER + 2];  // a signal's kept coefficients (zero from its order on), shift, and whether its plan is LPC
-    __shared__ uint16_t s_crc_tab[256];
-    __shared__ uint16_t s_crc[NT];
-    __shared__ uint8_t s_hdr[16];
+    __shared__ KeptLpc s_lpc[LPC ? NSIG : 1];                       // (without LPC a placeholder)
+    __shared__ EmitLds<CH> s_emit;
 
     const FileDesc& fd = a.f[blockIdx.y];
     const uint32_t b = blockIdx.x;
     if (b >= fd.blocks) return;                                     // (the whole workgroup)
-    const uint32_t n = b + 1 == fd.blocks ? fd.last_n : BS;
-    const uint32_t depth = a.depth, sb = depth == 16 ? 2u : 3u, fb = CH * sb;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t frame_no = fd.first_block + b;
-    const uint32_t hdr_bytes = 4 + utf8_len(frame_no) + (n != BS ? 2u : 0u) + 1;
+    const Block B = block_context(fd, b, a.depth);
+    const uint32_t n = B.n, depth = B.depth, tid = B.tid, i0 = B.i0, pmax = B.pmax, fsz = B.fsz;
     const bool searched = n >= 16;
-    // the largest p <= 6 with n % 2^p == 0 and (n >> p) >= 16; the finest partitions and where this thread's samples lie in them
-    const uint32_t pmax = searched ? min(6u, min((uint32_t)__ffs(n) - 1u, 27u - (uint32_t)__clz(n))) : 0u;
-    const uint32_t fsz = n >> pmax, i0 = tid * SPT, pj0 = i0 / fsz, rem0 = i0 - pj0 * fsz;
 
     int32_t* pcm = reinterpret_cast<int32_t*>(smem);
     int32_t* yplane = pcm + CH * BS;                                // (LPC only: the launch asks for it)
-    load_planar<CH>(pcm, fd.pcm + (size_t)b * BS * fb, n, depth, tid);
-    build_crc_tab(s_crc_tab, tid);
+    load_planar<CH>(pcm, fd.pcm + (size_t)b * BS * CH * (depth == 16 ? 2u : 3u), n, depth, tid);
+    build_crc_tab(s_emit.crc_tab, tid);
     __syncthreads();
 
+    // a signal's plan and the k row of its partition order, which the partition search has just left in s_kt
+    auto keep = [&](uint32_t sg, uint32_t order, Partitions part, bool lpc) {
+        if (tid == 0) { s_plan[sg] = Plan{order, part.porder, part.cost}; if (LPC) s_lpc[sg].lpc = lpc; }
+        if (tid < (1u << part.porder)) s_ksel[sg][tid] = s_kt[(1u << part.porder) - 1 + tid];
+    };
 #pragma unroll 1
     for (uint32_t sg = 0; sg < (uint32_t)NSIG; ++sg) {
         const uint32_t bits = CH == 2 && sg == 3 ? depth + 1 : depth;
-        if (tid < NP) s_psum[tid] = 0;                              // (read last before the barriers of the previous round's sums)
-        // (a) the five residual sets as u = zigzag(r); |r| = (u + 1) >> 1
-        uint32_t u[5][SPT];
-        unsigned long long asum[5];
-        {
-            int32_t x[8];
-            load_window<CH>(x, pcm, i0, n, sg);
-#pragma unroll
-            for (int o = 0; o < 5; ++o) {
-                if (o) difference(x, o);
-                uint32_t acc = 0;                                   // |r_4| <= 2^28: four of them fit
-#pragma unroll
-                for (int j = 0; j < SPT; ++j) {
-                    u[o][j] = zigzag(x[4 + j]);
-                    if (i0 + j < n && i0 + j >= (uint32_t)o) acc += (u[o][j] + 1) >> 1;
-                }
-                asum[o] = acc;
-            }
-        }
-        wg_sum<5>(asum, s_red, lane, wave);
-        if (tid < 5) s_ko[tid] = rice_k(tid == 0 ? asum[0] : tid == 1 ? asum[1] : tid == 2 ? asum[2] : tid == 3 ? asum[3] : asum[4], n > tid ? n - tid : 1);
-        __syncthreads();
-        uint32_t len[5];
-#pragma unroll
-        for (int o = 0; o < 5; ++o) {
-            const uint32_t k = s_ko[o];
-            len[o] = 0;
-#pragma unroll
-            for (int j = 0; j < SPT; ++j)
-                if (i0 + j < n && i0 + j >= (uint32_t)o) len[o] += (u[o][j] >> k) + 1 + k;
-        }
-        wg_sum<5>(len, s_red, lane, wave);
-        uint32_t order = 0, cost = 0;
-#pragma unroll
-        for (int o = 0; o < 5; ++o) {                               // the smallest order wins a tie
-            const uint32_t c = 8 + o * bits + 6 + 5 + len[o];
-            if (o == 0 || c < cost) { order = o; cost = c; }
-        }
-        if (!searched) order = n > 2 ? 2u : n;                      // effort 0's frame: order 2, or verbatim (every sample a warm-up)
-
+        // the effort-1 plan (rules 3 to 6): (a) the predictor order, (b) and (c) its partition order
+        if (tid < NP) s_psum[tid] = 0;                              // (read last before the barriers of the previous plan's sums)
         uint32_t uo[SPT];
-#pragma unroll
-        for (int j = 0; j < SPT; ++j) uo[j] = order == 0 ? u[0][j] : order == 1 ? u[1][j] : order == 2 ? u[2][j] : order == 3 ? u[3][j] : u[4][j];
-        uint32_t hdrbits = 8 + order * bits + 6;                    // in front of the partitions: subframe header, warm-up, 01 pppp
-        uint32_t cost1 = 0, lbest = 0;
-        // pass 0: (b) and (c) for the fixed order; LPC only, pass 1: (f) to (h), then (b) and (c) again for the best LPC order.
-        // (The loop's body keeps effort 1's indentation: with LPC = false it is effort 1's code, run once.)
-#pragma unroll 1
-        for (int pass = 0; pass < (LPC ? 2 : 1); ++pass) {
-        if (LPC && pass == 1) {
-            if (n < d2dlpc::MIN_FRAME) break;
-            if (tid < NP) s_psum[tid] = 0;                          // (read last before the barriers of pass 0's sums)
-            // (f) the windowed signal, its autocorrelation
-            {
-                int32_t xw[16];
-                load_window16<CH>(xw, pcm, i0, n, sg);
-                const uint32_t ws = d2dlpc::lpc_window_shift(n);
-                int32_t y[SPT];
-#pragma unroll
-                for (int j = 0; j < SPT; ++j) y[j] = i0 + j < n ? d2dlpc::lpc_window(xw[12 + j], i0 + j, n, ws) : 0;
-                *reinterpret_cast<int4*>(yplane + i0) = make_int4(y[0], y[1], y[2], y[3]);
-            }
-            if (tid <= (uint32_t)d2dlpc::MAX_ORDER) s_R[tid] = 0;
-            __syncthreads();
-            {
-                int32_t yw[16];
-                const int4 z = make_int4(0, 0, 0, 0);
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int4 l = i0 + 4 * v >= 12 ? *reinterpret_cast<const int4*>(yplane + i0 + 4 * v - 12) : z;
-                    yw[4 * v] = l.x; yw[4 * v + 1] = l.y; yw[4 * v + 2] = l.z; yw[4 * v + 3] = l.w;
-                }
-#pragma unroll
-                for (int l = 0; l <= d2dlpc::MAX_ORDER; ++l) {
-                    long long part = 0;                             // |y| <= 2^24: a thread's part stays below 2^50, a wave's below 2^56
-#pragma unroll
-                    for (int j = 0; j < SPT; ++j) part += (long long)yw[12 + j] * yw[12 + j - l];
-                    part = wave_sum_i64(part);
-                    if (lane == 0) atomicAdd(&s_R[l], (unsigned long long)part);
-                }
-            }
-            __syncthreads();
-            // (g) from R to coefficients: one lane
-            if (tid == 0) {
-                int64_t R[d2dlpc::MAX_ORDER + 1];
-#pragma unroll
-                for (int l = 0; l <= d2dlpc::MAX_ORDER; ++l) R[l] = (int64_t)s_R[l];
-                d2dlpc::LpcCoefs co;
-                d2dlpc::lpc_coefficients(R, co);
-#pragma unroll
-                for (int c = 0; c < d2dlpc::CANDIDATES; ++c) {
-                    if (!(co.valid >> c & 1u)) continue;
-#pragma unroll
-                    for (int j = 0; j < d2dlpc::MAX_ORDER; ++j) s_co[c * d2dlpc::MAX_ORDER + j] = j < 4 * (c + 1) ? co.q[c][j] : 0;
-                    s_co[d2dlpc::CANDIDATES * d2dlpc::MAX_ORDER + c] = co.shift[c];
-                }
-                s_co[d2dlpc::CANDIDATES * (d2dlpc::MAX_ORDER + 1)] = (int32_t)co.valid;
-            }
-            __syncthreads();
-            const uint32_t valid = (uint32_t)s_co[d2dlpc::CANDIDATES * (d2dlpc::MAX_ORDER + 1)];
-            if (!valid) break;
-            // (h) the residuals of the three orders, their costs at one partition
-            int32_t xw[16];
-            load_window16<CH>(xw, pcm, i0, n, sg);
-            uint32_t ul[d2dlpc::CANDIDATES][SPT];
-            unsigned long long lsum[d2dlpc::CANDIDATES];
-#pragma unroll
-            for (int c = 0; c < d2dlpc::CANDIDATES; ++c) {
-                unsigned long long acc = 0;                         // |r| < 2^30
-                if (valid >> c & 1u) {
-                    int32_t r[SPT];
-                    lpc_residuals4(r, xw, &s_co[c * d2dlpc::MAX_ORDER], s_co[d2dlpc::CANDIDATES * d2dlpc::MAX_ORDER + c]);
-#pragma unroll
-                    for (int j = 0; j < SPT; ++j) {
-                        ul[c][j] = zigzag(r[j]);
-                        if (i0 + j < n && i0 + j >= 4u * (c + 1)) acc += (ul[c][j] + 1) >> 1;
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < SPT; ++j) ul[c][j] = 0;
-                }
-                lsum[c] = acc;
-            }
-            wg_sum<d2dlpc::CANDIDATES>(lsum, s_red, lane, wave);
-            if (tid < (uint32_t)d2dlpc::CANDIDATES) s_ko[tid] = rice_k(tid == 0 ? lsum[0] : tid == 1 ? lsum[1] : lsum[2], n - 4 * (tid + 1));
-            __syncthreads();
-            uint32_t llen[d2dlpc::CANDIDATES];
-#pragma unroll
-            for (int c = 0; c < d2dlpc::CANDIDATES; ++c) {
-                const uint32_t k = s_ko[c];
-                llen[c] = 0;
-#pragma unroll
-                for (int j = 0; j < SPT; ++j)
-                    if (i0 + j < n && i0 + j >= 4u * (c + 1)) llen[c] += (ul[c][j] >> k) + 1 + k;
-            }
-            wg_sum<d2dlpc::CANDIDATES>(llen, s_red, lane, wave);
-            bool any = false;
-            uint32_t lcost = 0;
-#pragma unroll
-            for (int c = 0; c < d2dlpc::CANDIDATES; ++c) {         // the smaller order wins a tie
-                const uint32_t P = 4 * (c + 1), cc = 8 + P * bits + 9 + 14 * P + 6 + 5 + llen[c];
-                if ((valid >> c & 1u) && (!any || cc < lcost)) { any = true; lbest = c; lcost = cc; }
-            }
-            order = 4 * (lbest + 1);
-            hdrbits = 8 + order * bits + 9 + 14 * order + 6;
-#pragma unroll
-            for (int j = 0; j < SPT; ++j) uo[j] = lbest == 0 ? ul[0][j] : lbest == 1 ? ul[1][j] : ul[2][j];
-        }
+        const uint32_t order = fixed_order<CH>(uo, bits, pcm, B, sg, s_ko, s_red);
+        const Partitions fixed = partition_search(uo, order, fixed_header_bits(order, bits), B, s_psum, s_kt, s_red);
+        keep(sg, order, fixed, false);
 
-        // (b) sum |r| per finest partition, then k for every partition of every order
-        if (n == BS) {                                              // 16 lanes hold one partition
-            unsigned long long t = 0;
-#pragma unroll
-            for (int j = 0; j < SPT; ++j) if (i0 + j >= order) t += (uo[j] + 1) >> 1;
-            t = row_sum(t);
-            if ((lane & 15u) == 0) s_psum[tid >> 4] = t;
-        } else {
-            unsigned long long run = 0;
-            uint32_t pj = pj0, rem = rem0;
-#pragma unroll
-            for (int j = 0; j < SPT; ++j) {
-                if (i0 + j < n && i0 + j >= order) run += (uo[j] + 1) >> 1;
-                const bool ends = j == SPT - 1 || rem + 1 == fsz;
-                if (ends && run) { atomicAdd(&s_psum[pj], run); run = 0; }     // (run != 0 only below n: pj < 2^pmax)
-                if (++rem == fsz) { rem = 0; ++pj; }
-            }
-        }
-        __syncthreads();
-        if (tid < 2 * NP - 1) {
-            const uint32_t p = 31u - (uint32_t)__clz(tid + 1), j = tid + 1 - (1u << p);
-            if (p <= pmax) {
-                const uint32_t span = 1u << (pmax - p);
-                unsigned long long sum = 0;
-                for (uint32_t t = 0; t < span; ++t) sum += s_psum[j * span + t];
-                s_kt[tid] = (uint8_t)rice_k(sum, (n >> p) - (j == 0 ? order : 0u));
-            }
-        }
-        __syncthreads();
-
-        // (c) the cost of every partition order
-        uint32_t plen[7];
-#pragma unroll
-        for (int p = 0; p < 7; ++p) plen[p] = 0;
-        {
-            uint32_t pj = pj0, rem = rem0;
-#pragma unroll
-            for (int j = 0; j < SPT; ++j) {
-                if (i0 + j < n && i0 + j >= order) {
-#pragma unroll
-                    for (int p = 0; p < 7; ++p)
-                        if ((uint32_t)p <= pmax) { const uint32_t k = s_kt[(1u << p) - 1 + (pj >> (pmax - p))]; plen[p] += (uo[j] >> k) + 1 + k; }
-                }
-                if (++rem == fsz) { rem = 0; ++pj; }
-            }
-        }
-        wg_sum<7>(plen, s_red, lane, wave);
-        uint32_t porder = 0;
-#pragma unroll
-        for (int p = 0; p < 7; ++p) {                               // the smallest partition order wins a tie
-            const uint32_t c = hdrbits + (5u << p) + plen[p];
-            if (p == 0) cost = c;
-            else if ((uint32_t)p <= pmax && c < cost) { porder = p; cost = c; }
-        }
-        if (LPC && pass == 1) {                                     // (i) the LPC plan only where it is strictly cheaper
-            if (!(cost < cost1)) break;
-            if (tid < (uint32_t)d2dlpc::MAX_ORDER) s_lq[sg][tid] = s_co[lbest * d2dlpc::MAX_ORDER + tid];
-            if (tid == 0) { s_lq[sg][d2dlpc::MAX_ORDER] = s_co[d2dlpc::CANDIDATES * d2dlpc::MAX_ORDER + lbest]; s_lq[sg][d2dlpc::MAX_ORDER + 1] = 1; }
-        } else if (LPC && tid == 0) s_lq[sg][d2dlpc::MAX_ORDER + 1] = 0;
-        cost1 = cost;
-        if (tid == 0) { s_sel[sg][0] = order; s_sel[sg][1] = porder; s_sel[sg][2] = cost; }
-        if (tid < (1u << porder)) s_ksel[sg][tid] = s_kt[(1u << porder) - 1 + tid];
+        // the LPC plan (rules 11 to 16): (f) and (g) the candidates, (h) the order, (i) its partition order; it replaces the effort-1
+        // plan only where it is strictly cheaper (rule 17)
+        if constexpr (LPC) {
+            __shared__ unsigned long long s_R[MAX_ORDER + 1];
+            __shared__ LpcCoefs s_cand;
+            if (n < MIN_FRAME) continue;
+            if (tid < NP) s_psum[tid] = 0;                          // (read last before the barriers of the effort-1 plan's sums)
+            const uint32_t valid = lpc_candidates<CH>(s_cand, s_R, yplane, pcm, B, sg);
+            if (!valid) continue;
+            const uint32_t best = lpc_order<CH>(uo, bits, valid, s_cand, pcm, B, sg, s_ko, s_red), P = 4 * (best + 1);
+            const Partitions lpc = partition_search(uo, P, lpc_header_bits(P, bits), B, s_psum, s_kt, s_red);
+            if (!(lpc.cost < fixed.cost)) continue;
+            if (tid < (uint32_t)MAX_ORDER) s_lpc[sg].q[tid] = s_cand.q[best][tid];
+            if (tid == 0) s_lpc[sg].shift = s_cand.shift[best];
+            keep(sg, P, lpc, true);
         }
     }
     __syncthreads();
@@ -722,13 +747,13 @@ __global__ __launch_bounds__(NT) void flac_search_kernel(const FlacArgs a) {
     // (d) the channel assignment: independent, left/side, side/right, mid/side; ties in this order
     uint32_t mode = 0;
     if (CH == 2 && searched) {
-        const uint32_t L = s_sel[0][2], R = s_sel[1][2], M = s_sel[NSIG > 2 ? 2 : 0][2], S = s_sel[NSIG > 3 ? 3 : 0][2];
+        const uint32_t L = s_plan[0].cost, R = s_plan[1].cost, M = s_plan[NSIG > 2 ? 2 : 0].cost, S = s_plan[NSIG > 3 ? 3 : 0].cost;
         uint32_t total = L + R;
         if (L + S < total) { total = L + S; mode = 1; }
         if (S + R < total) { total = S + R; mode = 2; }
         if (M + S < total) { total = M + S; mode = 3; }
     }
-    if (tid == 0) build_header(s_hdr, n, mode == 0 ? CH - 1 : 7 + mode, depth, frame_no);
+    if (tid == 0) build_header(s_emit.hdr, n, mode == 0 ? CH - 1 : 7 + mode, depth, B.frame_no);
     auto subframe_signal = [&](int c) -> uint32_t {
         if (CH != 2) return (uint32_t)c;
         return c == 0 ? (mode == 2 ? 3u : mode == 3 ? 2u : 0u) : (mode == 0 || mode == 2 ? 1u : 3u);
@@ -736,86 +761,62 @@ __global__ __launch_bounds__(NT) void flac_search_kernel(const FlacArgs a) {
 
     // (e) the chosen residuals (warm-up samples as they are), code lengths, and where every thread's bits begin
     int32_t val[CH][SPT];
-    uint32_t start[CH];
-    uint32_t total_bits = hdr_bytes * 8;
-    {
-        uint32_t incl[CH], mine[CH];
+    uint32_t mine[CH], start[CH];
 #pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            const uint32_t sg = subframe_signal(c), order = s_sel[sg][0], sh = pmax - s_sel[sg][1];
-            const uint32_t bits = CH == 2 && sg == 3 ? depth + 1 : depth;
-            int32_t x[8];
-            int32_t raw[SPT];
-            const bool lp = LPC && s_lq[LPC ? sg : 0][d2dlpc::MAX_ORDER + 1];
-            if (LPC && lp) {
-                int32_t xw[16], r[SPT];
-                load_window16<CH>(xw, pcm, i0, n, sg);
-                lpc_residuals4(r, xw, s_lq[sg], s_lq[sg][d2dlpc::MAX_ORDER]);
+    for (int c = 0; c < CH; ++c) {
+        const uint32_t sg = subframe_signal(c), order = s_plan[sg].order, sh = pmax - s_plan[sg].porder;
+        const uint32_t bits = CH == 2 && sg == 3 ? depth + 1 : depth;
+        const bool lp = LPC && s_lpc[LPC ? sg : 0].lpc;
+        int32_t x[8], raw[SPT];
+        if (LPC && lp) {
+            int32_t xw[16], r[SPT];
+            load_window16<CH>(xw, pcm, i0, n, sg);
+            lpc_residuals4(r, xw, s_lpc[sg].q, s_lpc[sg].shift);
 #pragma unroll
-                for (int j = 0; j < SPT; ++j) { raw[j] = xw[12 + j]; x[4 + j] = r[j]; }
-            } else {
+            for (int j = 0; j < SPT; ++j) { raw[j] = xw[12 + j]; x[4 + j] = r[j]; }
+        } else {
             load_window<CH>(x, pcm, i0, n, sg);
 #pragma unroll
             for (int j = 0; j < SPT; ++j) raw[j] = x[4 + j];
 #pragma unroll
             for (int o = 1; o < 5; ++o) if ((uint32_t)o <= order) difference(x, o);
-            }
-            uint32_t len = tid == 0 ? 8 : 0;                        // the subframe header
-            uint32_t pj = pj0, rem = rem0;
+        }
+        uint32_t len = tid == 0 ? SUBFRAME_BITS : 0;
+        uint32_t pj = B.pj0, rem = B.rem0;
 #pragma unroll
-            for (int j = 0; j < SPT; ++j) {
-                const uint32_t i = i0 + j;
-                val[c][j] = i < order ? raw[j] : x[4 + j];
-                if (i < n) {
-                    if (i < order) len += bits;
-                    else {
-                        if (i == order) len += 6;                   // 01 pppp
-                        if (LPC && lp && i == order) len += 9 + 14 * order;     // 1101 sssss and the coefficients
-                        if (i == order || (rem == 0 && (pj & ((1u << sh) - 1)) == 0)) len += 5;     // a partition's first residual: kkkkk
-                        const uint32_t k = s_ksel[sg][pj >> sh];
-                        len += (zigzag(val[c][j]) >> k) + 1 + k;
-                    }
+        for (int j = 0; j < SPT; ++j) {
+            const uint32_t i = i0 + j;
+            val[c][j] = i < order ? raw[j] : x[4 + j];
+            if (i < n) {
+                if (i < order) len += bits;
+                else {
+                    if (i == order) len += METHOD_BITS;             // 01 pppp
+                    if (LPC && lp && i == order) len += lpc_coef_bits(order);     // 1101 sssss and the coefficients
+                    if (i == order || (rem == 0 && (pj & ((1u << sh) - 1)) == 0)) len += PARAM_BITS;     // a partition's first residual: kkkkk
+                    const uint32_t k = s_ksel[sg][pj >> sh];
+                    len += (zigzag(val[c][j]) >> k) + 1 + k;
                 }
-                if (++rem == fsz) { rem = 0; ++pj; }
             }
-            mine[c] = len;
-            uint32_t y = len;
-            for (int o = 1; o < 64; o <<= 1) { const uint32_t z = __shfl_up(y, o, 64); if (lane >= (uint32_t)o) y += z; }
-            incl[c] = y;
+            if (++rem == fsz) { rem = 0; ++pj; }
         }
-        if (lane == 63) {
-#pragma unroll
-            for (int c = 0; c < CH; ++c) s_wtot[wave][c] = incl[c];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            uint32_t all = s_wtot[lane & (NW - 1)][c], before = (lane & (NW - 1)) < wave ? all : 0;      // 16 lanes hold the 16 waves' totals
-            for (int o = NW / 2; o >= 1; o >>= 1) { all += __shfl_xor(all, o, 64); before += __shfl_xor(before, o, 64); }
-            start[c] = total_bits + before + incl[c] - mine[c];
-            total_bits += all;
-        }
+        mine[c] = len;
     }
-    const uint32_t data_bytes = (total_bits + 7) >> 3, frame_bytes = data_bytes + 2;
-    const uint32_t out_vecs = (frame_bytes + 15) >> 4;
-    // (an effort-1 frame is no longer than the effort-0 frame, so the bound of include/dsd2dxd_amd.h holds; as there, a frame that broke it would be dropped whole)
-    if (frame_bytes > a.slot_bytes) { if (tid == 0) fd.sizes[b] = 0; return; }
+    const uint32_t data_bytes = (scan_starts<CH>(start, mine, B.hdr_bytes * 8, s_emit.wtot, B) + 7) >> 3;
 
     // the image: zero fill, then the bits that are one
     uint32_t* img = reinterpret_cast<uint32_t*>(smem);
-    for (uint32_t w = tid; w < out_vecs * 4 + 4; w += NT) img[w] = 0;             // (every thread has passed the barrier behind its PCM reads)
-    __syncthreads();
-    if (tid < hdr_bytes && s_hdr[tid]) put_bits(img, tid * 8, s_hdr[tid], 8);
+    if (!begin_image(img, data_bytes, a.slot_bytes, &fd.sizes[b], s_emit.hdr, B)) return;
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
-        const uint32_t sg = subframe_signal(c), order = s_sel[sg][0], porder = s_sel[sg][1], sh = pmax - porder;
+        const uint32_t sg = subframe_signal(c), order = s_plan[sg].order, porder = s_plan[sg].porder, sh = pmax - porder;
         const uint32_t bits = CH == 2 && sg == 3 ? depth + 1 : depth;
+        const bool lp = LPC && s_lpc[LPC ? sg : 0].lpc;
         uint32_t p = start[c];
-        const bool lp = LPC && s_lq[LPC ? sg : 0][d2dlpc::MAX_ORDER + 1];
-        if (LPC && lp) { if (tid == 0) { put_bits(img, p, (0x20u | (order - 1)) << 1, 8); p += 8; } }   // 0 1ppppp 0: LPC order ppppp + 1
-        else
-        if (tid == 0) { put_bits(img, p, n > 2 ? (8u | order) << 1 : 0x02u, 8); p += 8; }   // 0 001ooo 0: fixed order ooo; 0 000001 0: verbatim
-        uint32_t pj = pj0, rem = rem0;
+        if (tid == 0) {                                             // 0 1ppppp 0: LPC order ppppp + 1; 0 001ooo 0: fixed order ooo; 0 000001 0: verbatim
+            put_bits(img, p, LPC && lp ? (0x20u | (order - 1)) << 1 : n > 2 ? (8u | order) << 1 : 0x02u, SUBFRAME_BITS);
+            p += SUBFRAME_BITS;
+        }
+        uint32_t pj = B.pj0, rem = B.rem0;
 #pragma unroll
         for (int j = 0; j < SPT; ++j) {
             const uint32_t i = i0 + j;
@@ -827,24 +828,18 @@ __global__ __launch_bounds__(NT) void flac_search_kernel(const FlacArgs a) {
                 } else {
                     const uint32_t k = s_ksel[sg][pj >> sh];
                     if (LPC && lp && i == order) {                  // 1101: 14-bit coefficients; their shift; the coefficients
-                        put_bits(img, p, ((uint32_t)(d2dlpc::PRECISION - 1) << 5) | (uint32_t)s_lq[sg][d2dlpc::MAX_ORDER], 9); p += 9;
-                        for (uint32_t m = 0; m < order; ++m) { put_bits(img, p, (uint32_t)s_lq[sg][m] & 0x3FFFu, d2dlpc::PRECISION); p += d2dlpc::PRECISION; }
+                        put_bits(img, p, ((uint32_t)(PRECISION - 1) << 5) | (uint32_t)s_lpc[sg].shift, 9); p += 9;
+                        for (uint32_t m = 0; m < order; ++m) { put_bits(img, p, (uint32_t)s_lpc[sg].q[m] & 0x3FFFu, PRECISION); p += PRECISION; }
                     }
-                    if (i == order) { put_bits(img, p, (1u << 4) | porder, 6); p += 6; }          // 01: 5-bit Rice parameters, pppp
-                    if (i == order || (rem == 0 && (pj & ((1u << sh) - 1)) == 0)) { if (k) put_bits(img, p, k, 5); p += 5; }
-                    const uint32_t v = zigzag(val[c][j]), q = v >> k;
-                    put_bits(img, p + q, (1u << k) | (v & ((1u << k) - 1)), k + 1);
-                    p += q + 1 + k;
+                    if (i == order) { put_bits(img, p, (1u << 4) | porder, METHOD_BITS); p += METHOD_BITS; }      // 01: 5-bit Rice parameters, pppp
+                    if (i == order || (rem == 0 && (pj & ((1u << sh) - 1)) == 0)) { if (k) put_bits(img, p, k, PARAM_BITS); p += PARAM_BITS; }
+                    p = put_rice(img, p, zigzag(val[c][j]), k);
                 }
             }
             if (++rem == fsz) { rem = 0; ++pj; }
         }
     }
-    __syncthreads();
-
-    frame_crc16(img, data_bytes, s_crc_tab, s_crc, tid);
-    store_frame(img, fd.slots + (size_t)b * a.slot_bytes, out_vecs, tid);
-    if (tid == 0) fd.sizes[b] = frame_bytes;
+    finish_frame(img, data_bytes, s_emit, fd.slots + (size_t)b * a.slot_bytes, &fd.sizes[b], tid);
 }
 
 // sum, min and max of sizes[lo, hi) over the workgroup; every thread gets them
@@ -892,19 +887,22 @@ __global__ __launch_bounds__(PT) void flac_pack_kernel(const FlacArgs a) {
     }
 }
 
+enum class Encoder { fixed2, search, search_lpc };                  // flac_encode_kernel; flac_search_kernel<CH, false>; flac_search_kernel<CH, true>
+
 // the frame image over the block's PCM: packed as it comes at effort 0, planar 32-bit samples in the search kernel, whose LPC flavour
-// (`effort` 2 here) keeps the windowed signal's plane behind them
-size_t encode_lds_bytes(uint32_t ch, uint32_t depth, int effort) {
-    return std::max<size_t>(slot_bytes(ch, depth) + 32, (size_t)BS * ch * (effort ? 4 : sample_bytes(depth)) + (effort == 2 ? (size_t)BS * 4 : 0));
+// keeps the windowed signal's plane behind them
+size_t encode_lds_bytes(uint32_t ch, uint32_t depth, Encoder enc) {
+    const size_t pcm = (size_t)BS * ch * (enc == Encoder::fixed2 ? sample_bytes(depth) : 4) + (enc == Encoder::search_lpc ? (size_t)BS * 4 : 0);
+    return std::max<size_t>(slot_bytes(ch, depth) + 32, pcm);
 }
 
-template <int CH, int EFFORT>
+template <int CH, Encoder ENC>
 hipError_t launch_encode(const FlacArgs& a, uint32_t max_blocks, uint32_t nf, hipStream_t s) {
-    const auto kernel = EFFORT == 0 ? &flac_encode_kernel<CH> : EFFORT == 1 ? &flac_search_kernel<CH, false> : &flac_search_kernel<CH, true>;
+    const auto kernel = ENC == Encoder::fixed2 ? &flac_encode_kernel<CH> : ENC == Encoder::search ? &flac_search_kernel<CH, false> : &flac_search_kernel<CH, true>;
     // hipFuncSetAttribute acts on the current device: remembered per device, under a lock
     static std::mutex mu;
     static size_t allowed[64] = {};
-    const size_t lds = encode_lds_bytes(CH, a.depth, EFFORT);
+    const size_t lds = encode_lds_bytes(CH, a.depth, ENC);
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -921,23 +919,15 @@ hipError_t launch_encode(const FlacArgs& a, uint32_t max_blocks, uint32_t nf, hi
     return hipGetLastError();
 }
 
-template <int EFFORT>
+template <Encoder ENC, int CH = 8>                                  // ch = 1 .. 8 to launch_encode<ch, ENC>
 hipError_t launch_encode_ch(uint32_t ch, const FlacArgs& a, uint32_t max_blocks, uint32_t nf, hipStream_t s) {
-    switch (ch) {
-        case 1: return launch_encode<1, EFFORT>(a, max_blocks, nf, s);
-        case 2: return launch_encode<2, EFFORT>(a, max_blocks, nf, s);
-        case 3: return launch_encode<3, EFFORT>(a, max_blocks, nf, s);
-        case 4: return launch_encode<4, EFFORT>(a, max_blocks, nf, s);
-        case 5: return launch_encode<5, EFFORT>(a, max_blocks, nf, s);
-        case 6: return launch_encode<6, EFFORT>(a, max_blocks, nf, s);
-        case 7: return launch_encode<7, EFFORT>(a, max_blocks, nf, s);
-        default: return launch_encode<8, EFFORT>(a, max_blocks, nf, s);
-    }
+    if constexpr (CH > 1) if (ch < (uint32_t)CH) return launch_encode_ch<ENC, CH - 1>(ch, a, max_blocks, nf, s);
+    return launch_encode<CH, ENC>(a, max_blocks, nf, s);
 }
 
-int hip_fail(hipError_t e, const char* what) { return fail(D2D_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
-
 }  // namespace
+
+int d2dflac::hip_fail(hipError_t e, const char* what) { return fail(D2D_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
 
 extern "C" {
 
@@ -988,8 +978,8 @@ int d2d_flac_encode_device_effort(uint32_t channels, uint32_t bit_depth, uint32_
             max_blocks = std::max(max_blocks, d.blocks);
         }
         if (max_blocks) {
-            hipError_t e = effort == D2D_FLAC_EFFORT_LPC ? launch_encode_ch<2>(channels, a, max_blocks, nf, s)
-                         : effort == D2D_FLAC_EFFORT_SEARCH ? launch_encode_ch<1>(channels, a, max_blocks, nf, s) : launch_encode_ch<0>(channels, a, max_blocks, nf, s);
+            hipError_t e = effort == D2D_FLAC_EFFORT_LPC ? launch_encode_ch<Encoder::search_lpc>(channels, a, max_blocks, nf, s)          // (the one place efforts become encoders)
+                         : effort == D2D_FLAC_EFFORT_SEARCH ? launch_encode_ch<Encoder::search>(channels, a, max_blocks, nf, s) : launch_encode_ch<Encoder::fixed2>(channels, a, max_blocks, nf, s);
             if (e != hipSuccess) return hip_fail(e, effort == D2D_FLAC_EFFORT_FIXED2 ? "flac_encode_kernel" : "flac_search_kernel");
         }
         hipLaunchKernelGGL(flac_pack_kernel, dim3(std::max(1u, (max_blocks + PB - 1) / PB), nf), dim3(PT), 0, s, a);
@@ -1004,115 +994,3 @@ int d2d_flac_encode_device_effort(uint32_t channels, uint32_t bit_depth, uint32_
 }
 
 }  // extern "C"
-
-// ---- the whole-stream driver ---------------------------------------------------------------------------------------------------
-
-namespace {
-
-struct DevBuf {
-    void* p = nullptr; size_t bytes = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { bytes = n; return hipMalloc(&p, std::max<size_t>(n, 16)); }
-};
-struct PinBuf {
-    void* p = nullptr;
-    ~PinBuf() { if (p) (void)hipHostFree(p); }
-    hipError_t alloc(size_t n) { return hipHostMalloc(&p, std::max<size_t>(n, 16), hipHostMallocDefault); }
-};
-// All device work of the stream driver goes to the null stream: the engine remembers the stream of its last call (d2d_peak waits on
-// it), so it must not be one that ends with this function.  (The buffers' release waits for the device.)
-struct Stream { hipStream_t s = nullptr; };
-
-}  // namespace
-
-#define FLAC_HIP(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(e_, what); } while (0)
-
-extern "C" int d2d_convert_stream_flac(d2d_engine* e, uint32_t bit_depth, d2d_read_fn read, void* ru, d2d_write_fn write, void* wu,
-                                       const volatile int* cancel, d2d_progress_fn progress, void* pu,
-                                       uint64_t total, size_t chunk, d2d_flac_stream_stats* stats) {
-    return d2d_convert_stream_flac_effort(e, bit_depth, D2D_FLAC_EFFORT_FIXED2, read, ru, write, wu, cancel, progress, pu, total, chunk, stats);
-}
-
-extern "C" int d2d_convert_stream_flac_effort(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
-                                              d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
-                                              uint64_t total, size_t chunk, d2d_flac_stream_stats* stats) {
-    if (!effort_ok(effort)) return fail(D2D_ERR_PARAM, EFFORT_MESSAGE);
-    if (!e) return fail(D2D_ERR_PARAM, "null engine");
-    if (!read) return fail(D2D_ERR_PARAM, "null read callback");
-    if (!stats) return fail(D2D_ERR_PARAM, "null stats");
-    if (!depth_ok(bit_depth)) return fail(D2D_ERR_PARAM, "FLAC holds 16, 20 or 24-bit integers (Invalid bit depth)");
-    const size_t fb = d2d_frame_bytes(e), sb = sample_bytes(bit_depth);
-    if (fb == 0 || fb % sb || fb / sb > 8) return fail(D2D_ERR_PARAM, "the engine's frames do not hold 1 to 8 channels of this bit depth");
-    const uint32_t ch = (uint32_t)(fb / sb);
-    if (chunk == 0) chunk = 1u << 22;
-    // the engine's device becomes this thread's current device (d2d_peak selects it and waits for the engine's pending work)
-    double peak0 = 0.0;
-    if (d2d_peak(e, 0, 0, &peak0) != D2D_OK) return fail(D2D_ERR_DEVICE, d2d_last_error(e));
-    *stats = d2d_flac_stream_stats{0, 0, 0, 0};
-
-    // frames one chunk can add: the engine's own count for a chunk from where it stands, and a margin for the rounding of later ones
-    const size_t chunk_frames = d2d_next_frames(e, 0, chunk) + 64, cap_frames = chunk_frames + BS;
-    const size_t out_cap = d2d_flac_bound_bytes(ch, bit_depth, cap_frames, 1), ws_cap = d2d_flac_workspace_bytes(ch, bit_depth, cap_frames, 1);
-    Stream st;
-    PinBuf h_in[2], h_out, h_res;
-    DevBuf d_in, d_new, d_pcm, d_out, d_ws;
-    FLAC_HIP(h_in[0].alloc(chunk * ch), "hipHostMalloc"); FLAC_HIP(h_in[1].alloc(chunk * ch), "hipHostMalloc");
-    FLAC_HIP(h_out.alloc(out_cap), "hipHostMalloc"); FLAC_HIP(h_res.alloc(sizeof(d2d_flac_result)), "hipHostMalloc");
-    FLAC_HIP(d_in.alloc(chunk * ch), "hipMalloc"); FLAC_HIP(d_new.alloc(chunk_frames * fb), "hipMalloc");
-    FLAC_HIP(d_pcm.alloc(cap_frames * fb), "hipMalloc"); FLAC_HIP(d_out.alloc(out_cap), "hipMalloc"); FLAC_HIP(d_ws.alloc(ws_cap), "hipMalloc");
-    d2d_flac_result* res = (d2d_flac_result*)h_res.p;
-
-    size_t carry = 0;                 // frames in front of d_pcm that no block has taken yet
-    uint64_t done = 0;
-    int cur = 0;
-    long got = read(ru, (uint8_t*)h_in[cur].p, chunk);
-    if (got < 0) return fail(D2D_ERR_IO, "read callback failed");
-    while (got > 0) {
-        if (cancel && *cancel) return fail(D2D_ERR_CANCELLED, "Conversion cancelled");
-        const size_t L = (size_t)got;
-        if (L > chunk) return fail(D2D_ERR_IO, "read callback returned more than it was asked for");
-        // upload and convert; the PCM lands in a buffer of its own (the translate call wants 16-byte alignment, the end of the carry
-        // has none) and is copied behind the carry on the same stream
-        d2d_file_io tio{};
-        tio.dsd = d_in.p; tio.bytes_per_channel = L; tio.pcm = d_new.p; tio.pcm_capacity_bytes = d_new.bytes;
-        FLAC_HIP(hipMemcpyAsync(d_in.p, h_in[cur].p, L * ch, hipMemcpyHostToDevice, st.s), "hipMemcpyAsync");
-        if (d2d_translate_batch_device(e, &tio, 1, st.s) != D2D_OK) return fail(D2D_ERR_DEVICE, d2d_last_error(e));
-        const size_t nf = tio.frames_out;
-        if (carry + nf > cap_frames) return fail(D2D_ERR_STATE, "a chunk produced more frames than planned");
-        if (nf) FLAC_HIP(hipMemcpyAsync((uint8_t*)d_pcm.p + carry * fb, d_new.p, nf * fb, hipMemcpyDeviceToDevice, st.s), "hipMemcpyAsync");
-        // the next chunk is read while the GPU works: the stream ends with this chunk if there is none
-        const long next = read(ru, (uint8_t*)h_in[cur ^ 1].p, chunk);
-        if (next < 0) return fail(D2D_ERR_IO, "read callback failed");
-        d2d_flac_io fio{};
-        fio.pcm = d_pcm.p; fio.frames = carry + nf; fio.first_block = (uint32_t)stats->blocks; fio.final = next == 0;
-        fio.out = d_out.p; fio.out_capacity_bytes = d_out.bytes; fio.result = res;
-        if (stats->blocks > 0xFFFFFFFFull) return fail(D2D_ERR_PARAM, "frame numbers are 31 bits");
-        const int rc = d2d_flac_encode_device_effort(ch, bit_depth, effort, &fio, 1, d_ws.p, d_ws.bytes, st.s);
-        if (rc != D2D_OK) return rc;
-        FLAC_HIP(hipStreamSynchronize(st.s), "hipStreamSynchronize");
-        const d2d_flac_result r = *res;
-        if (r.bytes_out) {
-            FLAC_HIP(hipMemcpy(h_out.p, d_out.p, r.bytes_out, hipMemcpyDeviceToHost), "hipMemcpy");
-            if (write && write(wu, h_out.p, r.bytes_out) != 0) return fail(D2D_ERR_IO, "write callback failed");
-        }
-        if (fio.blocks) {
-            stats->min_frame_bytes = stats->blocks ? std::min(stats->min_frame_bytes, r.min_frame_bytes) : r.min_frame_bytes;
-            stats->max_frame_bytes = std::max(stats->max_frame_bytes, r.max_frame_bytes);
-            stats->blocks += fio.blocks;
-            stats->samples_per_channel += fio.frames_consumed;
-        }
-        // the remainder moves to the front (it lies wholly behind its destination: a block was taken, or nothing moves)
-        carry = fio.frames - fio.frames_consumed;
-        if (carry && fio.frames_consumed)
-            FLAC_HIP(hipMemcpyAsync(d_pcm.p, (uint8_t*)d_pcm.p + fio.frames_consumed * fb, carry * fb, hipMemcpyDeviceToDevice, st.s), "hipMemcpyAsync");
-        done += (uint64_t)L;
-        if (progress && total) {
-            float pct = (float)(100.0 * (double)done / (double)total);
-            if (pct >= 100.0f) pct = 99.99f;       // exactly 100 is reserved for the end
-            progress(pu, pct);
-        }
-        got = next; cur ^= 1;
-    }
-    if (progress) progress(pu, 100.0f);
-    return D2D_OK;
-}

@@ -26,5 +26,9 @@ inline size_t block_count(size_t frames, int final) { return frames / BS + ((fin
 
 // the message d2d_flac_error() returns (thread-local); returns `code`
 int fail(int code, const std::string& message);
+#ifdef HIP_INCLUDE_HIP_HIP_RUNTIME_API_H           // (the units that include HIP's host API in front of this header)
+// ... with "`what`: HIP's message"; returns D2D_ERR_DEVICE (d2d_flac.hip)
+int hip_fail(hipError_t e, const char* what);
+#endif
 
 }  // namespace d2dflac

@@ -1,0 +1,117 @@
+// d2d_flac_stream.cpp -- d2d_convert_stream_flac: a whole DSD stream to FLAC frames through the public calls (d2d_translate_batch_device,
+// d2d_flac_encode_device_effort) and HIP's host API.  Host code: it launches no kernel.
+#include <hip/hip_runtime_api.h>
+#include <algorithm>
+#include "d2d_flac_internal.h"
+
+using namespace d2dflac;
+
+namespace {
+
+struct DevBuf {
+    void* p = nullptr; size_t bytes = 0;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t n) { bytes = n; return hipMalloc(&p, std::max<size_t>(n, 16)); }
+};
+struct PinBuf {
+    void* p = nullptr;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t alloc(size_t n) { return hipHostMalloc(&p, std::max<size_t>(n, 16), hipHostMallocDefault); }
+};
+// All device work of the stream driver goes to the null stream: the engine remembers the stream of its last call (d2d_peak waits on
+// it), so it must not be one that ends with this function.  (The buffers' release waits for the device.)
+struct Stream { hipStream_t s = nullptr; };
+
+}  // namespace
+
+#define FLAC_HIP(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(e_, what); } while (0)
+
+extern "C" int d2d_convert_stream_flac(d2d_engine* e, uint32_t bit_depth, d2d_read_fn read, void* ru, d2d_write_fn write, void* wu,
+                                       const volatile int* cancel, d2d_progress_fn progress, void* pu,
+                                       uint64_t total, size_t chunk, d2d_flac_stream_stats* stats) {
+    return d2d_convert_stream_flac_effort(e, bit_depth, D2D_FLAC_EFFORT_FIXED2, read, ru, write, wu, cancel, progress, pu, total, chunk, stats);
+}
+
+extern "C" int d2d_convert_stream_flac_effort(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
+                                              d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
+                                              uint64_t total, size_t chunk, d2d_flac_stream_stats* stats) {
+    if (!effort_ok(effort)) return fail(D2D_ERR_PARAM, EFFORT_MESSAGE);
+    if (!e) return fail(D2D_ERR_PARAM, "null engine");
+    if (!read) return fail(D2D_ERR_PARAM, "null read callback");
+    if (!stats) return fail(D2D_ERR_PARAM, "null stats");
+    if (!depth_ok(bit_depth)) return fail(D2D_ERR_PARAM, "FLAC holds 16, 20 or 24-bit integers (Invalid bit depth)");
+    const size_t fb = d2d_frame_bytes(e), sb = sample_bytes(bit_depth);
+    if (fb == 0 || fb % sb || fb / sb > 8) return fail(D2D_ERR_PARAM, "the engine's frames do not hold 1 to 8 channels of this bit depth");
+    const uint32_t ch = (uint32_t)(fb / sb);
+    if (chunk == 0) chunk = 1u << 22;
+    // the engine's device becomes this thread's current device (d2d_peak selects it and waits for the engine's pending work)
+    double peak0 = 0.0;
+    if (d2d_peak(e, 0, 0, &peak0) != D2D_OK) return fail(D2D_ERR_DEVICE, d2d_last_error(e));
+    *stats = d2d_flac_stream_stats{0, 0, 0, 0};
+
+    // frames one chunk can add: the engine's own count for a chunk from where it stands, and a margin for the rounding of later ones
+    const size_t chunk_frames = d2d_next_frames(e, 0, chunk) + 64, cap_frames = chunk_frames + BS;
+    const size_t out_cap = d2d_flac_bound_bytes(ch, bit_depth, cap_frames, 1), ws_cap = d2d_flac_workspace_bytes(ch, bit_depth, cap_frames, 1);
+    Stream st;
+    PinBuf h_in[2], h_out, h_res;
+    DevBuf d_in, d_new, d_pcm, d_out, d_ws;
+    FLAC_HIP(h_in[0].alloc(chunk * ch), "hipHostMalloc"); FLAC_HIP(h_in[1].alloc(chunk * ch), "hipHostMalloc");
+    FLAC_HIP(h_out.alloc(out_cap), "hipHostMalloc"); FLAC_HIP(h_res.alloc(sizeof(d2d_flac_result)), "hipHostMalloc");
+    FLAC_HIP(d_in.alloc(chunk * ch), "hipMalloc"); FLAC_HIP(d_new.alloc(chunk_frames * fb), "hipMalloc");
+    FLAC_HIP(d_pcm.alloc(cap_frames * fb), "hipMalloc"); FLAC_HIP(d_out.alloc(out_cap), "hipMalloc"); FLAC_HIP(d_ws.alloc(ws_cap), "hipMalloc");
+    d2d_flac_result* res = (d2d_flac_result*)h_res.p;
+
+    size_t carry = 0;                 // frames in front of d_pcm that no block has taken yet
+    uint64_t done = 0;
+    int cur = 0;
+    long got = read(ru, (uint8_t*)h_in[cur].p, chunk);
+    if (got < 0) return fail(D2D_ERR_IO, "read callback failed");
+    while (got > 0) {
+        if (cancel && *cancel) return fail(D2D_ERR_CANCELLED, "Conversion cancelled");
+        const size_t L = (size_t)got;
+        if (L > chunk) return fail(D2D_ERR_IO, "read callback returned more than it was asked for");
+        // upload and convert; the PCM lands in a buffer of its own (the translate call wants 16-byte alignment, the end of the carry
+        // has none) and is copied behind the carry on the same stream
+        d2d_file_io tio{};
+        tio.dsd = d_in.p; tio.bytes_per_channel = L; tio.pcm = d_new.p; tio.pcm_capacity_bytes = d_new.bytes;
+        FLAC_HIP(hipMemcpyAsync(d_in.p, h_in[cur].p, L * ch, hipMemcpyHostToDevice, st.s), "hipMemcpyAsync");
+        if (d2d_translate_batch_device(e, &tio, 1, st.s) != D2D_OK) return fail(D2D_ERR_DEVICE, d2d_last_error(e));
+        const size_t nf = tio.frames_out;
+        if (carry + nf > cap_frames) return fail(D2D_ERR_STATE, "a chunk produced more frames than planned");
+        if (nf) FLAC_HIP(hipMemcpyAsync((uint8_t*)d_pcm.p + carry * fb, d_new.p, nf * fb, hipMemcpyDeviceToDevice, st.s), "hipMemcpyAsync");
+        // the next chunk is read while the GPU works: the stream ends with this chunk if there is none
+        const long next = read(ru, (uint8_t*)h_in[cur ^ 1].p, chunk);
+        if (next < 0) return fail(D2D_ERR_IO, "read callback failed");
+        d2d_flac_io fio{};
+        fio.pcm = d_pcm.p; fio.frames = carry + nf; fio.first_block = (uint32_t)stats->blocks; fio.final = next == 0;
+        fio.out = d_out.p; fio.out_capacity_bytes = d_out.bytes; fio.result = res;
+        if (stats->blocks > 0xFFFFFFFFull) return fail(D2D_ERR_PARAM, "frame numbers are 31 bits");
+        const int rc = d2d_flac_encode_device_effort(ch, bit_depth, effort, &fio, 1, d_ws.p, d_ws.bytes, st.s);
+        if (rc != D2D_OK) return rc;
+        FLAC_HIP(hipStreamSynchronize(st.s), "hipStreamSynchronize");
+        const d2d_flac_result r = *res;
+        if (r.bytes_out) {
+            FLAC_HIP(hipMemcpy(h_out.p, d_out.p, r.bytes_out, hipMemcpyDeviceToHost), "hipMemcpy");
+            if (write && write(wu, h_out.p, r.bytes_out) != 0) return fail(D2D_ERR_IO, "write callback failed");
+        }
+        if (fio.blocks) {
+            stats->min_frame_bytes = stats->blocks ? std::min(stats->min_frame_bytes, r.min_frame_bytes) : r.min_frame_bytes;
+            stats->max_frame_bytes = std::max(stats->max_frame_bytes, r.max_frame_bytes);
+            stats->blocks += fio.blocks;
+            stats->samples_per_channel += fio.frames_consumed;
+        }
+        // the remainder moves to the front (it lies wholly behind its destination: a block was taken, or nothing moves)
+        carry = fio.frames - fio.frames_consumed;
+        if (carry && fio.frames_consumed)
+            FLAC_HIP(hipMemcpyAsync(d_pcm.p, (uint8_t*)d_pcm.p + fio.frames_consumed * fb, carry * fb, hipMemcpyDeviceToDevice, st.s), "hipMemcpyAsync");
+        done += (uint64_t)L;
+        if (progress && total) {
+            float pct = (float)(100.0 * (double)done / (double)total);
+            if (pct >= 100.0f) pct = 99.99f;       // exactly 100 is reserved for the end
+            progress(pu, pct);
+        }
+        got = next; cur ^= 1;
+    }
+    if (progress) progress(pu, 100.0f);
+    return D2D_OK;
+}

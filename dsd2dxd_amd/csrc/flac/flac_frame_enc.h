@@ -1,6 +1,8 @@
 // flac_frame_enc.h -- the host FLAC frame encoder: the one copy that FlacSink (host/pcm_sink.cpp) and
 // d2d_flac_encode_host (flac/d2d_flac_host.cpp) both run, and the byte-for-byte definition of what the GPU
-// kernels of flac/d2d_flac.hip produce.  Host code only (no HIP).
+// kernels of flac/d2d_flac.hip produce.  Host code only (no HIP).  The rules' small arithmetic -- rice_k, zigzag,
+// search_pmax, the header bit counts, the LPC routine -- is flac_lpc.h, the one copy the kernels compile as well.  Every
+// subframe, effort 0's too, is a Plan written by put_subframe.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -10,6 +12,8 @@
 #include "flac_lpc.h"
 
 namespace d2dhost {
+
+using namespace d2drice;       // rice_k, zigzag, search_pmax and the header bit counts: the copy the GPU kernels compile too
 
 // Integer depths only.  Frames are independent of each other, so a batch of them is encoded on as many threads and written in
 // order.  (The reference uses the flac-codec crate, Cargo.lock:299-307.)  Three efforts, all with fixed block size:
@@ -63,7 +67,6 @@ namespace d2dhost {
 //      of 14 bits, two's complement, q[1] first; then 01, pppp and the partitions as in rule 8.
 struct FlacFrameEnc {
     std::vector<uint8_t> out;
-    std::vector<int32_t> res;
     uint64_t bitacc = 0; int bitn = 0;
     // (the tables are function-local statics of class type: built once, by whichever thread asks first)
     struct Crc8Table { uint8_t t[256]; Crc8Table() { for (int i = 0; i < 256; ++i) { uint8_t c = (uint8_t)i; for (int k = 0; k < 8; ++k) c = (uint8_t)((c & 0x80) ? (c << 1) ^ 0x07 : (c << 1)); t[i] = c; } } };
@@ -108,30 +111,16 @@ struct FlacFrameEnc {
     }
 
     // ---- effort 1: the search (see the head of this file) --------------------------------------------------------------------
-    // the smallest k with 2^k >= floor(sum / count), at most 30: effort 0's rule, here per partition
-    static uint32_t rice_k(uint64_t sum, uint32_t count) {
-        const uint64_t mean = sum / (count ? count : 1);
-        uint32_t k = 0;
-        while (k < 30 && (1ull << k) < mean) ++k;
-        return k;
-    }
-    static uint32_t zigzag(int32_t r) { return r >= 0 ? (uint32_t)r << 1 : (((uint32_t)(-(int64_t)r)) << 1) - 1; }
-    // the largest p <= 6 with n % 2^p == 0 and (n >> p) >= 16
-    static uint32_t search_pmax(uint32_t n) {
-        uint32_t p = 0;
-        while (p < 6 && n % (2u << p) == 0 && (n >> (p + 1)) >= 16) ++p;
-        return p;
-    }
     // cost(o, p) of a signal of b bits whose order-o residuals are r[o .. n); ks (may be null) receives the 2^p parameters
     static uint32_t search_cost(const int32_t* r, uint32_t n, uint32_t o, uint32_t p, uint32_t b, uint8_t* ks) {
-        uint32_t cost = 8 + o * b + 2 + 4;
+        uint32_t cost = fixed_header_bits(o, b);
         const uint32_t psz = n >> p;
         for (uint32_t j = 0; j < (1u << p); ++j) {
             const uint32_t lo = j * psz > o ? j * psz : o, hi = (j + 1) * psz;
             uint64_t sum = 0;
             for (uint32_t i = lo; i < hi; ++i) sum += (uint64_t)(r[i] < 0 ? -(int64_t)r[i] : (int64_t)r[i]);
             const uint32_t k = rice_k(sum, hi - lo);
-            cost += 5;
+            cost += PARAM_BITS;
             for (uint32_t i = lo; i < hi; ++i) cost += (zigzag(r[i]) >> k) + 1 + k;
             if (ks) ks[j] = (uint8_t)k;
         }
@@ -139,7 +128,7 @@ struct FlacFrameEnc {
     }
     struct Plan {                               // what the search chose for one candidate signal
         uint32_t order = 0, porder = 0, bits = 0, cost = 0;
-        bool lpc = false;                       // effort 12: `order` is an LPC order, with these coefficients
+        bool lpc = false, verbatim = false;     // effort 12: `order` is an LPC order, with these coefficients; a frame of one or two samples, all warm-up
         int32_t q[d2dlpc::MAX_ORDER] = {}, shift = 0;
         uint8_t k[64];
         std::vector<int32_t> x, r;              // the signal, and its residuals at `order` (valid from index `order`)
@@ -147,7 +136,7 @@ struct FlacFrameEnc {
     Plan plans[4];
     std::vector<int32_t> rs[5];
     void search(Plan& pl, uint32_t n, uint32_t b) {
-        pl.bits = b; pl.lpc = false;
+        pl.bits = b; pl.lpc = false; pl.verbatim = false;
         rs[0] = pl.x;
         for (uint32_t o = 1; o <= 4; ++o) {
             rs[o].resize(n);
@@ -193,25 +182,26 @@ struct FlacFrameEnc {
                 r[i] = P == 4 ? lpc_residual<4>(pl.x[i], before, co.q[c], co.shift[c]) : P == 8 ? lpc_residual<8>(pl.x[i], before, co.q[c], co.shift[c])
                                                                                          : lpc_residual<12>(pl.x[i], before, co.q[c], co.shift[c]);
             }
-            const uint32_t cc = 9 + 14 * P + search_cost(r.data(), n, P, 0, b, nullptr);
+            const uint32_t cc = lpc_coef_bits(P) + search_cost(r.data(), n, P, 0, b, nullptr);
             if (best < 0 || cc < cost) { best = c; cost = cc; }
         }
         if (best < 0) return;
         const uint32_t P = 4 * (best + 1), pmax = search_pmax(n);
         uint32_t porder = 0;
         for (uint32_t p = 1; p <= pmax; ++p) {                         // the smallest partition order wins a tie
-            const uint32_t cc = 9 + 14 * P + search_cost(lres[best].data(), n, P, p, b, nullptr);
+            const uint32_t cc = lpc_coef_bits(P) + search_cost(lres[best].data(), n, P, p, b, nullptr);
             if (cc < cost) { porder = p; cost = cc; }
         }
         if (!(cost < pl.cost)) return;                                 // rule 17: the effort-1 plan stays unless LPC is strictly cheaper
         pl.lpc = true; pl.order = P; pl.porder = porder; pl.shift = co.shift[best];
         for (uint32_t j = 0; j < P; ++j) pl.q[j] = co.q[best][j];
         pl.r = lres[best];
-        pl.cost = 9 + 14 * P + search_cost(pl.r.data(), n, P, porder, b, pl.k);
+        pl.cost = lpc_coef_bits(P) + search_cost(pl.r.data(), n, P, porder, b, pl.k);
     }
     void put_subframe(const Plan& pl, uint32_t n) {
-        bits_put(0, 1); bits_put(pl.lpc ? 32 + pl.order - 1 : 8 + pl.order, 6); bits_put(0, 1);
+        bits_put(0, 1); bits_put(pl.verbatim ? 1 : pl.lpc ? 32 + pl.order - 1 : 8 + pl.order, 6); bits_put(0, 1);
         for (uint32_t i = 0; i < pl.order; ++i) bits_put((uint64_t)(int64_t)pl.x[i] & ((1ull << pl.bits) - 1), (int)pl.bits);
+        if (pl.verbatim) return;
         if (pl.lpc) {
             bits_put(d2dlpc::PRECISION - 1, 4); bits_put((uint64_t)pl.shift, 5);
             for (uint32_t j = 0; j < pl.order; ++j) bits_put((uint64_t)(int64_t)pl.q[j] & 0x3FFF, d2dlpc::PRECISION);
@@ -264,38 +254,21 @@ struct FlacFrameEnc {
     // one frame of `n` interleaved samples starting at `buf`; effort 0 = fixed order 2, 1 = the search, 12 = the search with LPC
     void encode(const int32_t* buf, uint32_t n, uint32_t ch, uint32_t depth, uint32_t frame_no, uint32_t BS, uint32_t effort = 0) {
         if (effort != 0 && n >= 16) { encode_search(buf, n, ch, depth, frame_no, BS, effort == 12 && n >= d2dlpc::MIN_FRAME); return; }
-        begin_frame(n, ch - 1, depth, frame_no, BS);                   // independent channels
-        res.resize(n);
+        // effort 0's frame: independent channels, each the plan (order 2, partition order 0).  Both callers (FlacSink::write,
+        // d2d_flac_encode_host_effort) sign-extend the samples from packed PCM of `depth` bits: |r| <= 2^25, no escape is needed.
+        begin_frame(n, ch - 1, depth, frame_no, BS);
+        Plan& pl = plans[0];
+        pl.lpc = false; pl.verbatim = n <= 2; pl.order = pl.verbatim ? n : 2; pl.porder = 0; pl.bits = depth;
+        pl.x.resize(n); pl.r.resize(n);
         for (uint32_t c = 0; c < ch; ++c) {
-            auto s = [&](uint32_t i) -> int64_t { return buf[(size_t)i * ch + c]; };
-            const uint32_t order = n > 2 ? 2 : 0;
             uint64_t sum = 0;
-            bool fits = true;
-            for (uint32_t i = order; i < n; ++i) {
-                int64_t r = order == 2 ? s(i) - 2 * s(i - 1) + s(i - 2) : s(i);
-                if (r > 0x3FFFFFFF || r < -0x3FFFFFFF) fits = false;
-                res[i] = (int32_t)r; sum += (uint64_t)(r < 0 ? -r : r);
+            for (uint32_t i = 0; i < n; ++i) pl.x[i] = buf[(size_t)i * ch + c];
+            for (uint32_t i = 2; i < n; ++i) {
+                pl.r[i] = pl.x[i] - 2 * pl.x[i - 1] + pl.x[i - 2];
+                sum += (uint64_t)(pl.r[i] < 0 ? -(int64_t)pl.r[i] : (int64_t)pl.r[i]);
             }
-            if (!fits || order == 0) {                                   // verbatim subframe
-                bits_put(0, 1); bits_put(1, 6); bits_put(0, 1);
-                for (uint32_t i = 0; i < n; ++i) bits_put((uint64_t)s(i) & ((1ull << depth) - 1), (int)depth);
-                continue;
-            }
-            bits_put(0, 1); bits_put(8 + order, 6); bits_put(0, 1);    // fixed predictor, no wasted bits
-            for (uint32_t i = 0; i < order; ++i) bits_put((uint64_t)s(i) & ((1ull << depth) - 1), (int)depth);
-            uint32_t k = 0;
-            const uint64_t mean = sum / (n - order ? n - order : 1);
-            while (k < 30 && (1ull << k) < mean) ++k;
-            bits_put(1, 2);                                             // residual coding method 1: 5-bit Rice parameters
-            bits_put(0, 4);                                             // partition order 0
-            bits_put(k, 5);
-            for (uint32_t i = order; i < n; ++i) {
-                uint32_t u = res[i] >= 0 ? (uint32_t)res[i] << 1 : (((uint32_t)(-(int64_t)res[i])) << 1) - 1;
-                uint32_t q = u >> k;
-                while (q >= 32) { bits_put(0, 32); q -= 32; }
-                bits_put(1, (int)q + 1);
-                if (k) bits_put(u & ((1u << k) - 1), (int)k);
-            }
+            pl.k[0] = (uint8_t)rice_k(sum, n > 2 ? n - 2 : 1);
+            put_subframe(pl, n);
         }
         end_frame();
     }

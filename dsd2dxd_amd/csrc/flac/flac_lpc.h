@@ -1,6 +1,7 @@
-// flac_lpc.h -- the arithmetic of FLAC effort 12 (rules 9 to 19 at the head of flac_frame_enc.h) that the host encoder and the GPU
-// kernel must agree on bit for bit: the window, the way from the autocorrelation to quantised coefficients, and the residual.  One
-// copy, plain C++, compiled for the host (g++) and for the device (hipcc).
+// flac_lpc.h -- the arithmetic of the rules at the head of flac_frame_enc.h that the host encoder and the GPU kernels must agree on
+// bit for bit.  d2drice (every effort): Rice parameter, zigzag, pmax, the bits in front of a subframe's partitions.  d2dlpc (effort 12,
+// rules 9 to 19): the window, the way from the autocorrelation to quantised coefficients, and the residual.  One copy, plain C++,
+// compiled for the host (g++) and for the device (hipcc).
 //
 // The floating-point part, lpc_coefficients, is a short serial routine in IEEE f64: every operation is the single operation written,
 // in the order written.  Both builds use -ffp-contract=off (no fused multiply-add); under clang the routine says so itself.
@@ -18,6 +19,32 @@
 #else
 #define D2D_LPC_UNROLL
 #endif
+
+namespace d2drice {
+
+constexpr uint32_t SUBFRAME_BITS = 8, METHOD_BITS = 6, PARAM_BITS = 5;      // 0 tttttt 0;  01 pppp;  a partition's kkkkk
+
+// the smallest k with 2^k >= floor(sum / count), at most 30 (rule 4); sum is a partition's sum |r|
+D2D_LPC_HD uint32_t rice_k(uint64_t sum, uint32_t count) {
+    const uint64_t mean = sum / (count ? count : 1);
+    uint32_t k = 0;
+    while (k < 30 && (1ull << k) < mean) ++k;
+    return k;
+}
+// u = 2 r for r >= 0, -2 r - 1 below: what the code writes; |r| = (u + 1) >> 1
+D2D_LPC_HD uint32_t zigzag(int32_t r) { return r >= 0 ? (uint32_t)r << 1 : ((uint32_t)(-(int64_t)r) << 1) - 1; }
+// the largest p <= 6 with n % 2^p == 0 and (n >> p) >= 16 (rule 6)
+D2D_LPC_HD uint32_t search_pmax(uint32_t n) {
+    uint32_t p = 0;
+    while (p < 6 && n % (2u << p) == 0 && (n >> (p + 1)) >= 16) ++p;
+    return p;
+}
+// the bits in front of the partitions of a subframe of b-bit samples: fixed order o (rule 4); LPC order P (rule 15: 1101 sssss, P q's)
+D2D_LPC_HD uint32_t fixed_header_bits(uint32_t o, uint32_t b) { return SUBFRAME_BITS + o * b + METHOD_BITS; }
+D2D_LPC_HD uint32_t lpc_coef_bits(uint32_t P) { return 4 + 5 + 14 * P; }
+D2D_LPC_HD uint32_t lpc_header_bits(uint32_t P, uint32_t b) { return fixed_header_bits(P, b) + lpc_coef_bits(P); }
+
+}  // namespace d2drice
 
 namespace d2dlpc {
 

@@ -3,7 +3,8 @@ go: every channel count, last blocks of every residue mod 4, every Rice paramete
 alignment, files of more than one pack workgroup (32 blocks) and of more sizes than one pass of its reduction (256), a caller's stream,
 and the stream driver at chunks below a block and above 32 blocks and at every kind of ending.  The inputs and the proof of what they
 reach are in tests/test_flac_edges_cpu.py.  Every comparison is against d2d_flac_encode_host, byte for byte: frames, result record,
-frames_consumed and blocks.  Up to 16 files share a d2d_flac_encode_device call."""
+frames_consumed and blocks.  Up to 16 files share a d2d_flac_encode_device call.  flac_search_kernel<1..8, LPC or not> gets its own
+sweep of the channel counts (test_every_channel_count_of_the_search), against d2d_flac_encode_host_effort."""
 import numpy as np
 import pytest
 
@@ -11,6 +12,7 @@ import flac_ref as R
 import test_flac_edges_cpu as E
 from helpers import pack_layout, synth
 from test_gpu_flac import device_encode, host_encode
+from test_gpu_flac_search import device_encode as search_device_encode, host_encode as search_host_encode
 
 gpu = pytest.mark.gpu
 B = R.BLOCK
@@ -46,6 +48,26 @@ def test_every_channel_count(engine_lib, channels, depth):
             cases.append((f"{sig} {frames}", R.signal(sig, frames, channels, depth, seed=frames + channels), 7 + i, final))
     want = compare(engine_lib, channels, depth, cases)
     assert [w[1][0] > 0 for w in want] == [True, True, False] * 3
+
+
+@gpu
+@pytest.mark.parametrize("depth", (16, 24))                        # the 2-byte and the 3-byte loader (20 bits is a shift of the latter)
+@pytest.mark.parametrize("effort", (1, 12))
+@pytest.mark.parametrize("channels", range(1, 9))
+def test_every_channel_count_of_the_search(engine_lib, channels, effort, depth):
+    """flac_search_kernel<1..8, LPC or not>: a whole block (partition sums by DPP rows) and a short one (by LDS adds; LPC present), the
+    smallest LPC frame, and an unsearched one (the effort-0 frame), all in one call"""
+    cases = []
+    for sig in ("random", "alternate"):
+        for i, frames in enumerate((B + 1000, 64, 15)):
+            cases.append((f"{sig} {frames}", R.signal(sig, frames, channels, depth, seed=frames + channels), 7 + i, True))
+    files = [(R.pack_pcm(s, depth), first, final) for _, s, first, final in cases]
+    want = search_host_encode(engine_lib, channels, depth, files, effort=effort)
+    got = search_device_encode(engine_lib, channels, depth, files, effort=effort)
+    for (label, _, _, _), g, w in zip(cases, got, want):
+        assert g[1] == w[1], label                                 # the result record
+        assert g[0] == w[0], label                                 # the frames
+        assert g[2] == w[2], label                                 # frames_consumed
 
 
 @gpu
