@@ -68,6 +68,21 @@ class FlacStreamStats(C.Structure):
                 ("min_frame_bytes", C.c_uint32), ("max_frame_bytes", C.c_uint32)]
 
 
+class FlacCheck(C.Structure):
+    """d2d_flac_check: what a verify or decode call found"""
+    _fields_ = [("samples_checked", C.c_uint64), ("blocks_checked", C.c_uint32), ("bad_blocks", C.c_uint32),
+                ("first_bad_block", C.c_uint32), ("first_bad_reason", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.samples_checked, self.blocks_checked, self.bad_blocks, self.first_bad_block, self.first_bad_reason)
+
+
+# D2D_FLAC_BAD_*
+(FLAC_BAD_NONE, FLAC_BAD_SIZE, FLAC_BAD_HEADER, FLAC_BAD_CRC8, FLAC_BAD_CRC16, FLAC_BAD_UNSUPPORTED, FLAC_BAD_SYNTAX, FLAC_BAD_LENGTH,
+ FLAC_BAD_SAMPLES) = range(9)
+FLAC_NO_BAD_BLOCK = 0xFFFFFFFF
+ERR_VERIFY = -60
+
 FLAC_BLOCK = 4096
 FLAC_EFFORT_FIXED2, FLAC_EFFORT_SEARCH, FLAC_EFFORT_LPC = 0, 1, 12      # D2D_FLAC_EFFORT_*
 
@@ -84,7 +99,8 @@ EXPORTS = ["d2d_create", "d2d_create_error", "d2d_destroy", "d2d_reset", "d2d_la
            "d2d_seek", "d2d_tell", "d2d_preroll_bytes", "d2d_slice_align_bytes", "d2d_prime", "d2d_prime_batch_device",
            "d2d_flac_bound_bytes", "d2d_flac_workspace_bytes", "d2d_flac_encode_device", "d2d_flac_error",
            "d2d_flac_encode_host", "d2d_convert_stream_flac",
-           "d2d_flac_encode_device_effort", "d2d_flac_encode_host_effort", "d2d_convert_stream_flac_effort"]
+           "d2d_flac_encode_device_effort", "d2d_flac_encode_host_effort", "d2d_convert_stream_flac_effort",
+           "d2d_flac_verify_device", "d2d_flac_verify_host", "d2d_flac_decode_host", "d2d_convert_stream_flac_verified"]
 
 _lib = None
 
@@ -161,6 +177,12 @@ def lib():
     L.d2d_convert_stream_flac_effort.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, READ_FN, C.c_void_p, WRITE_FN, C.c_void_p,
                                                  C.POINTER(C.c_int), PROGRESS_FN, C.c_void_p, C.c_uint64, C.c_size_t,
                                                  C.POINTER(FlacStreamStats)]
+    L.d2d_flac_verify_device.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(FlacIO), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.d2d_flac_verify_host.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t,
+                                       C.c_void_p, C.POINTER(FlacCheck)]
+    L.d2d_flac_decode_host.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t,
+                                       C.POINTER(C.c_size_t), C.POINTER(FlacCheck)]
+    L.d2d_convert_stream_flac_verified.argtypes = L.d2d_convert_stream_flac_effort.argtypes + [C.POINTER(FlacCheck)]
     _lib = L
     return L
 
@@ -197,6 +219,44 @@ def flac_encode_device(channels, bit_depth, ios, workspace_ptr, workspace_bytes,
     """d2d_flac_encode_device_effort: ios is a ctypes array of FlacIO with DEVICE pointers; asynchronous on `stream` (hipStream_t int)."""
     _flac_check(lib().d2d_flac_encode_device_effort(channels, bit_depth, effort, ios, len(ios), C.c_void_p(workspace_ptr), workspace_bytes,
                                                     C.c_void_p(stream or 0)))
+
+
+def _u8(data):
+    import numpy as np
+    return np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).reshape(-1))
+
+
+def flac_decode_host(channels, bit_depth, frames, first_block=0, capacity=None, pcm=None):
+    """d2d_flac_decode_host on a bytes-like of whole frames: returns (packed PCM bytes, frames_out, FlacCheck).  `capacity` defaults
+    to what 4096 samples per frame byte could never exceed; `pcm` (a uint8 array) is written in place when given."""
+    import numpy as np
+    buf = _u8(frames)
+    fb = channels * (2 if bit_depth == 16 else 3)
+    out = pcm if pcm is not None else np.zeros(max((buf.size // 6 + 1) * FLAC_BLOCK * fb if capacity is None else capacity, 1), dtype=np.uint8)
+    cap = out.size if capacity is None else capacity
+    n, chk = C.c_size_t(), FlacCheck()
+    _flac_check(lib().d2d_flac_decode_host(channels, bit_depth, buf.ctypes.data, buf.size, first_block, out.ctypes.data, cap, C.byref(n), C.byref(chk)))
+    return out[:n.value * fb].tobytes(), n.value, chk
+
+
+def flac_verify_host(channels, bit_depth, pcm, out, first_block=0, final=True, sizes=None):
+    """d2d_flac_verify_host: the frames `out` against the packed PCM they were made from; `sizes` the per-block sizes or None (the
+    frames are then walked by decoding).  Returns the FlacCheck."""
+    import numpy as np
+    p, o = _u8(pcm), _u8(out)
+    fb = channels * (2 if bit_depth == 16 else 3)
+    sz = None if sizes is None else np.ascontiguousarray(np.asarray(sizes, dtype=np.uint32))
+    chk = FlacCheck()
+    _flac_check(lib().d2d_flac_verify_host(channels, bit_depth, p.ctypes.data, p.size // fb if fb else 0, first_block, int(bool(final)),
+                                           o.ctypes.data, o.size, None if sz is None else sz.ctypes.data, C.byref(chk)))
+    return chk
+
+
+def flac_verify_device(channels, bit_depth, ios, workspace_ptr, workspace_bytes, checks_ptr, stream=None):
+    """d2d_flac_verify_device after flac_encode_device on the same ios, workspace and stream; checks_ptr: len(ios) d2d_flac_check
+    records (24 bytes each) in memory the GPU can address.  Asynchronous on `stream`."""
+    _flac_check(lib().d2d_flac_verify_device(channels, bit_depth, ios, len(ios), C.c_void_p(workspace_ptr), workspace_bytes,
+                                             C.c_void_p(checks_ptr), C.c_void_p(stream or 0)))
 
 
 class D2DError(Exception):
@@ -381,9 +441,11 @@ class Engine:
                                              keep["p"], None, total_bytes_per_channel, chunk_bytes_per_channel))
 
     def convert_stream_flac(self, read, write, total_bytes_per_channel=0, chunk_bytes_per_channel=1 << 22,
-                            cancel=None, progress=None, effort=0):
+                            cancel=None, progress=None, effort=0, verify=False):
         """d2d_convert_stream_flac_effort: as convert_stream, but write() receives FLAC frames (whole frames, in order); returns the
-        FlacStreamStats STREAMINFO needs.  Errors carry d2d_flac_error()'s message."""
+        FlacStreamStats STREAMINFO needs.  Errors carry d2d_flac_error()'s message.  verify=True: d2d_convert_stream_flac_verified --
+        every chunk's frames are checked against their PCM on the GPU before write() sees them; returns (stats, FlacCheck), and a bad
+        block raises D2DError with code ERR_VERIFY (the record so far is the exception's `check`)."""
         def _read(_u, dst, cap):
             data = read(cap)
             if not data:
@@ -402,6 +464,15 @@ class Engine:
         r, w, p = READ_FN(_read), WRITE_FN(_write), PROGRESS_FN(_prog)
         cflag = cancel if cancel is not None else C.c_int(0)
         stats = FlacStreamStats()
+        if verify:
+            chk = FlacCheck()
+            rc = lib().d2d_convert_stream_flac_verified(self._h, self.params.bit_depth, effort, r, None, w, None, C.byref(cflag), p, None,
+                                                        total_bytes_per_channel, chunk_bytes_per_channel, C.byref(stats), C.byref(chk))
+            if rc:
+                err = D2DError(rc, lib().d2d_flac_error().decode())
+                err.check = chk
+                raise err
+            return stats, chk
         _flac_check(lib().d2d_convert_stream_flac_effort(self._h, self.params.bit_depth, effort, r, None, w, None, C.byref(cflag), p, None,
                                                          total_bytes_per_channel, chunk_bytes_per_channel, C.byref(stats)))
         return stats

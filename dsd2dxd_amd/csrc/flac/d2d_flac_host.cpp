@@ -1,5 +1,6 @@
-// d2d_flac_host.cpp -- the host half of the FLAC entry points: sizes, the error slot and d2d_flac_encode_host, which is the sink's
-// own frame encoder (flac_frame_enc.h) behind the C ABI.  No HIP: tools and tests build this file with g++ alone.
+// d2d_flac_host.cpp -- the host half of the FLAC entry points: sizes, the error slot, d2d_flac_encode_host, which is the sink's
+// own frame encoder (flac_frame_enc.h) behind the C ABI, and the readers on flac_parse.h: d2d_flac_decode_host and d2d_flac_verify_host,
+// the CPU twin of the GPU verify call.  No HIP: tools and tests build this file with g++ alone.
 #include <string.h>
 
 #include <algorithm>
@@ -7,15 +8,57 @@
 
 #include "d2d_flac_internal.h"
 #include "flac_frame_enc.h"
+#include "flac_parse.h"
 
 namespace d2dflac {
 
 static thread_local std::string g_flac_error;
 int fail(int code, const std::string& message) { g_flac_error = message; return code; }
 
+const char* reason_name(uint32_t reason) {
+    static const char* const names[] = {"none", "SIZE", "HEADER", "CRC8", "CRC16", "UNSUPPORTED", "SYNTAX", "LENGTH", "SAMPLES"};
+    return reason < sizeof(names) / sizeof(names[0]) ? names[reason] : "?";
+}
+
 }  // namespace d2dflac
 
 using namespace d2dflac;
+
+namespace {
+
+// the decoder's side of flac_parse.h: keeps the coded signals of one frame, then undoes the stereo assignment
+struct DecodeSig {
+    std::vector<int32_t> x[8];
+    int32_t store[2 * d2dparse::MAX_LPC_ORDER];
+    uint32_t s = 0;
+    void begin(uint32_t subframe, uint32_t) { s = subframe; x[s].clear(); }
+    bool put(uint32_t, int32_t v) { x[s].push_back(v); return true; }
+    int32_t& hist(uint32_t k) { return store[k]; }
+    int32_t& coef(uint32_t k) { return store[d2dparse::MAX_LPC_ORDER + k]; }
+    // rule 8: left and right from the assignment; false where one does not fit the depth
+    bool undo_stereo(uint32_t assignment, uint32_t n, uint32_t depth) {
+        if (assignment < 8) return true;
+        const int64_t lo = -((int64_t)1 << (depth - 1)), hi = ((int64_t)1 << (depth - 1)) - 1;
+        for (uint32_t i = 0; i < n; ++i) {
+            int64_t l, r;
+            if (assignment == 8) { l = x[0][i]; r = l - x[1][i]; }
+            else if (assignment == 9) { r = x[1][i]; l = r + x[0][i]; }
+            else { const int64_t side = x[1][i], mid = (int64_t)x[0][i] * 2 + (side & 1); l = (mid + side) >> 1; r = (mid - side) >> 1; }
+            if (l < lo || l > hi || r < lo || r > hi) return false;
+            x[0][i] = (int32_t)l; x[1][i] = (int32_t)r;
+        }
+        return true;
+    }
+};
+
+void clean_record(d2d_flac_check& c) { c = d2d_flac_check{0, 0, 0, 0xFFFFFFFFu, D2D_FLAC_BAD_NONE}; }
+void count_block(d2d_flac_check& c, uint32_t b, uint32_t reason, uint32_t n) {
+    ++c.blocks_checked;
+    if (!reason) { c.samples_checked += n; return; }
+    if (c.bad_blocks++ == 0) { c.first_bad_block = b; c.first_bad_reason = reason; }
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -71,6 +114,88 @@ int d2d_flac_encode_host_effort(uint32_t channels, uint32_t bit_depth, uint32_t 
     }
     *result = r;
     if (frames_consumed) *frames_consumed = final ? frames : (frames / BS) * BS;
+    return D2D_OK;
+}
+
+int d2d_flac_decode_host(uint32_t channels, uint32_t bit_depth, const void* frames, size_t bytes, uint32_t first_block,
+                         void* pcm, size_t pcm_capacity_bytes, size_t* frames_out, d2d_flac_check* check) {
+    if (!depth_ok(bit_depth)) return fail(D2D_ERR_PARAM, "FLAC holds 16, 20 or 24-bit integers (Invalid bit depth)");
+    if (channels == 0 || channels > 8) return fail(D2D_ERR_PARAM, "FLAC holds 1 to 8 channels (Invalid channel count)");
+    if (!check || !frames_out) return fail(D2D_ERR_PARAM, "null check record or frames_out");
+    if (bytes && !frames) return fail(D2D_ERR_PARAM, "null frames pointer");
+    const uint8_t* p = (const uint8_t*)frames;
+    const uint16_t* tab = d2dhost::FlacFrameEnc::crc16_table();
+    const size_t bound = frame_bound(channels, bit_depth, BS);
+    const uint32_t sb = sample_bytes(bit_depth);
+    std::vector<uint8_t> decoded;
+    DecodeSig sig;
+    d2d_flac_check c;
+    clean_record(c);
+    bool ended = false;                                               // a short block was the stream's last
+    for (size_t off = 0, b = 0; off < bytes; ++b) {
+        const uint64_t number = (uint64_t)first_block + b;
+        d2dparse::Header h{0, 0, 0};
+        uint32_t size = 0;
+        uint32_t reason = ended || number >= (1ull << 31) ? (uint32_t)D2D_FLAC_BAD_HEADER
+                        : d2dparse::parse_frame(p + off, (uint32_t)std::min(bytes - off, bound), false, d2dparse::Expect{channels, bit_depth, 0, (uint32_t)number}, tab, sig, h, &size);
+        if (!reason && !sig.undo_stereo(h.assignment, h.n, bit_depth)) reason = D2D_FLAC_BAD_SAMPLES;
+        count_block(c, (uint32_t)b, reason, h.n);
+        if (reason) break;
+        const size_t at = decoded.size();
+        decoded.resize(at + (size_t)h.n * channels * sb);
+        uint8_t* q = decoded.data() + at;
+        for (uint32_t i = 0; i < h.n; ++i)
+            for (uint32_t ch = 0; ch < channels; ++ch, q += sb) {
+                const uint32_t v = (uint32_t)sig.x[ch][i] << (bit_depth == 20 ? 4 : 0);
+                q[0] = (uint8_t)v; q[1] = (uint8_t)(v >> 8);
+                if (sb == 3) q[2] = (uint8_t)(v >> 16);
+            }
+        ended = h.n != BS;
+        off += size;
+    }
+    if (decoded.size() > pcm_capacity_bytes) return fail(D2D_ERR_CAPACITY, "pcm buffer below the decoded frames");
+    if (!decoded.empty() && !pcm) return fail(D2D_ERR_PARAM, "null pcm pointer");
+    if (!decoded.empty()) memcpy(pcm, decoded.data(), decoded.size());
+    *frames_out = (size_t)c.samples_checked;
+    *check = c;
+    return D2D_OK;
+}
+
+int d2d_flac_verify_host(uint32_t channels, uint32_t bit_depth, const void* pcm, size_t frames, uint32_t first_block, int final,
+                         const void* out, size_t bytes_out, const uint32_t* sizes, d2d_flac_check* check) {
+    if (!depth_ok(bit_depth)) return fail(D2D_ERR_PARAM, "FLAC holds 16, 20 or 24-bit integers (Invalid bit depth)");
+    if (channels == 0 || channels > 8) return fail(D2D_ERR_PARAM, "FLAC holds 1 to 8 channels (Invalid channel count)");
+    if (!check) return fail(D2D_ERR_PARAM, "null check record");
+    const size_t blocks = block_count(frames, final);
+    if ((uint64_t)first_block + blocks > (1ull << 31)) return fail(D2D_ERR_PARAM, "frame numbers are 31 bits: first_block + blocks exceeds 2^31");
+    if (blocks && (!pcm || !out)) return fail(D2D_ERR_PARAM, "null pcm or out pointer");
+    const uint8_t* o = (const uint8_t*)out;
+    const uint16_t* tab = d2dhost::FlacFrameEnc::crc16_table();
+    const uint32_t bound = (uint32_t)frame_bound(channels, bit_depth, BS);
+    const size_t fb = (size_t)channels * sample_bytes(bit_depth);
+    int32_t store[2 * d2dparse::MAX_LPC_ORDER];
+    d2d_flac_check c;
+    clean_record(c);
+    uint64_t off = 0;
+    bool lost = false;                                                // sizes == NULL: a walk that failed cannot find the later frames
+    for (size_t b = 0; b < blocks; ++b) {
+        const uint32_t n = (uint32_t)std::min<size_t>(BS, frames - b * BS);
+        const d2dparse::Expect ex{channels, bit_depth, n, first_block + (uint32_t)b};
+        const uint8_t* block_pcm = (const uint8_t*)pcm + b * BS * fb;
+        uint32_t reason = D2D_FLAC_BAD_SIZE, size = 0;
+        if (sizes) {
+            size = sizes[b];
+            if (d2dparse::size_ok(off, size, bytes_out, bound, b + 1 == blocks))
+                reason = d2dparse::verify_frame(o + off, size, true, ex, block_pcm, tab, store, 1, nullptr);
+        } else if (!lost && off < bytes_out) {
+            reason = d2dparse::verify_frame(o + off, (uint32_t)std::min<uint64_t>(bytes_out - off, bound), false, ex, block_pcm, tab, store, 1, &size);
+            if (reason && reason != D2D_FLAC_BAD_SAMPLES) lost = true;       // (a frame that is not the PCM still has its end)
+            else if (b + 1 == blocks && off + size != bytes_out) reason = D2D_FLAC_BAD_SIZE;
+        }
+        count_block(c, (uint32_t)b, reason, n);
+        off += size;
+    }
+    *check = c;
     return D2D_OK;
 }
 

@@ -26,6 +26,8 @@ inline size_t block_count(size_t frames, int final) { return frames / BS + ((fin
 
 // the message d2d_flac_error() returns (thread-local); returns `code`
 int fail(int code, const std::string& message);
+// "CRC16" for D2D_FLAC_BAD_CRC16, ...
+const char* reason_name(uint32_t reason);
 #ifdef HIP_INCLUDE_HIP_HIP_RUNTIME_API_H           // (the units that include HIP's host API in front of this header)
 // ... with "`what`: HIP's message"; returns D2D_ERR_DEVICE (d2d_flac.hip)
 int hip_fail(hipError_t e, const char* what);

@@ -1,5 +1,5 @@
 // d2d_flac_stream.cpp -- d2d_convert_stream_flac: a whole DSD stream to FLAC frames through the public calls (d2d_translate_batch_device,
-// d2d_flac_encode_device_effort) and HIP's host API.  Host code: it launches no kernel.
+// d2d_flac_encode_device_effort, and for the verified twin d2d_flac_verify_device) and HIP's host API.  Host code: it launches no kernel.
 #include <hip/hip_runtime_api.h>
 #include <algorithm>
 #include "d2d_flac_internal.h"
@@ -32,9 +32,27 @@ extern "C" int d2d_convert_stream_flac(d2d_engine* e, uint32_t bit_depth, d2d_re
     return d2d_convert_stream_flac_effort(e, bit_depth, D2D_FLAC_EFFORT_FIXED2, read, ru, write, wu, cancel, progress, pu, total, chunk, stats);
 }
 
+// the driver behind both twins; `check` non-null: every chunk's frames are verified on the device before `write` sees them
+static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
+                               d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
+                               uint64_t total, size_t chunk, d2d_flac_stream_stats* stats, d2d_flac_check* check);
+
 extern "C" int d2d_convert_stream_flac_effort(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
                                               d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
                                               uint64_t total, size_t chunk, d2d_flac_stream_stats* stats) {
+    return convert_stream_flac(e, bit_depth, effort, read, ru, write, wu, cancel, progress, pu, total, chunk, stats, nullptr);
+}
+
+extern "C" int d2d_convert_stream_flac_verified(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
+                                                d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
+                                                uint64_t total, size_t chunk, d2d_flac_stream_stats* stats, d2d_flac_check* check) {
+    if (!check) return fail(D2D_ERR_PARAM, "null check record");
+    return convert_stream_flac(e, bit_depth, effort, read, ru, write, wu, cancel, progress, pu, total, chunk, stats, check);
+}
+
+static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
+                               d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
+                               uint64_t total, size_t chunk, d2d_flac_stream_stats* stats, d2d_flac_check* check) {
     if (!effort_ok(effort)) return fail(D2D_ERR_PARAM, EFFORT_MESSAGE);
     if (!e) return fail(D2D_ERR_PARAM, "null engine");
     if (!read) return fail(D2D_ERR_PARAM, "null read callback");
@@ -48,18 +66,21 @@ extern "C" int d2d_convert_stream_flac_effort(d2d_engine* e, uint32_t bit_depth,
     double peak0 = 0.0;
     if (d2d_peak(e, 0, 0, &peak0) != D2D_OK) return fail(D2D_ERR_DEVICE, d2d_last_error(e));
     *stats = d2d_flac_stream_stats{0, 0, 0, 0};
+    if (check) *check = d2d_flac_check{0, 0, 0, 0xFFFFFFFFu, D2D_FLAC_BAD_NONE};
 
     // frames one chunk can add: the engine's own count for a chunk from where it stands, and a margin for the rounding of later ones
     const size_t chunk_frames = d2d_next_frames(e, 0, chunk) + 64, cap_frames = chunk_frames + BS;
     const size_t out_cap = d2d_flac_bound_bytes(ch, bit_depth, cap_frames, 1), ws_cap = d2d_flac_workspace_bytes(ch, bit_depth, cap_frames, 1);
     Stream st;
-    PinBuf h_in[2], h_out, h_res;
+    PinBuf h_in[2], h_out, h_res, h_chk;
     DevBuf d_in, d_new, d_pcm, d_out, d_ws;
     FLAC_HIP(h_in[0].alloc(chunk * ch), "hipHostMalloc"); FLAC_HIP(h_in[1].alloc(chunk * ch), "hipHostMalloc");
     FLAC_HIP(h_out.alloc(out_cap), "hipHostMalloc"); FLAC_HIP(h_res.alloc(sizeof(d2d_flac_result)), "hipHostMalloc");
     FLAC_HIP(d_in.alloc(chunk * ch), "hipMalloc"); FLAC_HIP(d_new.alloc(chunk_frames * fb), "hipMalloc");
     FLAC_HIP(d_pcm.alloc(cap_frames * fb), "hipMalloc"); FLAC_HIP(d_out.alloc(out_cap), "hipMalloc"); FLAC_HIP(d_ws.alloc(ws_cap), "hipMalloc");
     d2d_flac_result* res = (d2d_flac_result*)h_res.p;
+    if (check) FLAC_HIP(h_chk.alloc(sizeof(d2d_flac_check)), "hipHostMalloc");
+    d2d_flac_check* chk = (d2d_flac_check*)h_chk.p;
 
     size_t carry = 0;                 // frames in front of d_pcm that no block has taken yet
     uint64_t done = 0;
@@ -88,8 +109,20 @@ extern "C" int d2d_convert_stream_flac_effort(d2d_engine* e, uint32_t bit_depth,
         if (stats->blocks > 0xFFFFFFFFull) return fail(D2D_ERR_PARAM, "frame numbers are 31 bits");
         const int rc = d2d_flac_encode_device_effort(ch, bit_depth, effort, &fio, 1, d_ws.p, d_ws.bytes, st.s);
         if (rc != D2D_OK) return rc;
+        if (check) {
+            const int vrc = d2d_flac_verify_device(ch, bit_depth, &fio, 1, d_ws.p, d_ws.bytes, chk, st.s);
+            if (vrc != D2D_OK) return vrc;
+        }
         FLAC_HIP(hipStreamSynchronize(st.s), "hipStreamSynchronize");
         const d2d_flac_result r = *res;
+        if (check) {                                                  // the record comes with the result; a bad block keeps its chunk from `write`
+            check->samples_checked += chk->samples_checked; check->blocks_checked += chk->blocks_checked;
+            if (chk->bad_blocks) {
+                if (!check->bad_blocks) { check->first_bad_block = (uint32_t)stats->blocks + chk->first_bad_block; check->first_bad_reason = chk->first_bad_reason; }
+                check->bad_blocks += chk->bad_blocks;
+                return fail(D2D_ERR_VERIFY, "FLAC verify failed: block " + std::to_string(check->first_bad_block) + " (" + reason_name(check->first_bad_reason) + ")");
+            }
+        }
         if (r.bytes_out) {
             FLAC_HIP(hipMemcpy(h_out.p, d_out.p, r.bytes_out, hipMemcpyDeviceToHost), "hipMemcpy");
             if (write && write(wu, h_out.p, r.bytes_out) != 0) return fail(D2D_ERR_IO, "write callback failed");

@@ -4,6 +4,9 @@
 //   levels [opts] files   peak dBFS per file and overall (src/bin/dsd_levels/main.rs)
 //   tags [-a RATE] <file>...   the source's ID3v2 tag as the converted file would carry it, as JSON
 //                         (text frames under their Vorbis names; -a applies the album suffix; no GPU needed)
+//   verify <file.flac>... read back FLAC files the sinks here wrote: every frame is decoded (d2d_flac_decode_host) and the frame numbers,
+//                         the sample count, the smallest and largest frame and -- where STREAMINFO has one -- the MD5 are checked; one
+//                         line per file, a non-zero exit if any is bad (no GPU needed)
 // It is not the reference's CLI (logging, progress bars, Rayon pool are out of scope).
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,9 +17,12 @@
 #include <string>
 #include <vector>
 
+#include "../../../include/dsd2dxd_amd.h"
 #include "../../../include/rdsd2pcm.hpp"
+#include "../flac/flac_parse.h"
 #include "dsd_reader.h"
 #include "id3_tag.h"
+#include "md5.h"
 
 using namespace rdsd2pcm;
 static std::atomic<bool> CANCEL_FLAG{false};
@@ -74,8 +80,101 @@ static int tags_main(int argc, char** argv) {
     return 0;
 }
 
+// ---- verify: a FLAC file of the sinks here, read back ------------------------------------------------------------------------------
+static const char* const REASONS[] = {"none", "SIZE", "HEADER", "CRC8", "CRC16", "UNSUPPORTED", "SYNTAX", "LENGTH", "SAMPLES"};
+
+// takes the samples of a frame and drops them: the walk below wants the frames' sizes only
+struct NoSamples {
+    int32_t store[2 * d2dparse::MAX_LPC_ORDER];
+    void begin(uint32_t, uint32_t) {}
+    bool put(uint32_t, int32_t) { return true; }
+    int32_t& hist(uint32_t k) { return store[k]; }
+    int32_t& coef(uint32_t k) { return store[d2dparse::MAX_LPC_ORDER + k]; }
+};
+
+// "" when the file is good (*no_md5: its STREAMINFO has no MD5), else what is wrong with it
+static std::string verify_file(const char* path, bool* no_md5) {
+    FILE* f = fopen(path, "rb");
+    if (!f) return "cannot open";
+    std::vector<uint8_t> file;
+    uint8_t chunk[1 << 16];
+    for (size_t n; (n = fread(chunk, 1, sizeof(chunk), f)) > 0;) file.insert(file.end(), chunk, chunk + n);
+    fclose(f);
+    if (file.size() < 42 || memcmp(file.data(), "fLaC", 4) || (file[4] & 0x7F) != 0 || file[5] || file[6] || file[7] != 34) return "not a FLAC file that begins with STREAMINFO";
+    const uint8_t* si = file.data() + 8;
+    size_t pos = 4;
+    for (bool last = false; !last;) {                                 // metadata blocks are skipped by their length
+        if (pos + 4 > file.size()) return "metadata runs past the end of the file";
+        last = file[pos] & 0x80;
+        pos += 4 + (((size_t)file[pos + 1] << 16) | ((size_t)file[pos + 2] << 8) | file[pos + 3]);
+    }
+    if (pos > file.size()) return "metadata runs past the end of the file";
+    const uint32_t block_min = (si[0] << 8) | si[1], block_max = (si[2] << 8) | si[3];
+    const uint32_t frame_min = (si[4] << 16) | (si[5] << 8) | si[6], frame_max = (si[7] << 16) | (si[8] << 8) | si[9];
+    uint64_t v = 0;
+    for (int i = 0; i < 8; ++i) v = (v << 8) | si[10 + i];
+    const uint32_t channels = (uint32_t)((v >> 41) & 7) + 1, depth = (uint32_t)((v >> 36) & 31) + 1;
+    const uint64_t total = v & 0xFFFFFFFFFull;
+    if (block_min != D2D_FLAC_BLOCK || block_max != D2D_FLAC_BLOCK) return "not a stream of 4096-sample blocks";
+    if (depth != 16 && depth != 20 && depth != 24) return "not 16, 20 or 24 bits";
+    const uint8_t* audio = file.data() + pos;
+    const size_t bytes = file.size() - pos, frame_bytes = (size_t)channels * (depth == 16 ? 2 : 3);
+    std::vector<uint8_t> pcm((size_t)(total + D2D_FLAC_BLOCK) * frame_bytes);
+    size_t frames_out = 0;
+    d2d_flac_check check{};
+    const int rc = d2d_flac_decode_host(channels, depth, audio, bytes, 0, pcm.data(), pcm.size(), &frames_out, &check);
+    if (rc == D2D_ERR_CAPACITY) return "the frames hold more samples than STREAMINFO's " + std::to_string(total);
+    if (rc != D2D_OK) return d2d_flac_error();
+    if (check.bad_blocks) return "block " + std::to_string(check.first_bad_block) + ": " + REASONS[check.first_bad_reason < 9 ? check.first_bad_reason : 0];
+    if (frames_out != total) return "the frames hold " + std::to_string(frames_out) + " samples, STREAMINFO says " + std::to_string(total);
+    // the frames' sizes: the same parser once more, without the samples
+    uint16_t tab[256];
+    for (uint32_t i = 0; i < 256; ++i) tab[i] = (uint16_t)d2dparse::crc16_entry(i);
+    uint32_t smallest = 0, largest = 0;
+    NoSamples sig;
+    size_t off = 0;
+    for (uint32_t b = 0; off < bytes; ++b) {
+        d2dparse::Header h{0, 0, 0};
+        uint32_t size = 0;
+        const uint32_t avail = (uint32_t)std::min<size_t>(bytes - off, (size_t)1 << 20);
+        const uint32_t reason = d2dparse::parse_frame(audio + off, avail, false, d2dparse::Expect{channels, depth, 0, b}, tab, sig, h, &size);
+        if (reason) return "block " + std::to_string(b) + ": " + REASONS[reason];
+        smallest = b ? std::min(smallest, size) : size; largest = std::max(largest, size);
+        off += size;
+    }
+    if (smallest != frame_min || largest != frame_max)
+        return "frames of " + std::to_string(smallest) + " to " + std::to_string(largest) + " bytes, STREAMINFO says " + std::to_string(frame_min) + " to " + std::to_string(frame_max);
+    static const uint8_t zero[16] = {};
+    *no_md5 = !memcmp(si + 18, zero, 16);
+    if (*no_md5) return "";
+    d2dhost::Md5 md5;                                               // over the samples as little-endian whole-byte integers, interleaved
+    if (depth == 20) {
+        for (size_t i = 0; i < frames_out * channels; ++i) {
+            const int32_t s = (int32_t)((uint32_t)(pcm[3 * i] | (pcm[3 * i + 1] << 8) | (pcm[3 * i + 2] << 16)) << 8) >> 12;
+            const uint8_t le[3] = {(uint8_t)s, (uint8_t)(s >> 8), (uint8_t)(s >> 16)};
+            md5.update(le, 3);
+        }
+    } else md5.update(pcm.data(), frames_out * frame_bytes);
+    uint8_t digest[16];
+    md5.finish(digest);
+    return memcmp(digest, si + 18, 16) ? "the decoded samples do not have STREAMINFO's MD5" : "";
+}
+
+static int verify_main(int argc, char** argv) {
+    if (argc == 0) { fprintf(stderr, "verify: no files\n"); return 2; }
+    int bad = 0;
+    for (int i = 0; i < argc; ++i) {
+        bool no_md5 = false;
+        const std::string err = verify_file(argv[i], &no_md5);
+        if (!err.empty()) { printf("%s: BAD: %s\n", argv[i], err.c_str()); ++bad; }
+        else printf("%s: %s\n", argv[i], no_md5 ? "ok (no MD5 in STREAMINFO)" : "ok");
+    }
+    return bad ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 2 && !strcmp(argv[1], "probe")) return probe_main(argc - 2, argv + 2);
+    if (argc >= 2 && !strcmp(argv[1], "verify")) return verify_main(argc - 2, argv + 2);
     if (argc >= 2 && !strcmp(argv[1], "tags")) return tags_main(argc - 2, argv + 2);
     bool levels = false;
     int ai = 1;
@@ -85,7 +184,7 @@ int main(int argc, char** argv) {
     std::string out_dir; bool have_out_dir = false;
     size_t channels = 2, bit_depth = 24; char fmt = 'I', filt = 'E', endian = 'M', dither = 0, output = 'S';
     uint32_t block = 4096, rate = 352800, inrate = 1; double level = 0.0; bool append = false, recurse = false, quiet = false;
-    int device = 0; unsigned long long seed = 0; uint32_t tap_bits = 0; bool gpu_flac = false; int flac_effort = 0;
+    int device = 0; unsigned long long seed = 0; uint32_t tap_bits = 0; bool gpu_flac = false, flac_verify = false; int flac_effort = 0;
     std::vector<std::string> files;
     for (; ai < argc; ++ai) {
         std::string a = argv[ai];
@@ -112,7 +211,12 @@ int main(int argc, char** argv) {
         else if (a == "--tap-bits") tap_bits = (uint32_t)strtoul(val(), 0, 10);
         else if (a == "--gpu-flac") gpu_flac = true;               // -o f only: encode the frames on the GPU (Rdsd2Pcm::set_gpu_flac)
         else if (a == "--flac-effort") flac_effort = atoi(val());  // -o f only: 0 (default), 1, the search, or 12, the search with LPC (Rdsd2Pcm::set_flac_effort)
+        else if (a == "--flac-verify") flac_verify = true;         // --gpu-flac -o f only: check every frame against its PCM on the GPU before it is written (Rdsd2Pcm::set_flac_verify)
         else files.push_back(a);
+    }
+    if (flac_verify && !(gpu_flac && tolower(output) == 'f')) {
+        fprintf(stderr, "ERROR: --flac-verify checks the frames --gpu-flac encodes: it needs --gpu-flac and -o f\n");
+        return 2;
     }
     if (files.empty()) files.push_back("-");
     try {
@@ -150,7 +254,7 @@ int main(int argc, char** argv) {
             Rdsd2Pcm lib = (!is_stdin && DsdFileFormat::from(path).is_container())
                                ? Rdsd2Pcm::from_container(bit_depth, ot, level, rate, od, dt, fl, append, ".", path)
                                : Rdsd2Pcm::create(bit_depth, ot, level, rate, od, dt, ft, en, inrate, block, channels, fl, append, ".", ip);
-            lib.set_device(device); lib.set_seed(seed); lib.set_tap_bits(tap_bits); lib.set_gpu_flac(gpu_flac); lib.set_flac_effort(flac_effort);
+            lib.set_device(device); lib.set_seed(seed); lib.set_tap_bits(tap_bits); lib.set_gpu_flac(gpu_flac); lib.set_flac_effort(flac_effort); lib.set_flac_verify(flac_verify);
             lib.do_conversion(CANCEL_FLAG);
             if (!quiet && !lib.warnings().empty()) fprintf(stderr, "WARNING: %s: %s\n", lib.file_name().c_str(), lib.warnings().c_str());
             if (!quiet && lib.audio_seconds() > 0)

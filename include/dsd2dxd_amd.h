@@ -20,11 +20,13 @@
 extern "C" {
 #endif
 
-#define D2D_ABI_VERSION 9   /* 3: the table blob header names the table variant; 4: d2d_params.tap_bits; 5: d2d_params.debug_flags (was reserved0);
+#define D2D_ABI_VERSION 10  /* 3: the table blob header names the table variant; 4: d2d_params.tap_bits; 5: d2d_params.debug_flags (was reserved0);
                              * 6: d2d_seek / d2d_tell / d2d_prime* and the two size queries (d2d_params unchanged);
                              * 7: the d2d_flac_* entry points and d2d_convert_stream_flac (d2d_params unchanged);
                              * 8: the FLAC efforts: d2d_flac_encode_device_effort / _host_effort, d2d_convert_stream_flac_effort (d2d_params unchanged);
-                             * 9: FLAC effort 12, D2D_FLAC_EFFORT_LPC, through the same entry points (d2d_params unchanged) */
+                             * 9: FLAC effort 12, D2D_FLAC_EFFORT_LPC, through the same entry points (d2d_params unchanged);
+                             * 10: verifying FLAC frames: d2d_flac_verify_device / _host, d2d_flac_decode_host, d2d_convert_stream_flac_verified,
+                             *     d2d_flac_check, D2D_FLAC_BAD_*, D2D_ERR_VERIFY (d2d_params unchanged) */
 
 /* status codes */
 enum {
@@ -36,7 +38,8 @@ enum {
     D2D_ERR_CAPACITY = -20,    /* output buffer too small                                       */
     D2D_ERR_CANCELLED = -30,   /* cancel flag was raised (do_conversion's &AtomicBool)          */
     D2D_ERR_STATE = -40,       /* call sequence error                                           */
-    D2D_ERR_IO = -50           /* reader / sink callback failed                                 */
+    D2D_ERR_IO = -50,          /* reader / sink callback failed                                 */
+    D2D_ERR_VERIFY = -60       /* a FLAC frame did not verify (d2d_convert_stream_flac_verified) */
 };
 
 /* enum values mirror the reference's CLI characters so a binding can pass them through:
@@ -357,6 +360,79 @@ int d2d_convert_stream_flac_effort(d2d_engine* e, uint32_t bit_depth, uint32_t e
                                    d2d_write_fn write, void* write_user,
                                    const volatile int* cancel, d2d_progress_fn progress, void* progress_user,
                                    uint64_t total_bytes_per_channel, size_t chunk_bytes_per_channel, d2d_flac_stream_stats* stats);
+
+/* ---- Verifying the frames (ABI 10) ---------------------------------------------------------- */
+
+/* The counterpart of `flac --verify`: every frame an encode call wrote is parsed, decoded and compared with the PCM it was made from,
+ * where both still are.  One parser (csrc/flac/flac_parse.h, the same source on the host and in the kernel) reads what the encoders
+ * here can write, a little generalised: verbatim subframes, fixed orders 0 .. 4, LPC orders 1 .. 32 with precision 1 .. 15 and shift
+ * 0 .. 15 (the field is signed: 16 .. 31 are negative shifts, which FLAC forbids), Rice method `01` with partition orders 0 .. 15; block-size
+ * codes of every kind, sample-rate code 0, independent channels up to 8 and the three stereo assignments, 16 / 20 / 24 bits, frame
+ * numbers up to 31 bits.
+ *
+ * THE REASONS, in the order of the checks: the first check a block fails is its reason (the numbered rules at the head of
+ * flac_parse.h).  CRC-16 comes before any subframe is parsed, so a frame damaged in storage or transit is CRC8 or CRC16, and the later
+ * reasons are what an encoder bug would produce.  D2D_FLAC_BAD_SAMPLES is the last: the frame parses from its first bit to its last
+ * and does not give the PCM.  The host and the device give the same record for the same bytes. */
+enum { D2D_FLAC_BAD_NONE = 0,
+       D2D_FLAC_BAD_SIZE,        /* size-table entry 0, or above the frame bound, or the frames of a file do not add up to bytes_out */
+       D2D_FLAC_BAD_HEADER,      /* sync, reserved bits, or a field that is not this call's: n, channels, depth, frame number      */
+       D2D_FLAC_BAD_CRC8, D2D_FLAC_BAD_CRC16,
+       D2D_FLAC_BAD_UNSUPPORTED, /* valid FLAC that the encoders here never write: constant subframes, wasted bits, Rice method 00,
+                                    escape partitions, the variable-block-size bit, sample-rate codes other than 0                */
+       D2D_FLAC_BAD_SYNTAX,      /* reserved values, partition order impossible for n, bits run out                                */
+       D2D_FLAC_BAD_LENGTH,      /* the subframes end, padding is not zero or the frame is not exactly its size                     */
+       D2D_FLAC_BAD_SAMPLES };   /* decodes, and is not the PCM                                                                     */
+typedef struct d2d_flac_check {
+    uint64_t samples_checked;    /* samples per channel of the blocks that passed */
+    uint32_t blocks_checked;     /* blocks looked at (= io.blocks)                */
+    uint32_t bad_blocks;
+    uint32_t first_bad_block;    /* index within the call; 0xFFFFFFFF: none       */
+    uint32_t first_bad_reason;   /* D2D_FLAC_BAD_* of that block                  */
+} d2d_flac_check;
+
+/* Called after d2d_flac_encode_device[_effort] on the same `io` (blocks, frames_consumed and first_block as that call left them),
+ * the same untouched `workspace` and the same stream.  Asynchronous: checks[f], one record per file in memory the GPU can address
+ * (device or pinned), is valid once the stream has synchronised.  It checks the PACKED bytes [0, bytes_out) of each file's `out`
+ * against `pcm`; bytes_out comes from the result record, the frame starts from the size table the encode call left at the front of
+ * the file's workspace -- the one thing taken from the encoder, and checked: an entry that is 0, above D2D_FLAC_FRAME_BOUND(4096) or
+ * reaching beyond bytes_out, and a last block that does not end at bytes_out, are D2D_FLAC_BAD_SIZE.  Two launches per sixteen files:
+ * one lane per frame decides each (file, block) and leaves a status word in the first word of the block's workspace slot, then one
+ * workgroup per file turns the words into the record with plain stores.  No atomics, no waiting.
+ *
+ * Refused before anything is launched, with the codes of the encode call: a depth that is not 16 / 20 / 24, channels 0 or above 8, null
+ * or misaligned pointers (checks: 8-byte aligned), first_block + blocks above 2^31 -> D2D_ERR_PARAM; a workspace too small ->
+ * D2D_ERR_CAPACITY.
+ *
+ * WHAT A CALL MAY TOUCH (tests/test_gpu_flac_verify.py pins it): it writes the check records and bytes inside [workspace, workspace +
+ * workspace_bytes) -- never `out`, `pcm` or the result records.  It reads pcm[0, frames_consumed * frame_bytes), out[0, bytes_out), the
+ * size table and the result record.  A refused call writes nothing. */
+int d2d_flac_verify_device(uint32_t channels, uint32_t bit_depth, const d2d_flac_io* io, uint32_t n_files,
+                           void* workspace, size_t workspace_bytes, d2d_flac_check* checks, void* hip_stream);
+/* The CPU twin, no device: the same rules on one file in host memory; what the GPU tests compare against.  `out` holds bytes_out
+ * bytes of frames made from the `frames` frames at `pcm` (first_block, final as at the encode call); `sizes` is the per-block size
+ * array, or NULL: then the frames are walked by decoding (rule 10 of flac_parse.h: the CRC-16 is checked once the frame's end is
+ * found, and a walk that loses the frame's end -- any reason but SAMPLES -- ends there: every later block is D2D_FLAC_BAD_SIZE).  Parameter checks and codes of
+ * d2d_flac_encode_host. */
+int d2d_flac_verify_host(uint32_t channels, uint32_t bit_depth, const void* pcm, size_t frames, uint32_t first_block, int final,
+                         const void* out, size_t bytes_out, const uint32_t* sizes, d2d_flac_check* check);
+/* A small FLAC decoder for what the sinks here write: a run of whole frames, numbered from first_block, into the packed little-endian
+ * PCM the translate calls write (20-bit samples as the 3-byte container, the value shifted left by 4).  Every frame holds 4096
+ * samples per channel but the last, which may hold fewer.  It writes exactly [0, *frames_out * frame_bytes) of `pcm` and stops at the
+ * first bad frame: *frames_out counts the samples per channel up to there, `check` says why (blocks_checked counts the frames looked
+ * at, the bad one included), and the return code is still D2D_OK.  pcm_capacity_bytes below what the frames' headers announce ->
+ * D2D_ERR_CAPACITY, nothing written. */
+int d2d_flac_decode_host(uint32_t channels, uint32_t bit_depth, const void* frames, size_t bytes, uint32_t first_block,
+                         void* pcm, size_t pcm_capacity_bytes, size_t* frames_out, d2d_flac_check* check);
+/* d2d_convert_stream_flac_effort with a verify pass: after each chunk's encode the verify is enqueued on the same stream and its
+ * record read with the frame bytes.  `check` accumulates the whole stream (first_bad_block is a stream block index).  On a bad block
+ * the call stops BEFORE that chunk is handed to `write` and returns D2D_ERR_VERIFY; d2d_flac_error() names the block and the reason.
+ * With no bad block, `write` receives the bytes of the unverified call. */
+int d2d_convert_stream_flac_verified(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* read_user,
+                                     d2d_write_fn write, void* write_user,
+                                     const volatile int* cancel, d2d_progress_fn progress, void* progress_user,
+                                     uint64_t total_bytes_per_channel, size_t chunk_bytes_per_channel, d2d_flac_stream_stats* stats,
+                                     d2d_flac_check* check);
 
 /* ---- shared tables (multi-GPU) ------------------------------------------------------------ */
 

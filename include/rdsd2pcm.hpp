@@ -79,6 +79,11 @@ class Rdsd2Pcm {
     // predictors of order 4, 8 and 12.  It applies to the host sink and to the set_gpu_flac path alike, which write the same frames
     // at every effort.  Any other value throws.
     void set_flac_effort(int effort);
+    // With set_gpu_flac only (ignored otherwise); off by default.  On: every chunk's frames are parsed, decoded and compared with the PCM
+    // they were made from, on the GPU, before they are written (d2d_convert_stream_flac_verified): the counterpart of `flac --verify`.
+    // The file is the one written without it; a block that does not verify ends do_conversion with an exception that names the block and
+    // the reason.  The C mirror (rdsd2pcm_c.h) does not have it, as it does not have set_gpu_flac.
+    void set_flac_verify(bool on);
 
     struct Impl;                              // opaque state (public only so the .cpp's helpers can name it)
 

@@ -10,7 +10,11 @@ own encoder -- on the same PCM in host memory, one block per task on 16 threads,
 two passes.  File 0's device frames are compared with the host's.  With --effort 1 (the search, D2D_FLAC_EFFORT_SEARCH) both sides run
 at that effort, and the effort-0 call is timed beside it on the same buffers for the size ratio.  With --effort 12 (the search with
 LPC, D2D_FLAC_EFFORT_LPC) the call timed beside it is effort 1's, in the same session on the same buffers: bytes and time are stated
-over effort 1's, and no file may come out longer than at effort 1."""
+over effort 1's, and no file may come out longer than at effort 1.
+
+   tools/flac_probe.py --verify [files] [seconds] [reps] [out.json]      (default bench_out/flac_verify_probe.json)
+times ONE d2d_flac_verify_device call over the batch (both kernels) at each effort, after that effort's encode call on the same buffers,
+beside the encode call itself; every record must be clean.  The ratio verify / encode at the same effort is the figure of interest."""
 import ctypes as C
 import json
 import os
@@ -32,10 +36,13 @@ if "--effort" in argv:
     at = argv.index("--effort")
     effort = int(argv[at + 1])
     del argv[at:at + 2]
+verify_mode = "--verify" in argv
+if verify_mode:
+    argv.remove("--verify")
 n_files = int(argv[0]) if len(argv) > 0 else 64
 seconds = float(argv[1]) if len(argv) > 1 else 60.0
 reps = int(argv[2]) if len(argv) > 2 else 9
-out_path = argv[3] if len(argv) > 3 else os.path.join(ROOT, "bench_out", "flac_probe.json")
+out_path = argv[3] if len(argv) > 3 else os.path.join(ROOT, "bench_out", "flac_verify_probe.json" if verify_mode else "flac_probe.json")
 blocks_in = max(1, int(round(seconds * DSD64 / 8 / 4096)))
 bpc = blocks_in * 4096
 CH, DEPTH, BS, THREADS = 2, 24, 4096, 16
@@ -84,6 +91,26 @@ fio = (d.FlacIO * n_files)()
 for f in range(n_files):
     fio[f].pcm, fio[f].frames, fio[f].first_block, fio[f].final = pcm[f].data_ptr(), frames, 0, 1
     fio[f].out, fio[f].out_capacity_bytes, fio[f].result = out[f].data_ptr(), cap, rec.data_ptr() + 16 * f
+if verify_mode:
+    chk = torch.zeros(n_files * 24, dtype=torch.uint8, device=dev)
+    res = dict(files=n_files, seconds_per_file=seconds, frames_per_file=frames, reps=reps, efforts={})
+    print("batch: %d files x %d frames, stereo 24-bit" % (n_files, frames))
+    for eff in (d.FLAC_EFFORT_FIXED2, d.FLAC_EFFORT_SEARCH, d.FLAC_EFFORT_LPC):
+        e_ms = timed(lambda: d.flac_encode_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), stream, effort=eff))
+        v_ms = timed(lambda: d.flac_verify_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), chk.data_ptr(), stream))
+        c = chk.cpu().numpy()
+        for f in range(n_files):
+            r = c[24 * f:24 * f + 24]
+            got = (int(r[:8].view(np.uint64)[0]),) + tuple(int(v) for v in r[8:].view(np.uint32))
+            assert got == (frames, int(fio[f].blocks), 0, 0xFFFFFFFF, 0), (eff, f, got)
+        res["efforts"][str(eff)] = dict(gpu_encode_ms=dict(median=e_ms[0], min=e_ms[1], max=e_ms[2]), gpu_verify_ms=dict(median=v_ms[0], min=v_ms[1], max=v_ms[2]),
+                                        verify_over_encode=v_ms[0] / e_ms[0], blocks=n_files * int(fio[0].blocks))
+        print("effort %2d: encode median %.3f ms (min %.3f, max %.3f); verify median %.3f ms (min %.3f, max %.3f); verify / encode %.2fx; %d blocks, all good" %
+              (eff, *e_ms, *v_ms, v_ms[0] / e_ms[0], n_files * int(fio[0].blocks)))
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        json.dump(res, fh, indent=1)
+    sys.exit(0)
 enc0, bytes0, per_file0 = None, None, None
 base = 1 if effort == d.FLAC_EFFORT_LPC else 0                  # the effort this one is held against
 if effort:                                                      # the base effort on the same buffers first: its time and its bytes
