@@ -4,8 +4,9 @@ The product is the C-ABI shared library `libdsd2dxd_amd.so` (include/dsd2dxd_amd
 dsd2dxd_amd/csrc for gfx950.  This package is only the thin ctypes binding the tests and bench.py
 drive it through; there is no Python or CPU implementation of the conversion behind it.
 """
-from ._capi import (D2DError, Engine, FileIO, Params, lib, library_path, build_library,  # noqa: F401
+from ._capi import (D2DError, Engine, FileIO, Info, Params, lib, library_path, build_library,  # noqa: F401
                     KERNEL_AUTO, KERNEL_LUT, KERNEL_MFMA,
+                    FILTER_EQUIRIPPLE, FILTER_XLD, FILTER_DSD2PCM, FILTER_CHEBYSHEV, FILTER_EQUIRIPPLE_CASCADE,
                     DBG_NO_MX, DBG_NO_GAINQ, DBG_NO_COOP, DBG_HOST_STAGED, DBG_NO_PIPE, DBG_MFMA_V1, DBG_NO_INTQ, DBG_NS_GENERAL, DBG_TAPS32_2PASS, dbg_waves,
                     FLAC_BLOCK, FLAC_EFFORT_FIXED2, FLAC_EFFORT_SEARCH, FLAC_EFFORT_LPC, FlacIO, FlacResult, FlacStreamStats, flac_bound_bytes, flac_workspace_bytes, flac_encode_host, flac_encode_device,
                     FlacCheck, flac_decode_host, flac_verify_host, flac_verify_device, ERR_VERIFY, FLAC_NO_BAD_BLOCK,

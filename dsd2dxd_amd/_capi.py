@@ -6,6 +6,8 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 KERNEL_AUTO, KERNEL_LUT, KERNEL_MFMA = 0, 1, 2
+# d2d_params.filter (D2D_FILTER_*): the reference CLI's letters, and "S", the equiripple filter of the 48 kHz multiples in two stages
+FILTER_EQUIRIPPLE, FILTER_XLD, FILTER_DSD2PCM, FILTER_CHEBYSHEV, FILTER_EQUIRIPPLE_CASCADE = "E", "X", "D", "C", "S"
 # d2d_params.debug_flags (include/dsd2dxd_amd.h: D2D_DBG_*): diagnostic dispatch switches, 0 in production
 DBG_NO_MX, DBG_NO_GAINQ, DBG_NO_COOP, DBG_HOST_STAGED, DBG_NO_PIPE, DBG_MFMA_V1, DBG_NO_INTQ, DBG_NS_GENERAL = (1 << i for i in range(8))
 DBG_TAPS32_2PASS = 1 << 16
@@ -270,7 +272,9 @@ def make_params(dsd_rate=1, output_rate=352800, channels=2, fmt="I", endianness=
                 filter="E", bit_depth=24, dither="X", level_db=0.0, seed=0, kernel=KERNEL_AUTO, device=0,
                 channel_first=0, channel_count=0, tap_bits=0, debug=0):
     """Argument names and defaults follow the reference CLI (src/main.rs:40-110); channel_first/count
-    select a channel subset (0 = all), tap_bits the tap grid (0 / 24, or 32), see include/dsd2dxd_amd.h."""
+    select a channel subset (0 = all), tap_bits the tap grid (0 / 24, or 32), see include/dsd2dxd_amd.h.
+    filter: the CLI's letters E, X, D, C, or "S" (FILTER_EQUIRIPPLE_CASCADE): the 48 kHz multiples as stage A
+    to 352.8 kHz and a polyphase stage B, where "E" runs the two composed into one pass."""
     return Params(C.sizeof(Params), dsd_rate, output_rate, channels, 1 if fmt.upper() == "P" else 0,
                   1 if endianness.upper() == "M" else 0, block_size, ord(filter.upper()), bit_depth,
                   ord(dither.upper()), kernel, device, level_db, seed, channel_first, channel_count, tap_bits, debug)

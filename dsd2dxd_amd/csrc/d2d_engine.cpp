@@ -183,9 +183,11 @@ struct d2d_engine {
     std::vector<int32_t> lo_half;
     d2d_filter_def lo_def{};
     Buf<uint8_t> d_fir_tables_lo;
-    // DSD64 / DSD128 -> 48k multiples: one polyphase pass over the bits (d2d_kernels_px.hip); fc.fir / fc.resamp only count frames then
+    // filter 'E', DSD64 / DSD128 -> 48k multiples and DSD256 -> 192 / 384 kHz: one polyphase pass over the bits (d2d_kernels_px.hip); fc.fir / fc.resamp
+    // only count frames then
     const d2d_poly_def* poly = nullptr;
-    bool cascade() const { return fc.resamp && !poly; }      // the two-kernel 48k path (DSD256 / DSD512 input)
+    // the two-kernel 48k path: DSD256 -> 96 kHz and DSD512 input, and every 48k multiple of an engine with filter 'S' (d2d_filters.h)
+    bool cascade() const { return fc.resamp && !poly; }
     // route.mono2_pipe: calls the mono pair does not fit (odd sizes, very short ones) take the engine's ordinary mono kernel: same bytes either way
     bool mono2_ok() const { return route.mono2_pipe != PIPE_NONE; }
     Buf<uint8_t> d_fir_tables_m2;

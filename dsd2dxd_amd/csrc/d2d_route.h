@@ -31,7 +31,7 @@ int mfma2_pipelined(const FirArgs& a, int M, int N);
 // ---- the route of an engine ----
 struct FirRoute {
     uint32_t kernel = D2D_KERNEL_LUT;
-    bool poly = false;                    // DSD64 / DSD128 -> 48k multiples: one polyphase pass over the bits (d2d_kernels_px.hip)
+    bool poly = false;                    // filter E, DSD64 / DSD128 -> 48k multiples, DSD256 -> 192 / 384 kHz: one polyphase pass over the bits (d2d_kernels_px.hip)
     bool poly_plain = false;              // ... through the bit-by-bit kernel (D2D_KERNEL_LUT engines)
     bool mfma_v2 = false;                 // the two-group matrix-core kernel (d2d_kernels_mfma2.hip) serves this shape
     int mfma_pipe = PIPE_NONE;            // ... through a software-pipelined variant: PIPE_INT8 (d2d_kernels_mfma3.hip) or PIPE_FP6 (d2d_kernels_mx.hip)

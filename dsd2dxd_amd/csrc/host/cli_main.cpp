@@ -2,6 +2,7 @@
 // (/root/reference/src/main.rs:40-133) for the conversion-relevant subset, plus:
 //   probe  <file>...      print what the container readers see, as JSON (no GPU needed)
 //   levels [opts] files   peak dBFS per file and overall (src/bin/dsd_levels/main.rs)
+//   -t S                  (convert and levels) not a reference letter: the 48 kHz multiples in two stages, D2D_FILTER_EQUIRIPPLE_CASCADE
 //   tags [-a RATE] <file>...   the source's ID3v2 tag as the converted file would carry it, as JSON
 //                         (text frames under their Vorbis names; -a applies the album suffix; no GPU needed)
 //   verify <file.flac>... read back FLAC files the sinks here wrote: every frame is decoded (d2d_flac_decode_host) and the frame numbers,
@@ -231,7 +232,8 @@ int main(int argc, char** argv) {
         switch (tolower(fmt)) { case 'i': ft = FmtType::Interleaved; break; case 'p': ft = FmtType::Planar; break;
             default: throw std::runtime_error("Invalid format; must be I (interleaved) or P (planar)"); }
         Endianness en = tolower(endian) == 'l' ? Endianness::LsbFirst : Endianness::MsbFirst;
-        FilterType fl = toupper(filt) == 'X' ? FilterType::XLD : toupper(filt) == 'D' ? FilterType::Dsd2Pcm : toupper(filt) == 'C' ? FilterType::Chebyshev : FilterType::Equiripple;
+        FilterType fl = toupper(filt) == 'X' ? FilterType::XLD : toupper(filt) == 'D' ? FilterType::Dsd2Pcm : toupper(filt) == 'C' ? FilterType::Chebyshev :
+                        toupper(filt) == 'S' ? FilterType::EquirippleCascade : FilterType::Equiripple;      // S: extension, the 48 kHz multiples in two stages
         OutputType ot = tolower(output) == 'a' ? OutputType::Aiff : tolower(output) == 'c' ? OutputType::Aifc : tolower(output) == 'w' ? OutputType::Wav : tolower(output) == 'f' ? OutputType::Flac : OutputType::Stdout;
         bool has_stdin = false;
         std::vector<std::string> paths;
@@ -244,7 +246,9 @@ int main(int argc, char** argv) {
             std::optional<std::string> od; if (have_out_dir) od = out_dir;
             std::optional<std::string> ip; if (!is_stdin) ip = path;
             if (levels) {
-                Rdsd2Pcm lib = Rdsd2Pcm::new_level_check(rate, ip, ft, en, channels, block, inrate);
+                // (the reference's level check is always the equiripple filter, whatever -t says; -t S chooses which of its two definitions)
+                Rdsd2Pcm lib = Rdsd2Pcm::new_level_check(rate, ip, ft, en, channels, block, inrate,
+                                                         fl == FilterType::EquirippleCascade ? fl : FilterType::Equiripple);
                 lib.set_device(device);
                 float db = lib.check_level(CANCEL_FLAG);
                 printf("%s: %.4f dBFS\n", lib.file_name().c_str(), db);

@@ -51,7 +51,9 @@ struct Rdsd2Pcm::Impl {
 };
 
 static uint32_t dither_code(DitherType d) { return d == DitherType::TPDF ? 'T' : d == DitherType::Rectangular ? 'R' : d == DitherType::FPD ? 'F' : d == DitherType::NoiseShaped ? 'N' : 'X'; }
-static uint32_t filter_code(FilterType f) { return f == FilterType::Equiripple ? 'E' : f == FilterType::XLD ? 'X' : f == FilterType::Dsd2Pcm ? 'D' : 'C'; }
+static uint32_t filter_code(FilterType f) {
+    return f == FilterType::Equiripple ? 'E' : f == FilterType::XLD ? 'X' : f == FilterType::Dsd2Pcm ? 'D' : f == FilterType::EquirippleCascade ? 'S' : 'C';
+}
 
 static std::string dirname_of(const std::string& p) { size_t s = p.find_last_of('/'); return s == std::string::npos ? "." : (s == 0 ? "/" : p.substr(0, s)); }
 static std::string basename_of(const std::string& p) { size_t s = p.find_last_of('/'); return s == std::string::npos ? p : p.substr(s + 1); }
@@ -126,12 +128,12 @@ Rdsd2Pcm Rdsd2Pcm::from_container(size_t bit_depth, OutputType output, double le
 }
 
 Rdsd2Pcm Rdsd2Pcm::new_level_check(uint32_t output_rate, std::optional<std::string> path, FmtType fmt, Endianness endian,
-                                   size_t channels, uint32_t block_size, uint32_t input_rate) {
+                                   size_t channels, uint32_t block_size, uint32_t input_rate, FilterType filter) {
     Rdsd2Pcm r = (path && DsdFileFormat::from(*path).is_container())
                      ? from_container(32, OutputType::Stdout, 0.0, output_rate, std::nullopt, DitherType::None,
-                                      FilterType::Equiripple, false, ".", *path)
+                                      filter, false, ".", *path)
                      : create(32, OutputType::Stdout, 0.0, output_rate, std::nullopt, DitherType::None, fmt, endian,
-                              input_rate, block_size, channels, FilterType::Equiripple, false, ".", path);
+                              input_rate, block_size, channels, filter, false, ".", path);
     r.p_->level_only = true;
     return r;
 }

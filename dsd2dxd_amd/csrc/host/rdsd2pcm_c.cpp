@@ -35,7 +35,8 @@ FmtType fmt_of(uint32_t c) {
 }
 Endianness endian_of(uint32_t c) { return (c == 'L' || c == 'l') ? Endianness::LsbFirst : Endianness::MsbFirst; }       // :193-197
 FilterType filter_of(uint32_t c) {                                                                                       // :199-205
-    switch (c) { case 'X': case 'x': return FilterType::XLD; case 'D': case 'd': return FilterType::Dsd2Pcm; case 'C': case 'c': return FilterType::Chebyshev; }
+    switch (c) { case 'X': case 'x': return FilterType::XLD; case 'D': case 'd': return FilterType::Dsd2Pcm; case 'C': case 'c': return FilterType::Chebyshev;
+                 case 'S': case 's': return FilterType::EquirippleCascade; }                                                         // (extension: dsd2dxd_amd.h)
     return FilterType::Equiripple;
 }
 OutputType output_of(uint32_t c) {                                                                                       // :207-214

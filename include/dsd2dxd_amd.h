@@ -20,13 +20,15 @@
 extern "C" {
 #endif
 
-#define D2D_ABI_VERSION 10  /* 3: the table blob header names the table variant; 4: d2d_params.tap_bits; 5: d2d_params.debug_flags (was reserved0);
+#define D2D_ABI_VERSION 11  /* 3: the table blob header names the table variant; 4: d2d_params.tap_bits; 5: d2d_params.debug_flags (was reserved0);
                              * 6: d2d_seek / d2d_tell / d2d_prime* and the two size queries (d2d_params unchanged);
                              * 7: the d2d_flac_* entry points and d2d_convert_stream_flac (d2d_params unchanged);
                              * 8: the FLAC efforts: d2d_flac_encode_device_effort / _host_effort, d2d_convert_stream_flac_effort (d2d_params unchanged);
                              * 9: FLAC effort 12, D2D_FLAC_EFFORT_LPC, through the same entry points (d2d_params unchanged);
                              * 10: verifying FLAC frames: d2d_flac_verify_device / _host, d2d_flac_decode_host, d2d_convert_stream_flac_verified,
-                             *     d2d_flac_check, D2D_FLAC_BAD_*, D2D_ERR_VERIFY (d2d_params unchanged) */
+                             *     d2d_flac_check, D2D_FLAC_BAD_*, D2D_ERR_VERIFY (d2d_params unchanged);
+                             * 11: D2D_FILTER_EQUIRIPPLE_CASCADE, the two-stage definition of the 48 kHz multiples, as a value of
+                             *     d2d_params.filter (d2d_params unchanged) */
 
 /* status codes */
 enum {
@@ -47,7 +49,15 @@ enum {
  *   FilterType  src/main.rs:199-205    DitherType src/main.rs:171-181 */
 enum { D2D_FMT_INTERLEAVED = 0, D2D_FMT_PLANAR = 1 };
 enum { D2D_LSB_FIRST = 0, D2D_MSB_FIRST = 1 };
-enum { D2D_FILTER_EQUIRIPPLE = 'E', D2D_FILTER_XLD = 'X', D2D_FILTER_DSD2PCM = 'D', D2D_FILTER_CHEBYSHEV = 'C' };
+enum { D2D_FILTER_EQUIRIPPLE = 'E', D2D_FILTER_XLD = 'X', D2D_FILTER_DSD2PCM = 'D', D2D_FILTER_CHEBYSHEV = 'C',
+       /* extension (ABI 11; no counterpart in src/main.rs:199-205), "stages": the equiripple filter of the 48 kHz multiples (96000 /
+        * 192000 / 384000) as the cascade the reference describes.  Stage A decimates the bits to 352.8 kHz and its samples are
+        * rounded to the stage's own grid; stage B, a polyphase L/147 resampler, reads those samples.  'E' composes the two stages
+        * into one polyphase filter on the bits wherever such a table ships (DSD64 and DSD128 to every 48 kHz multiple, DSD256 to
+        * 192 and 384 kHz): no sample at 352.8 kHz, so none of the images that sampling folds down, and other bytes (DESIGN.md
+        * section 0 has the differences).  Where 'E' is already two-stage (DSD256 to 96 kHz, DSD512) the two letters give the same
+        * bytes.  44.1 kHz-family rates are refused with D2D_ERR_FILTER. */
+       D2D_FILTER_EQUIRIPPLE_CASCADE = 'S' };
 enum { D2D_DITHER_TPDF = 'T', D2D_DITHER_RECT = 'R', D2D_DITHER_FPD = 'F', D2D_DITHER_NONE = 'X',
        /* extension (no counterpart in src/main.rs:171-181): TPDF dither inside a second-order error-feedback
         * loop, noise transfer function (1 - z^-1)^2; integer depths, 44.1 kHz-family output rates.  The loop is a

@@ -24,7 +24,8 @@ enum class DitherType { TPDF, Rectangular, FPD, None,              // src/main.r
                         NoiseShaped };                            // extension ('N'): see dsd2dxd_amd.h
 enum class FmtType { Interleaved, Planar };                       // src/main.rs:185-186
 enum class Endianness { LsbFirst, MsbFirst };                     // src/main.rs:194-196
-enum class FilterType { Equiripple, XLD, Dsd2Pcm, Chebyshev };    // src/main.rs:200-204
+enum class FilterType { Equiripple, XLD, Dsd2Pcm, Chebyshev,      // src/main.rs:200-204
+                        EquirippleCascade };                      // extension ('S'): the 48 kHz multiples in two stages, see dsd2dxd_amd.h
 enum class OutputType { Stdout, Aiff, Aifc, Wav, Flac };          // src/main.rs:208-213
 
 struct ProgressUpdate { float percent; };
@@ -51,8 +52,9 @@ class Rdsd2Pcm {
                                    std::optional<std::string> out_dir, DitherType dither, FilterType filter,
                                    bool append_rate, std::string base_dir, std::string path);
     // path: nullopt = stdin (src/bin/dsd_levels/main.rs:214-223 passes Some(path), :273-281 None)
+    // filter: not a reference argument (its level check is always the equiripple filter); EquirippleCascade measures the two-stage definition
     static Rdsd2Pcm new_level_check(uint32_t output_rate, std::optional<std::string> path, FmtType fmt, Endianness endian,
-                                    size_t channels, uint32_t block_size, uint32_t input_rate);
+                                    size_t channels, uint32_t block_size, uint32_t input_rate, FilterType filter = FilterType::Equiripple);
     Rdsd2Pcm(Rdsd2Pcm&&) noexcept;
     Rdsd2Pcm& operator=(Rdsd2Pcm&&) noexcept;
     ~Rdsd2Pcm();

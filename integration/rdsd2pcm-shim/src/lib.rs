@@ -24,14 +24,15 @@ pub enum FmtType { Interleaved, Planar } // src/main.rs:185-186
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum Endianness { LsbFirst, MsbFirst } // src/main.rs:194-196
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
-pub enum FilterType { Equiripple, XLD, Dsd2Pcm, Chebyshev } // src/main.rs:200-204
+pub enum FilterType { Equiripple, XLD, Dsd2Pcm, Chebyshev, // src/main.rs:200-204
+                      EquirippleCascade } // extension ('S'): the 48 kHz multiples in two stages, see dsd2dxd_amd.h
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum OutputType { Stdout, Aiff, Aifc, Wav, Flac } // src/main.rs:208-213
 
 impl DitherType { fn code(self) -> u32 { match self { Self::TPDF => b'T', Self::Rectangular => b'R', Self::FPD => b'F', Self::None => b'X', Self::NoiseShaped => b'N' } as u32 } }
 impl FmtType { fn code(self) -> u32 { match self { Self::Interleaved => b'I', Self::Planar => b'P' } as u32 } }
 impl Endianness { fn code(self) -> u32 { match self { Self::LsbFirst => b'L', Self::MsbFirst => b'M' } as u32 } }
-impl FilterType { fn code(self) -> u32 { match self { Self::Equiripple => b'E', Self::XLD => b'X', Self::Dsd2Pcm => b'D', Self::Chebyshev => b'C' } as u32 } }
+impl FilterType { fn code(self) -> u32 { match self { Self::Equiripple => b'E', Self::XLD => b'X', Self::Dsd2Pcm => b'D', Self::Chebyshev => b'C', Self::EquirippleCascade => b'S' } as u32 } }
 impl OutputType { fn code(self) -> u32 { match self { Self::Stdout => b'S', Self::Aiff => b'A', Self::Aifc => b'C', Self::Wav => b'W', Self::Flac => b'F' } as u32 } }
 
 /// The DSD rate as a multiple of 2.8224 MHz.  The call sites write `cli.input_rate.try_into()?`

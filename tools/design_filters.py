@@ -180,7 +180,7 @@ def stage_b_dense(out_rate, L, P, dens):
 
 
 def compose_polyphase(dsd_rate, r, hA_half):
-    """The 48k cascade composed into ONE polyphase filter on the DSD bits (DSD64 / DSD128 input).
+    """The 48k cascade composed into ONE polyphase filter on the DSD bits (DSD64 / DSD128 input, DSD256 -> 192 / 384 kHz).
 
     Stage A (hA, at the bit rate) and stage B (its prototype g at 352.8 kHz * L) are two LTI filters; without the sampling at 352.8 kHz
     between them their cascade is the single filter p = g (*) upsample(hA) on the fine grid of Lp ticks per bit

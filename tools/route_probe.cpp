@@ -16,6 +16,9 @@
 //   route_probe launches -     for those keys the launch plans of the engine (d2d_route.h: fir_launch), "<key>\t<pass> <field>=<value> ...[\t<pass> ...]":
 //                              the passes it has (main; lo: the residual table's; m2: the mono pair), each with the plan's family, unit, LDS bytes,
 //                              waves per block, outputs per wave-tile, wave-tiles per block, grid rows per file and the kernel's name
+//   route_probe filters -      for those keys what d2d_filters.h: choose_filters picked and what follows from it at once, "<key>\tfir=<table> M=<decimation>
+//                              resamp=<L>/<M>/<P> poly=<table or -> cascade=<0|1> to_scratch=<0|1>", or error=<code>:<text>.  The filter letter of a
+//                              key is any d2d_params.filter value: E, X, D, C, or S, the two-stage definition of the 48 kHz multiples
 #include <math.h>
 #include <stdio.h>
 
@@ -114,7 +117,29 @@ static const Rate RATE_MATRIX[] = {       // tests/test_gpu_parity.py: RATE_MATR
     {2, 96000, 'E'}, {2, 192000, 'E'}, {2, 384000, 'E'},
     {4, 96000, 'E'}, {4, 192000, 'E'}, {4, 384000, 'E'},
     {8, 96000, 'E'},
+    // filter 'S', the 48 kHz multiples in two stages: tests/test_cascade_cpu.py, tests/golden/route_cascade.json
+    {1, 96000, 'S'}, {1, 192000, 'S'}, {1, 384000, 'S'},
+    {2, 96000, 'S'}, {2, 192000, 'S'}, {2, 384000, 'S'},
+    {4, 96000, 'S'}, {4, 192000, 'S'}, {4, 384000, 'S'},
+    {8, 96000, 'S'},
 };
+
+// what choose_filters picked for a key, and the two facts every later decision hangs on: two kernels with a scratch between them or one pass
+static void filters_line(const Rate& rt, uint32_t ch, char fmt, uint32_t bits, char dither, double level, uint32_t tap_bits, uint32_t kernel, uint32_t dbg) {
+    d2d_params p{};
+    p.struct_size = sizeof(p);
+    p.dsd_rate = rt.dsd_rate; p.output_rate = rt.output_rate; p.filter = (uint32_t)rt.filter; p.channels = ch;
+    p.fmt = fmt == 'P' ? D2D_FMT_PLANAR : D2D_FMT_INTERLEAVED; p.endianness = fmt == 'P' ? D2D_LSB_FIRST : D2D_MSB_FIRST; p.block_size = 4096;
+    p.bit_depth = bits; p.dither = (uint32_t)dither; p.level_db = level; p.seed = 7; p.tap_bits = tap_bits; p.kernel = kernel; p.debug_flags = dbg;
+    printf("%u:%u:%c:%u%c%u%c:%d:%u:%u:%u\t", rt.dsd_rate, rt.output_rate, rt.filter, ch, fmt, bits, dither, (int)level, tap_bits, kernel, dbg);
+    FilterChoice fc; FirRoute r; std::string err;
+    int rc = choose_filters(p, fc, err);
+    if (rc == D2D_OK) rc = choose_route(p, fc, r, err);
+    if (rc != D2D_OK) { printf("error=%d:%s\n", rc, err.c_str()); return; }
+    const FirArgs a = fir_args_static(p, fc, epilogue_of(p), r);
+    printf("fir=%s M=%d resamp=%d/%d/%d poly=%s cascade=%d to_scratch=%u\n", fc.fir->name, fc.fir->M, fc.resamp ? fc.resamp->L : 0, fc.resamp ? fc.resamp->Mdn : 0,
+           fc.resamp ? fc.resamp->P : 0, fc.poly ? fc.poly->name : "-", fc.resamp && !fc.poly, a.to_scratch);
+}
 
 static void launch_field(const char* pass, const FirLaunch& l) {
     printf("\t%s family=%d unit=%d lds=%zu nwaves=%u tile=%u block_tiles=%u rows=%u name=%s", pass, l.family, l.unit, l.lds, l.nwaves, l.tile, l.block_tiles,
@@ -189,14 +214,15 @@ int main(int argc, char** argv) {
     if (argc > 1 && std::string(argv[1]) == "predicates") { predicates(); return 0; }
 #ifndef ROUTE_PROBE_PREDICATES_ONLY
     if (argc == 1) { routes(); return 0; }
-    const bool launches = std::string(argv[1]) == "launches";
-    if (std::string(argv[launches && argc > 2 ? 2 : 1]) == "-") {
+    const bool launches = std::string(argv[1]) == "launches", filters = std::string(argv[1]) == "filters";
+    if (std::string(argv[(launches || filters) && argc > 2 ? 2 : 1]) == "-") {
         Rate rt; unsigned ch, bits, tap_bits, kernel, dbg; int level; char fmt, dither;
         while (scanf("%u:%u:%c:%u%c%u%c:%d:%u:%u:%u", &rt.dsd_rate, &rt.output_rate, &rt.filter, &ch, &fmt, &bits, &dither, &level, &tap_bits, &kernel, &dbg) == 11)
-            route_line(rt, ch, fmt, bits, dither, level, tap_bits, kernel, dbg, launches);
+            if (filters) filters_line(rt, ch, fmt, bits, dither, level, tap_bits, kernel, dbg);
+            else route_line(rt, ch, fmt, bits, dither, level, tap_bits, kernel, dbg, launches);
         return 0;
     }
 #endif
-    fprintf(stderr, "usage: route_probe [predicates | - | launches -]\n");
+    fprintf(stderr, "usage: route_probe [predicates | - | launches - | filters -]\n");
     return 2;
 }
