@@ -79,6 +79,15 @@ class FlacCheck(C.Structure):
         return (self.samples_checked, self.blocks_checked, self.bad_blocks, self.first_bad_block, self.first_bad_reason)
 
 
+class FlacVerifyStats(C.Structure):
+    """d2d_flac_verify_stats: the blocks the cooperative path accepted, and those the serial parser decided"""
+    _fields_ = [("fast_blocks", C.c_uint32), ("fallback_blocks", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.fast_blocks, self.fallback_blocks)
+
+
+FLAC_VERIFY_AUTO, FLAC_VERIFY_SERIAL, FLAC_VERIFY_COOP = 0, 1, 2       # D2D_FLAC_VERIFY_*
 # D2D_FLAC_BAD_*
 (FLAC_BAD_NONE, FLAC_BAD_SIZE, FLAC_BAD_HEADER, FLAC_BAD_CRC8, FLAC_BAD_CRC16, FLAC_BAD_UNSUPPORTED, FLAC_BAD_SYNTAX, FLAC_BAD_LENGTH,
  FLAC_BAD_SAMPLES) = range(9)
@@ -102,7 +111,8 @@ EXPORTS = ["d2d_create", "d2d_create_error", "d2d_destroy", "d2d_reset", "d2d_la
            "d2d_flac_bound_bytes", "d2d_flac_workspace_bytes", "d2d_flac_encode_device", "d2d_flac_error",
            "d2d_flac_encode_host", "d2d_convert_stream_flac",
            "d2d_flac_encode_device_effort", "d2d_flac_encode_host_effort", "d2d_convert_stream_flac_effort",
-           "d2d_flac_verify_device", "d2d_flac_verify_host", "d2d_flac_decode_host", "d2d_convert_stream_flac_verified"]
+           "d2d_flac_verify_device", "d2d_flac_verify_host", "d2d_flac_decode_host", "d2d_convert_stream_flac_verified",
+           "d2d_flac_verify_device_method", "d2d_flac_verify_host_method"]
 
 _lib = None
 
@@ -182,6 +192,9 @@ def lib():
     L.d2d_flac_verify_device.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(FlacIO), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.d2d_flac_verify_host.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.POINTER(FlacCheck)]
+    L.d2d_flac_verify_device_method.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(FlacIO), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]
+    L.d2d_flac_verify_host_method.argtypes = L.d2d_flac_verify_host.argtypes + [C.c_uint32, C.POINTER(FlacVerifyStats)]
     L.d2d_flac_decode_host.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t,
                                        C.POINTER(C.c_size_t), C.POINTER(FlacCheck)]
     L.d2d_convert_stream_flac_verified.argtypes = L.d2d_convert_stream_flac_effort.argtypes + [C.POINTER(FlacCheck)]
@@ -241,24 +254,26 @@ def flac_decode_host(channels, bit_depth, frames, first_block=0, capacity=None, 
     return out[:n.value * fb].tobytes(), n.value, chk
 
 
-def flac_verify_host(channels, bit_depth, pcm, out, first_block=0, final=True, sizes=None):
-    """d2d_flac_verify_host: the frames `out` against the packed PCM they were made from; `sizes` the per-block sizes or None (the
-    frames are then walked by decoding).  Returns the FlacCheck."""
+def flac_verify_host(channels, bit_depth, pcm, out, first_block=0, final=True, sizes=None, method=0, stats=None):
+    """d2d_flac_verify_host_method: the frames `out` against the packed PCM they were made from; `sizes` the per-block sizes or None (the
+    frames are then walked by decoding); `method` a FLAC_VERIFY_*; `stats` a FlacVerifyStats to fill.  Returns the FlacCheck."""
     import numpy as np
     p, o = _u8(pcm), _u8(out)
     fb = channels * (2 if bit_depth == 16 else 3)
     sz = None if sizes is None else np.ascontiguousarray(np.asarray(sizes, dtype=np.uint32))
     chk = FlacCheck()
-    _flac_check(lib().d2d_flac_verify_host(channels, bit_depth, p.ctypes.data, p.size // fb if fb else 0, first_block, int(bool(final)),
-                                           o.ctypes.data, o.size, None if sz is None else sz.ctypes.data, C.byref(chk)))
+    _flac_check(lib().d2d_flac_verify_host_method(channels, bit_depth, p.ctypes.data, p.size // fb if fb else 0, first_block, int(bool(final)),
+                                                  o.ctypes.data, o.size, None if sz is None else sz.ctypes.data, C.byref(chk), method,
+                                                  None if stats is None else C.byref(stats)))
     return chk
 
 
-def flac_verify_device(channels, bit_depth, ios, workspace_ptr, workspace_bytes, checks_ptr, stream=None):
-    """d2d_flac_verify_device after flac_encode_device on the same ios, workspace and stream; checks_ptr: len(ios) d2d_flac_check
-    records (24 bytes each) in memory the GPU can address.  Asynchronous on `stream`."""
-    _flac_check(lib().d2d_flac_verify_device(channels, bit_depth, ios, len(ios), C.c_void_p(workspace_ptr), workspace_bytes,
-                                             C.c_void_p(checks_ptr), C.c_void_p(stream or 0)))
+def flac_verify_device(channels, bit_depth, ios, workspace_ptr, workspace_bytes, checks_ptr, stream=None, method=0, stats_ptr=None):
+    """d2d_flac_verify_device_method after flac_encode_device on the same ios, workspace and stream; checks_ptr: len(ios) d2d_flac_check
+    records (24 bytes each) in memory the GPU can address; stats_ptr: as many d2d_flac_verify_stats (8 bytes each), or None.
+    Asynchronous on `stream`."""
+    _flac_check(lib().d2d_flac_verify_device_method(channels, bit_depth, method, ios, len(ios), C.c_void_p(workspace_ptr), workspace_bytes,
+                                                    C.c_void_p(checks_ptr), C.c_void_p(stats_ptr or 0), C.c_void_p(stream or 0)))
 
 
 class D2DError(Exception):

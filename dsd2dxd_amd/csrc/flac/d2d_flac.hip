@@ -4,6 +4,8 @@
 // rules' small arithmetic (Rice parameter, zigzag, pmax, header bit counts, the LPC routine) is flac_lpc.h, the host encoder's copy.
 // Both encode kernels are a front of their own (PCM in LDS, the decisions, every thread's code lengths) and one emit path:
 // block_context in front of everything, then scan_starts, begin_image, put_bits / put_rice and finish_frame (steps 3 to 6 below).
+// The helpers the cooperative verify kernel (d2d_flac_verify.hip) needs as well -- put_bits, frame_crc16, scan_starts, the DPP sums and the
+// workgroup's shape, NT and SPT -- live in flac_device.h.
 //   flac_encode_kernel<CH>   effort 0: one workgroup of 1024 threads per (file, block); thread t owns samples 4t .. 4t+3 of every channel.
 //     1. the block's PCM comes into LDS with 16-byte loads (4096 * frame_bytes is a multiple of 16; a short block's tail by bytes)
 //     2. residuals r = s[i] - 2 s[i-1] + s[i-2] stay in registers; sum |r| per channel is reduced over the workgroup (64-bit) and
@@ -27,6 +29,7 @@
 #include <vector>
 
 #include "d2d_flac_internal.h"
+#include "flac_device.h"
 #include "flac_lpc.h"
 
 using namespace d2dflac;
@@ -34,9 +37,6 @@ using namespace d2drice;
 
 namespace {
 
-constexpr int NT = 1024;          // threads of an encode workgroup
-constexpr int NW = NT / 64;
-constexpr int SPT = BS / NT;      // samples per thread and channel
 constexpr int MAXF = 16;          // files per launch: their descriptors ride in the kernel arguments
 constexpr int PT = 256;           // threads of a pack workgroup
 constexpr uint32_t PB = 32;       // blocks per pack workgroup
@@ -55,40 +55,6 @@ struct FlacArgs {
 };
 
 __device__ __forceinline__ uint32_t utf8_len(uint32_t v) { return v < 0x80 ? 1 : v < 0x800 ? 2 : v < 0x10000 ? 3 : v < 0x200000 ? 4 : v < 0x4000000 ? 5 : 6; }
-
-// `len` (1..32) bits of `val` at bit `pos` of the image, most significant bit first
-__device__ __forceinline__ void put_bits(uint32_t* img, uint32_t pos, uint32_t val, uint32_t len) {
-    const uint32_t w = pos >> 5, o = pos & 31;
-    const uint64_t v = (uint64_t)val << (64 - o - len);
-    const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
-    if (hi) atomicOr(&img[w], hi);
-    if (lo) atomicOr(&img[w + 1], lo);
-}
-
-// a * b in GF(2)[x] / (x^16 + x^15 + x^2 + 1)
-__device__ __forceinline__ uint32_t gf_mul(uint32_t a, uint32_t b) {
-    uint32_t r = 0;
-    for (int i = 15; i >= 0; --i) {
-        r <<= 1;
-        if (r & 0x10000u) r ^= 0x18005u;
-        if ((b >> i) & 1u) r ^= a;
-    }
-    return r;
-}
-__device__ __forceinline__ uint32_t gf_xpow(uint32_t e) {     // x^e
-    uint32_t r = 1, base = 2;
-    for (; e; e >>= 1) { if (e & 1u) r = gf_mul(r, base); base = gf_mul(base, base); }
-    return r;
-}
-
-// the CRC-16 table (x^16 + x^15 + x^2 + 1)
-__device__ __forceinline__ void build_crc_tab(uint16_t* s_crc_tab, uint32_t tid) {
-    if (tid < 256) {
-        uint32_t c = tid << 8;
-        for (int i = 0; i < 8; ++i) c = (c & 0x8000u) ? ((c << 1) ^ 0x8005u) & 0xFFFFu : (c << 1) & 0xFFFFu;
-        s_crc_tab[tid] = (uint16_t)c;
-    }
-}
 
 // the frame header and its CRC-8 (x^8 + x^2 + x + 1); `assignment` is the channel-assignment nibble.  One thread.
 __device__ __forceinline__ void build_header(uint8_t* s_hdr, uint32_t n, uint32_t assignment, uint32_t depth, uint32_t frame_no) {
@@ -111,26 +77,6 @@ __device__ __forceinline__ void build_header(uint8_t* s_hdr, uint32_t n, uint32_
     s_hdr[p] = (uint8_t)c;
 }
 
-// CRC-16 of the image's first data_bytes, placed behind them.  The whole workgroup, all bits of the image placed and a barrier passed;
-// ends with a barrier.
-__device__ __forceinline__ void frame_crc16(uint32_t* img, uint32_t data_bytes, const uint16_t* s_crc_tab, uint16_t* s_crc, uint32_t tid) {
-    auto image_byte = [&](uint32_t j) -> uint32_t { return (img[j >> 2] >> (24 - 8 * (j & 3))) & 0xFFu; };
-    const uint32_t L = (data_bytes + NT - 1) / NT, padz = NT * L - data_bytes;
-    uint32_t c = 0;
-    for (uint32_t v = tid * L; v < (tid + 1) * L; ++v)
-        if (v >= padz) c = ((c << 8) & 0xFFFFu) ^ s_crc_tab[(c >> 8) ^ image_byte(v - padz)];
-    s_crc[tid] = (uint16_t)c;
-    uint32_t m = gf_xpow(8 * L);
-    for (uint32_t stride = 1; stride < NT; stride <<= 1) {
-        __syncthreads();
-        if ((tid & (2 * stride - 1)) == 0) s_crc[tid] = (uint16_t)(gf_mul(s_crc[tid], m) ^ s_crc[tid + stride]);
-        m = gf_mul(m, m);
-    }
-    __syncthreads();
-    if (tid == 0 && s_crc[0]) put_bits(img, data_bytes * 8, s_crc[0], 16);
-    __syncthreads();
-}
-
 // the image (big-endian words) to its 16-byte aligned slot
 __device__ __forceinline__ void store_frame(const uint32_t* img, uint8_t* slot, uint32_t out_vecs, uint32_t tid) {
     uint4* dst = reinterpret_cast<uint4*>(slot);
@@ -143,13 +89,6 @@ __device__ __forceinline__ void store_frame(const uint32_t* img, uint8_t* slot, 
 
 // ---- what both encode kernels share: the block's context in front, the emit path behind -------------------------------------
 
-// What a workgroup knows of its block before it reads a sample.  Passed by value: every field is uniform or a function of the thread.
-struct Block {
-    uint32_t n, depth;                              // samples per channel, their bits
-    uint32_t tid, lane, wave, i0;                   // this thread; its first sample
-    uint32_t frame_no, hdr_bytes;
-    uint32_t pmax, fsz, pj0, rem0;                  // the search: rule 6's pmax; a finest partition's samples, n >> pmax; i0 = pj0 * fsz + rem0
-};
 __device__ __forceinline__ Block block_context(const FileDesc& fd, uint32_t b, uint32_t depth) {
     Block B;
     B.n = b + 1 == fd.blocks ? fd.last_n : BS; B.depth = depth;
@@ -168,32 +107,6 @@ struct EmitLds {                                    // the emit path's static LD
     uint8_t hdr[16];
 };
 
-// Step 3: where this thread's bits of every channel begin, from its code lengths mine[c]: an inclusive scan over the wave's lanes, the
-// 16 waves' totals through LDS into 16 lanes; channel 0 starts at first_bit.  Returns the bits behind the last channel.  One barrier.
-template <int CH>
-__device__ __forceinline__ uint32_t scan_starts(uint32_t (&start)[CH], const uint32_t (&mine)[CH], uint32_t first_bit, uint32_t (*s_wtot)[CH], const Block B) {
-    uint32_t incl[CH];
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-        uint32_t x = mine[c];
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(x, o, 64); if (B.lane >= (uint32_t)o) x += y; }
-        incl[c] = x;
-    }
-    if (B.lane == 63) {
-#pragma unroll
-        for (int c = 0; c < CH; ++c) s_wtot[B.wave][c] = incl[c];
-    }
-    __syncthreads();
-    uint32_t total_bits = first_bit;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-        uint32_t all = s_wtot[B.lane & (NW - 1)][c], before = (B.lane & (NW - 1)) < B.wave ? all : 0;
-        for (int o = NW / 2; o >= 1; o >>= 1) { all += __shfl_xor(all, o, 64); before += __shfl_xor(before, o, 64); }
-        start[c] = total_bits + before + incl[c] - mine[c];
-        total_bits += all;
-    }
-    return total_bits;
-}
 // Step 4's beginning: the LDS behind `img` zeroed for a frame of data_bytes and its CRC-16, the header bytes placed.  Every thread must
 // have passed a barrier behind its last read of what lay there.  False, for the whole workgroup, for a frame beyond the slot: the bound of
 // include/dsd2dxd_amd.h says there is none at any effort; one that broke it is dropped whole, size 0, not written past the image.
@@ -386,45 +299,6 @@ __device__ __forceinline__ void load_window(int32_t (&x)[8], const int32_t* pcm,
 __device__ __forceinline__ void difference(int32_t (&x)[8], int o) {
 #pragma unroll
     for (int w = 7; w >= 1; --w) if (w >= o) x[w] -= x[w - 1];
-}
-// Sums across lanes without LDS traffic: four DPP adds leave the sum of each row of 16 lanes in all its lanes (lane ^ 1, lane ^ 2 by
-// quad permutes, then the half row and the row mirrored); four lane reads add the rows of a wave into a wave-uniform value.  Every
-// lane of the wave must be active.
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_move(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true); }
-__device__ __forceinline__ uint32_t row_sum(uint32_t v) {
-    v += dpp_move<0xB1>(v);                                          // quad_perm [1, 0, 3, 2]
-    v += dpp_move<0x4E>(v);                                          // quad_perm [2, 3, 0, 1]
-    v += dpp_move<0x141>(v);                                         // row_half_mirror
-    v += dpp_move<0x140>(v);                                         // row_mirror
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    v = row_sum(v);
-    return (uint32_t)(__builtin_amdgcn_readlane((int)v, 0) + __builtin_amdgcn_readlane((int)v, 16) + __builtin_amdgcn_readlane((int)v, 32) +
-                      __builtin_amdgcn_readlane((int)v, 48));
-}
-// ... of 64-bit values below 2^48 as two 32-bit sums of 24-bit halves: neither can overflow over 64 lanes
-__device__ __forceinline__ unsigned long long row_sum(unsigned long long v) {
-    return ((unsigned long long)row_sum((uint32_t)(v >> 24)) << 24) + row_sum((uint32_t)v & 0xFFFFFFu);
-}
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-    return ((unsigned long long)wave_sum((uint32_t)(v >> 24)) << 24) + wave_sum((uint32_t)v & 0xFFFFFFu);
-}
-// v[i] summed over the workgroup, in every thread; N sums share the two barriers.  32-bit sums must fit 32 bits, 64-bit sums 48.
-template <int N, typename T>
-__device__ __forceinline__ void wg_sum(T (&v)[N], unsigned long long* s_red, uint32_t lane, uint32_t wave) {
-    T* red = reinterpret_cast<T*>(s_red);
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = wave_sum(v[i]);
-    __syncthreads();                                                 // (the readers of the last use are through)
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) red[wave * N + i] = v[i];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = row_sum(red[(lane & (NW - 1)) * N + i]);      // 16 lanes hold the 16 waves' sums
 }
 
 // ---- effort 12: what the LPC flavour of the search kernel adds ----------------------------------------------------------------

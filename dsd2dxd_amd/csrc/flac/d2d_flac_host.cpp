@@ -7,8 +7,8 @@
 #include <vector>
 
 #include "d2d_flac_internal.h"
+#include "flac_expect.h"
 #include "flac_frame_enc.h"
-#include "flac_parse.h"
 
 namespace d2dflac {
 
@@ -163,6 +163,13 @@ int d2d_flac_decode_host(uint32_t channels, uint32_t bit_depth, const void* fram
 
 int d2d_flac_verify_host(uint32_t channels, uint32_t bit_depth, const void* pcm, size_t frames, uint32_t first_block, int final,
                          const void* out, size_t bytes_out, const uint32_t* sizes, d2d_flac_check* check) {
+    return d2d_flac_verify_host_method(channels, bit_depth, pcm, frames, first_block, final, out, bytes_out, sizes, check, D2D_FLAC_VERIFY_AUTO, nullptr);
+}
+
+int d2d_flac_verify_host_method(uint32_t channels, uint32_t bit_depth, const void* pcm, size_t frames, uint32_t first_block, int final,
+                                const void* out, size_t bytes_out, const uint32_t* sizes, d2d_flac_check* check, uint32_t method,
+                                d2d_flac_verify_stats* stats) {
+    if (!verify_method_ok(method)) return fail(D2D_ERR_PARAM, VERIFY_METHOD_MESSAGE);
     if (!depth_ok(bit_depth)) return fail(D2D_ERR_PARAM, "FLAC holds 16, 20 or 24-bit integers (Invalid bit depth)");
     if (channels == 0 || channels > 8) return fail(D2D_ERR_PARAM, "FLAC holds 1 to 8 channels (Invalid channel count)");
     if (!check) return fail(D2D_ERR_PARAM, "null check record");
@@ -174,8 +181,10 @@ int d2d_flac_verify_host(uint32_t channels, uint32_t bit_depth, const void* pcm,
     const uint32_t bound = (uint32_t)frame_bound(channels, bit_depth, BS);
     const size_t fb = (size_t)channels * sample_bytes(bit_depth);
     int32_t store[2 * d2dparse::MAX_LPC_ORDER];
+    std::vector<int32_t> signal(method == D2D_FLAC_VERIFY_SERIAL ? 0 : BS);      // the cooperative rule's room for one coded signal
     d2d_flac_check c;
     clean_record(c);
+    uint32_t fast = 0;
     uint64_t off = 0;
     bool lost = false;                                                // sizes == NULL: a walk that failed cannot find the later frames
     for (size_t b = 0; b < blocks; ++b) {
@@ -185,8 +194,10 @@ int d2d_flac_verify_host(uint32_t channels, uint32_t bit_depth, const void* pcm,
         uint32_t reason = D2D_FLAC_BAD_SIZE, size = 0;
         if (sizes) {
             size = sizes[b];
-            if (d2dparse::size_ok(off, size, bytes_out, bound, b + 1 == blocks))
-                reason = d2dparse::verify_frame(o + off, size, true, ex, block_pcm, tab, store, 1, nullptr);
+            if (d2dparse::size_ok(off, size, bytes_out, bound, b + 1 == blocks)) {
+                if (method != D2D_FLAC_VERIFY_SERIAL && d2dexpect::accept_frame(o + off, size, ex, block_pcm, tab, signal.data())) { reason = D2D_FLAC_BAD_NONE; ++fast; }
+                else reason = d2dparse::verify_frame(o + off, size, true, ex, block_pcm, tab, store, 1, nullptr);
+            }
         } else if (!lost && off < bytes_out) {
             reason = d2dparse::verify_frame(o + off, (uint32_t)std::min<uint64_t>(bytes_out - off, bound), false, ex, block_pcm, tab, store, 1, &size);
             if (reason && reason != D2D_FLAC_BAD_SAMPLES) lost = true;       // (a frame that is not the PCM still has its end)
@@ -196,6 +207,7 @@ int d2d_flac_verify_host(uint32_t channels, uint32_t bit_depth, const void* pcm,
         off += size;
     }
     *check = c;
+    if (stats) *stats = d2d_flac_verify_stats{fast, (uint32_t)blocks - fast};
     return D2D_OK;
 }
 

@@ -15,6 +15,8 @@ constexpr uint32_t MAX_HEADER_BYTES = 13;      // 4 fixed + 6 frame number + 2 b
 
 inline bool depth_ok(uint32_t d) { return d == 16 || d == 20 || d == 24; }
 inline bool effort_ok(uint32_t e) { return e == D2D_FLAC_EFFORT_FIXED2 || e == D2D_FLAC_EFFORT_SEARCH || e == D2D_FLAC_EFFORT_LPC; }
+inline bool verify_method_ok(uint32_t m) { return m == D2D_FLAC_VERIFY_AUTO || m == D2D_FLAC_VERIFY_SERIAL || m == D2D_FLAC_VERIFY_COOP; }
+constexpr const char* VERIFY_METHOD_MESSAGE = "unknown FLAC verify method: 0 (auto), 1 (serial) or 2 (cooperative)";
 constexpr const char* EFFORT_MESSAGE = "unknown FLAC effort: 0 (fixed order 2), 1 (search) or 12 (search with LPC)";
 inline uint32_t sample_bytes(uint32_t depth) { return depth == 16 ? 2 : 3; }
 // the header's bound: D2D_FLAC_FRAME_BOUND(n)

@@ -28,7 +28,9 @@ extern "C" {
                              * 10: verifying FLAC frames: d2d_flac_verify_device / _host, d2d_flac_decode_host, d2d_convert_stream_flac_verified,
                              *     d2d_flac_check, D2D_FLAC_BAD_*, D2D_ERR_VERIFY (d2d_params unchanged);
                              * 11: D2D_FILTER_EQUIRIPPLE_CASCADE, the two-stage definition of the 48 kHz multiples, as a value of
-                             *     d2d_params.filter (d2d_params unchanged) */
+                             *     d2d_params.filter (d2d_params unchanged);
+                             *     added under 11, nothing existing changed: the verify method, d2d_flac_verify_device_method / _host_method,
+                             *     D2D_FLAC_VERIFY_*, d2d_flac_verify_stats */
 
 /* status codes */
 enum {
@@ -407,7 +409,8 @@ typedef struct d2d_flac_check {
  * against `pcm`; bytes_out comes from the result record, the frame starts from the size table the encode call left at the front of
  * the file's workspace -- the one thing taken from the encoder, and checked: an entry that is 0, above D2D_FLAC_FRAME_BOUND(4096) or
  * reaching beyond bytes_out, and a last block that does not end at bytes_out, are D2D_FLAC_BAD_SIZE.  Two launches per sixteen files:
- * one lane per frame decides each (file, block) and leaves a status word in the first word of the block's workspace slot, then one
+ * a status kernel decides each (file, block) -- one lane per frame, or by the METHOD below one workgroup per frame, which is what
+ * this call runs -- and leaves a status word in the first word of the block's workspace slot, then one
  * workgroup per file turns the words into the record with plain stores.  No atomics, no waiting.
  *
  * Refused before anything is launched, with the codes of the encode call: a depth that is not 16 / 20 / 24, channels 0 or above 8, null
@@ -419,6 +422,25 @@ typedef struct d2d_flac_check {
  * size table and the result record.  A refused call writes nothing. */
 int d2d_flac_verify_device(uint32_t channels, uint32_t bit_depth, const d2d_flac_io* io, uint32_t n_files,
                            void* workspace, size_t workspace_bytes, d2d_flac_check* checks, void* hip_stream);
+/* Added under ABI 11 (no existing call or structure changed): the METHOD of the verify pass.  The record of a call does not depend on
+ * it -- csrc/flac/flac_expect.h says why -- only its cost does, and the count of blocks each path decided.
+ *   D2D_FLAC_VERIFY_SERIAL  the kernel described above: one lane per frame runs the parser, flac_parse.h, code after code.
+ *   D2D_FLAC_VERIFY_COOP    one workgroup per frame.  The verifier holds the PCM, so it computes every residual, every code and every
+ *                           bit position from the samples and COMPARES the frame's bits with them, all samples at once; only the
+ *                           headers and one 5-bit parameter per Rice partition are read in order.  This path only ever says "good":
+ *                           a frame it does not accept -- any mismatch, any field the encoders here never write -- is decided by the
+ *                           serial parser in one lane of the same workgroup, so reasons and their order are SERIAL's.
+ *   D2D_FLAC_VERIFY_AUTO    COOP.  d2d_flac_verify_device, d2d_flac_verify_host, d2d_convert_stream_flac_verified and the CLI's
+ *                           --flac-verify are AUTO with stats = NULL.
+ * An unknown method -> D2D_ERR_PARAM before anything is launched, nothing written.  `stats`, one per file in memory the GPU can address
+ * (4-byte aligned) or NULL, is valid with the check records: fast_blocks counts the blocks the cooperative path accepted,
+ * fallback_blocks those the serial parser decided (under SERIAL: all of them); the two add up to blocks_checked.  Everything else --
+ * refusals, launches per sixteen files, what a call may touch (with `stats` beside the check records) -- is d2d_flac_verify_device's. */
+enum { D2D_FLAC_VERIFY_AUTO = 0, D2D_FLAC_VERIFY_SERIAL = 1, D2D_FLAC_VERIFY_COOP = 2 };
+typedef struct d2d_flac_verify_stats { uint32_t fast_blocks, fallback_blocks; } d2d_flac_verify_stats;
+int d2d_flac_verify_device_method(uint32_t channels, uint32_t bit_depth, uint32_t method, const d2d_flac_io* io, uint32_t n_files,
+                                  void* workspace, size_t workspace_bytes, d2d_flac_check* checks,
+                                  d2d_flac_verify_stats* stats /* one per file, GPU-addressable, may be NULL */, void* hip_stream);
 /* The CPU twin, no device: the same rules on one file in host memory; what the GPU tests compare against.  `out` holds bytes_out
  * bytes of frames made from the `frames` frames at `pcm` (first_block, final as at the encode call); `sizes` is the per-block size
  * array, or NULL: then the frames are walked by decoding (rule 10 of flac_parse.h: the CRC-16 is checked once the frame's end is
@@ -426,6 +448,12 @@ int d2d_flac_verify_device(uint32_t channels, uint32_t bit_depth, const d2d_flac
  * d2d_flac_encode_host. */
 int d2d_flac_verify_host(uint32_t channels, uint32_t bit_depth, const void* pcm, size_t frames, uint32_t first_block, int final,
                          const void* out, size_t bytes_out, const uint32_t* sizes, d2d_flac_check* check);
+/* ... at a chosen method (added under ABI 11): COOP runs the rule of flac_expect.h frame by frame and the serial parser on a frame it
+ * does not accept, as the kernel does, so the agreement of the two methods can be tested without a GPU.  With sizes = NULL a frame's
+ * end is only known by parsing: every block is then the serial parser's, under either method.  `stats` (one record, or NULL) as above. */
+int d2d_flac_verify_host_method(uint32_t channels, uint32_t bit_depth, const void* pcm, size_t frames, uint32_t first_block, int final,
+                                const void* out, size_t bytes_out, const uint32_t* sizes, d2d_flac_check* check, uint32_t method,
+                                d2d_flac_verify_stats* stats);
 /* A small FLAC decoder for what the sinks here write: a run of whole frames, numbered from first_block, into the packed little-endian
  * PCM the translate calls write (20-bit samples as the 3-byte container, the value shifted left by 4).  Every frame holds 4096
  * samples per channel but the last, which may hold fewer.  It writes exactly [0, *frames_out * frame_bytes) of `pcm` and stops at the

@@ -12,9 +12,11 @@ at that effort, and the effort-0 call is timed beside it on the same buffers for
 LPC, D2D_FLAC_EFFORT_LPC) the call timed beside it is effort 1's, in the same session on the same buffers: bytes and time are stated
 over effort 1's, and no file may come out longer than at effort 1.
 
-   tools/flac_probe.py --verify [files] [seconds] [reps] [out.json]      (default bench_out/flac_verify_probe.json)
-times ONE d2d_flac_verify_device call over the batch (both kernels) at each effort, after that effort's encode call on the same buffers,
-beside the encode call itself; every record must be clean.  The ratio verify / encode at the same effort is the figure of interest."""
+   tools/flac_probe.py --verify [--method serial|coop] [files] [seconds] [reps] [out.json]      (default bench_out/flac_verify_probe.json)
+times ONE d2d_flac_verify_device_method call over the batch (both kernels) at each effort, after that effort's encode call on the same
+buffers, beside the encode call itself; every record must be clean.  The ratio verify / encode at the same effort is the figure of
+interest.  --method chooses D2D_FLAC_VERIFY_SERIAL (one lane per frame) or D2D_FLAC_VERIFY_COOP (one workgroup per frame); without it
+the call is AUTO's.  Under coop every block must have been accepted by the fast path."""
 import ctypes as C
 import json
 import os
@@ -39,6 +41,11 @@ if "--effort" in argv:
 verify_mode = "--verify" in argv
 if verify_mode:
     argv.remove("--verify")
+method_name = "auto"
+if "--method" in argv:
+    at = argv.index("--method")
+    method_name = argv[at + 1]
+    del argv[at:at + 2]
 n_files = int(argv[0]) if len(argv) > 0 else 64
 seconds = float(argv[1]) if len(argv) > 1 else 60.0
 reps = int(argv[2]) if len(argv) > 2 else 9
@@ -92,13 +99,17 @@ for f in range(n_files):
     fio[f].pcm, fio[f].frames, fio[f].first_block, fio[f].final = pcm[f].data_ptr(), frames, 0, 1
     fio[f].out, fio[f].out_capacity_bytes, fio[f].result = out[f].data_ptr(), cap, rec.data_ptr() + 16 * f
 if verify_mode:
+    method = dict(auto=d.FLAC_VERIFY_AUTO, serial=d.FLAC_VERIFY_SERIAL, coop=d.FLAC_VERIFY_COOP)[method_name]
     chk = torch.zeros(n_files * 24, dtype=torch.uint8, device=dev)
-    res = dict(files=n_files, seconds_per_file=seconds, frames_per_file=frames, reps=reps, efforts={})
-    print("batch: %d files x %d frames, stereo 24-bit" % (n_files, frames))
+    vst = torch.zeros(n_files * 8, dtype=torch.uint8, device=dev)
+    res = dict(files=n_files, seconds_per_file=seconds, frames_per_file=frames, reps=reps, method=method_name, efforts={})
+    print("batch: %d files x %d frames, stereo 24-bit; verify method %s" % (n_files, frames, method_name))
     for eff in (d.FLAC_EFFORT_FIXED2, d.FLAC_EFFORT_SEARCH, d.FLAC_EFFORT_LPC):
         e_ms = timed(lambda: d.flac_encode_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), stream, effort=eff))
-        v_ms = timed(lambda: d.flac_verify_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), chk.data_ptr(), stream))
+        v_ms = timed(lambda: d.flac_verify_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), chk.data_ptr(), stream, method=method, stats_ptr=vst.data_ptr()))
         c = chk.cpu().numpy()
+        fast = vst.cpu().numpy().view(np.uint32).reshape(n_files, 2)
+        assert (fast[:, 0] == (0 if method_name == "serial" else int(fio[0].blocks))).all() and (fast.sum(axis=1) == int(fio[0].blocks)).all(), fast
         for f in range(n_files):
             r = c[24 * f:24 * f + 24]
             got = (int(r[:8].view(np.uint64)[0]),) + tuple(int(v) for v in r[8:].view(np.uint32))
