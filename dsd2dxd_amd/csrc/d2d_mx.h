@@ -48,6 +48,26 @@ __host__ __device__ constexpr int mx_slot(int MB, int NT, int G, int u, int g, i
     return k;
 }
 
+// the first group with an MFMA at step u, and the MFMAs of the step
+__host__ __device__ constexpr int mx_first_group(int MB, int NT, int u, int PH = 6) { return u < mx_nf(MB, NT, PH) ? 0 : (u - mx_nf(MB, NT, PH)) / mx_dly(MB, PH) + 1; }
+__host__ __device__ constexpr int mx_step_mfmas(int MB, int NT, int G, int u, int PH = 6) {
+    int n = 0;
+    for (int g = 0; g < G; ++g) n += u - mx_dly(MB, PH) * g >= 0 && u - mx_dly(MB, PH) * g < mx_nf(MB, NT, PH) ? 1 : 0;
+    return n;
+}
+// D2D_MX_FEED (below): the step behind whose first MFMA the B operand of step v > 0 is expanded -- the last one before v, at most two back, that has
+// a second MFMA or a job riding on its first (NJ jobs over the chain's MFMAs, job j behind MFMA j NSLOT / NJ), so that something lies between the
+// expansion and the MFMA that reads it
+__host__ __device__ constexpr int mx_feed_step(int MB, int NT, int G, int v, int NJ, int PH = 6) {
+    const int nslot = mx_nf(MB, NT, PH) * G;
+    for (int u = v - 1; u >= 0 && u >= v - 2; --u) {
+        if (mx_step_mfmas(MB, NT, G, u, PH) >= 2) return u;
+        const int s = mx_slot(MB, NT, G, u, mx_first_group(MB, NT, u, PH), PH);
+        for (int j = 0; j < NJ; ++j) if ((j * nslot) / NJ == s) return u;
+    }
+    return v - 1;
+}
+
 // groups per column: three at M = 32; at M = 64 the tap fragments of three groups do not fit the register file next to two accumulator sets
 #ifndef D2D_MX_G4
 #define D2D_MX_G4 3
@@ -71,6 +91,12 @@ __host__ __device__ constexpr int mx_nres(int MB, int NT, int PH = 6) { return !
 // Fragments a wave of one instantiation keeps in registers: the stereo frame flavours of the M = 32 rows.  The scratch flavour, several pairs
 // per wave and the 32-bit taps read them from LDS like M = 64 and M = 128.
 __host__ __device__ constexpr int mx_nres_of(int MB, int NT, int SBY, int NPR, int ND) { return SBY != 0 && NPR == 1 && ND == 5 ? mx_nres(MB, NT) : 0; }
+
+// Where the fragments are resident, the chain expands a step's B operand a step or two ahead, behind an earlier MFMA (d2d_mx_kernel.h: chain).
+// -DD2D_MX_FEED=0: the resident flavours expand a step's B operand directly in front of its first MFMA, like the others (A/B builds)
+#ifndef D2D_MX_FEED
+#define D2D_MX_FEED 1
+#endif
 
 // ---- the compiled kernels: ONE row per object --------------------------------------------------------------------------------
 // X(unit, MB, NT, flavour, NPR).  Unit n is d2d_mx_unit.hip compiled with -DD2D_MX_UNIT=n (unit 0 rides in d2d_kernels_mx.hip, next to the

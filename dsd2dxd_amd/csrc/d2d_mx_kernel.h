@@ -90,6 +90,7 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
     // for the rest), and a region takes the draining accumulator set's integers in one burst before its chain starts (run_loop)
     constexpr int NRES = mx_nres_of(MB, NT, SBY, NPR, ND);
     constexpr bool RES = NRES > 0;
+    constexpr bool FEED = D2D_MX_FEED && RES;             // the chain's B operands are expanded a step ahead (chain below)
     constexpr uint32_t dbg = D2D_MX_ABL;                  // compile-time ablation mask: 1 no chain, 2 no epilogue, 4 no staging, 8 never slow, 64 no stores
     const FirArgs& a = m.f;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -320,7 +321,9 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
 
     // One chain: TP steps of 64 stream bits; group g runs its NF MFMAs from step DLY g on, with the fragments group 0 read
     // DLY g steps earlier; LDS reads are issued AHEAD steps before their use; `hook(k)` is whatever else the wave does behind its k-th MFMA.
-    auto chain = [&](uint32_t c, v16f (&acc)[G], auto&& hook) {
+    // FEED: `pre(first)` is what the region does between the chain's first reads and its first MFMA (the burst); it calls first() once, which
+    // expands step 0's B operand.
+    auto chain_pre = [&](uint32_t c, v16f (&acc)[G], auto&& hook, auto&& pre) {
         const uint8_t* rbc = wbase + c * SB + (FLAT ? 4u * (CS * r + h + X0) : 4u * ((CS + 1) * r + h));
         uint32_t W[TP];
         v4i F4[NF]; u32x2 F2[NF];
@@ -333,14 +336,28 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
 #ifndef D2D_MX_AHEAD
 #define D2D_MX_AHEAD 2
 #endif
-        constexpr int AHEAD = D2D_MX_AHEAD;
+        // FEED: a step's B operand is expanded one or two steps ahead, behind the first MFMA of step mx_feed_step(v) and in front of the job that
+        // rides there, into one of three register sets: a job or another MFMA then lies between the last v_and_b32 and the MFMA that reads it, and
+        // the compiler has no wait state to pad (it padded one or two in front of every step's first MFMA).  Step 0's is expanded inside `pre`,
+        // whose vector work also covers the latency of the first stream words.  The words are read two steps earlier to keep their lead.
+        constexpr int AHEAD = D2D_MX_AHEAD + (FEED ? 2 : 0);
+        constexpr int NJF = (DK == 0 ? 1 : 2) * NS;                 // the jobs that ride on a RES chain (NJR below, which asserts the two agree)
+        [[maybe_unused]] int Bx[3][4];
+        [[maybe_unused]] auto expand = [&](auto uc) {
+            constexpr int u = decltype(uc)::value;
+            const uint32_t w = W[u], w2 = w >> 2;
+            Bx[u % 3][0] = (int)(w & kmA); Bx[u % 3][1] = (int)(w & kmB); Bx[u % 3][2] = (int)(w2 & kmA); Bx[u % 3][3] = (int)(w2 & kmB);
+        };
         static_for<0, AHEAD>([&](auto uc) { rdW(uc); if constexpr (decltype(uc)::value >= NRES) rdF(uc); });
+        if constexpr (FEED) pre([&] { expand(std::integral_constant<int, 0>{}); });           // (otherwise nothing: the region ran its burst before the chain)
         static_for<0, TP>([&](auto uc) {
             constexpr int u = decltype(uc)::value;
             if constexpr (u + AHEAD < TP) rdW(std::integral_constant<int, u + AHEAD>{});
             if constexpr (u + AHEAD < NF && u + AHEAD >= NRES) rdF(std::integral_constant<int, u + AHEAD>{});
-            const uint32_t w = W[u], w2 = w >> 2;
-            const v8i Bv = {(int)(w & kmA), (int)(w & kmB), (int)(w2 & kmA), (int)(w2 & kmB), 0, 0, 0, 0};
+            v8i Bv;
+            if constexpr (FEED) Bv = v8i{Bx[u % 3][0], Bx[u % 3][1], Bx[u % 3][2], Bx[u % 3][3], 0, 0, 0, 0};
+            else { const uint32_t w = W[u], w2 = w >> 2; Bv = v8i{(int)(w & kmA), (int)(w & kmB), (int)(w2 & kmA), (int)(w2 & kmB), 0, 0, 0, 0}; }
+            constexpr int g_first = mx_first_group(MB, NT, u, PH);
             static_for<0, G>([&](auto gc) {
                 constexpr int g = decltype(gc)::value;
                 constexpr int f = u - DLY * g;
@@ -350,6 +367,12 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
                     else Av = v8i{F4[f].x, F4[f].y, F4[f].z, F4[f].w, (int)F2[f].x, (int)F2[f].y, 0, 0};
                     if constexpr (f == 0) acc[g] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(Av, Bv, cinit, 2, 4, 0, scA, 0, scB);
                     else acc[g] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(Av, Bv, acc[g], 2, 4, 0, scA, 0, scB);
+                    if constexpr (FEED && g == g_first) {
+                        constexpr bool x1 = u + 1 < TP && mx_feed_step(MB, NT, G, u + 1, NJF, PH) == u, x2 = u + 2 < TP && mx_feed_step(MB, NT, G, u + 2, NJF, PH) == u;
+                        if constexpr (x1) expand(std::integral_constant<int, u + 1>{});
+                        if constexpr (x2) expand(std::integral_constant<int, u + 2>{});
+                        if constexpr (x1 || x2) __builtin_amdgcn_sched_barrier(0);         // (in front of the job: or the compiler sinks the expansion behind it)
+                    }
                     // whatever else the wave does rides BEHIND an MFMA: an in-order wave that issues two MFMAs back to back sits out the
                     // first one's 32 cycles in the matrix pipe
                     hook(std::integral_constant<int, mx_slot(MB, NT, G, u, g, PH)>{});
@@ -358,6 +381,7 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
             });
         });
     };
+    auto chain = [&](uint32_t c, v16f (&acc)[G], auto&& hook) { chain_pre(c, acc, hook, [](auto&& first) { first(); }); };
     auto no_hook = [](auto) {};
     auto pin = [&](v16f (&acc)[G]) {
 #pragma unroll
@@ -552,10 +576,12 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
     // pin of the whole set and holds compiler-visible instructions only (the shift-add in plain C, not mx_lshl_add): the first read of a
     // register of the previous chain's last MFMA gets the compiler's wait states, and the scheduling barrier that closes the burst keeps
     // every inline-asm instruction of the jobs behind it.  That is what hold_acc is for in the other flavours (above: the round-4 hazard).
-    auto burst = [&](v16f (&o)[G], vint (&vv)[NS]) {
+    // (`mid` runs in front of the last sample: the chain's first B operand, FEED)
+    auto burst = [&](v16f (&o)[G], vint (&vv)[NS], auto&& mid) {
         pin(o);
 #pragma unroll
         for (int i = 0; i < NS; ++i) {
+            if (i == NS - 1) { mid(); if constexpr (FEED) __builtin_amdgcn_sched_barrier(0); }      // (or the compiler sinks it to the burst's end)
             const v16f& A = o[i / PHH];
             const int q = i % PHH;
             const float lo = __builtin_fmaf(A[5 * q + 2], k1024, __builtin_fmaf(A[5 * q + 1], k32, A[5 * q]));
@@ -567,6 +593,7 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
     };
     // ... and the hash and finish jobs ride behind the chain's MFMAs as before, respaced: job j behind MFMA (j * NSLOT) / NJR
     constexpr int NJR = (JPS - 1) * NS;
+    static_assert(NJR == (DK == 0 ? 1 : 2) * NS, "chain's NJF places the B expansions where these jobs ride");
     auto res_job = [&](Fast& f, const vint (&vv)[NS], const v16f (&o)[G], auto jc) {
         constexpr int j = decltype(jc)::value;
         constexpr int i = j / (JPS - 1);
@@ -914,10 +941,10 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
                 [[maybe_unused]] vint vv[NS];
                 fast_begin(f, tp, CHP{});
                 if constexpr (RES) {
-                    burst(accB, vv);
-                    if (dbg & 2) chain(0u, accA, no_hook);
-                    else if (dbg & 1) { static_for<0, NJR>([&](auto jc) { res_job(f, vv, accB, jc); }); for (int g = 0; g < G; ++g) accA[g] = cinit + (float)lane; }
-                    else chain(0u, accA, [&](auto uc) { res_hook(f, vv, accB, uc); });
+                    if (dbg & 2) { burst(accB, vv, [] {}); chain(0u, accA, no_hook); }
+                    else if (dbg & 1) { burst(accB, vv, [] {}); static_for<0, NJR>([&](auto jc) { res_job(f, vv, accB, jc); }); for (int g = 0; g < G; ++g) accA[g] = cinit + (float)lane; }
+                    else if constexpr (FEED) chain_pre(0u, accA, [&](auto uc) { res_hook(f, vv, accB, uc); }, [&](auto&& first) { burst(accB, vv, first); });
+                    else { burst(accB, vv, [] {}); chain(0u, accA, [&](auto uc) { res_hook(f, vv, accB, uc); }); }
                 }
                 else if (dbg & 2) chain(0u, accA, no_hook);
                 else if (dbg & 1) { static_for<0, NJ>([&](auto jc) { fast_job(f, accB, jc); }); for (int g = 0; g < G; ++g) accA[g] = cinit + (float)lane; }
@@ -957,10 +984,10 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
                 [[maybe_unused]] vint vv[NS];
                 fast_begin(f, wt, CHA{});
                 if constexpr (RES) {
-                    burst(accA, vv);
-                    if (dbg & 2) chain(1u, accB, no_hook);
-                    else if (dbg & 1) { static_for<0, NJR>([&](auto jc) { res_job(f, vv, accA, jc); }); for (int g = 0; g < G; ++g) accB[g] = cinit - (float)lane; }
-                    else chain(1u, accB, [&](auto uc) { res_hook(f, vv, accA, uc); });
+                    if (dbg & 2) { burst(accA, vv, [] {}); chain(1u, accB, no_hook); }
+                    else if (dbg & 1) { burst(accA, vv, [] {}); static_for<0, NJR>([&](auto jc) { res_job(f, vv, accA, jc); }); for (int g = 0; g < G; ++g) accB[g] = cinit - (float)lane; }
+                    else if constexpr (FEED) chain_pre(1u, accB, [&](auto uc) { res_hook(f, vv, accA, uc); }, [&](auto&& first) { burst(accA, vv, first); });
+                    else { burst(accA, vv, [] {}); chain(1u, accB, [&](auto uc) { res_hook(f, vv, accA, uc); }); }
                 }
                 else if (dbg & 2) chain(1u, accB, no_hook);
                 else if (dbg & 1) { static_for<0, NJ>([&](auto jc) { fast_job(f, accA, jc); }); for (int g = 0; g < G; ++g) accB[g] = cinit - (float)lane; }
@@ -983,7 +1010,7 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
             Fast f;
             fast_begin(f, pw, CHL{});
             [[maybe_unused]] vint vv[NS];
-            if constexpr (RES) { burst(accB, vv); static_for<0, NJR>([&](auto jc) { res_job(f, vv, accB, jc); }); }
+            if constexpr (RES) { burst(accB, vv, [] {}); static_for<0, NJR>([&](auto jc) { res_job(f, vv, accB, jc); }); }
             else static_for<0, NJ>([&](auto jc) { fast_job(f, accB, jc); });
             if constexpr (SCR) { hold_acc(accB); put_samples(1, f.res); wave_sync2(); store_scr_tile(pw); wave_sync2(); }
             else {

@@ -4,7 +4,7 @@
 # development only; bench.py names such a library in its line and cites no counter traffic for it).
 #   tools/ab_build.sh <name> <target> [flags...]     target: mx | mxm | mfma3 | kernels | px
 #     mx       the fp6 kernel, E_M32 shape only (-DD2D_MX_DEV: the dispatcher with unit 0, and the shape's gain unit):
-#              -DD2D_MX_ABL=<mask> -DD2D_MX_STAMPS=1 -DD2D_MX_G4=<groups> -DD2D_MX_NOFLAT=1 -DD2D_MX_NRES=<resident fragments> -DD2D_MX_RESIDENT=0
+#              -DD2D_MX_ABL=<mask> -DD2D_MX_STAMPS=1 -DD2D_MX_G4=<groups> -DD2D_MX_NOFLAT=1 -DD2D_MX_NRES=<resident fragments> -DD2D_MX_RESIDENT=0 -DD2D_MX_FEED=0
 #     mxm      the fp6 kernel, the three-pairs-per-wave unit of the E_M32 shape: -DD2D_MX_ABL=<mask>
 #     mfma3    the pipelined int8 kernel, E_M8 shape only (-DD2D_M3_DEV: the dispatcher with unit 0): -DD2D_M3_ABL=<mask> -DD2D_M3_STAMPS=1
 #     kernels  d2d_kernels.hip (LUT, resampler, de-interleave, noise shaping)
@@ -43,6 +43,7 @@ for n in d2d_kernels d2d_kernels_rs d2d_kernels_mfma d2d_kernels_mfma2 d2d_engin
          d2d_kernels_mfma3 $(for i in $(seq 1 $((M3_UNITS - 1))); do echo d2d_m3_unit$i; done) \
          d2d_kernels_mx $(for i in $(seq 1 $((MX_UNITS - 1))); do echo d2d_mx_unit$i; done) \
          d2d_kernels_px $(for i in $(seq 1 $((PX_UNITS - 1))); do echo d2d_px_unit$i; done) \
+         flac/d2d_flac flac/d2d_flac_verify flac/d2d_flac_host flac/d2d_flac_stream \
          host/dsd_reader host/pcm_sink host/id3_tag host/rdsd2pcm host/rdsd2pcm_c; do
   if [ -f $O/$(basename $n).o ]; then OBJS="$OBJS $O/$(basename $n).o"; else OBJS="$OBJS $CS/$n.o"; fi
 done
