@@ -11,4 +11,6 @@ from ._capi import (D2DError, Engine, FileIO, Info, Params, lib, library_path, b
                     FLAC_BLOCK, FLAC_EFFORT_FIXED2, FLAC_EFFORT_SEARCH, FLAC_EFFORT_LPC, FlacIO, FlacResult, FlacStreamStats, flac_bound_bytes, flac_workspace_bytes, flac_encode_host, flac_encode_device,
                     FlacCheck, flac_decode_host, flac_verify_host, flac_verify_device, ERR_VERIFY, FLAC_NO_BAD_BLOCK,
                     FlacVerifyStats, FLAC_VERIFY_AUTO, FLAC_VERIFY_SERIAL, FLAC_VERIFY_COOP,
+                    FlacMd5State, FlacMd5IO, flac_md5_init_host, flac_md5_update_host, flac_md5_final_host,
+                    flac_md5_init_device, flac_md5_update_device, flac_md5_final_device,
                     FLAC_BAD_NONE, FLAC_BAD_SIZE, FLAC_BAD_HEADER, FLAC_BAD_CRC8, FLAC_BAD_CRC16, FLAC_BAD_UNSUPPORTED, FLAC_BAD_SYNTAX, FLAC_BAD_LENGTH, FLAC_BAD_SAMPLES)

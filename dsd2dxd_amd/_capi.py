@@ -87,6 +87,17 @@ class FlacVerifyStats(C.Structure):
         return (self.fast_blocks, self.fallback_blocks)
 
 
+class FlacMd5State(C.Structure):
+    """d2d_flac_md5_state: one file's MD5 so far, 96 bytes (public layout: a caller may keep, copy or build one)"""
+    _fields_ = [("h", C.c_uint32 * 4), ("bytes", C.c_uint64), ("tail_bytes", C.c_uint32), ("reserved", C.c_uint32),
+                ("tail", C.c_uint8 * 64)]
+
+
+class FlacMd5IO(C.Structure):
+    """d2d_flac_md5_io: one file of a d2d_flac_md5_update_device call (DEVICE pointer, 16-byte aligned)"""
+    _fields_ = [("pcm", C.c_void_p), ("frames", C.c_size_t)]
+
+
 FLAC_VERIFY_AUTO, FLAC_VERIFY_SERIAL, FLAC_VERIFY_COOP = 0, 1, 2       # D2D_FLAC_VERIFY_*
 # D2D_FLAC_BAD_*
 (FLAC_BAD_NONE, FLAC_BAD_SIZE, FLAC_BAD_HEADER, FLAC_BAD_CRC8, FLAC_BAD_CRC16, FLAC_BAD_UNSUPPORTED, FLAC_BAD_SYNTAX, FLAC_BAD_LENGTH,
@@ -112,7 +123,9 @@ EXPORTS = ["d2d_create", "d2d_create_error", "d2d_destroy", "d2d_reset", "d2d_la
            "d2d_flac_encode_host", "d2d_convert_stream_flac",
            "d2d_flac_encode_device_effort", "d2d_flac_encode_host_effort", "d2d_convert_stream_flac_effort",
            "d2d_flac_verify_device", "d2d_flac_verify_host", "d2d_flac_decode_host", "d2d_convert_stream_flac_verified",
-           "d2d_flac_verify_device_method", "d2d_flac_verify_host_method"]
+           "d2d_flac_verify_device_method", "d2d_flac_verify_host_method",
+           "d2d_flac_md5_init_host", "d2d_flac_md5_init_device", "d2d_flac_md5_update_device", "d2d_flac_md5_final_device",
+           "d2d_flac_md5_update_host", "d2d_flac_md5_final_host", "d2d_convert_stream_flac_md5"]
 
 _lib = None
 
@@ -198,6 +211,14 @@ def lib():
     L.d2d_flac_decode_host.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t,
                                        C.POINTER(C.c_size_t), C.POINTER(FlacCheck)]
     L.d2d_convert_stream_flac_verified.argtypes = L.d2d_convert_stream_flac_effort.argtypes + [C.POINTER(FlacCheck)]
+    L.d2d_flac_md5_init_host.argtypes = [C.POINTER(FlacMd5State), C.c_uint32]
+    L.d2d_flac_md5_init_host.restype = None
+    L.d2d_flac_md5_init_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    L.d2d_flac_md5_update_device.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(FlacMd5IO), C.c_uint32, C.c_void_p, C.c_void_p]
+    L.d2d_flac_md5_final_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.d2d_flac_md5_update_host.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(FlacMd5State)]
+    L.d2d_flac_md5_final_host.argtypes = [C.POINTER(FlacMd5State), C.c_void_p]
+    L.d2d_convert_stream_flac_md5.argtypes = L.d2d_convert_stream_flac_verified.argtypes + [C.c_void_p]
     _lib = L
     return L
 
@@ -274,6 +295,43 @@ def flac_verify_device(channels, bit_depth, ios, workspace_ptr, workspace_bytes,
     Asynchronous on `stream`."""
     _flac_check(lib().d2d_flac_verify_device_method(channels, bit_depth, method, ios, len(ios), C.c_void_p(workspace_ptr), workspace_bytes,
                                                     C.c_void_p(checks_ptr), C.c_void_p(stats_ptr or 0), C.c_void_p(stream or 0)))
+
+
+def flac_md5_init_host(n_files=1):
+    """d2d_flac_md5_init_host: a ctypes array of n_files fresh FlacMd5State records"""
+    states = (FlacMd5State * n_files)()
+    lib().d2d_flac_md5_init_host(states, n_files)
+    return states
+
+
+def flac_md5_update_host(channels, bit_depth, pcm, state):
+    """d2d_flac_md5_update_host: continues `state` (a FlacMd5State) with a bytes-like of whole interleaved frames; no device"""
+    buf = _u8(pcm)
+    fb = channels * (2 if bit_depth == 16 else 3)
+    _flac_check(lib().d2d_flac_md5_update_host(channels, bit_depth, buf.ctypes.data if buf.size else None, buf.size // fb if fb else 0,
+                                               C.byref(state)))
+
+
+def flac_md5_final_host(state):
+    """d2d_flac_md5_final_host: the 16 digest bytes of `state` so far; the state is not modified"""
+    digest = (C.c_uint8 * 16)()
+    _flac_check(lib().d2d_flac_md5_final_host(C.byref(state), digest))
+    return bytes(digest)
+
+
+def flac_md5_init_device(states_ptr, n_files, stream=None):
+    """d2d_flac_md5_init_device: n_files records of 96 bytes at states_ptr (memory the GPU can address); asynchronous on `stream`"""
+    _flac_check(lib().d2d_flac_md5_init_device(C.c_void_p(states_ptr), n_files, C.c_void_p(stream or 0)))
+
+
+def flac_md5_update_device(channels, bit_depth, ios, states_ptr, stream=None):
+    """d2d_flac_md5_update_device: ios is a ctypes array of FlacMd5IO with DEVICE pointers; asynchronous on `stream`"""
+    _flac_check(lib().d2d_flac_md5_update_device(channels, bit_depth, ios, len(ios), C.c_void_p(states_ptr), C.c_void_p(stream or 0)))
+
+
+def flac_md5_final_device(states_ptr, n_files, digests_ptr, stream=None):
+    """d2d_flac_md5_final_device: 16 digest bytes per file to digests_ptr (memory the GPU can address); asynchronous on `stream`"""
+    _flac_check(lib().d2d_flac_md5_final_device(C.c_void_p(states_ptr), n_files, C.c_void_p(digests_ptr), C.c_void_p(stream or 0)))
 
 
 class D2DError(Exception):
@@ -460,11 +518,13 @@ class Engine:
                                              keep["p"], None, total_bytes_per_channel, chunk_bytes_per_channel))
 
     def convert_stream_flac(self, read, write, total_bytes_per_channel=0, chunk_bytes_per_channel=1 << 22,
-                            cancel=None, progress=None, effort=0, verify=False):
+                            cancel=None, progress=None, effort=0, verify=False, md5=False):
         """d2d_convert_stream_flac_effort: as convert_stream, but write() receives FLAC frames (whole frames, in order); returns the
         FlacStreamStats STREAMINFO needs.  Errors carry d2d_flac_error()'s message.  verify=True: d2d_convert_stream_flac_verified --
         every chunk's frames are checked against their PCM on the GPU before write() sees them; returns (stats, FlacCheck), and a bad
-        block raises D2DError with code ERR_VERIFY (the record so far is the exception's `check`)."""
+        block raises D2DError with code ERR_VERIFY (the record so far is the exception's `check`).  md5=True: d2d_convert_stream_flac_md5
+        -- the samples are hashed on the GPU as well; the 16 digest bytes for STREAMINFO are returned last: (stats, digest), or with
+        verify=True (stats, FlacCheck, digest)."""
         def _read(_u, dst, cap):
             data = read(cap)
             if not data:
@@ -483,6 +543,16 @@ class Engine:
         r, w, p = READ_FN(_read), WRITE_FN(_write), PROGRESS_FN(_prog)
         cflag = cancel if cancel is not None else C.c_int(0)
         stats = FlacStreamStats()
+        if md5:
+            chk, digest = FlacCheck(), (C.c_uint8 * 16)()
+            rc = lib().d2d_convert_stream_flac_md5(self._h, self.params.bit_depth, effort, r, None, w, None, C.byref(cflag), p, None,
+                                                   total_bytes_per_channel, chunk_bytes_per_channel, C.byref(stats),
+                                                   C.byref(chk) if verify else None, digest)
+            if rc:
+                err = D2DError(rc, lib().d2d_flac_error().decode())
+                err.check = chk
+                raise err
+            return (stats, chk, bytes(digest)) if verify else (stats, bytes(digest))
         if verify:
             chk = FlacCheck()
             rc = lib().d2d_convert_stream_flac_verified(self._h, self.params.bit_depth, effort, r, None, w, None, C.byref(cflag), p, None,

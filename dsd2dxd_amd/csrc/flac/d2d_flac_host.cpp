@@ -1,6 +1,7 @@
 // d2d_flac_host.cpp -- the host half of the FLAC entry points: sizes, the error slot, d2d_flac_encode_host, which is the sink's
 // own frame encoder (flac_frame_enc.h) behind the C ABI, and the readers on flac_parse.h: d2d_flac_decode_host and d2d_flac_verify_host,
-// the CPU twin of the GPU verify call.  No HIP: tools and tests build this file with g++ alone.
+// the CPU twin of the GPU verify call; and the CPU twins of the GPU MD5 calls on flac_md5.h.  No HIP: tools and tests build this file
+// with g++ alone.
 #include <string.h>
 
 #include <algorithm>
@@ -9,6 +10,7 @@
 #include "d2d_flac_internal.h"
 #include "flac_expect.h"
 #include "flac_frame_enc.h"
+#include "flac_md5.h"
 
 namespace d2dflac {
 
@@ -208,6 +210,65 @@ int d2d_flac_verify_host_method(uint32_t channels, uint32_t bit_depth, const voi
     }
     *check = c;
     if (stats) *stats = d2d_flac_verify_stats{fast, (uint32_t)blocks - fast};
+    return D2D_OK;
+}
+
+// ---- STREAMINFO's MD5: the CPU twins of d2d_flac_md5.hip ----
+
+// the next n message bytes behind the record's tail; whole blocks go into h as they fill
+static void md5_absorb(d2d_flac_md5_state& s, const uint8_t* p, size_t n) {
+    s.bytes += n;
+    uint32_t t = s.tail_bytes & 63u;
+    while (n) {
+        const uint32_t take = (uint32_t)std::min<size_t>(n, d2dmd5::BLOCK - t);
+        memcpy(s.tail + t, p, take);
+        t += take; p += take; n -= take;
+        if (t == d2dmd5::BLOCK) {
+            uint32_t m[16];
+            for (int i = 0; i < 16; ++i) m[i] = d2dmd5::word_le(s.tail + 4 * i);
+            d2dmd5::block(s.h, m);
+            t = 0;
+        }
+    }
+    s.tail_bytes = t;
+}
+
+void d2d_flac_md5_init_host(d2d_flac_md5_state* states, uint32_t n_files) {
+    for (uint32_t f = 0; states && f < n_files; ++f) {
+        memset(&states[f], 0, sizeof(states[f]));
+        states[f].h[0] = d2dmd5::H0; states[f].h[1] = d2dmd5::H1; states[f].h[2] = d2dmd5::H2; states[f].h[3] = d2dmd5::H3;
+    }
+}
+
+int d2d_flac_md5_update_host(uint32_t channels, uint32_t bit_depth, const void* pcm, size_t frames, d2d_flac_md5_state* state) {
+    if (!depth_ok(bit_depth)) return fail(D2D_ERR_PARAM, "FLAC holds 16, 20 or 24-bit integers (Invalid bit depth)");
+    if (channels == 0 || channels > 8) return fail(D2D_ERR_PARAM, "FLAC holds 1 to 8 channels (Invalid channel count)");
+    if (!state) return fail(D2D_ERR_PARAM, "null MD5 state");
+    if (frames && !pcm) return fail(D2D_ERR_PARAM, "null pcm pointer");
+    if (frames > MD5_MAX_FRAMES) return fail(D2D_ERR_PARAM, "more frames than a byte count of 64 bits holds");
+    if (!frames) return D2D_OK;
+    const uint8_t* p = (const uint8_t*)pcm;
+    const size_t n = frames * channels * sample_bytes(bit_depth);
+    if (bit_depth != 20) md5_absorb(*state, p, n);
+    else {
+        uint8_t buf[3 * 1024];                                        // the 20-bit rule, 1024 samples at a time
+        for (size_t at = 0; at < n;) {
+            const size_t take = std::min(n - at, sizeof(buf));
+            for (size_t i = 0; i < take; i += 3) {
+                const uint32_t v = d2dmd5::sample20((uint32_t)p[at + i] | ((uint32_t)p[at + i + 1] << 8) | ((uint32_t)p[at + i + 2] << 16));
+                buf[i] = (uint8_t)v; buf[i + 1] = (uint8_t)(v >> 8); buf[i + 2] = (uint8_t)(v >> 16);
+            }
+            md5_absorb(*state, buf, take);
+            at += take;
+        }
+    }
+    memset(state->tail + state->tail_bytes, 0, d2dmd5::BLOCK - state->tail_bytes);      // (as the kernel leaves the record)
+    return D2D_OK;
+}
+
+int d2d_flac_md5_final_host(const d2d_flac_md5_state* state, uint8_t digest[16]) {
+    if (!state || !digest) return fail(D2D_ERR_PARAM, "null MD5 state or digest");
+    d2dmd5::finish(state->h, state->bytes, state->tail, digest);
     return D2D_OK;
 }
 

@@ -24,6 +24,7 @@ inline size_t subframe_bits_bound(uint32_t depth, uint32_t n) { return 19 + 2 * 
 inline size_t frame_bound(uint32_t ch, uint32_t depth, uint32_t n) { return MAX_HEADER_BYTES + 2 + (ch * subframe_bits_bound(depth, n) + 7) / 8; }
 inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 inline size_t slot_bytes(uint32_t ch, uint32_t depth) { return align16(frame_bound(ch, depth, BS)); }
+constexpr size_t MD5_MAX_FRAMES = (size_t)1 << 56;      // one d2d_flac_md5_update call: frames * frame bytes stays far inside 64 bits
 inline size_t block_count(size_t frames, int final) { return frames / BS + ((final && frames % BS) ? 1 : 0); }
 
 // the message d2d_flac_error() returns (thread-local); returns `code`

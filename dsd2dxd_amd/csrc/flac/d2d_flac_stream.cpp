@@ -1,6 +1,8 @@
 // d2d_flac_stream.cpp -- d2d_convert_stream_flac: a whole DSD stream to FLAC frames through the public calls (d2d_translate_batch_device,
-// d2d_flac_encode_device_effort, and for the verified twin d2d_flac_verify_device) and HIP's host API.  Host code: it launches no kernel.
+// d2d_flac_encode_device_effort, for the verified twin d2d_flac_verify_device, for the hashing one d2d_flac_md5_*_device) and HIP's host API.  Host code: it launches no kernel.
 #include <hip/hip_runtime_api.h>
+#include <string.h>
+
 #include <algorithm>
 #include "d2d_flac_internal.h"
 
@@ -32,27 +34,35 @@ extern "C" int d2d_convert_stream_flac(d2d_engine* e, uint32_t bit_depth, d2d_re
     return d2d_convert_stream_flac_effort(e, bit_depth, D2D_FLAC_EFFORT_FIXED2, read, ru, write, wu, cancel, progress, pu, total, chunk, stats);
 }
 
-// the driver behind both twins; `check` non-null: every chunk's frames are verified on the device before `write` sees them
+// the driver behind the twins; `check` non-null: every chunk's frames are verified on the device before `write` sees them; `md5` non-null:
+// every chunk's new frames are hashed on the device and the digest is written there after the last
 static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
                                d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
-                               uint64_t total, size_t chunk, d2d_flac_stream_stats* stats, d2d_flac_check* check);
+                               uint64_t total, size_t chunk, d2d_flac_stream_stats* stats, d2d_flac_check* check, uint8_t* md5);
 
 extern "C" int d2d_convert_stream_flac_effort(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
                                               d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
                                               uint64_t total, size_t chunk, d2d_flac_stream_stats* stats) {
-    return convert_stream_flac(e, bit_depth, effort, read, ru, write, wu, cancel, progress, pu, total, chunk, stats, nullptr);
+    return convert_stream_flac(e, bit_depth, effort, read, ru, write, wu, cancel, progress, pu, total, chunk, stats, nullptr, nullptr);
 }
 
 extern "C" int d2d_convert_stream_flac_verified(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
                                                 d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
                                                 uint64_t total, size_t chunk, d2d_flac_stream_stats* stats, d2d_flac_check* check) {
     if (!check) return fail(D2D_ERR_PARAM, "null check record");
-    return convert_stream_flac(e, bit_depth, effort, read, ru, write, wu, cancel, progress, pu, total, chunk, stats, check);
+    return convert_stream_flac(e, bit_depth, effort, read, ru, write, wu, cancel, progress, pu, total, chunk, stats, check, nullptr);
+}
+
+extern "C" int d2d_convert_stream_flac_md5(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
+                                           d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
+                                           uint64_t total, size_t chunk, d2d_flac_stream_stats* stats, d2d_flac_check* check, uint8_t md5[16]) {
+    if (!md5) return fail(D2D_ERR_PARAM, "null md5");
+    return convert_stream_flac(e, bit_depth, effort, read, ru, write, wu, cancel, progress, pu, total, chunk, stats, check, md5);
 }
 
 static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
                                d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
-                               uint64_t total, size_t chunk, d2d_flac_stream_stats* stats, d2d_flac_check* check) {
+                               uint64_t total, size_t chunk, d2d_flac_stream_stats* stats, d2d_flac_check* check, uint8_t* md5) {
     if (!effort_ok(effort)) return fail(D2D_ERR_PARAM, EFFORT_MESSAGE);
     if (!e) return fail(D2D_ERR_PARAM, "null engine");
     if (!read) return fail(D2D_ERR_PARAM, "null read callback");
@@ -81,6 +91,13 @@ static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effor
     d2d_flac_result* res = (d2d_flac_result*)h_res.p;
     if (check) FLAC_HIP(h_chk.alloc(sizeof(d2d_flac_check)), "hipHostMalloc");
     d2d_flac_check* chk = (d2d_flac_check*)h_chk.p;
+    // the hash: one state record on the device, the digest in pinned memory
+    DevBuf d_md5; PinBuf h_dig;
+    if (md5) {
+        FLAC_HIP(d_md5.alloc(sizeof(d2d_flac_md5_state)), "hipMalloc"); FLAC_HIP(h_dig.alloc(16), "hipHostMalloc");
+        const int mrc = d2d_flac_md5_init_device(d_md5.p, 1, st.s);
+        if (mrc != D2D_OK) return mrc;
+    }
 
     size_t carry = 0;                 // frames in front of d_pcm that no block has taken yet
     uint64_t done = 0;
@@ -98,6 +115,11 @@ static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effor
         FLAC_HIP(hipMemcpyAsync(d_in.p, h_in[cur].p, L * ch, hipMemcpyHostToDevice, st.s), "hipMemcpyAsync");
         if (d2d_translate_batch_device(e, &tio, 1, st.s) != D2D_OK) return fail(D2D_ERR_DEVICE, d2d_last_error(e));
         const size_t nf = tio.frames_out;
+        if (md5) {                                                    // the chunk's new frames, where the translate call left them
+            const d2d_flac_md5_io mio{d_new.p, nf};
+            const int mrc = d2d_flac_md5_update_device(ch, bit_depth, &mio, 1, d_md5.p, st.s);
+            if (mrc != D2D_OK) return mrc;
+        }
         if (carry + nf > cap_frames) return fail(D2D_ERR_STATE, "a chunk produced more frames than planned");
         if (nf) FLAC_HIP(hipMemcpyAsync((uint8_t*)d_pcm.p + carry * fb, d_new.p, nf * fb, hipMemcpyDeviceToDevice, st.s), "hipMemcpyAsync");
         // the next chunk is read while the GPU works: the stream ends with this chunk if there is none
@@ -144,6 +166,12 @@ static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effor
             progress(pu, pct);
         }
         got = next; cur ^= 1;
+    }
+    if (md5) {
+        const int mrc = d2d_flac_md5_final_device(d_md5.p, 1, h_dig.p, st.s);
+        if (mrc != D2D_OK) return mrc;
+        FLAC_HIP(hipStreamSynchronize(st.s), "hipStreamSynchronize");
+        memcpy(md5, h_dig.p, 16);
     }
     if (progress) progress(pu, 100.0f);
     return D2D_OK;

@@ -185,7 +185,7 @@ int main(int argc, char** argv) {
     std::string out_dir; bool have_out_dir = false;
     size_t channels = 2, bit_depth = 24; char fmt = 'I', filt = 'E', endian = 'M', dither = 0, output = 'S';
     uint32_t block = 4096, rate = 352800, inrate = 1; double level = 0.0; bool append = false, recurse = false, quiet = false;
-    int device = 0; unsigned long long seed = 0; uint32_t tap_bits = 0; bool gpu_flac = false, flac_verify = false; int flac_effort = 0;
+    int device = 0; unsigned long long seed = 0; uint32_t tap_bits = 0; bool gpu_flac = false, flac_verify = false, flac_md5 = false; int flac_effort = 0;
     std::vector<std::string> files;
     for (; ai < argc; ++ai) {
         std::string a = argv[ai];
@@ -213,7 +213,12 @@ int main(int argc, char** argv) {
         else if (a == "--gpu-flac") gpu_flac = true;               // -o f only: encode the frames on the GPU (Rdsd2Pcm::set_gpu_flac)
         else if (a == "--flac-effort") flac_effort = atoi(val());  // -o f only: 0 (default), 1, the search, or 12, the search with LPC (Rdsd2Pcm::set_flac_effort)
         else if (a == "--flac-verify") flac_verify = true;         // --gpu-flac -o f only: check every frame against its PCM on the GPU before it is written (Rdsd2Pcm::set_flac_verify)
+        else if (a == "--flac-md5") flac_md5 = true;               // --gpu-flac -o f only: hash the samples on the GPU and fill in STREAMINFO's MD5 (Rdsd2Pcm::set_flac_md5)
         else files.push_back(a);
+    }
+    if (flac_md5 && !(gpu_flac && tolower(output) == 'f')) {
+        fprintf(stderr, "ERROR: --flac-md5 hashes the samples --gpu-flac encodes: it needs --gpu-flac and -o f\n");
+        return 2;
     }
     if (flac_verify && !(gpu_flac && tolower(output) == 'f')) {
         fprintf(stderr, "ERROR: --flac-verify checks the frames --gpu-flac encodes: it needs --gpu-flac and -o f\n");
@@ -258,7 +263,7 @@ int main(int argc, char** argv) {
             Rdsd2Pcm lib = (!is_stdin && DsdFileFormat::from(path).is_container())
                                ? Rdsd2Pcm::from_container(bit_depth, ot, level, rate, od, dt, fl, append, ".", path)
                                : Rdsd2Pcm::create(bit_depth, ot, level, rate, od, dt, ft, en, inrate, block, channels, fl, append, ".", ip);
-            lib.set_device(device); lib.set_seed(seed); lib.set_tap_bits(tap_bits); lib.set_gpu_flac(gpu_flac); lib.set_flac_effort(flac_effort); lib.set_flac_verify(flac_verify);
+            lib.set_device(device); lib.set_seed(seed); lib.set_tap_bits(tap_bits); lib.set_gpu_flac(gpu_flac); lib.set_flac_effort(flac_effort); lib.set_flac_verify(flac_verify); lib.set_flac_md5(flac_md5);
             lib.do_conversion(CANCEL_FLAG);
             if (!quiet && !lib.warnings().empty()) fprintf(stderr, "WARNING: %s: %s\n", lib.file_name().c_str(), lib.warnings().c_str());
             if (!quiet && lib.audio_seconds() > 0)

@@ -156,7 +156,9 @@ struct FlacSink : PcmSink {
     Md5 md5;                       // of the samples as little-endian whole-byte integers, interleaved (FLAC format, STREAMINFO)
     std::vector<FlacFrameEnc> encs;
     bool io_failed = false;
-    bool raw_frames = false;       // the frames came encoded (write_frames): no samples were seen, so there is no MD5
+    bool raw_frames = false;       // the frames came encoded (write_frames): no samples were seen, so there is no MD5 unless set_md5 brings one
+    bool have_digest = false; uint8_t digest[16];
+    void set_md5(const uint8_t* d) override { memcpy(digest, d, 16); have_digest = true; }
     uint32_t effort = 0;           // flac_frame_enc.h: 0 = fixed order 2, 1 = the search, 12 = the search with LPC
     void set_flac_effort(uint32_t e) override { effort = e; }
     uint32_t depth() const { return bits == 20 ? 20 : bits; }
@@ -259,7 +261,8 @@ struct FlacSink : PcmSink {
         si[4] = min_fs >> 16; si[5] = min_fs >> 8; si[6] = (uint8_t)min_fs; si[7] = max_fs >> 16; si[8] = max_fs >> 8; si[9] = (uint8_t)max_fs;
         const uint64_t v = ((uint64_t)rate << 44) | ((uint64_t)(ch - 1) << 41) | ((uint64_t)(depth() - 1) << 36) | (frames & 0xFFFFFFFFFull);
         for (int i = 0; i < 8; ++i) si[10 + i] = (uint8_t)(v >> (56 - 8 * i));
-        if (!raw_frames) md5.finish(si + 18);                            // (16 zero bytes otherwise: "not computed")
+        if (!raw_frames) md5.finish(si + 18);
+        else if (have_digest) memcpy(si + 18, digest, 16);               // (16 zero bytes otherwise: "not computed")
         fseek(f, 8, SEEK_SET); fwrite(si, 1, 34, f);
         if (fclose(f) != 0 || io_failed) return "close failed";
         return "";

@@ -19,11 +19,14 @@ class PcmSink {
     virtual std::string close() = 0;
     // The FLAC sink's raw-frame path (Rdsd2Pcm::set_gpu_flac): frames that d2d_convert_stream_flac encoded on the GPU are written as they
     // come, and STREAMINFO is filled from the stream's stats at close().  Its MD5 field stays 16 zero bytes -- FLAC's "not computed" --
-    // because the samples never reach the host.  Every other sink refuses.
+    // because the samples never reach the host, unless set_md5 brings the digest taken on the GPU (Rdsd2Pcm::set_flac_md5).  Every other sink refuses.
     virtual std::string write_frames(const uint8_t*, size_t) { return "this sink takes PCM, not FLAC frames"; }
     virtual void set_frame_stats(uint64_t /*samples_per_channel*/, uint64_t /*blocks*/, uint32_t /*min_frame_bytes*/, uint32_t /*max_frame_bytes*/) {}
     // The FLAC sink's encoder effort (D2D_FLAC_EFFORT_* of include/dsd2dxd_amd.h; 0 unless set), before the first write.  Other sinks ignore it.
     virtual void set_flac_effort(uint32_t /*effort*/) {}
+    // The FLAC sink's raw-frame path only: STREAMINFO's MD5 of the samples the frames were made from (d2d_convert_stream_flac_md5), before
+    // close().  Other sinks, and a FLAC sink that saw the samples itself, ignore it.
+    virtual void set_md5(const uint8_t* /*digest: 16 bytes*/) {}
 };
 
 // bit_depth 16/20/24 (integer, 20 in a 24-bit container) or 32 (float).  `id3` = the source's ID3v2

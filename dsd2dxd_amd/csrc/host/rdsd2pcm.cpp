@@ -42,7 +42,7 @@ struct Rdsd2Pcm::Impl {
     DsdInfo info;
     bool level_only = false;
     size_t chunk = 4u << 20;
-    bool gpu_flac = false, flac_verify = false;
+    bool gpu_flac = false, flac_verify = false, flac_md5 = false;
     uint32_t flac_effort = D2D_FLAC_EFFORT_FIXED2;
     std::string out_path;
     double dsp_s = 0.0, audio_s = 0.0;
@@ -149,6 +149,7 @@ void Rdsd2Pcm::set_tap_bits(uint32_t bits) { p_->prm.tap_bits = bits; }
 void Rdsd2Pcm::set_chunk_bytes(size_t b) { if (b) p_->chunk = b; }
 void Rdsd2Pcm::set_gpu_flac(bool on) { p_->gpu_flac = on; }
 void Rdsd2Pcm::set_flac_verify(bool on) { p_->flac_verify = on; }
+void Rdsd2Pcm::set_flac_md5(bool on) { p_->flac_md5 = on; }
 void Rdsd2Pcm::set_flac_effort(int effort) {
     if (effort != D2D_FLAC_EFFORT_FIXED2 && effort != D2D_FLAC_EFFORT_SEARCH && effort != D2D_FLAC_EFFORT_LPC) throw std::runtime_error("Invalid FLAC effort; must be 0, 1 or 12");
     p_->flac_effort = (uint32_t)effort;
@@ -245,12 +246,18 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
         if (B > 1) chunk = std::max(B, chunk / B * B);                  // whole planar blocks per read, as d2d_convert_stream cuts them
         d2d_flac_stream_stats stats{};
         d2d_flac_check check{};
-        rc = im.flac_verify ? d2d_convert_stream_flac_verified(e, im.prm.bit_depth, im.flac_effort, read_cb, &ctx, write_frames_cb, &ctx, &ctx.cancel_int,
+        uint8_t digest[16];
+        rc = im.flac_md5    ? d2d_convert_stream_flac_md5(e, im.prm.bit_depth, im.flac_effort, read_cb, &ctx, write_frames_cb, &ctx, &ctx.cancel_int,
+                                                          progress_cb, &ctx, info.bytes_per_channel, chunk, &stats, im.flac_verify ? &check : nullptr, digest)
+           : im.flac_verify ? d2d_convert_stream_flac_verified(e, im.prm.bit_depth, im.flac_effort, read_cb, &ctx, write_frames_cb, &ctx, &ctx.cancel_int,
                                                                progress_cb, &ctx, info.bytes_per_channel, chunk, &stats, &check)
                             : d2d_convert_stream_flac_effort(e, im.prm.bit_depth, im.flac_effort, read_cb, &ctx, write_frames_cb, &ctx, &ctx.cancel_int,
                                                              progress_cb, &ctx, info.bytes_per_channel, chunk, &stats);
         if (rc) msg = d2d_flac_error();
-        else sink->set_frame_stats(stats.samples_per_channel, stats.blocks, stats.min_frame_bytes, stats.max_frame_bytes);
+        else {
+            sink->set_frame_stats(stats.samples_per_channel, stats.blocks, stats.min_frame_bytes, stats.max_frame_bytes);
+            if (im.flac_md5) sink->set_md5(digest);
+        }
     } else {
         rc = d2d_convert_stream(e, read_cb, &ctx, levels ? nullptr : write_cb, &ctx, &ctx.cancel_int,
                                 progress_cb, &ctx, info.bytes_per_channel, im.chunk);

@@ -472,7 +472,68 @@ int d2d_convert_stream_flac_verified(d2d_engine* e, uint32_t bit_depth, uint32_t
                                      uint64_t total_bytes_per_channel, size_t chunk_bytes_per_channel, d2d_flac_stream_stats* stats,
                                      d2d_flac_check* check);
 
-/* ---- shared tables (multi-GPU) ------------------------------------------------------------ */
+/* ---- STREAMINFO's MD5 on the GPU (added under ABI 11: no existing call or structure changed) -- */
+
+/* FLAC's STREAMINFO carries the MD5 of the unencoded audio.  The GPU path keeps the samples on the device, so the hash is taken there:
+ * one chain per file, many files per call (MD5 is serial within a file; a batch is not).  OPT-IN: the calls above neither hash nor
+ * change; a file written without these calls keeps 16 zero bytes, FLAC's "not computed".
+ *
+ * WHAT IS HASHED is what the host sink hashes: the interleaved samples as little-endian whole-byte integers.  16 and 24 bits: the
+ * packed frames of the translate calls as they are.  20 bits: those calls keep the value shifted left by 4 in a 3-byte container;
+ * each 3-byte sample is shifted right by 4 ARITHMETICALLY and emitted again as 3 little-endian bytes (csrc/flac/flac_md5.h: one
+ * source for the host twin and the kernel).
+ *
+ * THE STATE is public, one record per file: a caller may keep, copy or build one.  `update` continues file i's hash with io[i].frames
+ * frames; the record carries the bytes behind the last whole 64-byte block, so a call may end anywhere.  frames == 0 leaves the record
+ * as it is; n_files == 0 launches nothing.  After an update the tail bytes at and behind tail_bytes are 0: for the same bytes the host
+ * twin and the device call leave the same 96 bytes.  `final` pads and writes the digest and does NOT modify the state, so a caller may
+ * ask for the digest so far; the bit length is the full 64-bit 8 * bytes.
+ *
+ * The device calls only enqueue on `hip_stream` (NULL = the null stream), like d2d_flac_encode_device, and take no engine: records and
+ * digests are valid once the stream has synchronised.  One wave per file, all files of a call in one launch of up to 128 files
+ * (their descriptors ride in the kernel arguments); a larger call is cut into launches of 128, which run one after another on the
+ * stream: A CALL'S TIME GROWS WITH ceil(n_files / 128), not with n_files (while the device has a free SIMD per file).  A caller may
+ * enqueue `update` on a stream of its own beside other work: it occupies one wave per file.
+ *
+ * Checked on the host before anything is launched: bit_depth not 16 / 20 / 24, channels 0 or above 8, a null `states` / `digests` /
+ * `io`, states not 16-byte aligned, a pcm pointer that is not 16-byte aligned, or null with frames > 0 -> D2D_ERR_PARAM;
+ * d2d_flac_error() has the message.
+ *
+ * WHAT A CALL MAY TOUCH (tests/test_gpu_flac_md5.py pins it): `init` and `update` write the n_files state records and nothing else;
+ * `update` reads exactly the frames it is given; `final` writes 16 * n_files digest bytes and nothing else.  A refused call writes
+ * nothing. */
+typedef struct d2d_flac_md5_state {      /* 96 bytes; memory the GPU can address (device or pinned host), 16-byte aligned */
+    uint32_t h[4];                       /* a, b, c, d */
+    uint64_t bytes;                      /* bytes hashed so far, the tail included */
+    uint32_t tail_bytes;                 /* 0 .. 63 (= bytes % 64) */
+    uint32_t reserved;                   /* 0 */
+    uint8_t  tail[64];                   /* the bytes behind the last whole 64-byte block */
+} d2d_flac_md5_state;
+typedef struct d2d_flac_md5_io {
+    const void* pcm;                     /* DEVICE pointer, 16-byte aligned: `frames` interleaved frames as the translate calls pack them */
+    size_t      frames;
+} d2d_flac_md5_io;
+
+void d2d_flac_md5_init_host(d2d_flac_md5_state* states, uint32_t n_files);
+int  d2d_flac_md5_init_device(void* states, uint32_t n_files, void* hip_stream);
+int  d2d_flac_md5_update_device(uint32_t channels, uint32_t bit_depth, const d2d_flac_md5_io* io, uint32_t n_files,
+                                void* states, void* hip_stream);
+int  d2d_flac_md5_final_device(const void* states, uint32_t n_files, void* digests /* 16 bytes per file, GPU-addressable */, void* hip_stream);
+/* The CPU twins, no device: one file in host memory (`pcm` needs no alignment), the same checks and codes. */
+int  d2d_flac_md5_update_host(uint32_t channels, uint32_t bit_depth, const void* pcm, size_t frames, d2d_flac_md5_state* state);
+int  d2d_flac_md5_final_host(const d2d_flac_md5_state* state, uint8_t digest[16]);
+
+/* d2d_convert_stream_flac_effort (check == NULL) or d2d_convert_stream_flac_verified (check != NULL) with one state record: after each
+ * chunk's d2d_translate_batch_device the chunk's new frames are hashed on the same stream, and after the last chunk `md5` receives the
+ * digest for STREAMINFO (an empty stream: the MD5 of no bytes, as the host sink writes for one).  `write` and `stats` receive what the
+ * call without the hash gives them.  On any failure `md5` is left untouched.  The three stream calls above do not hash. */
+int d2d_convert_stream_flac_md5(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* read_user,
+                                d2d_write_fn write, void* write_user,
+                                const volatile int* cancel, d2d_progress_fn progress, void* progress_user,
+                                uint64_t total_bytes_per_channel, size_t chunk_bytes_per_channel, d2d_flac_stream_stats* stats,
+                                d2d_flac_check* check /* NULL: not verified */, uint8_t md5[16]);
+
+/* ---- shared tables (multi-GPU)------------------------------------------------------------ */
 
 /* The device filter tables as one opaque blob, so that rank 0 can broadcast them (RCCL) and
  * the other ranks adopt them instead of rebuilding: size query, export to / import from a

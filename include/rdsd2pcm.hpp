@@ -74,7 +74,7 @@ class Rdsd2Pcm {
     // FLAC output only (ignored for every other output type); off by default.  On: the frames are encoded on the GPU
     // (d2d_convert_stream_flac, include/dsd2dxd_amd.h) and only they cross the link.  The file is byte for byte the one the host
     // encoder writes, except STREAMINFO's MD5 field, which is 16 zero bytes -- FLAC's "not computed" -- because the samples never
-    // reach the host.  Tags and pictures are written as before.  Not a reference option; the C mirror (rdsd2pcm_c.h) does not have it.
+    // reach the host, unless set_flac_md5 is on.  Tags and pictures are written as before.  Not a reference option; the C mirror (rdsd2pcm_c.h) does not have it.
     void set_gpu_flac(bool on);
     // FLAC output only; 0 by default.  The encoder effort, D2D_FLAC_EFFORT_* of include/dsd2dxd_amd.h: 0 = fixed order 2, one Rice
     // partition, independent channels; 1 = searched fixed predictors, partitioned Rice and stereo modes; 12 = that search with LPC
@@ -86,6 +86,11 @@ class Rdsd2Pcm {
     // The file is the one written without it; a block that does not verify ends do_conversion with an exception that names the block and
     // the reason.  The C mirror (rdsd2pcm_c.h) does not have it, as it does not have set_gpu_flac.
     void set_flac_verify(bool on);
+    // With set_gpu_flac only (ignored otherwise); off by default.  On: the samples are hashed on the GPU as they are made
+    // (d2d_convert_stream_flac_md5) and STREAMINFO's MD5 field is filled in: the file is then byte for byte the host encoder's.  It costs
+    // one serial MD5 chain per file on the device (README, the FLAC table).  It combines with set_flac_effort and set_flac_verify.  The C
+    // mirror (rdsd2pcm_c.h) does not have it, as it does not have set_gpu_flac.
+    void set_flac_md5(bool on);
 
     struct Impl;                              // opaque state (public only so the .cpp's helpers can name it)
 

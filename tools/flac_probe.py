@@ -16,7 +16,14 @@ over effort 1's, and no file may come out longer than at effort 1.
 times ONE d2d_flac_verify_device_method call over the batch (both kernels) at each effort, after that effort's encode call on the same
 buffers, beside the encode call itself; every record must be clean.  The ratio verify / encode at the same effort is the figure of
 interest.  --method chooses D2D_FLAC_VERIFY_SERIAL (one lane per frame) or D2D_FLAC_VERIFY_COOP (one workgroup per frame); without it
-the call is AUTO's.  Under coop every block must have been accepted by the fast path."""
+the call is AUTO's.  Under coop every block must have been accepted by the fast path.
+
+   tools/flac_probe.py --md5 [files] [seconds] [reps] [out.json]                                (default bench_out/flac_md5_probe.json)
+STREAMINFO's MD5 on the device, all in one session on the batch's PCM: (a) ONE d2d_flac_md5_update_device call over the whole batch,
+device events, ms and GB/s per file; (b) the same call over one file; (c) the encode call at efforts 0 / 1 / 12 beside it, and the update
+on a second stream beside the effort-12 encode (first event to last event: does it hide?); (d) what a caller has without the call: the
+batch's PCM copied to pinned host memory (events) and hashed there on 16 threads, one file per task (wall clock), by the host twin
+d2d_flac_md5_update_host and by hashlib (OpenSSL).  Every file's device digest must be hashlib's."""
 import ctypes as C
 import json
 import os
@@ -41,6 +48,9 @@ if "--effort" in argv:
 verify_mode = "--verify" in argv
 if verify_mode:
     argv.remove("--verify")
+md5_mode = "--md5" in argv
+if md5_mode:
+    argv.remove("--md5")
 method_name = "auto"
 if "--method" in argv:
     at = argv.index("--method")
@@ -49,7 +59,7 @@ if "--method" in argv:
 n_files = int(argv[0]) if len(argv) > 0 else 64
 seconds = float(argv[1]) if len(argv) > 1 else 60.0
 reps = int(argv[2]) if len(argv) > 2 else 9
-out_path = argv[3] if len(argv) > 3 else os.path.join(ROOT, "bench_out", "flac_verify_probe.json" if verify_mode else "flac_probe.json")
+out_path = argv[3] if len(argv) > 3 else os.path.join(ROOT, "bench_out", "flac_md5_probe.json" if md5_mode else "flac_verify_probe.json" if verify_mode else "flac_probe.json")
 blocks_in = max(1, int(round(seconds * DSD64 / 8 / 4096)))
 bpc = blocks_in * 4096
 CH, DEPTH, BS, THREADS = 2, 24, 4096, 16
@@ -121,6 +131,88 @@ if verify_mode:
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, "w") as fh:
         json.dump(res, fh, indent=1)
+    sys.exit(0)
+if md5_mode:
+    import hashlib
+    states = torch.zeros(n_files * 96, dtype=torch.uint8, device=dev)
+    digests = torch.zeros(n_files * 16, dtype=torch.uint8, device=dev)
+    mio = (d.FlacMd5IO * n_files)()
+    for f in range(n_files):
+        mio[f].pcm, mio[f].frames = pcm[f].data_ptr(), frames
+    one = (d.FlacMd5IO * 1)()
+    one[0].pcm, one[0].frames = pcm[0].data_ptr(), frames
+    file_bytes = frames * fb
+    fresh = lambda: d.flac_md5_init_device(states.data_ptr(), n_files, stream)
+    ms3 = lambda t: dict(median=t[0], min=t[1], max=t[2])
+    # (a), (b)
+    batch_ms = timed(lambda: d.flac_md5_update_device(CH, DEPTH, mio, states.data_ptr(), stream), before=fresh)
+    d.flac_md5_final_device(states.data_ptr(), n_files, digests.data_ptr(), stream)
+    got = digests.cpu().numpy().tobytes()
+    one_ms = timed(lambda: d.flac_md5_update_device(CH, DEPTH, one, states.data_ptr(), stream), before=fresh)
+    # (c)
+    enc_ms = {eff: timed(lambda: d.flac_encode_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), stream, effort=eff)) for eff in (0, 1, 12)}
+    s_enc, s_md5 = torch.cuda.Stream(), torch.cuda.Stream()
+
+    def beside():
+        ms = []
+        for i in range(3 + reps):
+            fresh()
+            torch.cuda.synchronize()
+            a, b1, b2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            a.record()
+            s_enc.wait_event(a)
+            s_md5.wait_event(a)
+            d.flac_md5_update_device(CH, DEPTH, mio, states.data_ptr(), s_md5.cuda_stream)
+            d.flac_encode_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), s_enc.cuda_stream, effort=12)
+            b1.record(s_enc)
+            b2.record(s_md5)
+            torch.cuda.synchronize()
+            if i >= 3:
+                ms.append((max(a.elapsed_time(b1), a.elapsed_time(b2)), a.elapsed_time(b1), a.elapsed_time(b2)))
+        return [statistics.median(m[k] for m in ms) for k in range(3)]
+
+    both_ms = beside()
+    # (d)
+    pinned = torch.empty((n_files, file_bytes), dtype=torch.uint8).pin_memory()
+    copy_ms = timed(lambda: [pinned[f].copy_(pcm[f, :file_bytes], non_blocking=True) for f in range(n_files)])      # (one contiguous copy per file)
+    host_pcm = pinned.numpy()
+    want = [hashlib.md5(host_pcm[f]).digest() for f in range(n_files)]
+    assert [got[16 * f:16 * f + 16] for f in range(n_files)] == want, "a device digest is not hashlib's"
+
+    def twin(f):
+        st = d.flac_md5_init_host(1)
+        d.flac_md5_update_host(CH, DEPTH, host_pcm[f], st[0])
+        return d.flac_md5_final_host(st[0])
+
+    host = {}
+    with ThreadPoolExecutor(THREADS) as pool:
+        for name, fn in (("host_twin", twin), ("hashlib", lambda f: hashlib.md5(host_pcm[f]).digest())):
+            s = []
+            for _ in range(2):
+                t0 = time.perf_counter()
+                assert list(pool.map(fn, range(n_files))) == want
+                s.append(time.perf_counter() - t0)
+            host[name] = s
+    gbs = lambda ms: file_bytes / ms / 1e6
+    res = dict(files=n_files, seconds_per_file=seconds, frames_per_file=frames, bytes_per_file=file_bytes, reps=reps,
+               update_batch_ms=ms3(batch_ms), update_one_file_ms=ms3(one_ms), gb_per_s_per_file_batch=gbs(batch_ms[0]), gb_per_s_one_file=gbs(one_ms[0]),
+               encode_ms={str(k): ms3(v) for k, v in enc_ms.items()}, conversion_ms=ms3(conv),
+               beside_effort12_ms=dict(first_to_last=both_ms[0], encode_end=both_ms[1], update_end=both_ms[2]),
+               copy_to_pinned_ms=ms3(copy_ms), host_16_threads_s=host, digests_equal_hashlib=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        json.dump(res, fh, indent=1)
+    print("batch: %d files x %d frames, stereo 24-bit: %.2f MB per file; every device digest equals hashlib's" % (n_files, frames, file_bytes / 1e6))
+    print("(a) update, whole batch, one call: median %.2f ms (min %.2f, max %.2f) = %.4f GB/s per file, %.3f GB/s in all" %
+          (*batch_ms, gbs(batch_ms[0]), n_files * gbs(batch_ms[0])))
+    print("(b) update, one file:              median %.2f ms (min %.2f, max %.2f) = %.4f GB/s" % (*one_ms, gbs(one_ms[0])))
+    for eff in (0, 1, 12):
+        print("(c) encode effort %2d alone: median %.2f ms (min %.2f, max %.2f)" % (eff, *enc_ms[eff]))
+    print("(c) conversion step alone: median %.2f ms" % conv[0])
+    print("(c) update on a second stream beside the effort-12 encode: first event to last %.2f ms (encode ends at %.2f, update at %.2f)" % tuple(both_ms))
+    print("(d) copy to pinned host memory: median %.2f ms (min %.2f, max %.2f) = %.1f GB/s" % (*copy_ms, n_files * file_bytes / copy_ms[0] / 1e6))
+    for name, s in host.items():
+        print("(d) %s on %d threads, one file per task: best %.3f s of %s" % (name, THREADS, min(s), ["%.3f" % v for v in s]))
     sys.exit(0)
 enc0, bytes0, per_file0 = None, None, None
 base = 1 if effort == d.FLAC_EFFORT_LPC else 0                  # the effort this one is held against
