@@ -12,6 +12,7 @@
 //   route_probe                one line per configuration, "<key>\t<field>=<value> ...": every FirRoute field, the predicted kernel name, the main
 //                              pass's launch geometry and the fp6 unit, or error=<code>:<text>.  The key is
 //                              <dsd_rate>:<output_rate>:<filter>:<channels><fmt><depth><dither>:<level>:<tap_bits>:<kernel>:<debug flags>
+//   route_probe keys           the keys of those lines alone, in their order (tools/kernel_instances.py feeds them back through `launches -`)
 //   route_probe -              the same lines for the keys on standard input, one per line
 //   route_probe launches -     for those keys the launch plans of the engine (d2d_route.h: fir_launch), "<key>\t<pass> <field>=<value> ...[\t<pass> ...]":
 //                              the passes it has (main; lo: the residual table's; m2: the mono pair), each with the plan's family, unit, LDS bytes,
@@ -146,6 +147,8 @@ static void launch_field(const char* pass, const FirLaunch& l) {
            l.rows_per_file, l.name.c_str());
 }
 
+static bool keys_only = false;       // `route_probe keys`: the sweep's keys and nothing about them
+
 static void route_line(const Rate& rt, uint32_t ch, char fmt, uint32_t bits, char dither, double level, uint32_t tap_bits, uint32_t kernel, uint32_t dbg,
                        bool launches = false) {
     d2d_params p{};
@@ -153,7 +156,8 @@ static void route_line(const Rate& rt, uint32_t ch, char fmt, uint32_t bits, cha
     p.dsd_rate = rt.dsd_rate; p.output_rate = rt.output_rate; p.filter = (uint32_t)rt.filter; p.channels = ch;
     p.fmt = fmt == 'P' ? D2D_FMT_PLANAR : D2D_FMT_INTERLEAVED; p.endianness = fmt == 'P' ? D2D_LSB_FIRST : D2D_MSB_FIRST; p.block_size = 4096;
     p.bit_depth = bits; p.dither = (uint32_t)dither; p.level_db = level; p.seed = 7; p.tap_bits = tap_bits; p.kernel = kernel; p.debug_flags = dbg;
-    printf("%u:%u:%c:%u%c%u%c:%d:%u:%u:%u\t", rt.dsd_rate, rt.output_rate, rt.filter, ch, fmt, bits, dither, (int)level, tap_bits, kernel, dbg);
+    printf("%u:%u:%c:%u%c%u%c:%d:%u:%u:%u%c", rt.dsd_rate, rt.output_rate, rt.filter, ch, fmt, bits, dither, (int)level, tap_bits, kernel, dbg, keys_only ? '\n' : '\t');
+    if (keys_only) return;
     FilterChoice fc; FirRoute r; std::string err;
     int rc = choose_filters(p, fc, err);
     if (rc == D2D_OK) rc = choose_route(p, fc, r, err);
@@ -213,7 +217,8 @@ static void routes() {
 int main(int argc, char** argv) {
     if (argc > 1 && std::string(argv[1]) == "predicates") { predicates(); return 0; }
 #ifndef ROUTE_PROBE_PREDICATES_ONLY
-    if (argc == 1) { routes(); return 0; }
+    keys_only = argc > 1 && std::string(argv[1]) == "keys";
+    if (argc == 1 || keys_only) { routes(); return 0; }
     const bool launches = std::string(argv[1]) == "launches", filters = std::string(argv[1]) == "filters";
     if (std::string(argv[(launches || filters) && argc > 2 ? 2 : 1]) == "-") {
         Rate rt; unsigned ch, bits, tap_bits, kernel, dbg; int level; char fmt, dither;
@@ -223,6 +228,6 @@ int main(int argc, char** argv) {
         return 0;
     }
 #endif
-    fprintf(stderr, "usage: route_probe [predicates | - | launches - | filters -]\n");
+    fprintf(stderr, "usage: route_probe [predicates | keys | - | launches - | filters -]\n");
     return 2;
 }
