@@ -98,6 +98,24 @@ class FlacMd5IO(C.Structure):
     _fields_ = [("pcm", C.c_void_p), ("frames", C.c_size_t)]
 
 
+class LoudCell(C.Structure):
+    """d2d_loud_cell: (energy, peak) of one sub-block (100 ms) of one channel"""
+    _fields_ = [("energy", C.c_double), ("peak", C.c_double)]
+
+
+class LoudIO(C.Structure):
+    """d2d_loud_io: one file of a d2d_loud_measure_device / _host call; subblocks, cells_out and next_subblock are written at return"""
+    _fields_ = [("pcm", C.c_void_p), ("frames", C.c_size_t), ("first_frame", C.c_uint64), ("first_subblock", C.c_uint64),
+                ("final", C.c_int32), ("reserved", C.c_uint32), ("cells", C.c_void_p), ("cells_capacity", C.c_size_t),
+                ("subblocks", C.c_size_t), ("cells_out", C.c_size_t), ("next_subblock", C.c_uint64)]
+
+
+class LoudResult(C.Structure):
+    """d2d_loud_result: integrated loudness, sample peak and the ReplayGain track gain of one stream"""
+    _fields_ = [("lufs", C.c_double), ("peak", C.c_double), ("gain_db", C.c_double), ("valid", C.c_int32), ("reserved", C.c_uint32),
+                ("blocks_total", C.c_uint64), ("blocks_gated", C.c_uint64)]
+
+
 FLAC_VERIFY_AUTO, FLAC_VERIFY_SERIAL, FLAC_VERIFY_COOP = 0, 1, 2       # D2D_FLAC_VERIFY_*
 # D2D_FLAC_BAD_*
 (FLAC_BAD_NONE, FLAC_BAD_SIZE, FLAC_BAD_HEADER, FLAC_BAD_CRC8, FLAC_BAD_CRC16, FLAC_BAD_UNSUPPORTED, FLAC_BAD_SYNTAX, FLAC_BAD_LENGTH,
@@ -125,7 +143,9 @@ EXPORTS = ["d2d_create", "d2d_create_error", "d2d_destroy", "d2d_reset", "d2d_la
            "d2d_flac_verify_device", "d2d_flac_verify_host", "d2d_flac_decode_host", "d2d_convert_stream_flac_verified",
            "d2d_flac_verify_device_method", "d2d_flac_verify_host_method",
            "d2d_flac_md5_init_host", "d2d_flac_md5_init_device", "d2d_flac_md5_update_device", "d2d_flac_md5_final_device",
-           "d2d_flac_md5_update_host", "d2d_flac_md5_final_host", "d2d_convert_stream_flac_md5"]
+           "d2d_flac_md5_update_host", "d2d_flac_md5_final_host", "d2d_convert_stream_flac_md5",
+           "d2d_loud_coefficients", "d2d_loud_measure_device", "d2d_loud_measure_host", "d2d_loud_create", "d2d_loud_add",
+           "d2d_loud_finish", "d2d_loud_destroy", "d2d_convert_stream_flac_loud"]
 
 _lib = None
 
@@ -219,6 +239,15 @@ def lib():
     L.d2d_flac_md5_update_host.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(FlacMd5State)]
     L.d2d_flac_md5_final_host.argtypes = [C.POINTER(FlacMd5State), C.c_void_p]
     L.d2d_convert_stream_flac_md5.argtypes = L.d2d_convert_stream_flac_verified.argtypes + [C.c_void_p]
+    L.d2d_loud_coefficients.argtypes = [C.c_uint32, C.POINTER(C.c_double)]
+    L.d2d_loud_measure_device.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(LoudIO), C.c_uint32, C.c_void_p]
+    L.d2d_loud_measure_host.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(LoudIO)]
+    L.d2d_loud_create.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_void_p)]
+    L.d2d_loud_add.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    L.d2d_loud_finish.argtypes = [C.c_void_p, C.POINTER(LoudResult)]
+    L.d2d_loud_destroy.argtypes = [C.c_void_p]
+    L.d2d_loud_destroy.restype = None
+    L.d2d_convert_stream_flac_loud.argtypes = L.d2d_convert_stream_flac_md5.argtypes + [C.c_void_p]
     _lib = L
     return L
 
@@ -332,6 +361,69 @@ def flac_md5_update_device(channels, bit_depth, ios, states_ptr, stream=None):
 def flac_md5_final_device(states_ptr, n_files, digests_ptr, stream=None):
     """d2d_flac_md5_final_device: 16 digest bytes per file to digests_ptr (memory the GPU can address); asynchronous on `stream`"""
     _flac_check(lib().d2d_flac_md5_final_device(C.c_void_p(states_ptr), n_files, C.c_void_p(digests_ptr), C.c_void_p(stream or 0)))
+
+
+def loud_coefficients(rate):
+    """d2d_loud_coefficients: the ten f64 K-weighting coefficients of `rate` (shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2)"""
+    out = (C.c_double * 10)()
+    _flac_check(lib().d2d_loud_coefficients(rate, out))
+    return list(out)
+
+
+def loud_measure_host(channels, bit_depth, rate, pcm, first_frame=0, first_subblock=0, final=True, capacity=None):
+    """d2d_loud_measure_host on a bytes-like of whole interleaved frames that begin at stream frame `first_frame`: returns (cells, io) --
+    cells a float64 array of shape (rows, channels, 2) holding (energy, peak), io the LoudIO with the counts.  No device."""
+    import numpy as np
+    buf = _u8(pcm)
+    fb = channels * (2 if bit_depth == 16 else 4 if bit_depth == 32 else 3)
+    frames = buf.size // fb if fb else 0
+    if capacity is None:
+        capacity = (frames // max(rate // 10, 1) + 2) * max(channels, 1)
+    cells = np.zeros((max(capacity, 1), 2), dtype=np.float64)
+    io = LoudIO(buf.ctypes.data if buf.size else None, frames, first_frame, first_subblock, int(bool(final)), 0, cells.ctypes.data, capacity, 0, 0, 0)
+    _flac_check(lib().d2d_loud_measure_host(channels, bit_depth, rate, C.byref(io)))
+    return cells[:io.cells_out].reshape(-1, channels, 2).copy(), io
+
+
+def loud_measure_device(channels, bit_depth, rate, ios, stream=None):
+    """d2d_loud_measure_device: ios is a ctypes array of LoudIO with DEVICE pcm pointers and GPU-addressable cells; asynchronous on
+    `stream`; the counts are in ios at return"""
+    _flac_check(lib().d2d_loud_measure_device(channels, bit_depth, rate, ios, len(ios), C.c_void_p(stream or 0)))
+
+
+class LoudMeter:
+    """d2d_loud_create / _add / _finish / _destroy: the host integration of one stream's cells (gates, loudness, ReplayGain)"""
+
+    def __init__(self, channels, rate, weights=None):
+        self._h = C.c_void_p()
+        self.channels = channels
+        w = (C.c_double * channels)(*weights) if weights is not None else None
+        _flac_check(lib().d2d_loud_create(channels, rate, w, C.byref(self._h)))
+
+    def add(self, cells, whole_subblocks=None, has_partial=False):
+        """cells: a float64 array of (rows, channels, 2); every row is a whole sub-block unless has_partial, which makes the last one partial"""
+        import numpy as np
+        a = np.ascontiguousarray(cells, dtype=np.float64)
+        rows = a.size // (2 * self.channels)
+        if whole_subblocks is None:
+            whole_subblocks = rows - (1 if has_partial else 0)
+        _flac_check(lib().d2d_loud_add(self._h, a.ctypes.data if a.size else None, whole_subblocks, int(bool(has_partial))))
+
+    def finish(self):
+        r = LoudResult()
+        _flac_check(lib().d2d_loud_finish(self._h, C.byref(r)))
+        return r
+
+    def close(self):
+        if self._h:
+            lib().d2d_loud_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class D2DError(Exception):
@@ -518,13 +610,14 @@ class Engine:
                                              keep["p"], None, total_bytes_per_channel, chunk_bytes_per_channel))
 
     def convert_stream_flac(self, read, write, total_bytes_per_channel=0, chunk_bytes_per_channel=1 << 22,
-                            cancel=None, progress=None, effort=0, verify=False, md5=False):
+                            cancel=None, progress=None, effort=0, verify=False, md5=False, loud=None):
         """d2d_convert_stream_flac_effort: as convert_stream, but write() receives FLAC frames (whole frames, in order); returns the
         FlacStreamStats STREAMINFO needs.  Errors carry d2d_flac_error()'s message.  verify=True: d2d_convert_stream_flac_verified --
         every chunk's frames are checked against their PCM on the GPU before write() sees them; returns (stats, FlacCheck), and a bad
         block raises D2DError with code ERR_VERIFY (the record so far is the exception's `check`).  md5=True: d2d_convert_stream_flac_md5
         -- the samples are hashed on the GPU as well; the 16 digest bytes for STREAMINFO are returned last: (stats, digest), or with
-        verify=True (stats, FlacCheck, digest)."""
+        verify=True (stats, FlacCheck, digest).  loud=a LoudMeter: d2d_convert_stream_flac_loud -- the samples are also measured on the
+        GPU and their cells go into the meter, which the caller finishes; what is returned is what the other switches make it."""
         def _read(_u, dst, cap):
             data = read(cap)
             if not data:
@@ -543,6 +636,17 @@ class Engine:
         r, w, p = READ_FN(_read), WRITE_FN(_write), PROGRESS_FN(_prog)
         cflag = cancel if cancel is not None else C.c_int(0)
         stats = FlacStreamStats()
+        if loud is not None:
+            chk, digest = FlacCheck(), (C.c_uint8 * 16)()
+            rc = lib().d2d_convert_stream_flac_loud(self._h, self.params.bit_depth, effort, r, None, w, None, C.byref(cflag), p, None,
+                                                    total_bytes_per_channel, chunk_bytes_per_channel, C.byref(stats),
+                                                    C.byref(chk) if verify else None, digest if md5 else None, loud._h)
+            if rc:
+                err = D2DError(rc, lib().d2d_flac_error().decode())
+                err.check = chk
+                raise err
+            out = (stats,) + ((chk,) if verify else ()) + ((bytes(digest),) if md5 else ())
+            return out if len(out) > 1 else stats
         if md5:
             chk, digest = FlacCheck(), (C.c_uint8 * 16)()
             rc = lib().d2d_convert_stream_flac_md5(self._h, self.params.bit_depth, effort, r, None, w, None, C.byref(cflag), p, None,

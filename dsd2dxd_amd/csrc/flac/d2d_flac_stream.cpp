@@ -1,10 +1,11 @@
 // d2d_flac_stream.cpp -- d2d_convert_stream_flac: a whole DSD stream to FLAC frames through the public calls (d2d_translate_batch_device,
-// d2d_flac_encode_device_effort, for the verified twin d2d_flac_verify_device, for the hashing one d2d_flac_md5_*_device) and HIP's host API.  Host code: it launches no kernel.
+// d2d_flac_encode_device_effort, for the verified twin d2d_flac_verify_device, for the hashing one d2d_flac_md5_*_device, for the measuring one d2d_loud_measure_device) and HIP's host API.  Host code: it launches no kernel.
 #include <hip/hip_runtime_api.h>
 #include <string.h>
 
 #include <algorithm>
 #include "d2d_flac_internal.h"
+#include "../loud/d2d_loud_internal.h"
 
 using namespace d2dflac;
 
@@ -35,34 +36,43 @@ extern "C" int d2d_convert_stream_flac(d2d_engine* e, uint32_t bit_depth, d2d_re
 }
 
 // the driver behind the twins; `check` non-null: every chunk's frames are verified on the device before `write` sees them; `md5` non-null:
-// every chunk's new frames are hashed on the device and the digest is written there after the last
+// every chunk's new frames are hashed on the device and the digest is written there after the last; `loud` non-null: every chunk's new
+// sub-blocks are measured on the device and their cells go into the meter
 static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
                                d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
-                               uint64_t total, size_t chunk, d2d_flac_stream_stats* stats, d2d_flac_check* check, uint8_t* md5);
+                               uint64_t total, size_t chunk, d2d_flac_stream_stats* stats, d2d_flac_check* check, uint8_t* md5, d2d_loud* loud);
 
 extern "C" int d2d_convert_stream_flac_effort(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
                                               d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
                                               uint64_t total, size_t chunk, d2d_flac_stream_stats* stats) {
-    return convert_stream_flac(e, bit_depth, effort, read, ru, write, wu, cancel, progress, pu, total, chunk, stats, nullptr, nullptr);
+    return convert_stream_flac(e, bit_depth, effort, read, ru, write, wu, cancel, progress, pu, total, chunk, stats, nullptr, nullptr, nullptr);
 }
 
 extern "C" int d2d_convert_stream_flac_verified(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
                                                 d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
                                                 uint64_t total, size_t chunk, d2d_flac_stream_stats* stats, d2d_flac_check* check) {
     if (!check) return fail(D2D_ERR_PARAM, "null check record");
-    return convert_stream_flac(e, bit_depth, effort, read, ru, write, wu, cancel, progress, pu, total, chunk, stats, check, nullptr);
+    return convert_stream_flac(e, bit_depth, effort, read, ru, write, wu, cancel, progress, pu, total, chunk, stats, check, nullptr, nullptr);
 }
 
 extern "C" int d2d_convert_stream_flac_md5(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
                                            d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
                                            uint64_t total, size_t chunk, d2d_flac_stream_stats* stats, d2d_flac_check* check, uint8_t md5[16]) {
     if (!md5) return fail(D2D_ERR_PARAM, "null md5");
-    return convert_stream_flac(e, bit_depth, effort, read, ru, write, wu, cancel, progress, pu, total, chunk, stats, check, md5);
+    return convert_stream_flac(e, bit_depth, effort, read, ru, write, wu, cancel, progress, pu, total, chunk, stats, check, md5, nullptr);
+}
+
+extern "C" int d2d_convert_stream_flac_loud(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
+                                            d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
+                                            uint64_t total, size_t chunk, d2d_flac_stream_stats* stats, d2d_flac_check* check, uint8_t md5[16],
+                                            d2d_loud* loud) {
+    if (!loud) return fail(D2D_ERR_PARAM, "null meter");
+    return convert_stream_flac(e, bit_depth, effort, read, ru, write, wu, cancel, progress, pu, total, chunk, stats, check, md5, loud);
 }
 
 static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* ru,
                                d2d_write_fn write, void* wu, const volatile int* cancel, d2d_progress_fn progress, void* pu,
-                               uint64_t total, size_t chunk, d2d_flac_stream_stats* stats, d2d_flac_check* check, uint8_t* md5) {
+                               uint64_t total, size_t chunk, d2d_flac_stream_stats* stats, d2d_flac_check* check, uint8_t* md5, d2d_loud* loud) {
     if (!effort_ok(effort)) return fail(D2D_ERR_PARAM, EFFORT_MESSAGE);
     if (!e) return fail(D2D_ERR_PARAM, "null engine");
     if (!read) return fail(D2D_ERR_PARAM, "null read callback");
@@ -98,6 +108,20 @@ static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effor
         const int mrc = d2d_flac_md5_init_device(d_md5.p, 1, st.s);
         if (mrc != D2D_OK) return mrc;
     }
+    // the meter: a PCM buffer of its own that keeps the pre-roll of the next sub-block (two sub-blocks, and what has come of the third) in
+    // front of each chunk's frames -- the encoder's carry stays what it was -- and the cells in pinned memory the kernel writes directly.
+    // What is kept moves to the front through the second buffer (the ranges may overlap).
+    if (loud && d2dloud::meter_channels(loud) != ch) return fail(D2D_ERR_PARAM, "the meter was created for another channel count than the engine's");
+    const uint32_t rate = loud ? d2dloud::meter_rate(loud) : 0;
+    const size_t S = rate / 10, l_cap = 3 * S + chunk_frames, l_rows = S ? l_cap / S + 2 : 0;
+    DevBuf d_loud[2]; PinBuf h_cells;
+    if (loud) {
+        FLAC_HIP(d_loud[0].alloc(l_cap * fb), "hipMalloc"); FLAC_HIP(d_loud[1].alloc(l_cap * fb), "hipMalloc");
+        FLAC_HIP(h_cells.alloc(l_rows * ch * sizeof(d2d_loud_cell)), "hipHostMalloc");
+    }
+    uint64_t l_first = 0, l_next = 0;  // the stream position of d_loud[l_cur]'s first frame; the next sub-block to measure
+    size_t l_have = 0;                 // frames in d_loud[l_cur]
+    int l_cur = 0;
 
     size_t carry = 0;                 // frames in front of d_pcm that no block has taken yet
     uint64_t done = 0;
@@ -125,6 +149,16 @@ static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effor
         // the next chunk is read while the GPU works: the stream ends with this chunk if there is none
         const long next = read(ru, (uint8_t*)h_in[cur ^ 1].p, chunk);
         if (next < 0) return fail(D2D_ERR_IO, "read callback failed");
+        d2d_loud_io lio{};
+        if (loud) {                                                   // the chunk's frames behind the kept ones; every sub-block they complete
+            if (l_have + nf > l_cap) return fail(D2D_ERR_STATE, "a chunk produced more frames than planned");
+            if (nf) FLAC_HIP(hipMemcpyAsync((uint8_t*)d_loud[l_cur].p + l_have * fb, d_new.p, nf * fb, hipMemcpyDeviceToDevice, st.s), "hipMemcpyAsync");
+            l_have += nf;
+            lio.pcm = d_loud[l_cur].p; lio.frames = l_have; lio.first_frame = l_first; lio.first_subblock = l_next; lio.final = next == 0;
+            lio.cells = (d2d_loud_cell*)h_cells.p; lio.cells_capacity = l_rows * ch; lio.next_subblock = l_next;
+            const int lrc = d2d_loud_measure_device(ch, bit_depth, rate, &lio, 1, st.s);
+            if (lrc != D2D_OK) return lrc;
+        }
         d2d_flac_io fio{};
         fio.pcm = d_pcm.p; fio.frames = carry + nf; fio.first_block = (uint32_t)stats->blocks; fio.final = next == 0;
         fio.out = d_out.p; fio.out_capacity_bytes = d_out.bytes; fio.result = res;
@@ -143,6 +177,18 @@ static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effor
                 if (!check->bad_blocks) { check->first_bad_block = (uint32_t)stats->blocks + chk->first_bad_block; check->first_bad_reason = chk->first_bad_reason; }
                 check->bad_blocks += chk->bad_blocks;
                 return fail(D2D_ERR_VERIFY, "FLAC verify failed: block " + std::to_string(check->first_bad_block) + " (" + reason_name(check->first_bad_reason) + ")");
+            }
+        }
+        if (loud) {                                                   // the cells came with the result
+            const int lrc = d2d_loud_add(loud, lio.cells, lio.subblocks, lio.cells_out > lio.subblocks * ch);
+            if (lrc != D2D_OK) return lrc;
+            l_next = lio.next_subblock;
+            const uint64_t keep_from = (l_next > 2 ? l_next - 2 : 0) * (uint64_t)S;     // the pre-roll of the next sub-block
+            const size_t drop = (size_t)(keep_from - l_first);
+            if (drop) {
+                l_have -= drop;
+                if (l_have) FLAC_HIP(hipMemcpyAsync(d_loud[l_cur ^ 1].p, (uint8_t*)d_loud[l_cur].p + drop * fb, l_have * fb, hipMemcpyDeviceToDevice, st.s), "hipMemcpyAsync");
+                l_cur ^= 1; l_first = keep_from;
             }
         }
         if (r.bytes_out) {

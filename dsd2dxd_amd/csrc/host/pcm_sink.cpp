@@ -4,9 +4,11 @@
 #include "id3_tag.h"
 #include "../flac/flac_frame_enc.h"
 
+#include <ctype.h>
 #include <math.h>
 
 #include <algorithm>
+#include <memory>
 #include <thread>
 #include <string.h>
 
@@ -26,6 +28,57 @@ static void put_le32(uint8_t* p, uint32_t v) { p[0] = v; p[1] = v >> 8; p[2] = v
 static void put_le16(uint8_t* p, uint16_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); }
 static void put_be32(uint8_t* p, uint32_t v) { p[3] = v; p[2] = v >> 8; p[1] = v >> 16; p[0] = v >> 24; }
 static void put_be16(uint8_t* p, uint16_t v) { p[1] = (uint8_t)v; p[0] = (uint8_t)(v >> 8); }
+
+// ---- loudness on the host: the feed and the tag texts ----
+
+LoudFeed::LoudFeed(uint32_t channels, uint32_t bit_depth, uint32_t rate)
+    : ch_(channels), depth_(bit_depth), rate_(rate), fb_((size_t)channels * (bit_depth == 16 ? 2 : bit_depth == 32 ? 4 : 3)) {
+    if (d2d_loud_create(channels, rate, nullptr, &meter_) != D2D_OK) err_ = d2d_flac_error();
+}
+LoudFeed::~LoudFeed() { d2d_loud_destroy(meter_); }
+
+std::string LoudFeed::measure(bool final) {
+    const size_t S = rate_ / 10, frames = pcm_.size() / fb_;
+    if (!frames) return "";
+    cells_.resize((frames / S + 2) * ch_);
+    d2d_loud_io io{};
+    io.pcm = pcm_.data(); io.frames = frames; io.first_frame = first_; io.first_subblock = next_; io.final = final;
+    io.cells = cells_.data(); io.cells_capacity = cells_.size();
+    if (d2d_loud_measure_host(ch_, depth_, rate_, &io) != D2D_OK) return d2d_flac_error();
+    if (d2d_loud_add(meter_, cells_.data(), io.subblocks, io.cells_out > io.subblocks * ch_) != D2D_OK) return d2d_flac_error();
+    next_ = io.next_subblock;
+    const uint64_t keep_from = (next_ > 2 ? next_ - 2 : 0) * (uint64_t)S;      // the pre-roll of the next sub-block
+    pcm_.erase(pcm_.begin(), pcm_.begin() + (size_t)(keep_from - first_) * fb_);
+    first_ = keep_from;
+    return "";
+}
+
+std::string LoudFeed::write(const uint8_t* frames, size_t bytes) {
+    if (!meter_) return err_;
+    pcm_.insert(pcm_.end(), frames, frames + bytes / fb_ * fb_);
+    // (not at every small write: once a sub-block or more is new)
+    if ((first_ + pcm_.size() / fb_) / (rate_ / 10) > next_) return measure(false);
+    return "";
+}
+
+std::string LoudFeed::finish(d2d_loud_result* result) {
+    if (!meter_) return err_;
+    const std::string e = measure(true);
+    if (!e.empty()) return e;
+    return d2d_loud_finish(meter_, result) == D2D_OK ? "" : d2d_flac_error();
+}
+
+std::string replaygain_reference_text() { return "-18.00 LUFS"; }
+std::string replaygain_gain_text(const d2d_loud_result& r) {
+    char b[32];
+    snprintf(b, sizeof(b), "%+06.2f dB", std::max(-99.99, std::min(99.99, r.valid ? r.gain_db : 0.0)));
+    return b;
+}
+std::string replaygain_peak_text(const d2d_loud_result& r) {
+    char b[32];
+    snprintf(b, sizeof(b), "%.6f", std::max(0.0, std::min(9.999999, r.peak)));
+    return b;
+}
 
 namespace {
 
@@ -161,6 +214,12 @@ struct FlacSink : PcmSink {
     void set_md5(const uint8_t* d) override { memcpy(digest, d, 16); have_digest = true; }
     uint32_t effort = 0;           // flac_frame_enc.h: 0 = fixed order 2, 1 = the search, 12 = the search with LPC
     void set_flac_effort(uint32_t e) override { effort = e; }
+    // ReplayGain (open_sink's `replaygain`): where the two values lie in the file, the sink's own meter, the GPU path's result
+    bool replaygain = false;
+    long gain_at = 0, peak_at = 0;
+    std::unique_ptr<LoudFeed> feed;
+    bool have_loudness = false; d2d_loud_result loudness{};
+    void set_loudness(const d2d_loud_result& r) override { loudness = r; have_loudness = true; }
     uint32_t depth() const { return bits == 20 ? 20 : bits; }
     std::string begin() {
         // metadata: STREAMINFO (filled in at close), then the source's tag as VORBIS_COMMENT and PICTURE
@@ -168,6 +227,21 @@ struct FlacSink : PcmSink {
         std::vector<std::pair<std::string, std::string>> fields;
         std::vector<TagPicture> pics;
         tag_to_vorbis(id3, fields, pics);
+        size_t gain_in_block = 0, peak_in_block = 0;
+        if (replaygain) {
+            // the source's own loudness fields go, ours come last: placeholders of the final width, patched at close()
+            auto ours = [](std::string k) {
+                for (char& c : k) c = (char)toupper((unsigned char)c);
+                return k.rfind("REPLAYGAIN_TRACK_", 0) == 0 || k == "REPLAYGAIN_REFERENCE_LOUDNESS";
+            };
+            fields.erase(std::remove_if(fields.begin(), fields.end(), [&](const std::pair<std::string, std::string>& kv) { return ours(kv.first); }), fields.end());
+            const d2d_loud_result none{};
+            fields.push_back({"REPLAYGAIN_REFERENCE_LOUDNESS", replaygain_reference_text()});
+            fields.push_back({"REPLAYGAIN_TRACK_GAIN", replaygain_gain_text(none)});
+            fields.push_back({"REPLAYGAIN_TRACK_PEAK", replaygain_peak_text(none)});
+            feed.reset(new LoudFeed(ch, bits, rate));
+            if (!feed->error().empty()) return feed->error();
+        }
         std::vector<std::vector<uint8_t>> blocks;
         if (!fields.empty()) {
             std::vector<uint8_t> b;
@@ -177,9 +251,14 @@ struct FlacSink : PcmSink {
             le32((uint32_t)fields.size());
             for (const auto& kv : fields) {
                 const std::string e = kv.first + "=" + kv.second;
-                le32((uint32_t)e.size()); b.insert(b.end(), e.begin(), e.end());
+                le32((uint32_t)e.size());
+                if (replaygain && kv.first == "REPLAYGAIN_TRACK_GAIN") gain_in_block = b.size() + kv.first.size() + 1;
+                if (replaygain && kv.first == "REPLAYGAIN_TRACK_PEAK") peak_in_block = b.size() + kv.first.size() + 1;
+                b.insert(b.end(), e.begin(), e.end());
             }
             b.insert(b.begin(), {4, 0, 0, 0});
+            // (the comment block is the first behind STREAMINFO: 4 + 4 + 34 bytes, then its own 4-byte header)
+            gain_at = (long)(42 + 4 + gain_in_block); peak_at = (long)(42 + 4 + peak_in_block);
             blocks.push_back(std::move(b));
         }
         for (const TagPicture& p : pics) {
@@ -242,6 +321,7 @@ struct FlacSink : PcmSink {
         if (bits == 20) {                                                // MD5 runs over the 20-bit values as 3-byte integers
             for (size_t i = buf.size() - nbytes / sb; i < buf.size(); ++i) { const int32_t v = buf[i]; const uint8_t le[3] = {(uint8_t)v, (uint8_t)(v >> 8), (uint8_t)(v >> 16)}; md5.update(le, 3); }
         } else md5.update(p, nbytes / sb * sb);                          // 16/24-bit: the little-endian input as it is
+        if (feed) { const std::string e = feed->write(p, nbytes); if (!e.empty()) return e; }
         if (buf.size() >= (size_t)BS * ch * 8) drain(false);
         return io_failed ? "short write" : "";
     }
@@ -264,7 +344,18 @@ struct FlacSink : PcmSink {
         if (!raw_frames) md5.finish(si + 18);
         else if (have_digest) memcpy(si + 18, digest, 16);               // (16 zero bytes otherwise: "not computed")
         fseek(f, 8, SEEK_SET); fwrite(si, 1, 34, f);
+        std::string loud_error;
+        if (replaygain) {
+            // the sink's own measurement when it saw the samples, the GPU's otherwise (none: the placeholders stay)
+            if (!raw_frames) { loud_error = feed->finish(&loudness); have_loudness = loud_error.empty(); }
+            if (have_loudness) {
+                const std::string g = replaygain_gain_text(loudness), p = replaygain_peak_text(loudness);
+                fseek(f, gain_at, SEEK_SET); fwrite(g.data(), 1, g.size(), f);
+                fseek(f, peak_at, SEEK_SET); fwrite(p.data(), 1, p.size(), f);
+            }
+        }
         if (fclose(f) != 0 || io_failed) return "close failed";
+        if (!loud_error.empty()) return loud_error;
         return "";
     }
 };
@@ -272,8 +363,9 @@ struct FlacSink : PcmSink {
 }  // namespace
 
 std::string open_sink(OutputType type, const std::string& path, uint32_t channels, uint32_t rate, uint32_t bit_depth, PcmSink** out,
-                      const std::vector<uint8_t>* id3) {
+                      const std::vector<uint8_t>* id3, bool replaygain) {
     *out = nullptr;
+    if (replaygain && type != OutputType::Flac) return "ReplayGain tags are written into FLAC files only; choose -o f";
     if (type == OutputType::Stdout) { *out = new RawSink(stdout); return ""; }
     if (type == OutputType::Flac && bit_depth == 32) return "FLAC cannot hold 32-bit float; choose 16, 20 or 24 bits";
     if (type == OutputType::Flac && rate > 655350) return "FLAC cannot describe this sample rate";
@@ -283,7 +375,7 @@ std::string open_sink(OutputType type, const std::string& path, uint32_t channel
     if (!f) return "cannot create " + path;
     std::string err;
     if (type == OutputType::Wav) { auto* s = new WavSink(); if (id3) s->id3 = *id3; s->f = f; s->ch = channels; s->rate = rate; s->bits = bit_depth; err = s->begin(); *out = s; }
-    else if (type == OutputType::Flac) { auto* s = new FlacSink(); if (id3) s->id3 = *id3; s->f = f; s->ch = channels; s->rate = rate; s->bits = bit_depth; err = s->begin(); *out = s; }
+    else if (type == OutputType::Flac) { auto* s = new FlacSink(); if (id3) s->id3 = *id3; s->f = f; s->ch = channels; s->rate = rate; s->bits = bit_depth; s->replaygain = replaygain; err = s->begin(); *out = s; }
     else { auto* s = new AiffSink(); if (id3) s->id3 = *id3; s->f = f; s->ch = channels; s->rate = rate; s->bits = bit_depth; s->aifc = type == OutputType::Aifc; err = s->begin(); *out = s; }
     return err;
 }

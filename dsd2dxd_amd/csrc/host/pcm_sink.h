@@ -8,6 +8,8 @@
 #include <string>
 #include <vector>
 
+#include "../../../include/dsd2dxd_amd.h"
+
 namespace d2dhost {
 
 enum class OutputType { Stdout, Aiff, Aifc, Wav, Flac };
@@ -27,13 +29,49 @@ class PcmSink {
     // The FLAC sink's raw-frame path only: STREAMINFO's MD5 of the samples the frames were made from (d2d_convert_stream_flac_md5), before
     // close().  Other sinks, and a FLAC sink that saw the samples itself, ignore it.
     virtual void set_md5(const uint8_t* /*digest: 16 bytes*/) {}
+    // A FLAC sink opened with `replaygain`, raw-frame path only: the loudness measured on the GPU (d2d_convert_stream_flac_loud), before
+    // close(), which writes it into the REPLAYGAIN_* fields.  Other sinks, and a FLAC sink that saw the samples itself, ignore it.
+    virtual void set_loudness(const d2d_loud_result& /*result*/) {}
 };
+
+// The CPU twin of the loudness measurement behind a stream of write() calls: whole interleaved frames go in as they come, the cells
+// of every sub-block they complete go into a meter (d2d_loud_measure_host, d2d_loud_add), and only the pre-roll of the next sub-block
+// is kept.  The FLAC sink's host path and `levels --loudness` feed it.
+class LoudFeed {
+   public:
+    LoudFeed(uint32_t channels, uint32_t bit_depth, uint32_t rate);
+    ~LoudFeed();
+    LoudFeed(const LoudFeed&) = delete;
+    LoudFeed& operator=(const LoudFeed&) = delete;
+    std::string error() const { return err_; }                           // "" or why the meter could not be created
+    std::string write(const uint8_t* frames, size_t bytes);              // "" or error
+    std::string finish(d2d_loud_result* result);                         // the partial last sub-block, then the integration
+
+   private:
+    std::string measure(bool final);
+    uint32_t ch_, depth_, rate_;
+    size_t fb_;
+    d2d_loud* meter_ = nullptr;
+    std::vector<uint8_t> pcm_;                                           // the frames from first_ on
+    std::vector<d2d_loud_cell> cells_;
+    uint64_t first_ = 0, next_ = 0;                                      // pcm_'s first frame; the next sub-block to measure
+    std::string err_;
+};
+
+// the three fixed-width Vorbis comment values of a result: "-18.00 LUFS", "%+06.2f dB" clamped to +-99.99, "%.6f"
+std::string replaygain_reference_text();
+std::string replaygain_gain_text(const d2d_loud_result& r);
+std::string replaygain_peak_text(const d2d_loud_result& r);
 
 // bit_depth 16/20/24 (integer, 20 in a 24-bit container) or 32 (float).  `id3` = the source's ID3v2
 // tag to carry over (may be null or empty): WAV 'id3 ' chunk, AIFF/AIFC 'ID3 ' chunk, FLAC
 // VORBIS_COMMENT + PICTURE blocks (id3_tag.h); the raw stdout stream has no place for it.
+// `replaygain` (FLAC only; any other type is refused): the file always gets a VORBIS_COMMENT block that ends with
+// REPLAYGAIN_REFERENCE_LOUDNESS, REPLAYGAIN_TRACK_GAIN and REPLAYGAIN_TRACK_PEAK -- fields of those names the source had are dropped --
+// whose values are placeholders until close() patches them, as it patches STREAMINFO: from the sink's own LoudFeed when it saw the
+// samples, from set_loudness on the raw-frame path.
 std::string open_sink(OutputType type, const std::string& path, uint32_t channels, uint32_t rate, uint32_t bit_depth,
-                      PcmSink** out, const std::vector<uint8_t>* id3 = nullptr);
+                      PcmSink** out, const std::vector<uint8_t>* id3 = nullptr, bool replaygain = false);
 const char* output_extension(OutputType t);
 
 }  // namespace d2dhost

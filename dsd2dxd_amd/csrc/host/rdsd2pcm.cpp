@@ -42,7 +42,8 @@ struct Rdsd2Pcm::Impl {
     DsdInfo info;
     bool level_only = false;
     size_t chunk = 4u << 20;
-    bool gpu_flac = false, flac_verify = false, flac_md5 = false;
+    bool gpu_flac = false, flac_verify = false, flac_md5 = false, replaygain = false, loudness = false;
+    d2d_loud_result loud_result{};
     uint32_t flac_effort = D2D_FLAC_EFFORT_FIXED2;
     std::string out_path;
     double dsp_s = 0.0, audio_s = 0.0;
@@ -150,6 +151,10 @@ void Rdsd2Pcm::set_chunk_bytes(size_t b) { if (b) p_->chunk = b; }
 void Rdsd2Pcm::set_gpu_flac(bool on) { p_->gpu_flac = on; }
 void Rdsd2Pcm::set_flac_verify(bool on) { p_->flac_verify = on; }
 void Rdsd2Pcm::set_flac_md5(bool on) { p_->flac_md5 = on; }
+void Rdsd2Pcm::set_replaygain(bool on) { p_->replaygain = on; }
+void Rdsd2Pcm::set_loudness(bool on) { p_->loudness = on; }
+bool Rdsd2Pcm::loudness_valid() const { return p_->loud_result.valid != 0; }
+double Rdsd2Pcm::loudness_lufs() const { return p_->loud_result.lufs; }
 void Rdsd2Pcm::set_flac_effort(int effort) {
     if (effort != D2D_FLAC_EFFORT_FIXED2 && effort != D2D_FLAC_EFFORT_SEARCH && effort != D2D_FLAC_EFFORT_LPC) throw std::runtime_error("Invalid FLAC effort; must be 0, 1 or 12");
     p_->flac_effort = (uint32_t)effort;
@@ -159,6 +164,7 @@ namespace {
 struct RunCtx {
     DsdSource* src; PcmSink* sink; const std::atomic<bool>* cancel; volatile int cancel_int = 0;
     ProgressSender* sender; std::string io_error;
+    LoudFeed* feed = nullptr;              // levels with set_loudness: the frames go here instead of a sink
     std::chrono::steady_clock::duration io_time{};
 };
 long read_cb(void* u, uint8_t* dst, size_t cap) {
@@ -172,7 +178,7 @@ long read_cb(void* u, uint8_t* dst, size_t cap) {
 int write_cb(void* u, const void* pcm, size_t bytes) {
     RunCtx* c = (RunCtx*)u;
     auto t0 = std::chrono::steady_clock::now();
-    std::string e = c->sink ? c->sink->write((const uint8_t*)pcm, bytes) : "";
+    std::string e = c->sink ? c->sink->write((const uint8_t*)pcm, bytes) : c->feed ? c->feed->write((const uint8_t*)pcm, bytes) : "";
     c->io_time += std::chrono::steady_clock::now() - t0;
     if (!e.empty()) { c->io_error = e; return 1; }
     if (c->cancel->load()) c->cancel_int = 1;
@@ -200,6 +206,9 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
     const DsdInfo& info = src.info();
     PcmSink* sink = nullptr;
     im.out_path.clear();
+    im.loud_result = d2d_loud_result{};
+    if (!levels && im.replaygain && im.output != OutputType::Flac)
+        throw std::runtime_error("ReplayGain tags are written into FLAC files only; choose FLAC output (-o f)");
     if (!levels) {
         if (im.output != OutputType::Stdout) {
             std::string dir;
@@ -227,7 +236,7 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
             // -p: artwork next to the sources follows them into the output tree (README.md:115-119)
             if (im.out_dir) im.artwork_copied = d2dhost::copy_artwork(dirname_of(*im.in_path), dirname_of(im.out_path));
         }
-        err = open_sink((d2dhost::OutputType)(int)im.output, im.out_path, im.prm.channels, im.prm.output_rate, im.prm.bit_depth, &sink, &tag);
+        err = open_sink((d2dhost::OutputType)(int)im.output, im.out_path, im.prm.channels, im.prm.output_rate, im.prm.bit_depth, &sink, &tag, im.replaygain);
         if (!err.empty()) throw std::runtime_error(err);
         sink->set_flac_effort(im.flac_effort);
     }
@@ -235,6 +244,12 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
     d2d_engine* e = nullptr;
     if (d2d_create(&im.prm, 1, &e) != D2D_OK) throw std::runtime_error(d2d_create_error());
     RunCtx ctx; ctx.src = &src; ctx.sink = sink; ctx.cancel = &cancel; ctx.sender = &sender;
+    std::unique_ptr<LoudFeed> feed;
+    if (levels && im.loudness) {
+        feed.reset(new LoudFeed(im.prm.channels, im.prm.bit_depth, im.prm.output_rate));
+        if (!feed->error().empty()) { d2d_destroy(e); throw std::runtime_error(feed->error()); }
+        ctx.feed = feed.get();
+    }
     auto t0 = std::chrono::steady_clock::now();
     const bool gpu_flac = !levels && im.gpu_flac && im.output == OutputType::Flac && sink;
     int rc;
@@ -247,6 +262,16 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
         d2d_flac_stream_stats stats{};
         d2d_flac_check check{};
         uint8_t digest[16];
+        d2d_loud* meter = nullptr;
+        if (im.replaygain && d2d_loud_create(im.prm.channels, im.prm.output_rate, nullptr, &meter) != D2D_OK) rc = D2D_ERR_PARAM;
+        else if (meter) {
+            // measured where the PCM is, on the stream that made it
+            rc = d2d_convert_stream_flac_loud(e, im.prm.bit_depth, im.flac_effort, read_cb, &ctx, write_frames_cb, &ctx, &ctx.cancel_int,
+                                              progress_cb, &ctx, info.bytes_per_channel, chunk, &stats, im.flac_verify ? &check : nullptr,
+                                              im.flac_md5 ? digest : nullptr, meter);
+            if (!rc) rc = d2d_loud_finish(meter, &im.loud_result);
+            d2d_loud_destroy(meter);
+        } else
         rc = im.flac_md5    ? d2d_convert_stream_flac_md5(e, im.prm.bit_depth, im.flac_effort, read_cb, &ctx, write_frames_cb, &ctx, &ctx.cancel_int,
                                                           progress_cb, &ctx, info.bytes_per_channel, chunk, &stats, im.flac_verify ? &check : nullptr, digest)
            : im.flac_verify ? d2d_convert_stream_flac_verified(e, im.prm.bit_depth, im.flac_effort, read_cb, &ctx, write_frames_cb, &ctx, &ctx.cancel_int,
@@ -257,15 +282,17 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
         else {
             sink->set_frame_stats(stats.samples_per_channel, stats.blocks, stats.min_frame_bytes, stats.max_frame_bytes);
             if (im.flac_md5) sink->set_md5(digest);
+            if (im.replaygain) sink->set_loudness(im.loud_result);
         }
     } else {
-        rc = d2d_convert_stream(e, read_cb, &ctx, levels ? nullptr : write_cb, &ctx, &ctx.cancel_int,
+        rc = d2d_convert_stream(e, read_cb, &ctx, levels && !feed ? nullptr : write_cb, &ctx, &ctx.cancel_int,
                                 progress_cb, &ctx, info.bytes_per_channel, im.chunk);
         if (rc) msg = d2d_last_error(e);
     }
     auto total = std::chrono::steady_clock::now() - t0;
     float db = 0.f;
     if (!rc && levels) { if (d2d_peak_dbfs(e, 0, &db) != D2D_OK) msg = d2d_last_error(e); }
+    if (!rc && feed) { const std::string fe = feed->finish(&im.loud_result); if (msg.empty()) msg = fe; }
     const uint64_t bpc = info.bytes_per_channel;
     d2d_destroy(e);
     im.dsp_s = std::chrono::duration<double>(total - ctx.io_time).count();

@@ -1,0 +1,183 @@
+// d2d_loud_host.cpp -- the host half of the loudness calls (include/dsd2dxd_amd.h, "Loudness where the PCM is"): the K-weighting
+// coefficients, d2d_loud_measure_host, the CPU twin of the GPU call on loud_meter.h, and the integration behind both twins (gates,
+// ReplayGain).  No HIP: tools and tests build this file with g++ alone.
+#include <math.h>
+#include <string.h>
+
+#include <new>
+#include <vector>
+
+#include "d2d_loud_internal.h"
+
+using namespace d2dloud;
+
+namespace {
+
+// a0 and the two feedback coefficients of a second-order section with this K and Q
+void feedback(double K, double Q, double& a0, double& a1, double& a2) {
+    a0 = 1.0 + K / Q + K * K;
+    a1 = 2.0 * (K * K - 1.0) / a0;
+    a2 = (1.0 - K / Q + K * K) / a0;
+}
+
+Coef coefficients(uint32_t rate) {
+    const double pi = 3.14159265358979323846;
+    Coef k;
+    {   // the shelf
+        const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+        const double K = tan(pi * f0 / (double)rate), Vh = pow(10.0, G / 20.0), Vb = pow(Vh, 0.4996667741545416);
+        double a0;
+        feedback(K, Q, a0, k.sa1, k.sa2);
+        k.sb0 = (Vh + Vb * K / Q + K * K) / a0;
+        k.sb1 = 2.0 * (K * K - Vh) / a0;
+        k.sb2 = (Vh - Vb * K / Q + K * K) / a0;
+    }
+    {   // the high-pass
+        const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+        const double K = tan(pi * f0 / (double)rate);
+        double a0;
+        feedback(K, Q, a0, k.ha1, k.ha2);
+        k.hb0 = 1.0; k.hb1 = -2.0; k.hb2 = 1.0;
+    }
+    return k;
+}
+
+inline uint32_t raw_le(const uint8_t* p, uint32_t sb) {
+    uint32_t v = (uint32_t)p[0] | ((uint32_t)p[1] << 8);
+    if (sb > 2) v |= (uint32_t)p[2] << 16;
+    if (sb > 3) v |= (uint32_t)p[3] << 24;
+    return v;
+}
+
+}  // namespace
+
+
+struct d2d_loud {
+    uint32_t channels = 0, rate = 0;
+    double weights[8] = {0};
+    double last[3][8] = {{0}};                                     // the energies of the three sub-blocks before the next one, oldest first
+    uint64_t subblocks = 0;
+    bool ended = false;                                            // a partial row was added: the stream is over
+    double peak = 0.0;
+    std::vector<double> power;                                     // sum_c G_c z_c of every 400 ms block, in order
+};
+
+namespace d2dloud {
+Coef host_coefficients(uint32_t rate) { return coefficients(rate); }
+uint32_t meter_rate(const d2d_loud* h) { return h->rate; }
+uint32_t meter_channels(const d2d_loud* h) { return h->channels; }
+}  // namespace d2dloud
+
+extern "C" {
+
+int d2d_loud_coefficients(uint32_t rate, double out[10]) {
+    if (!rate_ok(rate)) return fail(D2D_ERR_PARAM, "loudness is measured at rates that are a multiple of 10 in 8000 .. 1411200");
+    if (!out) return fail(D2D_ERR_PARAM, "null coefficients");
+    const Coef k = coefficients(rate);
+    static_assert(sizeof(Coef) == 10 * sizeof(double), "ten doubles");
+    memcpy(out, &k, sizeof(k));
+    return D2D_OK;
+}
+
+int d2d_loud_measure_host(uint32_t channels, uint32_t bit_depth, uint32_t rate, d2d_loud_io* io) {
+    const int rc = check_call(channels, bit_depth, rate);
+    if (rc != D2D_OK) return rc;
+    if (!io) return fail(D2D_ERR_PARAM, "no file");
+    if (io->frames == 0) return D2D_OK;
+    Plan p;
+    const int prc = plan_file(*io, channels, rate, 1, p);
+    if (prc != D2D_OK) return prc;
+    const Coef k = coefficients(rate);
+    const uint32_t sb = sample_bytes(bit_depth);
+    const size_t fb = (size_t)channels * sb;
+    const uint8_t* pcm = (const uint8_t*)io->pcm;
+    const uint64_t end = io->first_frame + io->frames;
+    for (uint64_t r = 0; r < p.rows(); ++r) {
+        const uint64_t j = io->first_subblock + r;
+        const uint64_t from = start_subblock(j) * p.S, at = j * p.S, to = at + p.S < end ? at + p.S : end;
+        for (uint32_t c = 0; c < channels; ++c) {
+            Unit u;
+            const uint8_t* q = pcm + (size_t)(from - io->first_frame) * fb + (size_t)c * sb;
+            for (uint64_t f = from; f < at; ++f, q += fb) preroll(u, k, sample(raw_le(q, sb), bit_depth));
+            for (uint64_t f = at; f < to; ++f, q += fb) measure(u, k, sample(raw_le(q, sb), bit_depth));
+            d2d_loud_cell cell{u.energy, u.peak};
+            memcpy((uint8_t*)io->cells + ((size_t)r * channels + c) * sizeof(cell), &cell, sizeof(cell));      // (cells need no alignment here)
+        }
+    }
+    write_counts(*io, p, channels);
+    return D2D_OK;
+}
+
+int d2d_loud_create(uint32_t channels, uint32_t rate, const double* weights, d2d_loud** out) {
+    if (!out) return fail(D2D_ERR_PARAM, "null meter pointer");
+    if (channels == 0 || channels > 8) return fail(D2D_ERR_PARAM, "loudness is measured on 1 to 8 channels (Invalid channel count)");
+    if (!rate_ok(rate)) return fail(D2D_ERR_PARAM, "loudness is measured at rates that are a multiple of 10 in 8000 .. 1411200");
+    d2d_loud* h = new (std::nothrow) d2d_loud();
+    if (!h) return fail(D2D_ERR_STATE, "out of memory");
+    h->channels = channels; h->rate = rate;
+    static const double six[6] = {1.0, 1.0, 1.0, 0.0, 1.41, 1.41};           // L R C LFE Ls Rs
+    for (uint32_t c = 0; c < channels; ++c) h->weights[c] = weights ? weights[c] : (channels == 6 ? six[c] : 1.0);
+    *out = h;
+    return D2D_OK;
+}
+
+int d2d_loud_add(d2d_loud* h, const d2d_loud_cell* cells, size_t whole_subblocks, int has_partial) {
+    if (!h) return fail(D2D_ERR_PARAM, "null meter");
+    if (!cells && (whole_subblocks || has_partial)) return fail(D2D_ERR_PARAM, "null cells");
+    if (h->ended && (whole_subblocks || has_partial)) return fail(D2D_ERR_STATE, "cells behind the partial sub-block that ended the stream");
+    const uint32_t ch = h->channels;
+    const double four_s = 4.0 * (double)(h->rate / 10);
+    for (size_t r = 0; r < whole_subblocks; ++r) {
+        d2d_loud_cell row[8];
+        memcpy(row, (const uint8_t*)cells + r * ch * sizeof(d2d_loud_cell), ch * sizeof(d2d_loud_cell));
+        for (uint32_t c = 0; c < ch; ++c)
+            if (row[c].peak > h->peak) h->peak = row[c].peak;
+        if (h->subblocks >= 3) {                                   // the block that ends with this sub-block
+            double w = 0.0;
+            for (uint32_t c = 0; c < ch; ++c) {
+                const double e = ((h->last[0][c] + h->last[1][c]) + h->last[2][c]) + row[c].energy;
+                const double z = e / four_s;
+                w = w + h->weights[c] * z;
+            }
+            h->power.push_back(w);
+        }
+        for (uint32_t c = 0; c < ch; ++c) { h->last[0][c] = h->last[1][c]; h->last[1][c] = h->last[2][c]; h->last[2][c] = row[c].energy; }
+        ++h->subblocks;
+    }
+    if (has_partial) {                                             // its peak only
+        d2d_loud_cell row[8];
+        memcpy(row, (const uint8_t*)cells + whole_subblocks * ch * sizeof(d2d_loud_cell), ch * sizeof(d2d_loud_cell));
+        for (uint32_t c = 0; c < ch; ++c)
+            if (row[c].peak > h->peak) h->peak = row[c].peak;
+        h->ended = true;
+    }
+    return D2D_OK;
+}
+
+int d2d_loud_finish(const d2d_loud* h, d2d_loud_result* result) {
+    if (!h || !result) return fail(D2D_ERR_PARAM, "null meter or result");
+    d2d_loud_result r{};
+    r.peak = h->peak;
+    r.blocks_total = h->power.size();
+    auto lufs = [](double w) { return -0.691 + 10.0 * log10(w); };
+    // the absolute gate
+    double sum = 0.0; uint64_t n = 0;
+    for (double w : h->power)
+        if (w > 0.0 && lufs(w) > -70.0) { sum = sum + w; ++n; }
+    if (n) {
+        const double relative = lufs(sum / (double)n) - 10.0;
+        double kept = 0.0; uint64_t m = 0;
+        for (double w : h->power)
+            if (w > 0.0 && lufs(w) > -70.0 && lufs(w) > relative) { kept = kept + w; ++m; }
+        r.valid = 1;                                               // (the loudest block lies above the mean less 10 LU: m > 0)
+        r.lufs = lufs(kept / (double)m);
+        r.gain_db = -18.0 - r.lufs;
+        r.blocks_gated = r.blocks_total - m;
+    } else r.blocks_gated = r.blocks_total;
+    *result = r;
+    return D2D_OK;
+}
+
+void d2d_loud_destroy(d2d_loud* h) { delete h; }
+
+}  // extern "C"

@@ -30,7 +30,8 @@ extern "C" {
                              * 11: D2D_FILTER_EQUIRIPPLE_CASCADE, the two-stage definition of the 48 kHz multiples, as a value of
                              *     d2d_params.filter (d2d_params unchanged);
                              *     added under 11, nothing existing changed: the verify method, d2d_flac_verify_device_method / _host_method,
-                             *     D2D_FLAC_VERIFY_*, d2d_flac_verify_stats */
+                             *     D2D_FLAC_VERIFY_*, d2d_flac_verify_stats; the d2d_flac_md5_* calls; the d2d_loud_* calls and
+                             *     d2d_convert_stream_flac_loud */
 
 /* status codes */
 enum {
@@ -532,6 +533,90 @@ int d2d_convert_stream_flac_md5(d2d_engine* e, uint32_t bit_depth, uint32_t effo
                                 const volatile int* cancel, d2d_progress_fn progress, void* progress_user,
                                 uint64_t total_bytes_per_channel, size_t chunk_bytes_per_channel, d2d_flac_stream_stats* stats,
                                 d2d_flac_check* check /* NULL: not verified */, uint8_t md5[16]);
+
+/* ---- Loudness where the PCM is (added under ABI 11: no existing call or structure changed) ---- */
+
+/* Integrated loudness (ITU-R BS.1770 / EBU R128) and the sample peak of PCM that lies on the device, for ReplayGain tags.  OPT-IN: no call
+ * above measures or changes.  The arithmetic is written once, in csrc/loud/loud_meter.h, for the host twin and the kernel: f64,
+ * multiplications and additions only, never fused; the order of operations in that header is the definition.
+ *
+ * INPUT: the packed little-endian frames of the translate calls.  16 bits: v / 2^15.  20 and 24 bits: the 3-byte container value / 2^23.
+ * 32 bits: the float widened to f64.  `rate` is a multiple of 10 in 8000 .. 1411200; a SUB-BLOCK is S = rate / 10 frames (100 ms).
+ *
+ * K-WEIGHTING: two biquads, transposed direct form II, whose ten f64 coefficients d2d_loud_coefficients derives on the host from the
+ * analogue prototypes by the bilinear transform (at 48000 Hz: the standard's table).  out[] = shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1
+ * a2.  They travel to the device in the kernel arguments: libm decides no device result.
+ *
+ * A CELL is (energy, peak) of sub-block j and channel c: energy = the sum of y * y over the sub-block's frames in frame order, peak = the
+ * largest |x| there.  THE ONE DEPARTURE FROM THE STANDARD: y over sub-block j is the filter's output when it is started from rest at
+ * frame max(0, j - 2) * S, two sub-blocks of pre-roll, fixed.  Against one uninterrupted pass the energies differ by about 1e-13 relative;
+ * in exchange every (file, sub-block, channel) is independent work -- one GPU lane each -- and no result depends on where a stream is cut
+ * into calls.
+ *
+ * A CALL: `pcm` holds frames [first_frame, first_frame + frames) of the stream and must hold the pre-roll of the first sub-block asked
+ * for: first_frame <= max(0, first_subblock - 2) * S, and first_frame == 0 when first_subblock < 2.  Every whole sub-block from
+ * first_subblock on that the buffer holds is measured; a `final` call adds one more row of cells for a partial last sub-block (energy and
+ * peak over the frames it has).  The cell of sub-block j, channel c is cells[(j - first_subblock) * channels + c].  Written at return, by
+ * host arithmetic: subblocks (whole ones measured), cells_out (cells written: (subblocks + the partial row) * channels), next_subblock.
+ * The caller keeps everything from frame max(0, next_subblock - 2) * S in front of its next PCM.  A file with frames == 0 is left
+ * alone (its three counts are not written either); n_files == 0 launches nothing.
+ *
+ * d2d_loud_measure_device only enqueues on `hip_stream` (NULL = the null stream) and takes no engine: one launch covers up to 64 files
+ * (their descriptors ride in the kernel arguments; a larger call is cut into launches of 64).  The counts are known at return, the cells
+ * are valid once the stream has synchronised.  Checked on the host before anything is launched: bit_depth not 16 / 20 / 24 / 32, channels
+ * 0 or above 8, a bad rate, a missing pre-roll, a null `io`, null or misaligned (16 bytes) pcm / cells -> D2D_ERR_PARAM; cells_capacity
+ * below cells_out -> D2D_ERR_CAPACITY; d2d_flac_error() has the message.  A refused call writes nothing, the counts included.  A
+ * successful call writes exactly cells_out cells per file and no other byte, and reads only the declared frames
+ * (tests/test_gpu_loudness.py pins it).  d2d_loud_measure_host is the CPU twin for one file in host memory (no alignment needed): the
+ * same checks, the same counts, the same cells bit for bit. */
+typedef struct d2d_loud_cell { double energy, peak; } d2d_loud_cell;
+typedef struct d2d_loud_io {
+    const void*    pcm;                  /* DEVICE pointer, 16-byte aligned (the host twin: host memory, any alignment) */
+    size_t         frames;               /* frames in pcm */
+    uint64_t       first_frame;          /* the stream position of pcm's first frame */
+    uint64_t       first_subblock;       /* the first sub-block to measure */
+    int32_t        final;                /* non-zero: the stream ends with this buffer */
+    uint32_t       reserved;             /* 0 */
+    d2d_loud_cell* cells;                /* GPU-addressable (device or pinned host), 16-byte aligned */
+    size_t         cells_capacity;       /* in cells */
+    size_t         subblocks;            /* out: whole sub-blocks measured */
+    size_t         cells_out;            /* out: cells written */
+    uint64_t       next_subblock;        /* out: first_subblock + subblocks */
+} d2d_loud_io;
+
+int d2d_loud_coefficients(uint32_t rate, double out[10]);
+int d2d_loud_measure_device(uint32_t channels, uint32_t bit_depth, uint32_t rate, d2d_loud_io* io, uint32_t n_files, void* hip_stream);
+int d2d_loud_measure_host(uint32_t channels, uint32_t bit_depth, uint32_t rate, d2d_loud_io* io);
+
+/* INTEGRATION, host only, plain f64, no device: the cells of one stream, in order, from either twin.  A 400 ms block b is sub-blocks
+ * b .. b + 3 (hop: one sub-block); z_c = sum(energy) / (4 S); l_b = -0.691 + 10 log10(sum_c G_c z_c); blocks at or under -70 LUFS are
+ * dropped, then blocks at or under (the loudness of the rest - 10 LU); `lufs` is the loudness of what remains.  `weights` NULL: G = 1 for
+ * every channel, and 1, 1, 1, 0, 1.41, 1.41 for six (L R C LFE Ls Rs).  d2d_loud_add takes whole_subblocks rows of `channels` cells and,
+ * with has_partial, one more row that contributes its peak only.  If no block lies above -70 LUFS, `valid` is 0, lufs is 0 and gain_db is
+ * 0.  ReplayGain: gain_db = -18 - lufs; peak is the sample peak.  blocks_gated counts the blocks either gate dropped. */
+typedef struct d2d_loud d2d_loud;
+typedef struct d2d_loud_result {
+    double   lufs, peak, gain_db;
+    int32_t  valid;
+    uint32_t reserved;
+    uint64_t blocks_total, blocks_gated;
+} d2d_loud_result;
+int  d2d_loud_create(uint32_t channels, uint32_t rate, const double* weights /* NULL: the defaults */, d2d_loud** out);
+int  d2d_loud_add(d2d_loud* h, const d2d_loud_cell* cells, size_t whole_subblocks, int has_partial);
+int  d2d_loud_finish(const d2d_loud* h, d2d_loud_result* result);
+void d2d_loud_destroy(d2d_loud* h);
+
+/* d2d_convert_stream_flac_md5 with `md5` allowed to be NULL (not hashed) and a meter behind it: after each chunk's
+ * d2d_translate_batch_device the new whole sub-blocks are measured on the same stream (at the last chunk: the partial one too); the cells
+ * come back with the frame bytes and go into `loud` (d2d_loud_add), which the caller created for the engine's channels and output rate
+ * and finishes afterwards.  The PCM the driver carries from chunk to chunk grows from "under one FLAC block" to also cover the
+ * pre-roll.  `write`, `stats`, `check` and `md5` receive what the calls without the meter give them.  The stream calls above do not
+ * measure. */
+int d2d_convert_stream_flac_loud(d2d_engine* e, uint32_t bit_depth, uint32_t effort, d2d_read_fn read, void* read_user,
+                                 d2d_write_fn write, void* write_user,
+                                 const volatile int* cancel, d2d_progress_fn progress, void* progress_user,
+                                 uint64_t total_bytes_per_channel, size_t chunk_bytes_per_channel, d2d_flac_stream_stats* stats,
+                                 d2d_flac_check* check /* NULL: not verified */, uint8_t md5[16] /* NULL: not hashed */, d2d_loud* loud);
 
 /* ---- shared tables (multi-GPU)------------------------------------------------------------ */
 

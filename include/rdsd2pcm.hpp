@@ -91,6 +91,17 @@ class Rdsd2Pcm {
     // one serial MD5 chain per file on the device (README, the FLAC table).  It combines with set_flac_effort and set_flac_verify.  The C
     // mirror (rdsd2pcm_c.h) does not have it, as it does not have set_gpu_flac.
     void set_flac_md5(bool on);
+    // FLAC output only (any other output type makes do_conversion throw); off by default.  On: the file's VORBIS_COMMENT block ends with
+    // REPLAYGAIN_REFERENCE_LOUDNESS, REPLAYGAIN_TRACK_GAIN and REPLAYGAIN_TRACK_PEAK (BS.1770 integrated loudness against -18 LUFS, the
+    // sample peak; include/dsd2dxd_amd.h, "Loudness where the PCM is").  With set_gpu_flac the samples are measured on the GPU
+    // (d2d_convert_stream_flac_loud), otherwise by the CPU twin as the sink receives them: the same cells, the same text.  The C mirror
+    // (rdsd2pcm_c.h) does not have it, as it does not have the other FLAC switches.
+    void set_replaygain(bool on);
+    // check_level only; off by default.  On: the float frames of the level check also go through the CPU twin of the loudness
+    // measurement; afterwards loudness_valid() says whether any 400 ms block lay above -70 LUFS and loudness_lufs() has the value.
+    void set_loudness(bool on);
+    bool loudness_valid() const;
+    double loudness_lufs() const;
 
     struct Impl;                              // opaque state (public only so the .cpp's helpers can name it)
 

@@ -23,7 +23,14 @@ STREAMINFO's MD5 on the device, all in one session on the batch's PCM: (a) ONE d
 device events, ms and GB/s per file; (b) the same call over one file; (c) the encode call at efforts 0 / 1 / 12 beside it, and the update
 on a second stream beside the effort-12 encode (first event to last event: does it hide?); (d) what a caller has without the call: the
 batch's PCM copied to pinned host memory (events) and hashed there on 16 threads, one file per task (wall clock), by the host twin
-d2d_flac_md5_update_host and by hashlib (OpenSSL).  Every file's device digest must be hashlib's."""
+d2d_flac_md5_update_host and by hashlib (OpenSSL).  Every file's device digest must be hashlib's.
+
+   tools/flac_probe.py --loud [files] [seconds] [reps] [out.json]                               (default bench_out/loud_probe.json)
+Loudness cells on the device, all in one session on the batch's PCM: (a) ONE d2d_loud_measure_device call over the whole batch, device
+events; (b) the same call over one file; (c) the encode call at efforts 0 / 1 / 12 beside it, and the measure call on a second stream
+beside the effort-12 encode; (d) the alternative: the batch's PCM copied to pinned host memory and measured there on 16 threads, one
+file per task, by the CPU twin d2d_loud_measure_host; (e) the CLI's single-file case: one call over one chunk (4 MiB of DSD per
+channel) of one file, a few waves whose lanes each walk 3 S frames.  Every file's device cells must be the CPU twin's bytes."""
 import ctypes as C
 import json
 import os
@@ -51,6 +58,9 @@ if verify_mode:
 md5_mode = "--md5" in argv
 if md5_mode:
     argv.remove("--md5")
+loud_mode = "--loud" in argv
+if loud_mode:
+    argv.remove("--loud")
 method_name = "auto"
 if "--method" in argv:
     at = argv.index("--method")
@@ -59,7 +69,7 @@ if "--method" in argv:
 n_files = int(argv[0]) if len(argv) > 0 else 64
 seconds = float(argv[1]) if len(argv) > 1 else 60.0
 reps = int(argv[2]) if len(argv) > 2 else 9
-out_path = argv[3] if len(argv) > 3 else os.path.join(ROOT, "bench_out", "flac_md5_probe.json" if md5_mode else "flac_verify_probe.json" if verify_mode else "flac_probe.json")
+out_path = argv[3] if len(argv) > 3 else os.path.join(ROOT, "bench_out", "loud_probe.json" if loud_mode else "flac_md5_probe.json" if md5_mode else "flac_verify_probe.json" if verify_mode else "flac_probe.json")
 blocks_in = max(1, int(round(seconds * DSD64 / 8 / 4096)))
 bpc = blocks_in * 4096
 CH, DEPTH, BS, THREADS = 2, 24, 4096, 16
@@ -213,6 +223,91 @@ if md5_mode:
     print("(d) copy to pinned host memory: median %.2f ms (min %.2f, max %.2f) = %.1f GB/s" % (*copy_ms, n_files * file_bytes / copy_ms[0] / 1e6))
     for name, s in host.items():
         print("(d) %s on %d threads, one file per task: best %.3f s of %s" % (name, THREADS, min(s), ["%.3f" % v for v in s]))
+    sys.exit(0)
+if loud_mode:
+    RATE, S = kw["output_rate"], kw["output_rate"] // 10
+    rows = frames // S + 1
+    cells = torch.zeros((n_files, rows * CH * 2), dtype=torch.float64, device=dev)
+    file_bytes = frames * fb
+    ms3 = lambda t: dict(median=t[0], min=t[1], max=t[2])
+
+    def ios(n, nframes):
+        x = (d.LoudIO * n)()
+        for f in range(n):
+            x[f] = d.LoudIO(pcm[f].data_ptr(), nframes, 0, 0, 1, 0, cells[f].data_ptr(), rows * CH, 0, 0, 0)
+        return x
+
+    lio, one = ios(n_files, frames), ios(1, frames)
+    chunk_frames = min(frames, (4 << 20) * 8 // 32)                     # what 4 MiB of DSD64 per channel make at 88.2 kHz
+    small = ios(1, chunk_frames)
+    # (a), (b), (e)
+    batch_ms = timed(lambda: d.loud_measure_device(CH, DEPTH, RATE, lio, stream))
+    got = cells.cpu().numpy().copy()
+    one_ms = timed(lambda: d.loud_measure_device(CH, DEPTH, RATE, one, stream))
+    small_ms = timed(lambda: d.loud_measure_device(CH, DEPTH, RATE, small, stream))
+    # (c)
+    enc_ms = {eff: timed(lambda: d.flac_encode_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), stream, effort=eff)) for eff in (0, 1, 12)}
+    s_enc, s_loud = torch.cuda.Stream(), torch.cuda.Stream()
+
+    def beside():
+        ms = []
+        for i in range(3 + reps):
+            torch.cuda.synchronize()
+            a, b1, b2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            a.record()
+            s_enc.wait_event(a)
+            s_loud.wait_event(a)
+            d.loud_measure_device(CH, DEPTH, RATE, lio, s_loud.cuda_stream)
+            d.flac_encode_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), s_enc.cuda_stream, effort=12)
+            b1.record(s_enc)
+            b2.record(s_loud)
+            torch.cuda.synchronize()
+            if i >= 3:
+                ms.append((max(a.elapsed_time(b1), a.elapsed_time(b2)), a.elapsed_time(b1), a.elapsed_time(b2)))
+        return [statistics.median(m[k] for m in ms) for k in range(3)]
+
+    both_ms = beside()
+    # (d)
+    pinned = torch.empty((n_files, file_bytes), dtype=torch.uint8).pin_memory()
+    copy_ms = timed(lambda: [pinned[f].copy_(pcm[f, :file_bytes], non_blocking=True) for f in range(n_files)])
+    host_pcm = pinned.numpy()
+
+    def twin(f):
+        c, io = d.loud_measure_host(CH, DEPTH, RATE, host_pcm[f])
+        return c.tobytes()
+
+    with ThreadPoolExecutor(THREADS) as pool:
+        t0 = time.perf_counter()
+        want = list(pool.map(twin, range(n_files)))
+        host_s = time.perf_counter() - t0
+    n_cells = int(lio[0].cells_out)
+    bad = [f for f in range(n_files) if got[f, :2 * n_cells].tobytes() != want[f]]
+    assert not bad, "the device cells of files %s are not the CPU twin's bytes" % bad
+    m = d.LoudMeter(CH, RATE)
+    m.add(got[0, :2 * n_cells].reshape(-1, CH, 2), has_partial=n_cells > int(lio[0].subblocks) * CH)
+    r0 = m.finish()
+    units = n_cells
+    res = dict(files=n_files, seconds_per_file=seconds, frames_per_file=frames, bytes_per_file=file_bytes, reps=reps, units_per_file=units,
+               measure_batch_ms=ms3(batch_ms), measure_one_file_ms=ms3(one_ms), measure_one_chunk_ms=ms3(small_ms), chunk_frames=chunk_frames,
+               encode_ms={str(k): ms3(v) for k, v in enc_ms.items()}, conversion_ms=ms3(conv),
+               beside_effort12_ms=dict(first_to_last=both_ms[0], encode_end=both_ms[1], measure_end=both_ms[2]),
+               copy_to_pinned_ms=ms3(copy_ms), host_twin_16_threads_s=host_s, cells_equal_host_twin=True, file0_lufs=r0.lufs, file0_peak=r0.peak)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        json.dump(res, fh, indent=1)
+    gbs = lambda ms, n=1: n * file_bytes / ms / 1e6
+    print("batch: %d files x %d frames, stereo 24-bit: %.2f MB per file, %d units (lanes) per file; every file's device cells are the CPU twin's bytes" %
+          (n_files, frames, file_bytes / 1e6, units))
+    print("file 0: %.3f LUFS, peak %.6f" % (r0.lufs, r0.peak))
+    print("(a) measure, whole batch, one call: median %.3f ms (min %.3f, max %.3f) = %.2f GB/s of PCM" % (*batch_ms, gbs(batch_ms[0], n_files)))
+    print("(b) measure, one file:              median %.3f ms (min %.3f, max %.3f) = %.2f GB/s" % (*one_ms, gbs(one_ms[0])))
+    print("(e) measure, one chunk of one file (%d frames, %d lanes): median %.3f ms (min %.3f, max %.3f)" % (chunk_frames, chunk_frames // S * CH + CH, *small_ms))
+    for eff in (0, 1, 12):
+        print("(c) encode effort %2d alone: median %.2f ms (min %.2f, max %.2f)" % (eff, *enc_ms[eff]))
+    print("(c) conversion step alone: median %.2f ms" % conv[0])
+    print("(c) measure on a second stream beside the effort-12 encode: first event to last %.2f ms (encode ends at %.2f, measure at %.2f)" % tuple(both_ms))
+    print("(d) copy to pinned host memory: median %.2f ms (min %.2f, max %.2f) = %.1f GB/s" % (*copy_ms, n_files * file_bytes / copy_ms[0] / 1e6))
+    print("(d) CPU twin on %d threads, one file per task: %.3f s" % (THREADS, host_s))
     sys.exit(0)
 enc0, bytes0, per_file0 = None, None, None
 base = 1 if effort == d.FLAC_EFFORT_LPC else 0                  # the effort this one is held against
