@@ -14,4 +14,5 @@ from ._capi import (D2DError, Engine, FileIO, Info, Params, lib, library_path, b
                     FlacMd5State, FlacMd5IO, flac_md5_init_host, flac_md5_update_host, flac_md5_final_host,
                     flac_md5_init_device, flac_md5_update_device, flac_md5_final_device,
                     LoudCell, LoudIO, LoudResult, LoudMeter, loud_coefficients, loud_measure_host, loud_measure_device,
+                    TruePeakIO, true_peak_measure_host, true_peak_measure_device,
                     FLAC_BAD_NONE, FLAC_BAD_SIZE, FLAC_BAD_HEADER, FLAC_BAD_CRC8, FLAC_BAD_CRC16, FLAC_BAD_UNSUPPORTED, FLAC_BAD_SYNTAX, FLAC_BAD_LENGTH, FLAC_BAD_SAMPLES)

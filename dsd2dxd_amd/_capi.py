@@ -110,6 +110,13 @@ class LoudIO(C.Structure):
                 ("subblocks", C.c_size_t), ("cells_out", C.c_size_t), ("next_subblock", C.c_uint64)]
 
 
+class TruePeakIO(C.Structure):
+    """d2d_tpeak_io: one file of a d2d_true_peak_measure_device / _host call; subblocks, peaks_out and next_subblock are written at return"""
+    _fields_ = [("pcm", C.c_void_p), ("frames", C.c_size_t), ("first_frame", C.c_uint64), ("first_subblock", C.c_uint64),
+                ("final", C.c_int32), ("reserved", C.c_uint32), ("peaks", C.c_void_p), ("peaks_capacity", C.c_size_t),
+                ("subblocks", C.c_size_t), ("peaks_out", C.c_size_t), ("next_subblock", C.c_uint64)]
+
+
 class LoudResult(C.Structure):
     """d2d_loud_result: integrated loudness, sample peak and the ReplayGain track gain of one stream"""
     _fields_ = [("lufs", C.c_double), ("peak", C.c_double), ("gain_db", C.c_double), ("valid", C.c_int32), ("reserved", C.c_uint32),
@@ -145,7 +152,9 @@ EXPORTS = ["d2d_create", "d2d_create_error", "d2d_destroy", "d2d_reset", "d2d_la
            "d2d_flac_md5_init_host", "d2d_flac_md5_init_device", "d2d_flac_md5_update_device", "d2d_flac_md5_final_device",
            "d2d_flac_md5_update_host", "d2d_flac_md5_final_host", "d2d_convert_stream_flac_md5",
            "d2d_loud_coefficients", "d2d_loud_measure_device", "d2d_loud_measure_host", "d2d_loud_create", "d2d_loud_add",
-           "d2d_loud_finish", "d2d_loud_destroy", "d2d_convert_stream_flac_loud"]
+           "d2d_loud_finish", "d2d_loud_destroy", "d2d_convert_stream_flac_loud",
+           "d2d_true_peak_measure_device", "d2d_true_peak_measure_host", "d2d_loud_set_true_peak", "d2d_loud_add_true_peaks",
+           "d2d_loud_true_peak"]
 
 _lib = None
 
@@ -248,6 +257,11 @@ def lib():
     L.d2d_loud_destroy.argtypes = [C.c_void_p]
     L.d2d_loud_destroy.restype = None
     L.d2d_convert_stream_flac_loud.argtypes = L.d2d_convert_stream_flac_md5.argtypes + [C.c_void_p]
+    L.d2d_true_peak_measure_device.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(TruePeakIO), C.c_uint32, C.c_void_p]
+    L.d2d_true_peak_measure_host.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(TruePeakIO)]
+    L.d2d_loud_set_true_peak.argtypes = [C.c_void_p, C.c_int]
+    L.d2d_loud_add_true_peaks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    L.d2d_loud_true_peak.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -391,14 +405,58 @@ def loud_measure_device(channels, bit_depth, rate, ios, stream=None):
     _flac_check(lib().d2d_loud_measure_device(channels, bit_depth, rate, ios, len(ios), C.c_void_p(stream or 0)))
 
 
-class LoudMeter:
-    """d2d_loud_create / _add / _finish / _destroy: the host integration of one stream's cells (gates, loudness, ReplayGain)"""
+def true_peak_measure_host(channels, bit_depth, rate, pcm, first_frame=0, first_subblock=0, final=True, capacity=None):
+    """d2d_true_peak_measure_host on a bytes-like of whole interleaved frames that begin at stream frame `first_frame`: returns
+    (peaks, io) -- peaks a float64 array of shape (rows, channels), io the TruePeakIO with the counts.  No device."""
+    import numpy as np
+    buf = _u8(pcm)
+    fb = channels * (2 if bit_depth == 16 else 4 if bit_depth == 32 else 3)
+    frames = buf.size // fb if fb else 0
+    if capacity is None:
+        capacity = (frames // max(rate // 10, 1) + 2) * max(channels, 1)
+    peaks = np.zeros(max(capacity, 1), dtype=np.float64)
+    io = TruePeakIO(buf.ctypes.data if buf.size else None, frames, first_frame, first_subblock, int(bool(final)), 0, peaks.ctypes.data, capacity, 0, 0, 0)
+    _flac_check(lib().d2d_true_peak_measure_host(channels, bit_depth, rate, C.byref(io)))
+    return peaks[:io.peaks_out].reshape(-1, channels).copy(), io
 
-    def __init__(self, channels, rate, weights=None):
+
+def true_peak_measure_device(channels, bit_depth, rate, ios, stream=None):
+    """d2d_true_peak_measure_device: ios is a ctypes array of TruePeakIO with DEVICE pcm pointers and GPU-addressable peaks;
+    asynchronous on `stream`; the counts are in ios at return"""
+    _flac_check(lib().d2d_true_peak_measure_device(channels, bit_depth, rate, ios, len(ios), C.c_void_p(stream or 0)))
+
+
+class LoudMeter:
+    """d2d_loud_create / _add / _finish / _destroy: the host integration of one stream's cells (gates, loudness, ReplayGain);
+    true_peak=True: d2d_loud_set_true_peak(h, 1) -- add_true_peaks() and true_peak() work, and Engine.convert_stream_flac(loud=)
+    measures the true peak too"""
+
+    def __init__(self, channels, rate, weights=None, true_peak=False):
         self._h = C.c_void_p()
         self.channels = channels
         w = (C.c_double * channels)(*weights) if weights is not None else None
         _flac_check(lib().d2d_loud_create(channels, rate, w, C.byref(self._h)))
+        if true_peak:
+            self.set_true_peak(True)
+
+    def set_true_peak(self, on):
+        """d2d_loud_set_true_peak: before the first add"""
+        _flac_check(lib().d2d_loud_set_true_peak(self._h, int(bool(on))))
+
+    def add_true_peaks(self, peaks, whole_subblocks=None, has_partial=False):
+        """peaks: a float64 array of (rows, channels); every row is a whole sub-block unless has_partial, which makes the last one partial"""
+        import numpy as np
+        a = np.ascontiguousarray(peaks, dtype=np.float64)
+        rows = a.size // self.channels
+        if whole_subblocks is None:
+            whole_subblocks = rows - (1 if has_partial else 0)
+        _flac_check(lib().d2d_loud_add_true_peaks(self._h, a.ctypes.data if a.size else None, whole_subblocks, int(bool(has_partial))))
+
+    def true_peak(self):
+        """d2d_loud_true_peak: max(sample peak, largest true-peak value added)"""
+        out = C.c_double()
+        _flac_check(lib().d2d_loud_true_peak(self._h, C.byref(out)))
+        return out.value
 
     def add(self, cells, whole_subblocks=None, has_partial=False):
         """cells: a float64 array of (rows, channels, 2); every row is a whole sub-block unless has_partial, which makes the last one partial"""

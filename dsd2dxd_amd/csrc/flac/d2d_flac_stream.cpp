@@ -1,5 +1,5 @@
 // d2d_flac_stream.cpp -- d2d_convert_stream_flac: a whole DSD stream to FLAC frames through the public calls (d2d_translate_batch_device,
-// d2d_flac_encode_device_effort, for the verified twin d2d_flac_verify_device, for the hashing one d2d_flac_md5_*_device, for the measuring one d2d_loud_measure_device) and HIP's host API.  Host code: it launches no kernel.
+// d2d_flac_encode_device_effort, for the verified twin d2d_flac_verify_device, for the hashing one d2d_flac_md5_*_device, for the measuring one d2d_loud_measure_device and d2d_true_peak_measure_device) and HIP's host API.  Host code: it launches no kernel.
 #include <hip/hip_runtime_api.h>
 #include <string.h>
 
@@ -114,11 +114,15 @@ static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effor
     if (loud && d2dloud::meter_channels(loud) != ch) return fail(D2D_ERR_PARAM, "the meter was created for another channel count than the engine's");
     const uint32_t rate = loud ? d2dloud::meter_rate(loud) : 0;
     const size_t S = rate / 10, l_cap = 3 * S + chunk_frames, l_rows = S ? l_cap / S + 2 : 0;
-    DevBuf d_loud[2]; PinBuf h_cells;
+    DevBuf d_loud[2]; PinBuf h_cells, h_peaks;
     if (loud) {
         FLAC_HIP(d_loud[0].alloc(l_cap * fb), "hipMalloc"); FLAC_HIP(d_loud[1].alloc(l_cap * fb), "hipMalloc");
         FLAC_HIP(h_cells.alloc(l_rows * ch * sizeof(d2d_loud_cell)), "hipHostMalloc");
     }
+    // a meter whose true peak was switched on (d2d_loud_set_true_peak): the same rows once more, as doubles, over the same buffer --
+    // what holds the pre-roll holds the eleven frames of history
+    const bool tpeak = loud && d2dloud::meter_true_peak(loud);
+    if (tpeak) FLAC_HIP(h_peaks.alloc(l_rows * ch * sizeof(double)), "hipHostMalloc");
     uint64_t l_first = 0, l_next = 0;  // the stream position of d_loud[l_cur]'s first frame; the next sub-block to measure
     size_t l_have = 0;                 // frames in d_loud[l_cur]
     int l_cur = 0;
@@ -159,6 +163,13 @@ static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effor
             const int lrc = d2d_loud_measure_device(ch, bit_depth, rate, &lio, 1, st.s);
             if (lrc != D2D_OK) return lrc;
         }
+        d2d_tpeak_io pio{};
+        if (tpeak) {
+            pio.pcm = lio.pcm; pio.frames = lio.frames; pio.first_frame = lio.first_frame; pio.first_subblock = lio.first_subblock; pio.final = lio.final;
+            pio.peaks = (double*)h_peaks.p; pio.peaks_capacity = l_rows * ch; pio.next_subblock = l_next;
+            const int prc = d2d_true_peak_measure_device(ch, bit_depth, rate, &pio, 1, st.s);
+            if (prc != D2D_OK) return prc;
+        }
         d2d_flac_io fio{};
         fio.pcm = d_pcm.p; fio.frames = carry + nf; fio.first_block = (uint32_t)stats->blocks; fio.final = next == 0;
         fio.out = d_out.p; fio.out_capacity_bytes = d_out.bytes; fio.result = res;
@@ -182,6 +193,10 @@ static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effor
         if (loud) {                                                   // the cells came with the result
             const int lrc = d2d_loud_add(loud, lio.cells, lio.subblocks, lio.cells_out > lio.subblocks * ch);
             if (lrc != D2D_OK) return lrc;
+            if (tpeak) {
+                const int prc = d2d_loud_add_true_peaks(loud, pio.peaks, pio.subblocks, pio.peaks_out > pio.subblocks * ch);
+                if (prc != D2D_OK) return prc;
+            }
             l_next = lio.next_subblock;
             const uint64_t keep_from = (l_next > 2 ? l_next - 2 : 0) * (uint64_t)S;     // the pre-roll of the next sub-block
             const size_t drop = (size_t)(keep_from - l_first);

@@ -1,7 +1,7 @@
 // dsd2dxd_amd -- a small driver over include/rdsd2pcm.hpp with the reference CLI's flags
 // (/root/reference/src/main.rs:40-133) for the conversion-relevant subset, plus:
 //   probe  <file>...      print what the container readers see, as JSON (no GPU needed)
-//   levels [opts] files   peak dBFS per file and overall (src/bin/dsd_levels/main.rs); --loudness adds each file's integrated loudness
+//   levels [opts] files   peak dBFS per file and overall (src/bin/dsd_levels/main.rs); --loudness adds each file's integrated loudness, --true-peak its true peak
 //   -t S                  (convert and levels) not a reference letter: the 48 kHz multiples in two stages, D2D_FILTER_EQUIRIPPLE_CASCADE
 //   tags [-a RATE] <file>...   the source's ID3v2 tag as the converted file would carry it, as JSON
 //                         (text frames under their Vorbis names; -a applies the album suffix; no GPU needed)
@@ -185,7 +185,7 @@ int main(int argc, char** argv) {
     std::string out_dir; bool have_out_dir = false;
     size_t channels = 2, bit_depth = 24; char fmt = 'I', filt = 'E', endian = 'M', dither = 0, output = 'S';
     uint32_t block = 4096, rate = 352800, inrate = 1; double level = 0.0; bool append = false, recurse = false, quiet = false;
-    int device = 0; unsigned long long seed = 0; uint32_t tap_bits = 0; bool gpu_flac = false, flac_verify = false, flac_md5 = false, replaygain = false, loudness = false; int flac_effort = 0;
+    int device = 0; unsigned long long seed = 0; uint32_t tap_bits = 0; bool gpu_flac = false, flac_verify = false, flac_md5 = false, replaygain = false, loudness = false, true_peak = false; int flac_effort = 0;
     std::vector<std::string> files;
     for (; ai < argc; ++ai) {
         std::string a = argv[ai];
@@ -216,7 +216,12 @@ int main(int argc, char** argv) {
         else if (a == "--flac-md5") flac_md5 = true;               // --gpu-flac -o f only: hash the samples on the GPU and fill in STREAMINFO's MD5 (Rdsd2Pcm::set_flac_md5)
         else if (a == "--replaygain") replaygain = true;           // -o f only, with or without --gpu-flac: measure BS.1770 loudness and the sample peak and write the REPLAYGAIN_* fields (Rdsd2Pcm::set_replaygain)
         else if (a == "--loudness") loudness = true;               // levels only: integrated loudness behind each file's peak (Rdsd2Pcm::set_loudness)
+        else if (a == "--true-peak") true_peak = true;             // convert with --replaygain: REPLAYGAIN_TRACK_PEAK is the true peak; levels: each file's true peak in dBTP (Rdsd2Pcm::set_true_peak)
         else files.push_back(a);
+    }
+    if (true_peak && !levels && !replaygain) {
+        fprintf(stderr, "ERROR: --true-peak writes REPLAYGAIN_TRACK_PEAK as a true peak: on a conversion it needs --replaygain\n");
+        return 2;
     }
     if (replaygain && (levels || tolower(output) != 'f')) {
         fprintf(stderr, "ERROR: --replaygain writes its tags into FLAC files only: it needs -o f\n");
@@ -264,18 +269,20 @@ int main(int argc, char** argv) {
                 // (the reference's level check is always the equiripple filter, whatever -t says; -t S chooses which of its two definitions)
                 Rdsd2Pcm lib = Rdsd2Pcm::new_level_check(rate, ip, ft, en, channels, block, inrate,
                                                          fl == FilterType::EquirippleCascade ? fl : FilterType::Equiripple);
-                lib.set_device(device); lib.set_loudness(loudness);
+                lib.set_device(device); lib.set_loudness(loudness); lib.set_true_peak(true_peak);
                 float db = lib.check_level(CANCEL_FLAG);
-                if (!loudness) printf("%s: %.4f dBFS\n", lib.file_name().c_str(), db);
-                else if (lib.loudness_valid()) printf("%s: %.4f dBFS, %.2f LUFS\n", lib.file_name().c_str(), db, lib.loudness_lufs());
-                else printf("%s: %.4f dBFS, -inf LUFS\n", lib.file_name().c_str(), db);
+                if (!loudness) printf("%s: %.4f dBFS", lib.file_name().c_str(), db);
+                else if (lib.loudness_valid()) printf("%s: %.4f dBFS, %.2f LUFS", lib.file_name().c_str(), db, lib.loudness_lufs());
+                else printf("%s: %.4f dBFS, -inf LUFS", lib.file_name().c_str(), db);
+                if (true_peak) printf(", %.4f dBTP", lib.true_peak_dbtp());
+                printf("\n");
                 if (!std::isnan(db) && db > overall) overall = db;          // dsd_levels/main.rs:184-202 skips NaN
                 continue;
             }
             Rdsd2Pcm lib = (!is_stdin && DsdFileFormat::from(path).is_container())
                                ? Rdsd2Pcm::from_container(bit_depth, ot, level, rate, od, dt, fl, append, ".", path)
                                : Rdsd2Pcm::create(bit_depth, ot, level, rate, od, dt, ft, en, inrate, block, channels, fl, append, ".", ip);
-            lib.set_device(device); lib.set_seed(seed); lib.set_tap_bits(tap_bits); lib.set_gpu_flac(gpu_flac); lib.set_flac_effort(flac_effort); lib.set_flac_verify(flac_verify); lib.set_flac_md5(flac_md5); lib.set_replaygain(replaygain);
+            lib.set_device(device); lib.set_seed(seed); lib.set_tap_bits(tap_bits); lib.set_gpu_flac(gpu_flac); lib.set_flac_effort(flac_effort); lib.set_flac_verify(flac_verify); lib.set_flac_md5(flac_md5); lib.set_replaygain(replaygain); lib.set_true_peak(true_peak);
             lib.do_conversion(CANCEL_FLAG);
             if (!quiet && !lib.warnings().empty()) fprintf(stderr, "WARNING: %s: %s\n", lib.file_name().c_str(), lib.warnings().c_str());
             if (!quiet && lib.audio_seconds() > 0)

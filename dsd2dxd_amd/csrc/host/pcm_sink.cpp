@@ -31,9 +31,10 @@ static void put_be16(uint8_t* p, uint16_t v) { p[1] = (uint8_t)v; p[0] = (uint8_
 
 // ---- loudness on the host: the feed and the tag texts ----
 
-LoudFeed::LoudFeed(uint32_t channels, uint32_t bit_depth, uint32_t rate)
-    : ch_(channels), depth_(bit_depth), rate_(rate), fb_((size_t)channels * (bit_depth == 16 ? 2 : bit_depth == 32 ? 4 : 3)) {
+LoudFeed::LoudFeed(uint32_t channels, uint32_t bit_depth, uint32_t rate, bool true_peak)
+    : ch_(channels), depth_(bit_depth), rate_(rate), fb_((size_t)channels * (bit_depth == 16 ? 2 : bit_depth == 32 ? 4 : 3)), tp_(true_peak) {
     if (d2d_loud_create(channels, rate, nullptr, &meter_) != D2D_OK) err_ = d2d_flac_error();
+    else if (tp_ && d2d_loud_set_true_peak(meter_, 1) != D2D_OK) { err_ = d2d_flac_error(); d2d_loud_destroy(meter_); meter_ = nullptr; }
 }
 LoudFeed::~LoudFeed() { d2d_loud_destroy(meter_); }
 
@@ -46,6 +47,15 @@ std::string LoudFeed::measure(bool final) {
     io.cells = cells_.data(); io.cells_capacity = cells_.size();
     if (d2d_loud_measure_host(ch_, depth_, rate_, &io) != D2D_OK) return d2d_flac_error();
     if (d2d_loud_add(meter_, cells_.data(), io.subblocks, io.cells_out > io.subblocks * ch_) != D2D_OK) return d2d_flac_error();
+    if (tp_) {                                                           // the same rows once more
+        peaks_.resize(cells_.size());
+        d2d_tpeak_io pio{};
+        pio.pcm = pcm_.data(); pio.frames = frames; pio.first_frame = first_; pio.first_subblock = next_; pio.final = final;
+        pio.peaks = peaks_.data(); pio.peaks_capacity = peaks_.size();
+        if (d2d_true_peak_measure_host(ch_, depth_, rate_, &pio) != D2D_OK) return d2d_flac_error();
+        if (d2d_loud_add_true_peaks(meter_, peaks_.data(), pio.subblocks, pio.peaks_out > pio.subblocks * ch_) != D2D_OK) return d2d_flac_error();
+        if (pio.peaks_out) tp_rows_ = true;
+    }
     next_ = io.next_subblock;
     const uint64_t keep_from = (next_ > 2 ? next_ - 2 : 0) * (uint64_t)S;      // the pre-roll of the next sub-block
     pcm_.erase(pcm_.begin(), pcm_.begin() + (size_t)(keep_from - first_) * fb_);
@@ -61,11 +71,17 @@ std::string LoudFeed::write(const uint8_t* frames, size_t bytes) {
     return "";
 }
 
-std::string LoudFeed::finish(d2d_loud_result* result) {
+std::string LoudFeed::finish(d2d_loud_result* result, double* true_peak) {
     if (!meter_) return err_;
     const std::string e = measure(true);
     if (!e.empty()) return e;
-    return d2d_loud_finish(meter_, result) == D2D_OK ? "" : d2d_flac_error();
+    if (d2d_loud_finish(meter_, result) != D2D_OK) return d2d_flac_error();
+    if (true_peak) {
+        if (!tp_) return "this feed does not measure the true peak";
+        *true_peak = result->peak;
+        if (tp_rows_ && d2d_loud_true_peak(meter_, true_peak) != D2D_OK) return d2d_flac_error();
+    }
+    return "";
 }
 
 std::string replaygain_reference_text() { return "-18.00 LUFS"; }
@@ -215,7 +231,7 @@ struct FlacSink : PcmSink {
     uint32_t effort = 0;           // flac_frame_enc.h: 0 = fixed order 2, 1 = the search, 12 = the search with LPC
     void set_flac_effort(uint32_t e) override { effort = e; }
     // ReplayGain (open_sink's `replaygain`): where the two values lie in the file, the sink's own meter, the GPU path's result
-    bool replaygain = false;
+    bool replaygain = false, true_peak = false;
     long gain_at = 0, peak_at = 0;
     std::unique_ptr<LoudFeed> feed;
     bool have_loudness = false; d2d_loud_result loudness{};
@@ -239,7 +255,7 @@ struct FlacSink : PcmSink {
             fields.push_back({"REPLAYGAIN_REFERENCE_LOUDNESS", replaygain_reference_text()});
             fields.push_back({"REPLAYGAIN_TRACK_GAIN", replaygain_gain_text(none)});
             fields.push_back({"REPLAYGAIN_TRACK_PEAK", replaygain_peak_text(none)});
-            feed.reset(new LoudFeed(ch, bits, rate));
+            feed.reset(new LoudFeed(ch, bits, rate, true_peak));
             if (!feed->error().empty()) return feed->error();
         }
         std::vector<std::vector<uint8_t>> blocks;
@@ -347,7 +363,11 @@ struct FlacSink : PcmSink {
         std::string loud_error;
         if (replaygain) {
             // the sink's own measurement when it saw the samples, the GPU's otherwise (none: the placeholders stay)
-            if (!raw_frames) { loud_error = feed->finish(&loudness); have_loudness = loud_error.empty(); }
+            if (!raw_frames) {
+                double tp = 0.0;
+                loud_error = feed->finish(&loudness, true_peak ? &tp : nullptr); have_loudness = loud_error.empty();
+                if (true_peak) loudness.peak = tp;
+            }
             if (have_loudness) {
                 const std::string g = replaygain_gain_text(loudness), p = replaygain_peak_text(loudness);
                 fseek(f, gain_at, SEEK_SET); fwrite(g.data(), 1, g.size(), f);
@@ -363,8 +383,9 @@ struct FlacSink : PcmSink {
 }  // namespace
 
 std::string open_sink(OutputType type, const std::string& path, uint32_t channels, uint32_t rate, uint32_t bit_depth, PcmSink** out,
-                      const std::vector<uint8_t>* id3, bool replaygain) {
+                      const std::vector<uint8_t>* id3, bool replaygain, bool true_peak) {
     *out = nullptr;
+    if (true_peak && !replaygain) return "the true peak is written as REPLAYGAIN_TRACK_PEAK: it needs ReplayGain tags (--replaygain)";
     if (replaygain && type != OutputType::Flac) return "ReplayGain tags are written into FLAC files only; choose -o f";
     if (type == OutputType::Stdout) { *out = new RawSink(stdout); return ""; }
     if (type == OutputType::Flac && bit_depth == 32) return "FLAC cannot hold 32-bit float; choose 16, 20 or 24 bits";
@@ -375,7 +396,7 @@ std::string open_sink(OutputType type, const std::string& path, uint32_t channel
     if (!f) return "cannot create " + path;
     std::string err;
     if (type == OutputType::Wav) { auto* s = new WavSink(); if (id3) s->id3 = *id3; s->f = f; s->ch = channels; s->rate = rate; s->bits = bit_depth; err = s->begin(); *out = s; }
-    else if (type == OutputType::Flac) { auto* s = new FlacSink(); if (id3) s->id3 = *id3; s->f = f; s->ch = channels; s->rate = rate; s->bits = bit_depth; s->replaygain = replaygain; err = s->begin(); *out = s; }
+    else if (type == OutputType::Flac) { auto* s = new FlacSink(); if (id3) s->id3 = *id3; s->f = f; s->ch = channels; s->rate = rate; s->bits = bit_depth; s->replaygain = replaygain; s->true_peak = true_peak; err = s->begin(); *out = s; }
     else { auto* s = new AiffSink(); if (id3) s->id3 = *id3; s->f = f; s->ch = channels; s->rate = rate; s->bits = bit_depth; s->aifc = type == OutputType::Aifc; err = s->begin(); *out = s; }
     return err;
 }

@@ -31,21 +31,26 @@ class PcmSink {
     virtual void set_md5(const uint8_t* /*digest: 16 bytes*/) {}
     // A FLAC sink opened with `replaygain`, raw-frame path only: the loudness measured on the GPU (d2d_convert_stream_flac_loud), before
     // close(), which writes it into the REPLAYGAIN_* fields.  Other sinks, and a FLAC sink that saw the samples itself, ignore it.
+    // (A sink opened with `true_peak` too expects d2d_loud_true_peak's value in result.peak.)
     virtual void set_loudness(const d2d_loud_result& /*result*/) {}
 };
 
 // The CPU twin of the loudness measurement behind a stream of write() calls: whole interleaved frames go in as they come, the cells
 // of every sub-block they complete go into a meter (d2d_loud_measure_host, d2d_loud_add), and only the pre-roll of the next sub-block
-// is kept.  The FLAC sink's host path and `levels --loudness` feed it.
+// is kept.  The FLAC sink's host path and `levels --loudness` feed it.  With `true_peak` the same frames also go through the CPU twin
+// of the true-peak measurement (d2d_true_peak_measure_host, d2d_loud_add_true_peaks; what holds the pre-roll holds its eleven frames
+// of history), and finish() can give d2d_loud_true_peak's value: the `levels --true-peak` and `--replaygain --true-peak` host paths.
 class LoudFeed {
    public:
-    LoudFeed(uint32_t channels, uint32_t bit_depth, uint32_t rate);
+    LoudFeed(uint32_t channels, uint32_t bit_depth, uint32_t rate, bool true_peak = false);
     ~LoudFeed();
     LoudFeed(const LoudFeed&) = delete;
     LoudFeed& operator=(const LoudFeed&) = delete;
     std::string error() const { return err_; }                           // "" or why the meter could not be created
     std::string write(const uint8_t* frames, size_t bytes);              // "" or error
-    std::string finish(d2d_loud_result* result);                         // the partial last sub-block, then the integration
+    // the partial last sub-block, then the integration; true_peak (a feed made with `true_peak` only): d2d_loud_true_peak's value, for
+    // a stream without a frame the sample peak, 0
+    std::string finish(d2d_loud_result* result, double* true_peak = nullptr);
 
    private:
     std::string measure(bool final);
@@ -54,6 +59,8 @@ class LoudFeed {
     d2d_loud* meter_ = nullptr;
     std::vector<uint8_t> pcm_;                                           // the frames from first_ on
     std::vector<d2d_loud_cell> cells_;
+    bool tp_ = false, tp_rows_ = false;                                  // true peak asked for; a row of it was added
+    std::vector<double> peaks_;
     uint64_t first_ = 0, next_ = 0;                                      // pcm_'s first frame; the next sub-block to measure
     std::string err_;
 };
@@ -69,9 +76,11 @@ std::string replaygain_peak_text(const d2d_loud_result& r);
 // `replaygain` (FLAC only; any other type is refused): the file always gets a VORBIS_COMMENT block that ends with
 // REPLAYGAIN_REFERENCE_LOUDNESS, REPLAYGAIN_TRACK_GAIN and REPLAYGAIN_TRACK_PEAK -- fields of those names the source had are dropped --
 // whose values are placeholders until close() patches them, as it patches STREAMINFO: from the sink's own LoudFeed when it saw the
-// samples, from set_loudness on the raw-frame path.
+// samples, from set_loudness on the raw-frame path.  `true_peak` (with `replaygain` only; refused without): REPLAYGAIN_TRACK_PEAK is
+// the true peak (d2d_loud_true_peak) instead of the sample peak, in the same fixed-width text, which holds values up to 9.999999 (the
+// filter's worst case is 2.03).
 std::string open_sink(OutputType type, const std::string& path, uint32_t channels, uint32_t rate, uint32_t bit_depth,
-                      PcmSink** out, const std::vector<uint8_t>* id3 = nullptr, bool replaygain = false);
+                      PcmSink** out, const std::vector<uint8_t>* id3 = nullptr, bool replaygain = false, bool true_peak = false);
 const char* output_extension(OutputType t);
 
 }  // namespace d2dhost

@@ -1,5 +1,6 @@
 #include "../../../include/rdsd2pcm.hpp"
 
+#include <math.h>
 #include <string.h>
 #include <sys/stat.h>
 
@@ -42,8 +43,9 @@ struct Rdsd2Pcm::Impl {
     DsdInfo info;
     bool level_only = false;
     size_t chunk = 4u << 20;
-    bool gpu_flac = false, flac_verify = false, flac_md5 = false, replaygain = false, loudness = false;
+    bool gpu_flac = false, flac_verify = false, flac_md5 = false, replaygain = false, loudness = false, true_peak = false;
     d2d_loud_result loud_result{};
+    double true_peak_value = 0.0;          // d2d_loud_true_peak's value of the last run with true_peak
     uint32_t flac_effort = D2D_FLAC_EFFORT_FIXED2;
     std::string out_path;
     double dsp_s = 0.0, audio_s = 0.0;
@@ -155,6 +157,8 @@ void Rdsd2Pcm::set_replaygain(bool on) { p_->replaygain = on; }
 void Rdsd2Pcm::set_loudness(bool on) { p_->loudness = on; }
 bool Rdsd2Pcm::loudness_valid() const { return p_->loud_result.valid != 0; }
 double Rdsd2Pcm::loudness_lufs() const { return p_->loud_result.lufs; }
+void Rdsd2Pcm::set_true_peak(bool on) { p_->true_peak = on; }
+double Rdsd2Pcm::true_peak_dbtp() const { return 20.0 * log10(p_->true_peak_value); }
 void Rdsd2Pcm::set_flac_effort(int effort) {
     if (effort != D2D_FLAC_EFFORT_FIXED2 && effort != D2D_FLAC_EFFORT_SEARCH && effort != D2D_FLAC_EFFORT_LPC) throw std::runtime_error("Invalid FLAC effort; must be 0, 1 or 12");
     p_->flac_effort = (uint32_t)effort;
@@ -207,6 +211,9 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
     PcmSink* sink = nullptr;
     im.out_path.clear();
     im.loud_result = d2d_loud_result{};
+    im.true_peak_value = 0.0;
+    if (!levels && im.true_peak && !im.replaygain)
+        throw std::runtime_error("The true peak of a conversion is written as REPLAYGAIN_TRACK_PEAK; it needs set_replaygain (--replaygain)");
     if (!levels && im.replaygain && im.output != OutputType::Flac)
         throw std::runtime_error("ReplayGain tags are written into FLAC files only; choose FLAC output (-o f)");
     if (!levels) {
@@ -236,7 +243,7 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
             // -p: artwork next to the sources follows them into the output tree (README.md:115-119)
             if (im.out_dir) im.artwork_copied = d2dhost::copy_artwork(dirname_of(*im.in_path), dirname_of(im.out_path));
         }
-        err = open_sink((d2dhost::OutputType)(int)im.output, im.out_path, im.prm.channels, im.prm.output_rate, im.prm.bit_depth, &sink, &tag, im.replaygain);
+        err = open_sink((d2dhost::OutputType)(int)im.output, im.out_path, im.prm.channels, im.prm.output_rate, im.prm.bit_depth, &sink, &tag, im.replaygain, im.true_peak);
         if (!err.empty()) throw std::runtime_error(err);
         sink->set_flac_effort(im.flac_effort);
     }
@@ -245,8 +252,8 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
     if (d2d_create(&im.prm, 1, &e) != D2D_OK) throw std::runtime_error(d2d_create_error());
     RunCtx ctx; ctx.src = &src; ctx.sink = sink; ctx.cancel = &cancel; ctx.sender = &sender;
     std::unique_ptr<LoudFeed> feed;
-    if (levels && im.loudness) {
-        feed.reset(new LoudFeed(im.prm.channels, im.prm.bit_depth, im.prm.output_rate));
+    if (levels && (im.loudness || im.true_peak)) {
+        feed.reset(new LoudFeed(im.prm.channels, im.prm.bit_depth, im.prm.output_rate, im.true_peak));
         if (!feed->error().empty()) { d2d_destroy(e); throw std::runtime_error(feed->error()); }
         ctx.feed = feed.get();
     }
@@ -264,12 +271,18 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
         uint8_t digest[16];
         d2d_loud* meter = nullptr;
         if (im.replaygain && d2d_loud_create(im.prm.channels, im.prm.output_rate, nullptr, &meter) != D2D_OK) rc = D2D_ERR_PARAM;
+        else if (meter && im.true_peak && d2d_loud_set_true_peak(meter, 1) != D2D_OK) { rc = D2D_ERR_PARAM; d2d_loud_destroy(meter); }
         else if (meter) {
             // measured where the PCM is, on the stream that made it
             rc = d2d_convert_stream_flac_loud(e, im.prm.bit_depth, im.flac_effort, read_cb, &ctx, write_frames_cb, &ctx, &ctx.cancel_int,
                                               progress_cb, &ctx, info.bytes_per_channel, chunk, &stats, im.flac_verify ? &check : nullptr,
                                               im.flac_md5 ? digest : nullptr, meter);
             if (!rc) rc = d2d_loud_finish(meter, &im.loud_result);
+            if (!rc && im.true_peak) {                                  // (a stream without a frame has no rows: its sample peak, 0)
+                im.true_peak_value = im.loud_result.peak;
+                if (stats.samples_per_channel) rc = d2d_loud_true_peak(meter, &im.true_peak_value);
+                im.loud_result.peak = im.true_peak_value;                // what the sink writes as REPLAYGAIN_TRACK_PEAK
+            }
             d2d_loud_destroy(meter);
         } else
         rc = im.flac_md5    ? d2d_convert_stream_flac_md5(e, im.prm.bit_depth, im.flac_effort, read_cb, &ctx, write_frames_cb, &ctx, &ctx.cancel_int,
@@ -292,7 +305,7 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
     auto total = std::chrono::steady_clock::now() - t0;
     float db = 0.f;
     if (!rc && levels) { if (d2d_peak_dbfs(e, 0, &db) != D2D_OK) msg = d2d_last_error(e); }
-    if (!rc && feed) { const std::string fe = feed->finish(&im.loud_result); if (msg.empty()) msg = fe; }
+    if (!rc && feed) { const std::string fe = feed->finish(&im.loud_result, im.true_peak ? &im.true_peak_value : nullptr); if (msg.empty()) msg = fe; }
     const uint64_t bpc = info.bytes_per_channel;
     d2d_destroy(e);
     im.dsp_s = std::chrono::duration<double>(total - ctx.io_time).count();

@@ -1,6 +1,7 @@
 // d2d_loud_host.cpp -- the host half of the loudness calls (include/dsd2dxd_amd.h, "Loudness where the PCM is"): the K-weighting
 // coefficients, d2d_loud_measure_host, the CPU twin of the GPU call on loud_meter.h, and the integration behind both twins (gates,
-// ReplayGain).  No HIP: tools and tests build this file with g++ alone.
+// ReplayGain); d2d_true_peak_measure_host, the CPU twin of the true-peak call on true_peak.h, and the meter's true-peak side.  No HIP:
+// tools and tests build this file with g++ alone.
 #include <math.h>
 #include <string.h>
 
@@ -60,12 +61,19 @@ struct d2d_loud {
     bool ended = false;                                            // a partial row was added: the stream is over
     double peak = 0.0;
     std::vector<double> power;                                     // sum_c G_c z_c of every 400 ms block, in order
+    // true peak (d2d_loud_set_true_peak): off, nothing below is touched
+    bool tp_on = false;
+    bool started = false;                                          // an add of either kind was accepted: the switch is fixed
+    uint64_t tp_subblocks = 0;
+    bool tp_ended = false;
+    double tp_peak = 0.0;                                          // the largest double added
 };
 
 namespace d2dloud {
 Coef host_coefficients(uint32_t rate) { return coefficients(rate); }
 uint32_t meter_rate(const d2d_loud* h) { return h->rate; }
 uint32_t meter_channels(const d2d_loud* h) { return h->channels; }
+bool meter_true_peak(const d2d_loud* h) { return h->tp_on; }
 }  // namespace d2dloud
 
 extern "C" {
@@ -125,6 +133,7 @@ int d2d_loud_add(d2d_loud* h, const d2d_loud_cell* cells, size_t whole_subblocks
     if (!h) return fail(D2D_ERR_PARAM, "null meter");
     if (!cells && (whole_subblocks || has_partial)) return fail(D2D_ERR_PARAM, "null cells");
     if (h->ended && (whole_subblocks || has_partial)) return fail(D2D_ERR_STATE, "cells behind the partial sub-block that ended the stream");
+    h->started = true;
     const uint32_t ch = h->channels;
     const double four_s = 4.0 * (double)(h->rate / 10);
     for (size_t r = 0; r < whole_subblocks; ++r) {
@@ -179,5 +188,74 @@ int d2d_loud_finish(const d2d_loud* h, d2d_loud_result* result) {
 }
 
 void d2d_loud_destroy(d2d_loud* h) { delete h; }
+
+int d2d_true_peak_measure_host(uint32_t channels, uint32_t bit_depth, uint32_t rate, d2d_tpeak_io* io) {
+    const int rc = check_call(channels, bit_depth, rate);
+    if (rc != D2D_OK) return rc;
+    if (!io) return fail(D2D_ERR_PARAM, "no file");
+    if (io->frames == 0) return D2D_OK;
+    Plan p;
+    const int prc = plan_tpeak_file(*io, channels, rate, 1, 1, p);
+    if (prc != D2D_OK) return prc;
+    const uint32_t sb = sample_bytes(bit_depth);
+    const size_t fb = (size_t)channels * sb;
+    const uint8_t* pcm = (const uint8_t*)io->pcm;
+    const uint64_t end = io->first_frame + io->frames;
+    std::vector<double> x(d2dtp::HISTORY + (size_t)p.S);              // a sub-block of one channel behind its history, in time order
+    for (uint64_t r = 0; r < p.rows(); ++r) {
+        const uint64_t j = io->first_subblock + r;
+        const uint64_t at = j * p.S, to = at + p.S < end ? at + p.S : end;
+        for (uint32_t c = 0; c < channels; ++c) {
+            for (uint32_t k = 0; k < d2dtp::HISTORY; ++k) {               // frames at - 11 .. at - 1: zeros before the stream
+                const uint64_t back = d2dtp::HISTORY - k;
+                x[k] = at >= back ? sample(raw_le(pcm + (size_t)(at - back - io->first_frame) * fb + (size_t)c * sb, sb), bit_depth) : 0.0;
+            }
+            const uint8_t* q = pcm + (size_t)(at - io->first_frame) * fb + (size_t)c * sb;
+            for (uint64_t f = at; f < to; ++f, q += fb) x[d2dtp::HISTORY + (size_t)(f - at)] = sample(raw_le(q, sb), bit_depth);
+            double m = 0.0;
+            for (size_t i = 0; i < (size_t)(to - at); ++i) {
+                const double y = d2dtp::frame_peak(&x[d2dtp::HISTORY + i]);
+                if (y > m) m = y;
+            }
+            const double peak = m * d2dtp::SCALE;
+            memcpy((uint8_t*)io->peaks + ((size_t)r * channels + c) * sizeof(double), &peak, sizeof(double));      // (peaks need no alignment here)
+        }
+    }
+    write_tpeak_counts(*io, p, channels);
+    return D2D_OK;
+}
+
+int d2d_loud_set_true_peak(d2d_loud* h, int on) {
+    if (!h) return fail(D2D_ERR_PARAM, "null meter");
+    if (h->started) return fail(D2D_ERR_PARAM, "true peak is switched before the meter's first add");
+    h->tp_on = on != 0;
+    return D2D_OK;
+}
+
+int d2d_loud_add_true_peaks(d2d_loud* h, const double* peaks, size_t whole_subblocks, int has_partial) {
+    if (!h) return fail(D2D_ERR_PARAM, "null meter");
+    if (!h->tp_on) return fail(D2D_ERR_PARAM, "the meter's true peak is not switched on (d2d_loud_set_true_peak)");
+    if (!peaks && (whole_subblocks || has_partial)) return fail(D2D_ERR_PARAM, "null peaks");
+    if (h->tp_ended && (whole_subblocks || has_partial)) return fail(D2D_ERR_STATE, "peaks behind the partial sub-block that ended the stream");
+    h->started = true;
+    const size_t n = (whole_subblocks + (has_partial ? 1 : 0)) * h->channels;
+    for (size_t i = 0; i < n; ++i) {
+        double v;
+        memcpy(&v, (const uint8_t*)peaks + i * sizeof(double), sizeof(double));
+        if (v > h->tp_peak) h->tp_peak = v;
+    }
+    h->tp_subblocks += whole_subblocks;
+    if (has_partial) h->tp_ended = true;
+    return D2D_OK;
+}
+
+int d2d_loud_true_peak(const d2d_loud* h, double* out) {
+    if (!h || !out) return fail(D2D_ERR_PARAM, "null meter or result");
+    if (!h->tp_on || (h->tp_subblocks == 0 && !h->tp_ended)) return fail(D2D_ERR_PARAM, "no true-peak rows were added");
+    if (h->tp_subblocks != h->subblocks || h->tp_ended != h->ended)
+        return fail(D2D_ERR_PARAM, "the true-peak rows added are not the rows of cells added");
+    *out = h->tp_peak > h->peak ? h->tp_peak : h->peak;
+    return D2D_OK;
+}
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 #pragma once
 #include "../flac/d2d_flac_internal.h"
 #include "loud_meter.h"
+#include "true_peak.h"
 
 namespace d2dloud {
 
@@ -18,6 +19,7 @@ Coef host_coefficients(uint32_t rate);
 // what a meter was created for (the stream driver measures at the meter's rate)
 uint32_t meter_rate(const d2d_loud* h);
 uint32_t meter_channels(const d2d_loud* h);
+bool meter_true_peak(const d2d_loud* h);                           // d2d_loud_set_true_peak(h, 1) was called
 
 // what one file of a call measures
 struct Plan {
@@ -35,6 +37,14 @@ inline int check_call(uint32_t channels, uint32_t bit_depth, uint32_t rate) {
     return D2D_OK;
 }
 
+// the rows of one file: p.S is set; every whole sub-block from first_subblock on that the buffer holds, and a final call's partial one
+inline void count_rows(uint64_t first_frame, uint64_t frames, uint64_t first_subblock, int32_t final, Plan& p) {
+    const uint64_t end = first_frame + frames, have = end / p.S;
+    p.whole = have > first_subblock ? have - first_subblock : 0;
+    const uint64_t measured_to = (first_subblock + p.whole) * p.S;
+    p.partial_frames = (final && end > measured_to) ? end - measured_to : 0;
+}
+
 // the checks and the counts of one file with frames > 0; align: the alignment pcm and cells must have (the device call: 16, the host twin: 1)
 inline int plan_file(const d2d_loud_io& io, uint32_t channels, uint32_t rate, uintptr_t align, Plan& p) {
     if (!io.pcm || !io.cells) return fail(D2D_ERR_PARAM, "pcm and cells must be non-null");
@@ -44,10 +54,7 @@ inline int plan_file(const d2d_loud_io& io, uint32_t channels, uint32_t rate, ui
     p.S = rate / 10;
     if (io.first_frame > start_subblock(io.first_subblock) * p.S)
         return fail(D2D_ERR_PARAM, "pcm does not hold the pre-roll: it must begin at or before frame max(0, first_subblock - 2) * rate / 10");
-    const uint64_t end = io.first_frame + io.frames, have = end / p.S;
-    p.whole = have > io.first_subblock ? have - io.first_subblock : 0;
-    const uint64_t measured_to = (io.first_subblock + p.whole) * p.S;
-    p.partial_frames = (io.final && end > measured_to) ? end - measured_to : 0;
+    count_rows(io.first_frame, io.frames, io.first_subblock, io.final, p);
     if (p.rows() * channels >= MAX_CELLS) return fail(D2D_ERR_PARAM, "more cells than one call writes; cut the call");
     if (p.rows() * channels > io.cells_capacity) return fail(D2D_ERR_CAPACITY, "cells_capacity is below the cells this call writes");
     return D2D_OK;
@@ -56,6 +63,27 @@ inline int plan_file(const d2d_loud_io& io, uint32_t channels, uint32_t rate, ui
 // the counts a successful call leaves in the record
 inline void write_counts(d2d_loud_io& io, const Plan& p, uint32_t channels) {
     io.subblocks = (size_t)p.whole; io.cells_out = (size_t)(p.rows() * channels); io.next_subblock = io.first_subblock + p.whole;
+}
+
+// plan_file's sibling for the true-peak calls: the same rows and counts; the buffer must hold eleven frames of history instead of the
+// pre-roll, and a cell is one double.  pcm_align, peaks_align: the device call 16 and 8, the host twin 1 and 1.
+inline int plan_tpeak_file(const d2d_tpeak_io& io, uint32_t channels, uint32_t rate, uintptr_t pcm_align, uintptr_t peaks_align, Plan& p) {
+    if (!io.pcm || !io.peaks) return fail(D2D_ERR_PARAM, "pcm and peaks must be non-null");
+    if (((uintptr_t)io.pcm & (pcm_align - 1)) || ((uintptr_t)io.peaks & (peaks_align - 1)))
+        return fail(D2D_ERR_PARAM, "pcm must be 16-byte aligned and peaks 8-byte aligned");
+    if (io.frames > MAX_FRAMES || io.first_frame > MAX_FRAMES * 16 || io.first_subblock > MAX_SUBBLOCK)
+        return fail(D2D_ERR_PARAM, "a stream position beyond what 64 bits of bytes hold");
+    p.S = rate / 10;
+    if (io.first_frame > d2dtp::history_start(io.first_subblock, p.S))
+        return fail(D2D_ERR_PARAM, "pcm does not hold the history: it must begin at or before frame max(0, first_subblock * rate / 10 - 11)");
+    count_rows(io.first_frame, io.frames, io.first_subblock, io.final, p);
+    if (p.rows() * channels >= MAX_CELLS) return fail(D2D_ERR_PARAM, "more cells than one call writes; cut the call");
+    if (p.rows() * channels > io.peaks_capacity) return fail(D2D_ERR_CAPACITY, "peaks_capacity is below the doubles this call writes");
+    return D2D_OK;
+}
+
+inline void write_tpeak_counts(d2d_tpeak_io& io, const Plan& p, uint32_t channels) {
+    io.subblocks = (size_t)p.whole; io.peaks_out = (size_t)(p.rows() * channels); io.next_subblock = io.first_subblock + p.whole;
 }
 
 }  // namespace d2dloud

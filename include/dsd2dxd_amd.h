@@ -31,7 +31,8 @@ extern "C" {
                              *     d2d_params.filter (d2d_params unchanged);
                              *     added under 11, nothing existing changed: the verify method, d2d_flac_verify_device_method / _host_method,
                              *     D2D_FLAC_VERIFY_*, d2d_flac_verify_stats; the d2d_flac_md5_* calls; the d2d_loud_* calls and
-                             *     d2d_convert_stream_flac_loud */
+                             *     d2d_convert_stream_flac_loud; the d2d_true_peak_measure_* calls, d2d_tpeak_io and the meter's
+                             *     d2d_loud_set_true_peak / _add_true_peaks / _true_peak */
 
 /* status codes */
 enum {
@@ -605,6 +606,50 @@ int  d2d_loud_create(uint32_t channels, uint32_t rate, const double* weights /* 
 int  d2d_loud_add(d2d_loud* h, const d2d_loud_cell* cells, size_t whole_subblocks, int has_partial);
 int  d2d_loud_finish(const d2d_loud* h, d2d_loud_result* result);
 void d2d_loud_destroy(d2d_loud* h);
+
+/* TRUE PEAK, opt-in beside the cells above: the largest magnitude of the signal oversampled four times, which the sample peak of a
+ * cell cannot see (a full-scale sine at fs/4 sampled at 45 degrees has the sample peak 0.70711 and reads 1.00956 here).  The definition
+ * is csrc/loud/true_peak.h, one source for the host twin and the kernel: four phases of twelve taps, INTEGER coefficients over 8192, the
+ * same at every rate; y_p(n) = sum over k = 0 .. 11 of C[p][k] * x(n - k) in f64, in that order, x = 0 before frame 0; the value is
+ * |y| * 2^-13.  Every product is exact and for integer input every sum is too, so no result depends on how the frames are spread over
+ * lanes or calls.  The TRUE PEAK OF A CELL (sub-block j, channel c) is the largest value over n in [j S, (j + 1) S) -- to the stream's end
+ * for the partial row -- and the four phases.  An output belongs to the sub-block of its index n: the filter's delay of about six frames
+ * is not compensated, and the eleven outputs behind a stream's last frame are dropped; hence the meter reports max(sample peak, largest
+ * cell).  Input is finite: non-finite float samples give an unspecified value.
+ *
+ * A CALL is d2d_loud_measure_device's / _host's, with one difference: `pcm` must hold eleven frames of history in front of the first
+ * sub-block asked for, not the pre-roll: first_frame <= max(0, first_subblock * S - 11).  A buffer that holds the loudness pre-roll
+ * therefore always qualifies.  The value of sub-block j, channel c is peaks[(j - first_subblock) * channels + c].  Rows, the counts
+ * (subblocks, peaks_out, next_subblock), `final`, the partial row, frames == 0 (left alone), launches of at most 64 files, the checks
+ * before anything is launched or written, D2D_ERR_PARAM / D2D_ERR_CAPACITY and d2d_flac_error() are as there; `peaks` is 8-byte aligned
+ * for the device call.  A successful call writes exactly peaks_out doubles per file and no other byte, and reads only the declared
+ * frames (tests/test_gpu_true_peak.py pins it).  d2d_true_peak_measure_host gives the same doubles bit for bit. */
+typedef struct d2d_tpeak_io {
+    const void*    pcm;                  /* DEVICE pointer, 16-byte aligned (the host twin: host memory, any alignment) */
+    size_t         frames;               /* frames in pcm */
+    uint64_t       first_frame;          /* the stream position of pcm's first frame */
+    uint64_t       first_subblock;       /* the first sub-block to measure */
+    int32_t        final;                /* non-zero: the stream ends with this buffer */
+    uint32_t       reserved;             /* 0 */
+    double*        peaks;                /* GPU-addressable (device or pinned host), 8-byte aligned */
+    size_t         peaks_capacity;       /* in doubles */
+    size_t         subblocks;            /* out: whole sub-blocks measured */
+    size_t         peaks_out;            /* out: doubles written */
+    uint64_t       next_subblock;        /* out: first_subblock + subblocks */
+} d2d_tpeak_io;
+int d2d_true_peak_measure_device(uint32_t channels, uint32_t bit_depth, uint32_t rate, d2d_tpeak_io* io, uint32_t n_files, void* hip_stream);
+int d2d_true_peak_measure_host(uint32_t channels, uint32_t bit_depth, uint32_t rate, d2d_tpeak_io* io);
+
+/* The meter's side.  d2d_loud_set_true_peak switches a meter's true peak on or off BEFORE its first d2d_loud_add /
+ * d2d_loud_add_true_peaks (afterwards: D2D_ERR_PARAM); off, a meter is what it was, and d2d_loud_finish and d2d_loud_result never
+ * change.  d2d_loud_add_true_peaks takes whole_subblocks rows of `channels` doubles and, with has_partial, one more, in stream order,
+ * independently of d2d_loud_add (a meter that was not switched on refuses: D2D_ERR_PARAM; rows behind the partial one: D2D_ERR_STATE).
+ * d2d_loud_true_peak gives max(d2d_loud_result.peak, the largest double added); D2D_ERR_PARAM unless true-peak rows were added and
+ * their whole and partial counts equal those given to d2d_loud_add.  d2d_convert_stream_flac_loud below, given a meter that was
+ * switched on, also enqueues d2d_true_peak_measure_device on the same stream over the same carried PCM and feeds the doubles in. */
+int d2d_loud_set_true_peak(d2d_loud* h, int on);
+int d2d_loud_add_true_peaks(d2d_loud* h, const double* peaks, size_t whole_subblocks, int has_partial);
+int d2d_loud_true_peak(const d2d_loud* h, double* out);
 
 /* d2d_convert_stream_flac_md5 with `md5` allowed to be NULL (not hashed) and a meter behind it: after each chunk's
  * d2d_translate_batch_device the new whole sub-blocks are measured on the same stream (at the last chunk: the partial one too); the cells

@@ -102,6 +102,13 @@ class Rdsd2Pcm {
     void set_loudness(bool on);
     bool loudness_valid() const;
     double loudness_lufs() const;
+    // off by default.  With set_replaygain: REPLAYGAIN_TRACK_PEAK carries the TRUE peak (the signal oversampled four times;
+    // include/dsd2dxd_amd.h, d2d_loud_true_peak) instead of the sample peak, measured on the GPU with set_gpu_flac and by the CPU twin
+    // otherwise: the same doubles, the same text.  A conversion with set_true_peak and without set_replaygain throws.  With check_level:
+    // the float frames of the level check go through the CPU twin, as with set_loudness, and true_peak_dbtp() has 20 log10 of the
+    // value afterwards (-inf for silence).
+    void set_true_peak(bool on);
+    double true_peak_dbtp() const;
 
     struct Impl;                              // opaque state (public only so the .cpp's helpers can name it)
 

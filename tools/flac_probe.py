@@ -30,7 +30,14 @@ Loudness cells on the device, all in one session on the batch's PCM: (a) ONE d2d
 events; (b) the same call over one file; (c) the encode call at efforts 0 / 1 / 12 beside it, and the measure call on a second stream
 beside the effort-12 encode; (d) the alternative: the batch's PCM copied to pinned host memory and measured there on 16 threads, one
 file per task, by the CPU twin d2d_loud_measure_host; (e) the CLI's single-file case: one call over one chunk (4 MiB of DSD per
-channel) of one file, a few waves whose lanes each walk 3 S frames.  Every file's device cells must be the CPU twin's bytes."""
+channel) of one file, a few waves whose lanes each walk 3 S frames.  Every file's device cells must be the CPU twin's bytes.
+
+   tools/flac_probe.py --true-peak [files] [seconds] [reps] [out.json]                          (default bench_out/true_peak_probe.json)
+True-peak doubles on the device, all in one session on the batch's PCM, each beside the loudness call measured again in the same session:
+(a) ONE d2d_true_peak_measure_device call over the whole batch; (b) over one file; (e) over one chunk of one file; a device-to-device copy
+of the same PCM, the memory floor; (c) the encode call at efforts 0 / 1 / 12, and the true-peak call on a second stream beside the
+effort-12 encode; (d) the batch's PCM copied to pinned host memory and measured there on 16 threads by the CPU twin
+d2d_true_peak_measure_host.  Every file's device doubles must be the CPU twin's bytes."""
 import ctypes as C
 import json
 import os
@@ -61,6 +68,9 @@ if md5_mode:
 loud_mode = "--loud" in argv
 if loud_mode:
     argv.remove("--loud")
+tpeak_mode = "--true-peak" in argv
+if tpeak_mode:
+    argv.remove("--true-peak")
 method_name = "auto"
 if "--method" in argv:
     at = argv.index("--method")
@@ -69,7 +79,7 @@ if "--method" in argv:
 n_files = int(argv[0]) if len(argv) > 0 else 64
 seconds = float(argv[1]) if len(argv) > 1 else 60.0
 reps = int(argv[2]) if len(argv) > 2 else 9
-out_path = argv[3] if len(argv) > 3 else os.path.join(ROOT, "bench_out", "loud_probe.json" if loud_mode else "flac_md5_probe.json" if md5_mode else "flac_verify_probe.json" if verify_mode else "flac_probe.json")
+out_path = argv[3] if len(argv) > 3 else os.path.join(ROOT, "bench_out", "true_peak_probe.json" if tpeak_mode else "loud_probe.json" if loud_mode else "flac_md5_probe.json" if md5_mode else "flac_verify_probe.json" if verify_mode else "flac_probe.json")
 blocks_in = max(1, int(round(seconds * DSD64 / 8 / 4096)))
 bpc = blocks_in * 4096
 CH, DEPTH, BS, THREADS = 2, 24, 4096, 16
@@ -306,6 +316,98 @@ if loud_mode:
         print("(c) encode effort %2d alone: median %.2f ms (min %.2f, max %.2f)" % (eff, *enc_ms[eff]))
     print("(c) conversion step alone: median %.2f ms" % conv[0])
     print("(c) measure on a second stream beside the effort-12 encode: first event to last %.2f ms (encode ends at %.2f, measure at %.2f)" % tuple(both_ms))
+    print("(d) copy to pinned host memory: median %.2f ms (min %.2f, max %.2f) = %.1f GB/s" % (*copy_ms, n_files * file_bytes / copy_ms[0] / 1e6))
+    print("(d) CPU twin on %d threads, one file per task: %.3f s" % (THREADS, host_s))
+    sys.exit(0)
+if tpeak_mode:
+    RATE, S = kw["output_rate"], kw["output_rate"] // 10
+    rows = frames // S + 1
+    peaks = torch.zeros((n_files, rows * CH), dtype=torch.float64, device=dev)
+    cells = torch.zeros((n_files, rows * CH * 2), dtype=torch.float64, device=dev)
+    file_bytes = frames * fb
+    ms3 = lambda t: dict(median=t[0], min=t[1], max=t[2])
+
+    def ios(kind, n, nframes):
+        x = (kind * n)()
+        for f in range(n):
+            x[f] = kind(pcm[f].data_ptr(), nframes, 0, 0, 1, 0, (peaks if kind is d.TruePeakIO else cells)[f].data_ptr(), rows * CH, 0, 0, 0)
+        return x
+
+    chunk_frames = min(frames, (4 << 20) * 8 // 32)                     # what 4 MiB of DSD64 per channel make at 88.2 kHz
+    pio, pone, psmall = ios(d.TruePeakIO, n_files, frames), ios(d.TruePeakIO, 1, frames), ios(d.TruePeakIO, 1, chunk_frames)
+    lio, lone, lsmall = ios(d.LoudIO, n_files, frames), ios(d.LoudIO, 1, frames), ios(d.LoudIO, 1, chunk_frames)
+    # (a), (b), (e): the true-peak call and, in the same session, the loudness call it accompanies
+    tp_batch = timed(lambda: d.true_peak_measure_device(CH, DEPTH, RATE, pio, stream))
+    got = peaks.cpu().numpy().copy()
+    tp_one = timed(lambda: d.true_peak_measure_device(CH, DEPTH, RATE, pone, stream))
+    tp_small = timed(lambda: d.true_peak_measure_device(CH, DEPTH, RATE, psmall, stream))
+    ld_batch = timed(lambda: d.loud_measure_device(CH, DEPTH, RATE, lio, stream))
+    ld_one = timed(lambda: d.loud_measure_device(CH, DEPTH, RATE, lone, stream))
+    ld_small = timed(lambda: d.loud_measure_device(CH, DEPTH, RATE, lsmall, stream))
+    # the memory floor: the same PCM copied device to device (it reads and writes: twice the traffic of a call that only reads)
+    twin_pcm = torch.empty_like(pcm)
+    d2d_ms = timed(lambda: twin_pcm.copy_(pcm))
+    # (c)
+    enc_ms = {eff: timed(lambda: d.flac_encode_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), stream, effort=eff)) for eff in (0, 1, 12)}
+    s_enc, s_tp = torch.cuda.Stream(), torch.cuda.Stream()
+
+    def beside():
+        ms = []
+        for i in range(3 + reps):
+            torch.cuda.synchronize()
+            a, b1, b2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            a.record()
+            s_enc.wait_event(a)
+            s_tp.wait_event(a)
+            d.true_peak_measure_device(CH, DEPTH, RATE, pio, s_tp.cuda_stream)
+            d.flac_encode_device(CH, DEPTH, fio, ws.data_ptr(), ws.numel(), s_enc.cuda_stream, effort=12)
+            b1.record(s_enc)
+            b2.record(s_tp)
+            torch.cuda.synchronize()
+            if i >= 3:
+                ms.append((max(a.elapsed_time(b1), a.elapsed_time(b2)), a.elapsed_time(b1), a.elapsed_time(b2)))
+        return [statistics.median(m[k] for m in ms) for k in range(3)]
+
+    both_ms = beside()
+    # (d)
+    pinned = torch.empty((n_files, file_bytes), dtype=torch.uint8).pin_memory()
+    copy_ms = timed(lambda: [pinned[f].copy_(pcm[f, :file_bytes], non_blocking=True) for f in range(n_files)])
+    host_pcm = pinned.numpy()
+
+    def twin(f):
+        p, io = d.true_peak_measure_host(CH, DEPTH, RATE, host_pcm[f])
+        return p.tobytes()
+
+    with ThreadPoolExecutor(THREADS) as pool:
+        t0 = time.perf_counter()
+        want = list(pool.map(twin, range(n_files)))
+        host_s = time.perf_counter() - t0
+    n_out = int(pio[0].peaks_out)
+    bad = [f for f in range(n_files) if got[f, :n_out].tobytes() != want[f]]
+    assert not bad, "the device doubles of files %s are not the CPU twin's bytes" % bad
+    sample0 = float(d.loud_measure_host(CH, DEPTH, RATE, host_pcm[0])[0][:, :, 1].max())
+    res = dict(files=n_files, seconds_per_file=seconds, frames_per_file=frames, bytes_per_file=file_bytes, reps=reps, rows_per_file=n_out // CH,
+               true_peak_batch_ms=ms3(tp_batch), true_peak_one_file_ms=ms3(tp_one), true_peak_one_chunk_ms=ms3(tp_small), chunk_frames=chunk_frames,
+               loudness_batch_ms=ms3(ld_batch), loudness_one_file_ms=ms3(ld_one), loudness_one_chunk_ms=ms3(ld_small),
+               device_to_device_copy_ms=ms3(d2d_ms), encode_ms={str(k): ms3(v) for k, v in enc_ms.items()}, conversion_ms=ms3(conv),
+               beside_effort12_ms=dict(first_to_last=both_ms[0], encode_end=both_ms[1], measure_end=both_ms[2]),
+               copy_to_pinned_ms=ms3(copy_ms), host_twin_16_threads_s=host_s, doubles_equal_host_twin=True,
+               file0_true_peak=float(got[0, :n_out].max()), file0_sample_peak=sample0)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        json.dump(res, fh, indent=1)
+    gbs = lambda ms, n=1: n * file_bytes / ms / 1e6
+    print("batch: %d files x %d frames, stereo 24-bit: %.2f MB per file, %d rows (workgroups) per file; every file's device doubles are the CPU twin's bytes" %
+          (n_files, frames, file_bytes / 1e6, n_out // CH))
+    print("file 0: true peak %.6f, sample peak %.6f" % (res["file0_true_peak"], sample0))
+    for name, tp, ld in (("(a) whole batch, one call", tp_batch, ld_batch), ("(b) one file", tp_one, ld_one), ("(e) one chunk of one file (%d frames)" % chunk_frames, tp_small, ld_small)):
+        print("%s: true peak median %.3f ms (min %.3f, max %.3f); loudness median %.3f ms (min %.3f, max %.3f); true peak / loudness %.3f" % (name, *tp, *ld, tp[0] / ld[0]))
+    print("(a) true peak over the batch = %.1f GB/s of PCM read; device-to-device copy of the same PCM: median %.3f ms (min %.3f, max %.3f) = %.1f GB/s read + as much written" %
+          (gbs(tp_batch[0], n_files), *d2d_ms, n_files * pcm.shape[1] / d2d_ms[0] / 1e6))
+    for eff in (0, 1, 12):
+        print("(c) encode effort %2d alone: median %.2f ms (min %.2f, max %.2f); true peak / encode %.3f" % (eff, *enc_ms[eff], tp_batch[0] / enc_ms[eff][0]))
+    print("(c) conversion step alone: median %.2f ms" % conv[0])
+    print("(c) true peak on a second stream beside the effort-12 encode: first event to last %.2f ms (encode ends at %.2f, true peak at %.2f)" % tuple(both_ms))
     print("(d) copy to pinned host memory: median %.2f ms (min %.2f, max %.2f) = %.1f GB/s" % (*copy_ms, n_files * file_bytes / copy_ms[0] / 1e6))
     print("(d) CPU twin on %d threads, one file per task: %.3f s" % (THREADS, host_s))
     sys.exit(0)
