@@ -8,6 +8,7 @@ from ._capi import (D2DError, Engine, FileIO, Info, Params, lib, library_path, b
                     KERNEL_AUTO, KERNEL_LUT, KERNEL_MFMA,
                     FILTER_EQUIRIPPLE, FILTER_XLD, FILTER_DSD2PCM, FILTER_CHEBYSHEV, FILTER_EQUIRIPPLE_CASCADE,
                     DBG_NO_MX, DBG_NO_GAINQ, DBG_NO_COOP, DBG_HOST_STAGED, DBG_NO_PIPE, DBG_MFMA_V1, DBG_NO_INTQ, DBG_NS_GENERAL, DBG_TAPS32_2PASS, dbg_waves,
+                    DBG_NO_DITHER_TABLE, DITHER_TABLE_MIN_FILES,
                     FLAC_BLOCK, FLAC_EFFORT_FIXED2, FLAC_EFFORT_SEARCH, FLAC_EFFORT_LPC, FlacIO, FlacResult, FlacStreamStats, flac_bound_bytes, flac_workspace_bytes, flac_encode_host, flac_encode_device,
                     FlacCheck, flac_decode_host, flac_verify_host, flac_verify_device, ERR_VERIFY, FLAC_NO_BAD_BLOCK,
                     FlacVerifyStats, FLAC_VERIFY_AUTO, FLAC_VERIFY_SERIAL, FLAC_VERIFY_COOP,

@@ -11,6 +11,9 @@ FILTER_EQUIRIPPLE, FILTER_XLD, FILTER_DSD2PCM, FILTER_CHEBYSHEV, FILTER_EQUIRIPP
 # d2d_params.debug_flags (include/dsd2dxd_amd.h: D2D_DBG_*): diagnostic dispatch switches, 0 in production
 DBG_NO_MX, DBG_NO_GAINQ, DBG_NO_COOP, DBG_HOST_STAGED, DBG_NO_PIPE, DBG_MFMA_V1, DBG_NO_INTQ, DBG_NS_GENERAL = (1 << i for i in range(8))
 DBG_TAPS32_2PASS = 1 << 16
+DBG_NO_DITHER_TABLE = 1 << 17
+# files a call needs at one output index before it hashes its dither words into a table (d2d_engine.cpp: kDitherTableMinFiles)
+DITHER_TABLE_MIN_FILES = 48
 
 
 def dbg_waves(n):
@@ -154,7 +157,7 @@ EXPORTS = ["d2d_create", "d2d_create_error", "d2d_destroy", "d2d_reset", "d2d_la
            "d2d_loud_coefficients", "d2d_loud_measure_device", "d2d_loud_measure_host", "d2d_loud_create", "d2d_loud_add",
            "d2d_loud_finish", "d2d_loud_destroy", "d2d_convert_stream_flac_loud",
            "d2d_true_peak_measure_device", "d2d_true_peak_measure_host", "d2d_loud_set_true_peak", "d2d_loud_add_true_peaks",
-           "d2d_loud_true_peak"]
+           "d2d_loud_true_peak", "d2d_dither_table_calls"]
 
 _lib = None
 
@@ -203,6 +206,9 @@ def lib():
     L.d2d_get_info.argtypes = [C.c_void_p, C.POINTER(Info)]
     L.d2d_kernel_name.argtypes = [C.c_void_p]
     L.d2d_kernel_name.restype = C.c_char_p
+    if hasattr(L, "d2d_dither_table_calls"):      # (a D2D_AMD_LIB build of an older tree lacks it; the shipped library is held to EXPORTS by the tests)
+        L.d2d_dither_table_calls.argtypes = [C.c_void_p]
+        L.d2d_dither_table_calls.restype = C.c_uint64
     L.d2d_profile_enable.argtypes = [C.c_void_p, C.c_int]
     L.d2d_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.d2d_profile_read_all.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
@@ -543,6 +549,10 @@ class Engine:
 
     def kernel_name(self):
         return lib().d2d_kernel_name(self._h).decode()
+
+    def dither_table_calls(self):
+        """calls so far whose files read their dither words from the per-call table (d2d_dither_table_calls)"""
+        return lib().d2d_dither_table_calls(self._h)
 
     def reset(self):
         self._check(lib().d2d_reset(self._h))

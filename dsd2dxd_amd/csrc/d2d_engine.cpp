@@ -179,6 +179,9 @@ struct d2d_engine {
     Buf<uint8_t> d_in, d_out;
     // planar copies of byte-interleaved inputs (one slice per file), see d2d_deinterleave_kernel
     Buf<uint8_t> d_planar;
+    // the dither words of a call whose files all start at the same output index, hashed once for all of them: [C][stride] (dither_table_serves)
+    Buf<uint32_t> d_dither;
+    uint64_t dither_table_calls = 0;      // calls that used it
     // route.fine (tap_bits = 32 in two passes): the second half of the scratch, of the job table and the residual table belong to the second pass
     std::vector<int32_t> lo_half;
     d2d_filter_def lo_def{};
@@ -557,8 +560,46 @@ static int plan_call(d2d_engine* e, d2d_file_io* io, const bool prime, CallPlan&
     return D2D_OK;
 }
 
-// Buffers: what the call's sizes ask of the scratch, the cascade's f64 line and the planar copy.  Each waits on the call's stream.
+// A batch started together asks every file for the same dither words: the word depends on the seed, the channel and the output index, not on
+// the file.  Files from this count on at one index share a table of the call's words (d2d_dither_words_kernel) instead of hashing each their
+// own inside the FIR kernel; below it the fill kernel and the reads cost more than the hashes (measured at 1 to 64 files of the bench's length:
+// the table wins every round from 48 on, profiles/dither_table_check.md).
+#ifndef D2D_DITHER_TABLE_MIN_FILES
+#define D2D_DITHER_TABLE_MIN_FILES 48    // (-DD2D_DITHER_TABLE_MIN_FILES=1: the A/B build the threshold was measured with)
+#endif
+constexpr uint32_t kDitherTableMinFiles = D2D_DITHER_TABLE_MIN_FILES;
+// words per channel: the call's longest file in whole wave-tiles (a partial tile's lanes read past its outputs and drop what they read)
+static uint32_t dither_table_stride(const d2d_engine* e, const CallPlan& pl) {
+    const uint32_t tile = std::max<uint32_t>(e->launch.fir.tile, 1u);
+    return (((pl.max_nx + tile - 1u) / tile) * tile + 1023u) & ~1023u;
+}
+
+// Does this call's FIR launch read its dither words from the table?  Decided per call: the launch is a resident stereo frame flavour of the fp6
+// kernel with a dither at unit gain (what compiles the reading form: d2d_mx.h, mx_dither_table), and the files that produce outputs, at least kDitherTableMinFiles,
+// all start at the same index.  first_file: one of them, whose job rows hold the keys and the index.
+static bool dither_table_serves(const d2d_engine* e, const CallPlan& pl, const bool prime, uint32_t* first_file) {
+    const FirLaunch& l = e->launch.fir;
+    if (prime || e->poly || pl.mono2 || !pl.run_fir || pl.max_nx == 0 || (e->p.debug_flags & D2D_DBG_NO_DITHER_TABLE)) return false;
+    if (l.family != FIR_MX || l.unit < 0 || e->C != 2 || l.m.f.coop || l.m.f.mono2) return false;
+    const int MB = l.t[0], NT = l.t[1], KIND = l.t[3], SBY = l.t[4], NPR = l.t[5], ND = l.t[6];
+    if (!mx_dither_table(MB, NT, KIND, SBY, NPR, ND)) return false;
+    uint32_t active = 0;
+    uint64_t n0 = 0;
+    for (uint32_t f = 0; f < e->n_files; ++f) {
+        const uint64_t nfir = e->files[f].nfir;
+        if (pl.files[f].nfir1 == nfir) continue;
+        if (active == 0) { n0 = nfir; *first_file = f; }
+        else if (nfir != n0) return false;
+        ++active;
+    }
+    return active >= kDitherTableMinFiles;
+}
+
+// Buffers: what the call's sizes ask of the scratch, the cascade's f64 line, the planar copy and the dither words.  Each waits on the call's stream.
 static int reserve_call_buffers(d2d_engine* e, const CallPlan& pl, hipStream_t s, const bool prime) {
+    uint32_t first_file = 0;
+    if (dither_table_serves(e, pl, prime, &first_file))
+        HIPCHK(e, e->d_dither.reserve(sizeof(uint32_t) * e->C * dither_table_stride(e, pl), wait_stream(s)));
     if (e->cascade() || e->noise_shape || e->route.fine) {
         int rc = grow_scratch(e, (size_t)e->xs_hist + (e->poly ? pl.max_frames : pl.max_nx), s);
         if (rc) return rc;
@@ -648,11 +689,23 @@ static int launch_call(d2d_engine* e, const CallPlan& pl, hipStream_t s, const b
     EventPairs::Pair* ps = nullptr;
     if (e->profiling && (max_nx || (prime && pl.max_L))) HIPCHK(e, e->step.open(s, &ps));
     if (e->route.deinterleave) HIPCHK(e, launch_deinterleave(e->d_jobs, n_files, e->Cin, e->C, pl.max_L, s));
+    // the call's dither words, once for all its files: inside the step bracket, in front of the FIR bracket, which stays the kernel alone
+    uint32_t dt_file = 0;
+    const bool dtab = dither_table_serves(e, pl, prime, &dt_file);
+    const uint32_t dt_stride = dither_table_stride(e, pl);
+    if (dtab) HIPCHK(e, launch_dither_words(e->d_jobs, dt_file * e->C, e->C, max_nx, e->d_dither, dt_stride, s));
 
     EventPairs::Pair* pe = nullptr;
     if (e->profiling && max_nx) HIPCHK(e, e->prof.open(s, &pe));
     {   // (the composed polyphase pass makes the frames themselves; the mono pair converts the two halves of a call side by side)
-        int rc = e->poly ? launch_fir_pass(e, l.fir, max_frames, s) : pl.mono2 ? launch_fir_pass(e, l.fir_m2, max_nx / 2, s) : launch_fir_pass(e, l.fir, max_nx, s);
+        int rc;
+        if (dtab) {
+            FirLaunch f = l.fir;                  // the plan's launch with this call's table
+            f.m.f.dither_words = e->d_dither; f.m.f.dither_stride = dt_stride;
+            rc = launch_fir_pass(e, f, max_nx, s);
+            if (!rc) ++e->dither_table_calls;
+        } else
+            rc = e->poly ? launch_fir_pass(e, l.fir, max_frames, s) : pl.mono2 ? launch_fir_pass(e, l.fir_m2, max_nx / 2, s) : launch_fir_pass(e, l.fir, max_nx, s);
         if (rc) return rc;
     }
     if ((e->poly ? max_frames : max_nx) && d2d_last_launched_kernel) e->launched = d2d_last_launched_kernel;
@@ -1135,6 +1188,8 @@ int d2d_get_info(const d2d_engine* e, d2d_info* out) {
 void d2d_debug_stamps(unsigned long long* out8) { hipDeviceSynchronize(); mfma_debug_stamps(out8); }
 void d2d_debug_stamps2(unsigned long long* out8) { hipDeviceSynchronize(); mfma2_debug_stamps(out8); }
 void d2d_debug_stamps3(unsigned long long* out8) { hipDeviceSynchronize(); mfma3_debug_stamps(out8); if (out8[3] == 0) mx_debug_stamps(out8); }
+
+uint64_t d2d_dither_table_calls(const d2d_engine* e) { return e ? e->dither_table_calls : 0; }
 
 const char* d2d_kernel_name(const d2d_engine* e) {
     if (!e) return "";

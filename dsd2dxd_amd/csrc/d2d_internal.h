@@ -81,6 +81,11 @@ struct FirArgs {
     uint32_t mono2;            // 1 (d2d_kernels_mx.hip, frames): a MONO stream served as a planar pair -- jobs 2 f, 2 f + 1 are the two halves of file f's call
                                // (equal lengths and outputs; the second's history is the end of the first, its frames follow the first's)
     Epilogue epi;
+    // (d2d_kernels_mx.hip, resident stereo frames, dithered) the raw dither words of THIS call's output indices, hashed once for every file
+    // (d2d_dither_words_kernel): word of channel c, output n0 + i at dither_words[c * dither_stride + i].  Null / 0 in the plan; the engine patches
+    // them into a call's copy of the launch when the call's files all start at the same index (d2d_engine.cpp: dither_table_serves)
+    const uint32_t* dither_words;
+    uint32_t dither_stride;
 };
 
 // the noise-shaping pass ('N' dither): one lane per (8192-output segment, channel) walks its integers in order

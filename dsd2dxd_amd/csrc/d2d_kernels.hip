@@ -533,6 +533,22 @@ __global__ void d2d_xhist_kernel(const StreamJob* jobs, uint32_t P) {
     if (threadIdx.x < P) s[threadIdx.x] = v;
 }
 
+// The dither words of one call, hashed once for all its files (FirArgs::dither_words): table[c * stride + i] = word of channel c, output
+// n0 + i, on the keys of job row job0 + c.  A lane writes four consecutive words (stride is a multiple of four); the rows' tails up to the
+// next multiple of four past nout are written too and lie inside the stride.
+__global__ __launch_bounds__(256) void d2d_dither_words_kernel(const StreamJob* jobs, uint32_t job0, uint32_t nout, uint32_t* table, uint32_t stride) {
+    const StreamJob& job = jobs[job0 + blockIdx.y];
+    const uint32_t key = job.rng_key, kstep = job.rng_kstep, lo0 = job.rng_lo0, n0 = (uint32_t)job.n0;
+    const uint32_t i = 4u * (blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= nout) return;
+    u32x4 w;
+    w.x = dither_word(n0 + i, key, kstep, lo0);
+    w.y = dither_word(n0 + i + 1u, key, kstep, lo0);
+    w.z = dither_word(n0 + i + 2u, key, kstep, lo0);
+    w.w = dither_word(n0 + i + 3u, key, kstep, lo0);
+    *reinterpret_cast<u32x4*>(table + (size_t)blockIdx.y * stride + i) = w;
+}
+
 // ---- launchers -------------------------------------------------------------------------------
 
 // (the arguments, the LDS bytes and the outputs per tile: d2d_route.cpp, lut_plan)
@@ -681,6 +697,13 @@ hipError_t launch_fine_combine(const StreamJob* jobs, uint32_t nstreams, uint32_
 hipError_t launch_history(const StreamJob* jobs, uint32_t nstreams, uint32_t C, uint32_t B, uint32_t keep, hipStream_t s) {
     if (nstreams == 0) return hipSuccess;
     hipLaunchKernelGGL(d2d_history_kernel, dim3(nstreams), dim3(256), 0, s, jobs, C, B, keep);
+    return hipGetLastError();
+}
+
+hipError_t launch_dither_words(const StreamJob* jobs, uint32_t job0, uint32_t channels, uint32_t max_nout, uint32_t* table, uint32_t stride, hipStream_t s) {
+    if (channels == 0 || max_nout == 0) return hipSuccess;
+    if ((stride & 3u) || stride < ((max_nout + 3u) & ~3u)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(d2d_dither_words_kernel, dim3((max_nout + 1023u) / 1024u, channels), dim3(256), 0, s, jobs, job0, max_nout, table, stride);
     return hipGetLastError();
 }
 

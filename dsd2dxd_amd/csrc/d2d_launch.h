@@ -101,6 +101,8 @@ hipError_t launch_noise_shape(const NoiseShapeArgs& a, hipStream_t s);
 hipError_t launch_fine_combine(const StreamJob* jobs, uint32_t nstreams, uint32_t max_nout, size_t lo_off, int64_t lo_bias, int sbits,
                                const Epilogue& epi, hipStream_t s);
 hipError_t launch_history(const StreamJob* jobs, uint32_t nstreams, uint32_t C, uint32_t B, uint32_t keep, hipStream_t s);
+// table[c * stride + i] = the dither word of channel c (of `channels`), output n0 + i, i < max_nout, on the keys of the job rows from `job0` on
+hipError_t launch_dither_words(const StreamJob* jobs, uint32_t job0, uint32_t channels, uint32_t max_nout, uint32_t* table, uint32_t stride, hipStream_t s);
 hipError_t launch_xhist(const StreamJob* jobs, uint32_t nstreams, uint32_t P, hipStream_t s);
 
 }  // namespace d2d

@@ -92,6 +92,21 @@ __host__ __device__ constexpr int mx_nres(int MB, int NT, int PH = 6) { return !
 // per wave and the 32-bit taps read them from LDS like M = 64 and M = 128.
 __host__ __device__ constexpr int mx_nres_of(int MB, int NT, int SBY, int NPR, int ND) { return SBY != 0 && NPR == 1 && ND == 5 ? mx_nres(MB, NT) : 0; }
 
+// The resident dithered stereo flavours of the integer requantiser (KIND 1, 2: units 0-3) compile a second form that reads a call's dither words
+// from a table (FirArgs::dither_words; d2d_mx_kernel.h: DT), taken by the calls whose files all start at one output index (d2d_engine.cpp:
+// dither_table_serves).  The f64 requantiser's flavours (KIND 5-7) do not: they have no registers for words requested a region ahead, and with the
+// words requested in the region that reads them a step was no faster than hashing (profiles/dither_table_check.md).  -DD2D_MX_DTAB=0 compiles the
+// form out (A/B builds).
+#ifndef D2D_MX_DTAB
+#define D2D_MX_DTAB 1
+#endif
+#ifndef D2D_MX_DTAB_AHEAD
+#define D2D_MX_DTAB_AHEAD 1 // the words are requested a region ahead of the epilogue that reads them, into two register sets; 0: in the same region, one set (measured: a third of the gain)
+#endif
+__host__ __device__ constexpr bool mx_dither_table(int MB, int NT, int KIND, int SBY, int NPR, int ND) {
+    return D2D_MX_DTAB && NPR == 1 && (KIND == 1 || KIND == 2) && mx_nres_of(MB, NT, SBY, NPR, ND) > 0;
+}
+
 // Where the fragments are resident, the chain expands a step's B operand a step or two ahead, behind an earlier MFMA (d2d_mx_kernel.h: chain).
 // -DD2D_MX_FEED=0: the resident flavours expand a step's B operand directly in front of its first MFMA, like the others (A/B builds)
 #ifndef D2D_MX_FEED

@@ -26,6 +26,7 @@ typedef int v8i __attribute__((ext_vector_type(8)));
 typedef int v6i __attribute__((ext_vector_type(6)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 typedef int32_t i32x3 __attribute__((ext_vector_type(3)));
+typedef uint32_t u32x3_a4 __attribute__((ext_vector_type(3), aligned(4)));      // a lane's run of three dither words (FirArgs::dither_words)
 
 __device__ __forceinline__ int32_t mx_lshl_add(int32_t x, uint32_t sh, int32_t y) {
     int32_t d;
@@ -64,7 +65,10 @@ __host__ __device__ constexpr uint32_t mx_pack_sel(int SBY, int o) {
 // to three partial writes: 14.0 ms against the 4.7 ms of the same samples as stereo, profiles/r04_experiments.txt item 10).
 // ND = 7 (tap_bits = 32 in ONE pass, round 4): the 32-bit taps in seven base-32 digits, four phases per group (28 of the 32 matrix rows; a lane half owns two
 // phases), v = sum q32 s as a 64-bit integer from three f32 parts, requantised by the f64 flavour's epilogue (KIND 4-7 only).
-template <int MB, int NT, int G, int KIND, int SBY, int NPR = 1, int ND = 5>
+// DT (the resident dithered flavours of the integer requantiser; a call whose files all start at one output index, FirArgs::dither_words): the fast epilogue takes its hash
+// words from the call's table, G loads of three words per (tile, channel), instead of hashing them -- eight vector instructions per sample that
+// every file of the batch would repeat.  The careful path, the tiles at a call's edges and partial tiles still hash (noise()): same words.
+template <int MB, int NT, int G, int KIND, int SBY, int NPR = 1, int ND = 5, bool DT = false>
 __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m) {
     constexpr bool WIDE = ND == 7;
     static_assert(ND == 5 || ND == 7, "five digits (24-bit taps) or seven (32-bit taps)");
@@ -91,6 +95,7 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
     constexpr int NRES = mx_nres_of(MB, NT, SBY, NPR, ND);
     constexpr bool RES = NRES > 0;
     constexpr bool FEED = D2D_MX_FEED && RES;             // the chain's B operands are expanded a step ahead (chain below)
+    static_assert(!DT || (RES && DK != 0 && NPR == 1 && !GN), "the dither table serves the resident dithered stereo flavours of the integer requantiser");
     constexpr uint32_t dbg = D2D_MX_ABL;                  // compile-time ablation mask: 1 no chain, 2 no epilogue, 4 no staging, 8 never slow, 64 no stores
     const FirArgs& a = m.f;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -491,6 +496,25 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
     };
 
     int32_t* ob = reinterpret_cast<int32_t*>(wbase + m.off_out);       // the wave's output slice [channel][TILE] (dwords)
+    // DT: the lane's words of a (tile, channel), sample PHH g + q in zw[.][g][q].  They are requested in front of the stream prefetch of the
+    // region's staging (loads return in order: waiting for them then leaves the prefetch in flight).  D2D_MX_DTAB_AHEAD: a region ahead of the
+    // epilogue that reads them, into the other of two sets (set 0: channel 0's, read by region B; set 1: channel 1's, read by the next region A).
+    // (The f64 requantiser's flavours have no room for the second set -- 24-bit frames: five spilled registers -- and do not read the table at all.)
+    constexpr bool DTA = DT && D2D_MX_DTAB_AHEAD;
+    [[maybe_unused]] u32x3_a4 zw[DTA ? 2 : 1][G];
+    if constexpr (DT) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) { zw[0][g] = u32x3_a4{0u, 0u, 0u}; if constexpr (DTA) zw[1][g] = u32x3_a4{0u, 0u, 0u}; }
+    }
+    [[maybe_unused]] auto issue_words = [&](auto sc, uint32_t tile, auto cc) {
+        if constexpr (DT) {
+            constexpr int set = decltype(sc)::value;
+            constexpr uint32_t c = decltype(cc)::value;
+            const uint32_t o = c * a.dither_stride + tile * (uint32_t)TILE + lane_fr;
+#pragma unroll
+            for (int g = 0; g < G; ++g) zw[set][g] = *reinterpret_cast<D2D_GLOBAL const u32x3_a4*>(as_global(a.dither_words) + (o + (uint32_t)(PH * g)));
+        }
+    };
     // ---- the fast epilogue of one (tile, channel), cut into jobs that ride on the steps of a chain ----
     struct Fast {
         uint32_t zb;            // hash input of the lane's first sample
@@ -509,18 +533,24 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
         f.tmn = kBias; f.tmx = kBias; f.tie = 0xFFFFu;
         f.slot = ob + c * TILE + lane_fr;
     };
+    using C0 = std::integral_constant<int, 0>;
+    using C1 = std::integral_constant<int, 1>;
     constexpr int JPS = DK == 0 ? 2 : 3;                    // jobs per sample: [hash,] recombine, finish
     constexpr int NJ = JPS * NS;                            // jobs per epilogue
     constexpr int NSLOT = NF * G;                           // MFMAs of a chain
-    auto fast_job = [&](Fast& f, const v16f (&o)[G], auto jc) {
+    auto fast_job = [&](Fast& f, const v16f (&o)[G], auto jc, [[maybe_unused]] auto sc) {
         constexpr int j = decltype(jc)::value;
         constexpr int i = j / JPS;                          // sample 0..NS-1: group i / PHH, q = i % PHH
         constexpr int t = j % JPS + (DK == 0 ? 1 : 0);      // 0 hash, 1 recombine, 2 finish
         if constexpr (t == 0) {
-            uint32_t z = f.zb + (uint32_t)(PH * (i / PHH) + (i % PHH));
-            z ^= z >> 16; z *= kC1;
-            z ^= z >> 15; z *= kC2;
-            z ^= z >> 16;
+            uint32_t z;
+            if constexpr (DT) z = zw[DTA ? decltype(sc)::value : 0][i / PHH][i % PHH];
+            else {
+                z = f.zb + (uint32_t)(PH * (i / PHH) + (i % PHH));
+                z ^= z >> 16; z *= kC1;
+                z ^= z >> 15; z *= kC2;
+                z ^= z >> 16;
+            }
             if constexpr (GN) f.T = DK == 1 ? __builtin_amdgcn_sad_u16(z, 0u, 1u) : DK == 2 ? ((z >> 15) | 1u) : z;      // lo16 + hi16 + 1; 2 hi16 + 1; the float dither's word
             else if constexpr (KIND == 1) f.T = __builtin_amdgcn_sad_u16(z, 0u, kTm);   // lo16 + hi16 - 32767, units of 2^-16 LSB
             else f.T = z >> kShR;                                                         // (2*hi16 + 1) >> (17 - F)
@@ -568,7 +598,7 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
         constexpr int k = decltype(kc)::value;
         static_for<0, NJ>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
-            if constexpr ((j * NSLOT) / NJ == k) fast_job(f, o, jc);
+            if constexpr ((j * NSLOT) / NJ == k) fast_job(f, o, jc, C0{});
         });
     };
     // RES: the draining set gives up ALL its integers in one burst at the start of a region, before the chain's first MFMA, and is dead from
@@ -594,18 +624,18 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
     // ... and the hash and finish jobs ride behind the chain's MFMAs as before, respaced: job j behind MFMA (j * NSLOT) / NJR
     constexpr int NJR = (JPS - 1) * NS;
     static_assert(NJR == (DK == 0 ? 1 : 2) * NS, "chain's NJF places the B expansions where these jobs ride");
-    auto res_job = [&](Fast& f, const vint (&vv)[NS], const v16f (&o)[G], auto jc) {
+    auto res_job = [&](Fast& f, const vint (&vv)[NS], const v16f (&o)[G], auto jc, auto sc) {
         constexpr int j = decltype(jc)::value;
         constexpr int i = j / (JPS - 1);
         constexpr bool fin = DK == 0 || (j % 2) == 1;
         if constexpr (fin) f.v = vv[i];
-        fast_job(f, o, std::integral_constant<int, i * JPS + (fin ? JPS - 1 : 0)>{});
+        fast_job(f, o, std::integral_constant<int, i * JPS + (fin ? JPS - 1 : 0)>{}, sc);
     };
-    auto res_hook = [&](Fast& f, const vint (&vv)[NS], const v16f (&o)[G], auto kc) {
+    auto res_hook = [&](Fast& f, const vint (&vv)[NS], const v16f (&o)[G], auto kc, auto sc) {
         constexpr int k = decltype(kc)::value;
         static_for<0, NJR>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
-            if constexpr ((j * NSLOT) / NJR == k) res_job(f, vv, o, jc);
+            if constexpr ((j * NSLOT) / NJR == k) res_job(f, vv, o, jc, sc);
         });
     };
     auto fast_failed = [&](const Fast& f, uint32_t tile) -> bool {
@@ -848,8 +878,6 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
 #else
     auto stamp = [](int) {};
 #endif
-    using C0 = std::integral_constant<int, 0>;
-    using C1 = std::integral_constant<int, 1>;
     // The pipelined loop over the tiles t_begin + wv + k * wstride < t_end:
     //   region A (tile t):  chain of channel 0  ||  requantise channel 1 of tile t-1; its frames leave after the next prefetch is out
     //   region B (tile t):  chain of channel 1  ||  requantise channel 0 of tile t
@@ -925,12 +953,14 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
             } else if constexpr (IL) {
                 wave_sync2();
                 il_second();
+                if constexpr (DTA) issue_words(C0{}, wt, CHA{}); else issue_words(C0{}, tp, CHP{});
                 il_issue(nxt, C0{});
                 wave_sync2();
             } else {
                 wave_sync2();
                 if (!(dbg & 4)) {
                     write_lds(C0{});
+                    if constexpr (DTA) issue_words(C0{}, wt, CHA{}); else issue_words(C0{}, tp, CHP{});
                     issue_loads(wt, CH1{}, af);
                 }
                 wave_sync2();
@@ -942,12 +972,12 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
                 fast_begin(f, tp, CHP{});
                 if constexpr (RES) {
                     if (dbg & 2) { burst(accB, vv, [] {}); chain(0u, accA, no_hook); }
-                    else if (dbg & 1) { burst(accB, vv, [] {}); static_for<0, NJR>([&](auto jc) { res_job(f, vv, accB, jc); }); for (int g = 0; g < G; ++g) accA[g] = cinit + (float)lane; }
-                    else if constexpr (FEED) chain_pre(0u, accA, [&](auto uc) { res_hook(f, vv, accB, uc); }, [&](auto&& first) { burst(accB, vv, first); });
-                    else { burst(accB, vv, [] {}); chain(0u, accA, [&](auto uc) { res_hook(f, vv, accB, uc); }); }
+                    else if (dbg & 1) { burst(accB, vv, [] {}); static_for<0, NJR>([&](auto jc) { res_job(f, vv, accB, jc, C1{}); }); for (int g = 0; g < G; ++g) accA[g] = cinit + (float)lane; }
+                    else if constexpr (FEED) chain_pre(0u, accA, [&](auto uc) { res_hook(f, vv, accB, uc, C1{}); }, [&](auto&& first) { burst(accB, vv, first); });
+                    else { burst(accB, vv, [] {}); chain(0u, accA, [&](auto uc) { res_hook(f, vv, accB, uc, C1{}); }); }
                 }
                 else if (dbg & 2) chain(0u, accA, no_hook);
-                else if (dbg & 1) { static_for<0, NJ>([&](auto jc) { fast_job(f, accB, jc); }); for (int g = 0; g < G; ++g) accA[g] = cinit + (float)lane; }
+                else if (dbg & 1) { static_for<0, NJ>([&](auto jc) { fast_job(f, accB, jc, C0{}); }); for (int g = 0; g < G; ++g) accA[g] = cinit + (float)lane; }
                 else chain(0u, accA, [&](auto uc) { fast_hook(f, accB, uc); });
                 pin(accA);                      // the chain ends HERE (or the compiler sinks its MFMAs into the blocks that use them, behind the epilogue)
                 stamp(1);
@@ -966,9 +996,11 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
             wave_sync2();
             if constexpr (IL) {
                 il_first();
+                if constexpr (DTA) issue_words(C1{}, wt, CH1{}); else issue_words(C0{}, wt, CHA{});
                 il_issue(nxt, C1{});
             } else if (!(dbg & 4) && !coop) {
                 write_lds(C1{});
+                if constexpr (DTA) issue_words(C1{}, wt, CH1{}); else issue_words(C0{}, wt, CHA{});
                 if constexpr (pp + 1 < NPR) issue_loads(wt, CHN{}, af);
                 else if (AF || more) issue_loads(nxt, C0{}, af);
             }
@@ -985,12 +1017,12 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
                 fast_begin(f, wt, CHA{});
                 if constexpr (RES) {
                     if (dbg & 2) { burst(accA, vv, [] {}); chain(1u, accB, no_hook); }
-                    else if (dbg & 1) { burst(accA, vv, [] {}); static_for<0, NJR>([&](auto jc) { res_job(f, vv, accA, jc); }); for (int g = 0; g < G; ++g) accB[g] = cinit - (float)lane; }
-                    else if constexpr (FEED) chain_pre(1u, accB, [&](auto uc) { res_hook(f, vv, accA, uc); }, [&](auto&& first) { burst(accA, vv, first); });
-                    else { burst(accA, vv, [] {}); chain(1u, accB, [&](auto uc) { res_hook(f, vv, accA, uc); }); }
+                    else if (dbg & 1) { burst(accA, vv, [] {}); static_for<0, NJR>([&](auto jc) { res_job(f, vv, accA, jc, C0{}); }); for (int g = 0; g < G; ++g) accB[g] = cinit - (float)lane; }
+                    else if constexpr (FEED) chain_pre(1u, accB, [&](auto uc) { res_hook(f, vv, accA, uc, C0{}); }, [&](auto&& first) { burst(accA, vv, first); });
+                    else { burst(accA, vv, [] {}); chain(1u, accB, [&](auto uc) { res_hook(f, vv, accA, uc, C0{}); }); }
                 }
                 else if (dbg & 2) chain(1u, accB, no_hook);
-                else if (dbg & 1) { static_for<0, NJ>([&](auto jc) { fast_job(f, accA, jc); }); for (int g = 0; g < G; ++g) accB[g] = cinit - (float)lane; }
+                else if (dbg & 1) { static_for<0, NJ>([&](auto jc) { fast_job(f, accA, jc, C0{}); }); for (int g = 0; g < G; ++g) accB[g] = cinit - (float)lane; }
                 else chain(1u, accB, [&](auto uc) { fast_hook(f, accA, uc); });
                 pin(accB);
                 stamp(1);
@@ -1010,8 +1042,9 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
             Fast f;
             fast_begin(f, pw, CHL{});
             [[maybe_unused]] vint vv[NS];
-            if constexpr (RES) { burst(accB, vv, [] {}); static_for<0, NJR>([&](auto jc) { res_job(f, vv, accB, jc); }); }
-            else static_for<0, NJ>([&](auto jc) { fast_job(f, accB, jc); });
+            if constexpr (!DTA) issue_words(C0{}, pw, CHL{});           // (ahead: the last region B asked for them)
+            if constexpr (RES) { burst(accB, vv, [] {}); static_for<0, NJR>([&](auto jc) { res_job(f, vv, accB, jc, C1{}); }); }
+            else static_for<0, NJ>([&](auto jc) { fast_job(f, accB, jc, C0{}); });
             if constexpr (SCR) { hold_acc(accB); put_samples(1, f.res); wave_sync2(); store_scr_tile(pw); wave_sync2(); }
             else {
                 if (fast_failed(f, pw)) { int32_t o[NS]; if constexpr (RES) redo_v(vv, pw, CHL{}, o); else redo_acc(accB, pw, CHL{}, o); put_samples(chl, o); } else merge_extremes(f, CHL{});
@@ -1063,7 +1096,7 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
                 pin(acc);
                 Fast f;
                 fast_begin(f, t, std::integral_constant<uint32_t, c>{});
-                static_for<0, NJ>([&](auto jc) { fast_job(f, acc, jc); });
+                static_for<0, NJ>([&](auto jc) { fast_job(f, acc, jc, C0{}); });
                 hold_acc(acc);
                 store_scr(t, c, f.res);
             });
@@ -1131,19 +1164,23 @@ __global__ __launch_bounds__(D2D_MX_THREADS) void d2d_fir_mx_kernel(Mfma2Args m)
 }
 
 // (the instantiation, its arguments and the block's LDS layout: d2d_route.cpp, mx_plan)
-template <int MB, int NT, int G, int KIND, int SBY, int NPR = 1, int ND = 5>
+// (DT: the instantiation that reads the call's dither words from the table the engine patched into its copy of the launch; same name, one kernel to a profile)
+template <int MB, int NT, int G, int KIND, int SBY, int NPR = 1, int ND = 5, bool DT = false>
 static hipError_t launch_mx_t(const FirLaunch& p, uint32_t max_nout, uint32_t nfiles, hipStream_t s) {
+    if constexpr (!DT && mx_dither_table(MB, NT, KIND, SBY, NPR, ND)) {
+        if (p.m.f.dither_words) return launch_mx_t<MB, NT, G, KIND, SBY, NPR, ND, true>(p, max_nout, nfiles, s);
+    }
     static KernelPrep prep;
     int dev = 0;
-    const void* fn = reinterpret_cast<const void*>(&d2d_fir_mx_kernel<MB, NT, G, KIND, SBY, NPR, ND>);
+    const void* fn = reinterpret_cast<const void*>(&d2d_fir_mx_kernel<MB, NT, G, KIND, SBY, NPR, ND, DT>);
     hipError_t e = prep.max_dynamic_lds(fn, 160 * 1024, &dev);
     if (e != hipSuccess) return e;
     // every wave loops over its share of the wave-tiles: launch what is resident at once
     const uint32_t nrows = nfiles * p.rows_per_file, nwt_max = (max_nout + p.tile - 1) / p.tile;
     uint32_t gx;
-    e = persistent_grid_x(&d2d_fir_mx_kernel<MB, NT, G, KIND, SBY, NPR, ND>, prep, dev, p.nwaves, p.lds, nrows, (nwt_max + p.block_tiles - 1) / p.block_tiles, &gx);
+    e = persistent_grid_x(&d2d_fir_mx_kernel<MB, NT, G, KIND, SBY, NPR, ND, DT>, prep, dev, p.nwaves, p.lds, nrows, (nwt_max + p.block_tiles - 1) / p.block_tiles, &gx);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((d2d_fir_mx_kernel<MB, NT, G, KIND, SBY, NPR, ND>), dim3(gx, nrows), dim3(64 * p.nwaves), p.lds, s, p.m);
+    hipLaunchKernelGGL((d2d_fir_mx_kernel<MB, NT, G, KIND, SBY, NPR, ND, DT>), dim3(gx, nrows), dim3(64 * p.nwaves), p.lds, s, p.m);
     d2d_last_launched_kernel = launched_name<MB, NT, G, KIND, SBY, NPR, ND>("d2d_fir_mx_kernel");     // (all seven arguments: the way rocprofv3 prints the instantiation)
     return hipGetLastError();
 }

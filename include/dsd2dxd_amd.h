@@ -32,7 +32,7 @@ extern "C" {
                              *     added under 11, nothing existing changed: the verify method, d2d_flac_verify_device_method / _host_method,
                              *     D2D_FLAC_VERIFY_*, d2d_flac_verify_stats; the d2d_flac_md5_* calls; the d2d_loud_* calls and
                              *     d2d_convert_stream_flac_loud; the d2d_true_peak_measure_* calls, d2d_tpeak_io and the meter's
-                             *     d2d_loud_set_true_peak / _add_true_peaks / _true_peak */
+                             *     d2d_loud_set_true_peak / _add_true_peaks / _true_peak; D2D_DBG_NO_DITHER_TABLE and d2d_dither_table_calls */
 
 /* status codes */
 enum {
@@ -83,7 +83,8 @@ enum {
     D2D_DBG_NO_INTQ     = 1u << 6,   /* the f64 epilogues instead of the all-integer requantisers                                           */
     D2D_DBG_NS_GENERAL  = 1u << 7,   /* the general noise-shaping kernel for stereo too                                                     */
     /* bits 8..15: waves per block of the matrix-core kernels (0 = their own choice)                                                        */
-    D2D_DBG_TAPS32_2PASS = 1u << 16  /* tap_bits = 32: the two scratch passes and the combining pass where the one-pass kernel would serve  */
+    D2D_DBG_TAPS32_2PASS = 1u << 16, /* tap_bits = 32: the two scratch passes and the combining pass where the one-pass kernel would serve  */
+    D2D_DBG_NO_DITHER_TABLE = 1u << 17 /* every file hashes its own dither words inside the FIR kernel (no per-call table, d2d_dither_table_calls) */
 };
 
 /* The conversion parameters of Rdsd2Pcm::new (src/main.rs:325-342) that concern the hot path.
@@ -686,6 +687,11 @@ typedef struct d2d_info {
 int d2d_get_info(const d2d_engine* e, d2d_info* out);
 /* Name of the device kernel that does the FIR, as rocprofv3 prints it (for bench/profiles). */
 const char* d2d_kernel_name(const d2d_engine* e);
+/* Added under ABI 11 (no existing call or structure changed).  A batch whose files all stand at the same output index asks every file
+ * for the same dither words: such a call of the fp6 x fp4 kernel's dithered stereo frames at 0 dB (16, 24 bits) hashes them once, into an engine-owned table of
+ * 4 bytes x channels x outputs of the call, and its files read them there (same bytes either way; D2D_DBG_NO_DITHER_TABLE keeps every
+ * call off the table).  The number of calls so far that used the table; 0 for a null engine. */
+uint64_t d2d_dither_table_calls(const d2d_engine* e);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 

@@ -43,7 +43,8 @@ for n in d2d_kernels d2d_kernels_rs d2d_kernels_mfma d2d_kernels_mfma2 d2d_engin
          d2d_kernels_mfma3 $(for i in $(seq 1 $((M3_UNITS - 1))); do echo d2d_m3_unit$i; done) \
          d2d_kernels_mx $(for i in $(seq 1 $((MX_UNITS - 1))); do echo d2d_mx_unit$i; done) \
          d2d_kernels_px $(for i in $(seq 1 $((PX_UNITS - 1))); do echo d2d_px_unit$i; done) \
-         flac/d2d_flac flac/d2d_flac_verify flac/d2d_flac_host flac/d2d_flac_stream \
+         flac/d2d_flac flac/d2d_flac_verify flac/d2d_flac_md5 flac/d2d_flac_host flac/d2d_flac_stream \
+         loud/d2d_loud loud/d2d_true_peak loud/d2d_loud_host \
          host/dsd_reader host/pcm_sink host/id3_tag host/rdsd2pcm host/rdsd2pcm_c; do
   if [ -f $O/$(basename $n).o ]; then OBJS="$OBJS $O/$(basename $n).o"; else OBJS="$OBJS $CS/$n.o"; fi
 done

@@ -44,7 +44,8 @@ common = {"files_per_gpu": bench["config"]["files_per_gpu"], "seconds_per_file":
 path = os.path.join(prof, "pmc_traffic.json")
 cur = json.load(open(path))
 fir = bench["config"]["kernel"]
-fir_key = next((k for k in per_kernel if k.replace("d2d::", "") == fir), None)
+# (an instantiation with a trailing bool argument -- the fp6 kernel's form that reads the dither table -- is launched under the engine's seven-argument name)
+fir_key = next((k for k in per_kernel if k.replace("d2d::", "").replace(", true>", ">").replace(", false>", ">") == fir), None)
 if fir_key:
     cur.setdefault(fir, {})[workload] = dict(per_kernel[fir_key], **common)
 cur.setdefault("step", {})[workload] = dict(common, hbm_bytes_per_launch=step_bytes, kernels=per_kernel)
