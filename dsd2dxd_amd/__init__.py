@@ -16,4 +16,6 @@ from ._capi import (D2DError, Engine, FileIO, Info, Params, lib, library_path, b
                     flac_md5_init_device, flac_md5_update_device, flac_md5_final_device,
                     LoudCell, LoudIO, LoudResult, LoudMeter, loud_coefficients, loud_measure_host, loud_measure_device,
                     TruePeakIO, true_peak_measure_host, true_peak_measure_device,
+                    Segment, PackSrc, PACK_GAVE_UP, segments_move_host, segments_move_device, segments_pack_host, segments_pack_device,
+                    StreamIO, StreamsOptions, STREAMS_VERIFY, STREAMS_MD5, loud_finish_album, loud_true_peak_album,
                     FLAC_BAD_NONE, FLAC_BAD_SIZE, FLAC_BAD_HEADER, FLAC_BAD_CRC8, FLAC_BAD_CRC16, FLAC_BAD_UNSUPPORTED, FLAC_BAD_SYNTAX, FLAC_BAD_LENGTH, FLAC_BAD_SAMPLES)

@@ -126,6 +126,16 @@ class LoudResult(C.Structure):
                 ("blocks_total", C.c_uint64), ("blocks_gated", C.c_uint64)]
 
 
+class Segment(C.Structure):
+    """d2d_segment: `bytes` bytes from src to dst (d2d_segments_move_device / _host)"""
+    _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p), ("bytes", C.c_size_t)]
+
+
+class PackSrc(C.Structure):
+    """d2d_pack_src: one source of d2d_segments_pack_device / _host; `bytes` points at the uint64 length, read where the call runs"""
+    _fields_ = [("base", C.c_void_p), ("bytes", C.c_void_p), ("max_bytes", C.c_size_t)]
+
+
 FLAC_VERIFY_AUTO, FLAC_VERIFY_SERIAL, FLAC_VERIFY_COOP = 0, 1, 2       # D2D_FLAC_VERIFY_*
 # D2D_FLAC_BAD_*
 (FLAC_BAD_NONE, FLAC_BAD_SIZE, FLAC_BAD_HEADER, FLAC_BAD_CRC8, FLAC_BAD_CRC16, FLAC_BAD_UNSUPPORTED, FLAC_BAD_SYNTAX, FLAC_BAD_LENGTH,
@@ -139,6 +149,24 @@ FLAC_EFFORT_FIXED2, FLAC_EFFORT_SEARCH, FLAC_EFFORT_LPC = 0, 1, 12      # D2D_FL
 READ_FN = C.CFUNCTYPE(C.c_long, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t)
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_float)
+
+STREAMS_VERIFY, STREAMS_MD5 = 1, 2                                      # D2D_STREAMS_*
+PACK_GAVE_UP = 0xFFFFFFFFFFFFFFFF                                       # every entry of a pack's table when a length was above its maximum
+
+
+class StreamIO(C.Structure):
+    """d2d_stream_io: one file of d2d_convert_streams_flac; stats, check and md5 are written by the call"""
+    _fields_ = [("read", READ_FN), ("read_user", C.c_void_p), ("write", WRITE_FN), ("write_user", C.c_void_p),
+                ("total_bytes_per_channel", C.c_uint64), ("loud", C.c_void_p), ("stats", FlacStreamStats), ("check", FlacCheck),
+                ("md5", C.c_uint8 * 16)]
+
+
+class StreamsOptions(C.Structure):
+    """d2d_streams_options"""
+    _fields_ = [("struct_size", C.c_uint32), ("bit_depth", C.c_uint32), ("effort", C.c_uint32), ("flags", C.c_uint32),
+                ("chunk_bytes_per_channel", C.c_size_t), ("cancel", C.POINTER(C.c_int)), ("progress", PROGRESS_FN),
+                ("progress_user", C.c_void_p), ("device_calls", C.POINTER(C.c_uint64)), ("chunks", C.POINTER(C.c_uint64))]
+
 
 EXPORTS = ["d2d_create", "d2d_create_error", "d2d_destroy", "d2d_reset", "d2d_last_error",
            "d2d_frame_bytes", "d2d_next_frames", "d2d_translate", "d2d_translate_batch_device",
@@ -157,7 +185,9 @@ EXPORTS = ["d2d_create", "d2d_create_error", "d2d_destroy", "d2d_reset", "d2d_la
            "d2d_loud_coefficients", "d2d_loud_measure_device", "d2d_loud_measure_host", "d2d_loud_create", "d2d_loud_add",
            "d2d_loud_finish", "d2d_loud_destroy", "d2d_convert_stream_flac_loud",
            "d2d_true_peak_measure_device", "d2d_true_peak_measure_host", "d2d_loud_set_true_peak", "d2d_loud_add_true_peaks",
-           "d2d_loud_true_peak", "d2d_dither_table_calls"]
+           "d2d_loud_true_peak", "d2d_dither_table_calls",
+           "d2d_segments_move_device", "d2d_segments_move_host", "d2d_segments_pack_device", "d2d_segments_pack_host",
+           "d2d_convert_streams_flac", "d2d_loud_finish_album", "d2d_loud_true_peak_album"]
 
 _lib = None
 
@@ -268,6 +298,14 @@ def lib():
     L.d2d_loud_set_true_peak.argtypes = [C.c_void_p, C.c_int]
     L.d2d_loud_add_true_peaks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     L.d2d_loud_true_peak.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    if hasattr(L, "d2d_segments_move_device"):    # (as above: a D2D_AMD_LIB build of an older tree lacks the album calls)
+        L.d2d_segments_move_device.argtypes = [C.POINTER(Segment), C.c_uint32, C.c_void_p]
+        L.d2d_segments_move_host.argtypes = [C.POINTER(Segment), C.c_uint32]
+        L.d2d_segments_pack_device.argtypes = [C.POINTER(PackSrc), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.d2d_segments_pack_host.argtypes = [C.POINTER(PackSrc), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.d2d_convert_streams_flac.argtypes = [C.c_void_p, C.POINTER(StreamIO), C.c_uint32, C.POINTER(StreamsOptions)]
+        L.d2d_loud_finish_album.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(LoudResult)]
+        L.d2d_loud_true_peak_album.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -430,6 +468,45 @@ def true_peak_measure_device(channels, bit_depth, rate, ios, stream=None):
     """d2d_true_peak_measure_device: ios is a ctypes array of TruePeakIO with DEVICE pcm pointers and GPU-addressable peaks;
     asynchronous on `stream`; the counts are in ios at return"""
     _flac_check(lib().d2d_true_peak_measure_device(channels, bit_depth, rate, ios, len(ios), C.c_void_p(stream or 0)))
+
+
+def segments_move_host(segs):
+    """d2d_segments_move_host: segs is a ctypes array of Segment with host pointers"""
+    _flac_check(lib().d2d_segments_move_host(segs, len(segs)))
+
+
+def segments_move_device(segs, stream=None):
+    """d2d_segments_move_device: segs is a ctypes array of Segment with GPU-addressable pointers; asynchronous on `stream`"""
+    _flac_check(lib().d2d_segments_move_device(segs, len(segs), C.c_void_p(stream or 0)))
+
+
+def segments_pack_host(srcs, dst_ptr, dst_capacity, offsets_ptr):
+    """d2d_segments_pack_host: srcs is a ctypes array of PackSrc; offsets_ptr holds len(srcs) + 1 uint64"""
+    _flac_check(lib().d2d_segments_pack_host(srcs, len(srcs), C.c_void_p(dst_ptr), dst_capacity, C.c_void_p(offsets_ptr)))
+
+
+def segments_pack_device(srcs, dst_ptr, dst_capacity, offsets_ptr, stream=None):
+    """d2d_segments_pack_device: as the twin, every pointer GPU-addressable, the lengths read on the device; asynchronous on `stream`"""
+    _flac_check(lib().d2d_segments_pack_device(srcs, len(srcs), C.c_void_p(dst_ptr), dst_capacity, C.c_void_p(offsets_ptr),
+                                               C.c_void_p(stream or 0)))
+
+
+def _meter_handles(meters):
+    return (C.c_void_p * len(meters))(*[m._h.value if m is not None else None for m in meters])
+
+
+def loud_finish_album(meters):
+    """d2d_loud_finish_album: the two gates over the 400 ms blocks of all LoudMeters; returns a LoudResult"""
+    r = LoudResult()
+    _flac_check(lib().d2d_loud_finish_album(_meter_handles(meters), len(meters), C.byref(r)))
+    return r
+
+
+def loud_true_peak_album(meters):
+    """d2d_loud_true_peak_album: the largest d2d_loud_true_peak of the LoudMeters"""
+    out = C.c_double()
+    _flac_check(lib().d2d_loud_true_peak_album(_meter_handles(meters), len(meters), C.byref(out)))
+    return out.value
 
 
 class LoudMeter:
@@ -737,3 +814,53 @@ class Engine:
         _flac_check(lib().d2d_convert_stream_flac_effort(self._h, self.params.bit_depth, effort, r, None, w, None, C.byref(cflag), p, None,
                                                          total_bytes_per_channel, chunk_bytes_per_channel, C.byref(stats)))
         return stats
+
+    def convert_streams_flac(self, reads, writes, totals=None, chunk_bytes_per_channel=0, cancel=None, progress=None, effort=0,
+                             verify=False, md5=False, louds=None):
+        """d2d_convert_streams_flac: the engine's n_files streams in lockstep.  reads[f](cap) -> bytes and writes[f](bytes) are file f's
+        callbacks (as convert_stream_flac's; a write may be None), louds[f] its LoudMeter or None.  Returns a dict: "stats", "checks"
+        (verify) and "md5" (md5) are lists per file, "device_calls" and "chunks" the driver's counts.  A failure raises D2DError with
+        d2d_flac_error()'s message; the exception's `ios` are the records so far."""
+        n = len(reads)
+        ios = (StreamIO * n)()
+
+        def reader(fn):
+            def _read(_u, dst, cap):
+                data = fn(cap)
+                if data is None:
+                    return -1
+                if not data:
+                    return 0
+                C.memmove(dst, data, len(data))
+                return len(data) // self.channels
+            return READ_FN(_read)
+
+        def writer(fn):
+            def _write(_u, p, k):
+                fn(C.string_at(p, k))
+                return 0
+            return WRITE_FN(_write)
+
+        for f in range(n):
+            ios[f].read = reader(reads[f])
+            if writes[f] is not None:
+                ios[f].write = writer(writes[f])
+            ios[f].total_bytes_per_channel = totals[f] if totals else 0
+            ios[f].loud = louds[f]._h if louds and louds[f] is not None else None
+        calls, chunks = C.c_uint64(), C.c_uint64()
+        cflag = cancel if cancel is not None else C.c_int(0)
+        opt = StreamsOptions(C.sizeof(StreamsOptions), self.params.bit_depth, effort, (STREAMS_VERIFY if verify else 0) | (STREAMS_MD5 if md5 else 0),
+                             chunk_bytes_per_channel, C.pointer(cflag), PROGRESS_FN(lambda _u, pct: progress(pct) if progress else None),
+                             None, C.pointer(calls), C.pointer(chunks))
+        rc = lib().d2d_convert_streams_flac(self._h, ios, n, C.byref(opt))
+        if rc:
+            err = D2DError(rc, lib().d2d_flac_error().decode())
+            err.ios = ios
+            raise err
+        out = {"stats": [ios[f].stats for f in range(n)], "device_calls": calls.value, "chunks": chunks.value}
+        if verify:
+            out["checks"] = [ios[f].check for f in range(n)]
+        if md5:
+            out["md5"] = [bytes(ios[f].md5) for f in range(n)]
+        out["_keep"] = ios
+        return out

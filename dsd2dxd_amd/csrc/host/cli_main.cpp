@@ -185,7 +185,7 @@ int main(int argc, char** argv) {
     std::string out_dir; bool have_out_dir = false;
     size_t channels = 2, bit_depth = 24; char fmt = 'I', filt = 'E', endian = 'M', dither = 0, output = 'S';
     uint32_t block = 4096, rate = 352800, inrate = 1; double level = 0.0; bool append = false, recurse = false, quiet = false;
-    int device = 0; unsigned long long seed = 0; uint32_t tap_bits = 0; bool gpu_flac = false, flac_verify = false, flac_md5 = false, replaygain = false, loudness = false, true_peak = false; int flac_effort = 0;
+    int device = 0; unsigned long long seed = 0; uint32_t tap_bits = 0; bool gpu_flac = false, flac_verify = false, flac_md5 = false, replaygain = false, loudness = false, true_peak = false, album = false; int flac_effort = 0;
     std::vector<std::string> files;
     for (; ai < argc; ++ai) {
         std::string a = argv[ai];
@@ -217,7 +217,12 @@ int main(int argc, char** argv) {
         else if (a == "--replaygain") replaygain = true;           // -o f only, with or without --gpu-flac: measure BS.1770 loudness and the sample peak and write the REPLAYGAIN_* fields (Rdsd2Pcm::set_replaygain)
         else if (a == "--loudness") loudness = true;               // levels only: integrated loudness behind each file's peak (Rdsd2Pcm::set_loudness)
         else if (a == "--true-peak") true_peak = true;             // convert with --replaygain: REPLAYGAIN_TRACK_PEAK is the true peak; levels: each file's true peak in dBTP (Rdsd2Pcm::set_true_peak)
+        else if (a == "--album") album = true;                     // convert -o f only: all inputs of the command are one album (Rdsd2Pcm::convert_album): with --gpu-flac one engine for all, with --replaygain the REPLAYGAIN_ALBUM_* fields
         else files.push_back(a);
+    }
+    if (album && (levels || tolower(output) != 'f')) {
+        fprintf(stderr, "ERROR: --album converts the inputs of the command as one album of FLAC files: it needs `convert` and -o f\n");
+        return 2;
     }
     if (true_peak && !levels && !replaygain) {
         fprintf(stderr, "ERROR: --true-peak writes REPLAYGAIN_TRACK_PEAK as a true peak: on a conversion it needs --replaygain\n");
@@ -261,6 +266,7 @@ int main(int argc, char** argv) {
         std::vector<std::string> expanded = find_dsd_files(paths, recurse);
         if (has_stdin) expanded.insert(expanded.begin(), "-");
         float overall = -INFINITY;
+        std::vector<Rdsd2Pcm> tracks;                                      // --album: every input, converted together behind the loop
         for (auto& path : expanded) {
             const bool is_stdin = path == "-";
             std::optional<std::string> od; if (have_out_dir) od = out_dir;
@@ -283,10 +289,18 @@ int main(int argc, char** argv) {
                                ? Rdsd2Pcm::from_container(bit_depth, ot, level, rate, od, dt, fl, append, ".", path)
                                : Rdsd2Pcm::create(bit_depth, ot, level, rate, od, dt, ft, en, inrate, block, channels, fl, append, ".", ip);
             lib.set_device(device); lib.set_seed(seed); lib.set_tap_bits(tap_bits); lib.set_gpu_flac(gpu_flac); lib.set_flac_effort(flac_effort); lib.set_flac_verify(flac_verify); lib.set_flac_md5(flac_md5); lib.set_replaygain(replaygain); lib.set_true_peak(true_peak);
+            if (album) { tracks.push_back(std::move(lib)); continue; }
             lib.do_conversion(CANCEL_FLAG);
             if (!quiet && !lib.warnings().empty()) fprintf(stderr, "WARNING: %s: %s\n", lib.file_name().c_str(), lib.warnings().c_str());
             if (!quiet && lib.audio_seconds() > 0)
                 fprintf(stderr, "DSP speed for %s: %.2fx\n", lib.file_name().c_str(), lib.audio_seconds() / std::max(lib.dsp_seconds(), 1e-9));
+        }
+        if (album) {
+            Rdsd2Pcm::convert_album(tracks, CANCEL_FLAG);
+            for (auto& lib : tracks)
+                if (!quiet && !lib.warnings().empty()) fprintf(stderr, "WARNING: %s: %s\n", lib.file_name().c_str(), lib.warnings().c_str());
+            if (!quiet && tracks[0].audio_seconds() > 0)
+                fprintf(stderr, "DSP speed for the album of %zu: %.2fx\n", tracks.size(), tracks[0].audio_seconds() / std::max(tracks[0].dsp_seconds(), 1e-9));
         }
         if (levels) printf("Highest peak: %.4f dBFS\n", overall);
     } catch (const std::exception& ex) {

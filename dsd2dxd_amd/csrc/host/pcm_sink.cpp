@@ -71,9 +71,16 @@ std::string LoudFeed::write(const uint8_t* frames, size_t bytes) {
     return "";
 }
 
+std::string LoudFeed::end() {
+    if (!meter_) return err_;
+    if (ended_) return "";
+    ended_ = true;
+    return measure(true);
+}
+
 std::string LoudFeed::finish(d2d_loud_result* result, double* true_peak) {
     if (!meter_) return err_;
-    const std::string e = measure(true);
+    const std::string e = end();
     if (!e.empty()) return e;
     if (d2d_loud_finish(meter_, result) != D2D_OK) return d2d_flac_error();
     if (true_peak) {
@@ -231,8 +238,17 @@ struct FlacSink : PcmSink {
     uint32_t effort = 0;           // flac_frame_enc.h: 0 = fixed order 2, 1 = the search, 12 = the search with LPC
     void set_flac_effort(uint32_t e) override { effort = e; }
     // ReplayGain (open_sink's `replaygain`): where the two values lie in the file, the sink's own meter, the GPU path's result
-    bool replaygain = false, true_peak = false;
-    long gain_at = 0, peak_at = 0;
+    bool replaygain = false, true_peak = false, album = false;
+    long gain_at = 0, peak_at = 0, album_gain_at = 0, album_peak_at = 0;
+    bool have_album = false; d2d_loud_result album_loudness{};
+    void set_album_loudness(const d2d_loud_result& r) override { album_loudness = r; have_album = true; }
+    std::string end_stream() override {
+        drain(true);
+        if (io_failed) return "short write";
+        return feed && !raw_frames ? feed->end() : "";
+    }
+    const d2d_loud* meter() const override { return feed && !raw_frames ? feed->meter() : nullptr; }
+    bool meter_has_true_peak_rows() const override { return feed && !raw_frames && feed->true_peak_rows(); }
     std::unique_ptr<LoudFeed> feed;
     bool have_loudness = false; d2d_loud_result loudness{};
     void set_loudness(const d2d_loud_result& r) override { loudness = r; have_loudness = true; }
@@ -243,18 +259,22 @@ struct FlacSink : PcmSink {
         std::vector<std::pair<std::string, std::string>> fields;
         std::vector<TagPicture> pics;
         tag_to_vorbis(id3, fields, pics);
-        size_t gain_in_block = 0, peak_in_block = 0;
+        size_t gain_in_block = 0, peak_in_block = 0, album_gain_in_block = 0, album_peak_in_block = 0;
         if (replaygain) {
             // the source's own loudness fields go, ours come last: placeholders of the final width, patched at close()
-            auto ours = [](std::string k) {
+            auto ours = [this](std::string k) {
                 for (char& c : k) c = (char)toupper((unsigned char)c);
-                return k.rfind("REPLAYGAIN_TRACK_", 0) == 0 || k == "REPLAYGAIN_REFERENCE_LOUDNESS";
+                return k.rfind("REPLAYGAIN_TRACK_", 0) == 0 || k == "REPLAYGAIN_REFERENCE_LOUDNESS" || (album && k.rfind("REPLAYGAIN_ALBUM_", 0) == 0);
             };
             fields.erase(std::remove_if(fields.begin(), fields.end(), [&](const std::pair<std::string, std::string>& kv) { return ours(kv.first); }), fields.end());
             const d2d_loud_result none{};
             fields.push_back({"REPLAYGAIN_REFERENCE_LOUDNESS", replaygain_reference_text()});
             fields.push_back({"REPLAYGAIN_TRACK_GAIN", replaygain_gain_text(none)});
             fields.push_back({"REPLAYGAIN_TRACK_PEAK", replaygain_peak_text(none)});
+            if (album) {
+                fields.push_back({"REPLAYGAIN_ALBUM_GAIN", replaygain_gain_text(none)});
+                fields.push_back({"REPLAYGAIN_ALBUM_PEAK", replaygain_peak_text(none)});
+            }
             feed.reset(new LoudFeed(ch, bits, rate, true_peak));
             if (!feed->error().empty()) return feed->error();
         }
@@ -270,11 +290,14 @@ struct FlacSink : PcmSink {
                 le32((uint32_t)e.size());
                 if (replaygain && kv.first == "REPLAYGAIN_TRACK_GAIN") gain_in_block = b.size() + kv.first.size() + 1;
                 if (replaygain && kv.first == "REPLAYGAIN_TRACK_PEAK") peak_in_block = b.size() + kv.first.size() + 1;
+                if (replaygain && album && kv.first == "REPLAYGAIN_ALBUM_GAIN") album_gain_in_block = b.size() + kv.first.size() + 1;
+                if (replaygain && album && kv.first == "REPLAYGAIN_ALBUM_PEAK") album_peak_in_block = b.size() + kv.first.size() + 1;
                 b.insert(b.end(), e.begin(), e.end());
             }
             b.insert(b.begin(), {4, 0, 0, 0});
             // (the comment block is the first behind STREAMINFO: 4 + 4 + 34 bytes, then its own 4-byte header)
             gain_at = (long)(42 + 4 + gain_in_block); peak_at = (long)(42 + 4 + peak_in_block);
+            album_gain_at = (long)(42 + 4 + album_gain_in_block); album_peak_at = (long)(42 + 4 + album_peak_in_block);
             blocks.push_back(std::move(b));
         }
         for (const TagPicture& p : pics) {
@@ -373,6 +396,11 @@ struct FlacSink : PcmSink {
                 fseek(f, gain_at, SEEK_SET); fwrite(g.data(), 1, g.size(), f);
                 fseek(f, peak_at, SEEK_SET); fwrite(p.data(), 1, p.size(), f);
             }
+            if (album && have_album) {
+                const std::string g = replaygain_gain_text(album_loudness), p = replaygain_peak_text(album_loudness);
+                fseek(f, album_gain_at, SEEK_SET); fwrite(g.data(), 1, g.size(), f);
+                fseek(f, album_peak_at, SEEK_SET); fwrite(p.data(), 1, p.size(), f);
+            }
         }
         if (fclose(f) != 0 || io_failed) return "close failed";
         if (!loud_error.empty()) return loud_error;
@@ -383,7 +411,7 @@ struct FlacSink : PcmSink {
 }  // namespace
 
 std::string open_sink(OutputType type, const std::string& path, uint32_t channels, uint32_t rate, uint32_t bit_depth, PcmSink** out,
-                      const std::vector<uint8_t>* id3, bool replaygain, bool true_peak) {
+                      const std::vector<uint8_t>* id3, bool replaygain, bool true_peak, bool album) {
     *out = nullptr;
     if (true_peak && !replaygain) return "the true peak is written as REPLAYGAIN_TRACK_PEAK: it needs ReplayGain tags (--replaygain)";
     if (replaygain && type != OutputType::Flac) return "ReplayGain tags are written into FLAC files only; choose -o f";
@@ -396,7 +424,7 @@ std::string open_sink(OutputType type, const std::string& path, uint32_t channel
     if (!f) return "cannot create " + path;
     std::string err;
     if (type == OutputType::Wav) { auto* s = new WavSink(); if (id3) s->id3 = *id3; s->f = f; s->ch = channels; s->rate = rate; s->bits = bit_depth; err = s->begin(); *out = s; }
-    else if (type == OutputType::Flac) { auto* s = new FlacSink(); if (id3) s->id3 = *id3; s->f = f; s->ch = channels; s->rate = rate; s->bits = bit_depth; s->replaygain = replaygain; s->true_peak = true_peak; err = s->begin(); *out = s; }
+    else if (type == OutputType::Flac) { auto* s = new FlacSink(); if (id3) s->id3 = *id3; s->f = f; s->ch = channels; s->rate = rate; s->bits = bit_depth; s->replaygain = replaygain; s->true_peak = true_peak; s->album = replaygain && album; err = s->begin(); *out = s; }
     else { auto* s = new AiffSink(); if (id3) s->id3 = *id3; s->f = f; s->ch = channels; s->rate = rate; s->bits = bit_depth; s->aifc = type == OutputType::Aifc; err = s->begin(); *out = s; }
     return err;
 }

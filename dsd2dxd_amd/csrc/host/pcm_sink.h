@@ -33,6 +33,14 @@ class PcmSink {
     // close(), which writes it into the REPLAYGAIN_* fields.  Other sinks, and a FLAC sink that saw the samples itself, ignore it.
     // (A sink opened with `true_peak` too expects d2d_loud_true_peak's value in result.peak.)
     virtual void set_loudness(const d2d_loud_result& /*result*/) {}
+    // An ALBUM (Rdsd2Pcm::convert_album) keeps its sinks open until every track is measured.  end_stream: no sample follows -- the FLAC
+    // sink writes its pending frames and ends its own measurement, so that meter() is complete; "" or error.  meter: the sink's own meter
+    // when it measured the samples itself (a FLAC sink opened with `replaygain` on the PCM path), else null.  set_album_loudness: a FLAC
+    // sink opened with `album`, before close(), which writes gain_db and peak into the REPLAYGAIN_ALBUM_* fields.  Other sinks ignore all three.
+    virtual std::string end_stream() { return ""; }
+    virtual const d2d_loud* meter() const { return nullptr; }
+    virtual bool meter_has_true_peak_rows() const { return false; }
+    virtual void set_album_loudness(const d2d_loud_result& /*album*/) {}
 };
 
 // The CPU twin of the loudness measurement behind a stream of write() calls: whole interleaved frames go in as they come, the cells
@@ -51,6 +59,10 @@ class LoudFeed {
     // the partial last sub-block, then the integration; true_peak (a feed made with `true_peak` only): d2d_loud_true_peak's value, for
     // a stream without a frame the sample peak, 0
     std::string finish(d2d_loud_result* result, double* true_peak = nullptr);
+    // the partial last sub-block alone, once (finish() begins with it): afterwards meter() holds the whole stream
+    std::string end();
+    const d2d_loud* meter() const { return meter_; }
+    bool true_peak_rows() const { return tp_rows_; }
 
    private:
     std::string measure(bool final);
@@ -60,6 +72,7 @@ class LoudFeed {
     std::vector<uint8_t> pcm_;                                           // the frames from first_ on
     std::vector<d2d_loud_cell> cells_;
     bool tp_ = false, tp_rows_ = false;                                  // true peak asked for; a row of it was added
+    bool ended_ = false;                                                 // end() has run
     std::vector<double> peaks_;
     uint64_t first_ = 0, next_ = 0;                                      // pcm_'s first frame; the next sub-block to measure
     std::string err_;
@@ -78,9 +91,12 @@ std::string replaygain_peak_text(const d2d_loud_result& r);
 // whose values are placeholders until close() patches them, as it patches STREAMINFO: from the sink's own LoudFeed when it saw the
 // samples, from set_loudness on the raw-frame path.  `true_peak` (with `replaygain` only; refused without): REPLAYGAIN_TRACK_PEAK is
 // the true peak (d2d_loud_true_peak) instead of the sample peak, in the same fixed-width text, which holds values up to 9.999999 (the
-// filter's worst case is 2.03).
+// filter's worst case is 2.03).  `album` (with `replaygain` only; ignored without): REPLAYGAIN_ALBUM_GAIN and REPLAYGAIN_ALBUM_PEAK follow
+// the three fields, in the track fields' formats, placeholders until set_album_loudness and close(); the source's REPLAYGAIN_ALBUM_*
+// fields are dropped like its track fields.
 std::string open_sink(OutputType type, const std::string& path, uint32_t channels, uint32_t rate, uint32_t bit_depth,
-                      PcmSink** out, const std::vector<uint8_t>* id3 = nullptr, bool replaygain = false, bool true_peak = false);
+                      PcmSink** out, const std::vector<uint8_t>* id3 = nullptr, bool replaygain = false, bool true_peak = false,
+                      bool album = false);
 const char* output_extension(OutputType t);
 
 }  // namespace d2dhost

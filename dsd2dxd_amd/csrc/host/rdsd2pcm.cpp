@@ -203,6 +203,43 @@ void progress_cb(void* u, float pct) {
 }
 }  // namespace
 
+// Where a track's output goes and what travels with it: the path below out_dir, the source's tag, the artwork; the sink, opened.
+// album: a FLAC sink whose ReplayGain fields include the album's (Rdsd2Pcm::convert_album).
+static PcmSink* open_output(Rdsd2Pcm::Impl& im, const DsdInfo& info, bool album) {
+    PcmSink* sink = nullptr;
+    std::string err;
+    if (im.output != OutputType::Stdout) {
+        std::string dir;
+        const std::string in_dir = im.in_path ? dirname_of(*im.in_path) : ".";
+        if (im.out_dir) {
+            dir = *im.out_dir;
+            // keep the input's position below base_dir (src/main.rs:255-273)
+            if (im.in_path && !im.base_dir.empty() && in_dir.compare(0, im.base_dir.size(), im.base_dir) == 0 &&
+                in_dir.size() > im.base_dir.size())
+                dir += in_dir.substr(im.base_dir.size());
+            mkdirs(dir);
+        } else dir = in_dir;
+        std::string stem = im.in_path ? stem_of(*im.in_path) : "output";
+        if (im.append_rate) stem += rate_suffix(im.prm.output_rate);
+        im.out_path = dir + "/" + stem + "." + output_extension((d2dhost::OutputType)(int)im.output);
+    }
+    // the source's ID3v2 tag travels with the audio (README.md:7); -a also marks the album (README.md:170-173)
+    std::vector<uint8_t> tag;
+    if (im.output != OutputType::Stdout && im.in_path) {
+        std::string twarn;
+        err = d2dhost::read_source_tag(*im.in_path, info, tag, twarn);
+        if (!err.empty()) throw std::runtime_error(err);
+        im.tag_warning = twarn;
+        if (!tag.empty() && im.append_rate) d2dhost::append_to_album(tag, d2dhost::album_rate_suffix(im.prm.output_rate));
+        // -p: artwork next to the sources follows them into the output tree (README.md:115-119)
+        if (im.out_dir) im.artwork_copied = d2dhost::copy_artwork(dirname_of(*im.in_path), dirname_of(im.out_path));
+    }
+    err = open_sink((d2dhost::OutputType)(int)im.output, im.out_path, im.prm.channels, im.prm.output_rate, im.prm.bit_depth, &sink, &tag, im.replaygain, im.true_peak, album);
+    if (!err.empty()) throw std::runtime_error(err);
+    sink->set_flac_effort(im.flac_effort);
+    return sink;
+}
+
 static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSender& sender, bool levels) {
     DsdSource src;
     std::string err = src.open(im.in_path ? *im.in_path : "-", im.info);
@@ -216,37 +253,7 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
         throw std::runtime_error("The true peak of a conversion is written as REPLAYGAIN_TRACK_PEAK; it needs set_replaygain (--replaygain)");
     if (!levels && im.replaygain && im.output != OutputType::Flac)
         throw std::runtime_error("ReplayGain tags are written into FLAC files only; choose FLAC output (-o f)");
-    if (!levels) {
-        if (im.output != OutputType::Stdout) {
-            std::string dir;
-            const std::string in_dir = im.in_path ? dirname_of(*im.in_path) : ".";
-            if (im.out_dir) {
-                dir = *im.out_dir;
-                // keep the input's position below base_dir (src/main.rs:255-273)
-                if (im.in_path && !im.base_dir.empty() && in_dir.compare(0, im.base_dir.size(), im.base_dir) == 0 &&
-                    in_dir.size() > im.base_dir.size())
-                    dir += in_dir.substr(im.base_dir.size());
-                mkdirs(dir);
-            } else dir = in_dir;
-            std::string stem = im.in_path ? stem_of(*im.in_path) : "output";
-            if (im.append_rate) stem += rate_suffix(im.prm.output_rate);
-            im.out_path = dir + "/" + stem + "." + output_extension((d2dhost::OutputType)(int)im.output);
-        }
-        // the source's ID3v2 tag travels with the audio (README.md:7); -a also marks the album (README.md:170-173)
-        std::vector<uint8_t> tag;
-        if (im.output != OutputType::Stdout && im.in_path) {
-            std::string twarn;
-            err = d2dhost::read_source_tag(*im.in_path, info, tag, twarn);
-            if (!err.empty()) throw std::runtime_error(err);
-            im.tag_warning = twarn;
-            if (!tag.empty() && im.append_rate) d2dhost::append_to_album(tag, d2dhost::album_rate_suffix(im.prm.output_rate));
-            // -p: artwork next to the sources follows them into the output tree (README.md:115-119)
-            if (im.out_dir) im.artwork_copied = d2dhost::copy_artwork(dirname_of(*im.in_path), dirname_of(im.out_path));
-        }
-        err = open_sink((d2dhost::OutputType)(int)im.output, im.out_path, im.prm.channels, im.prm.output_rate, im.prm.bit_depth, &sink, &tag, im.replaygain, im.true_peak);
-        if (!err.empty()) throw std::runtime_error(err);
-        sink->set_flac_effort(im.flac_effort);
-    }
+    if (!levels) sink = open_output(im, info, false);
     std::unique_ptr<PcmSink> sink_guard(sink);
     d2d_engine* e = nullptr;
     if (d2d_create(&im.prm, 1, &e) != D2D_OK) throw std::runtime_error(d2d_create_error());
@@ -319,5 +326,192 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
 void Rdsd2Pcm::do_conversion(const std::atomic<bool>& cancel, ProgressSender sender) { run(*p_, cancel, sender, false); }
 
 float Rdsd2Pcm::check_level(const std::atomic<bool>& cancel, ProgressSender sender) { return run(*p_, cancel, sender, true); }
+
+// ---- an album: all tracks through one engine, the sinks open until the album is measured ----
+
+// the first field in which a track's engine parameters or FLAC switches differ from track 0's; "" when none does
+static std::string album_difference(const Rdsd2Pcm::Impl& a, const Rdsd2Pcm::Impl& b) {
+    const d2d_params &p = a.prm, &q = b.prm;
+#define ALBUM_SAME(field, name) if (!(field)) return name
+    ALBUM_SAME(p.dsd_rate == q.dsd_rate, "DSD rate");
+    ALBUM_SAME(p.output_rate == q.output_rate, "output rate");
+    ALBUM_SAME(p.channels == q.channels, "channel count");
+    ALBUM_SAME(p.fmt == q.fmt, "format (planar / interleaved)");
+    ALBUM_SAME(p.endianness == q.endianness, "endianness");
+    ALBUM_SAME(p.block_size == q.block_size, "block size");
+    ALBUM_SAME(p.filter == q.filter, "filter");
+    ALBUM_SAME(p.bit_depth == q.bit_depth, "bit depth");
+    ALBUM_SAME(p.dither == q.dither, "dither");
+    ALBUM_SAME(p.kernel == q.kernel, "kernel");
+    ALBUM_SAME(p.device == q.device, "device");
+    ALBUM_SAME(p.level_db == q.level_db, "level");
+    ALBUM_SAME(p.seed == q.seed, "seed");
+    ALBUM_SAME(p.channel_first == q.channel_first && p.channel_count == q.channel_count, "channel subset");
+    ALBUM_SAME(p.tap_bits == q.tap_bits, "tap bits");
+    ALBUM_SAME(p.debug_flags == q.debug_flags, "debug flags");
+    ALBUM_SAME(a.output == b.output, "output type");
+    ALBUM_SAME(a.gpu_flac == b.gpu_flac, "GPU FLAC switch");
+    ALBUM_SAME(a.flac_effort == b.flac_effort, "FLAC effort");
+    ALBUM_SAME(a.flac_verify == b.flac_verify, "FLAC verify switch");
+    ALBUM_SAME(a.flac_md5 == b.flac_md5, "FLAC MD5 switch");
+    ALBUM_SAME(a.replaygain == b.replaygain, "ReplayGain switch");
+    ALBUM_SAME(a.true_peak == b.true_peak, "true-peak switch");
+#undef ALBUM_SAME
+    return "";
+}
+
+// the batch driver polls one cancel flag: every track's callbacks raise it
+namespace {
+struct AlbumCtx { RunCtx* c; volatile int* cancel; };
+long album_read_cb(void* u, uint8_t* dst, size_t cap) {
+    AlbumCtx* a = (AlbumCtx*)u;
+    const long n = read_cb(a->c, dst, cap);
+    if (a->c->cancel_int) *a->cancel = 1;
+    return n;
+}
+int album_write_frames_cb(void* u, const void* frames, size_t bytes) {
+    AlbumCtx* a = (AlbumCtx*)u;
+    const int rc = write_frames_cb(a->c, frames, bytes);
+    if (a->c->cancel_int) *a->cancel = 1;
+    return rc;
+}
+}  // namespace
+
+void Rdsd2Pcm::convert_album(std::vector<Rdsd2Pcm>& tracks, const std::atomic<bool>& cancel, ProgressSender sender) {
+    if (tracks.empty()) throw std::runtime_error("An album has at least one track");
+    const uint32_t n = (uint32_t)tracks.size();
+    Impl& first = *tracks[0].p_;
+    for (uint32_t t = 1; t < n; ++t) {
+        const std::string d = album_difference(first, *tracks[t].p_);
+        if (!d.empty()) throw std::runtime_error("The tracks of an album are converted alike: " + tracks[t].file_name() + " differs from " + tracks[0].file_name() + " in " + d);
+    }
+    if (first.output != OutputType::Flac) throw std::runtime_error("An album is written as FLAC files; choose FLAC output (-o f)");
+    if (first.true_peak && !first.replaygain)
+        throw std::runtime_error("The true peak of a conversion is written as REPLAYGAIN_TRACK_PEAK; it needs set_replaygain (--replaygain)");
+    const d2d_params& prm = first.prm;
+    const bool replaygain = first.replaygain, true_peak = first.true_peak;
+
+    // every track's source and sink, open from here to the end
+    std::vector<std::unique_ptr<DsdSource>> srcs(n);
+    std::vector<std::unique_ptr<PcmSink>> sinks(n);
+    std::vector<RunCtx> ctx(n);
+    uint64_t total = 0;
+    for (uint32_t t = 0; t < n; ++t) {
+        Impl& im = *tracks[t].p_;
+        srcs[t].reset(new DsdSource());
+        const std::string err = srcs[t]->open(im.in_path ? *im.in_path : "-", im.info);
+        if (!err.empty()) throw std::runtime_error(err);
+        im.out_path.clear(); im.loud_result = d2d_loud_result{}; im.true_peak_value = 0.0;
+        sinks[t].reset(open_output(im, srcs[t]->info(), true));
+        ctx[t].src = srcs[t].get(); ctx[t].sink = sinks[t].get(); ctx[t].cancel = &cancel; ctx[t].sender = nullptr;
+        total += srcs[t]->info().bytes_per_channel;
+    }
+    // the GPU path's meters, one per track (the host path's are the sinks' own)
+    struct Meters {
+        std::vector<d2d_loud*> m;
+        ~Meters() { for (d2d_loud* h : m) d2d_loud_destroy(h); }
+    } own;
+    std::string msg;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> samples(n, 0);
+    if (first.gpu_flac) {
+        d2d_engine* e = nullptr;
+        if (d2d_create(&prm, n, &e) != D2D_OK) throw std::runtime_error(d2d_create_error());
+        size_t chunk = 0;                                               // the batch driver's default, in whole planar blocks (it is a multiple of 4096)
+        const size_t B = prm.fmt == D2D_FMT_PLANAR ? prm.block_size : 1;
+        if (B > 1 && ((size_t)1 << 19) % B) chunk = std::max(B, ((size_t)1 << 19) / B * B);
+        std::vector<d2d_stream_io> io(n);
+        std::vector<AlbumCtx> actx(n);
+        volatile int album_cancel = 0;
+        for (uint32_t t = 0; t < n && msg.empty(); ++t) {
+            io[t] = d2d_stream_io{};
+            actx[t] = AlbumCtx{&ctx[t], &album_cancel};
+            io[t].read = album_read_cb; io[t].read_user = &actx[t]; io[t].write = album_write_frames_cb; io[t].write_user = &actx[t];
+            io[t].total_bytes_per_channel = srcs[t]->info().bytes_per_channel;
+            if (replaygain) {
+                d2d_loud* h = nullptr;
+                if (d2d_loud_create(prm.channels, prm.output_rate, nullptr, &h) != D2D_OK) { msg = d2d_flac_error(); break; }
+                own.m.push_back(h);
+                if (true_peak && d2d_loud_set_true_peak(h, 1) != D2D_OK) { msg = d2d_flac_error(); break; }
+                io[t].loud = h;
+            }
+        }
+        struct Progress { ProgressSender* s; } pg{&sender};
+        d2d_streams_options opt{};
+        opt.struct_size = sizeof(opt); opt.bit_depth = prm.bit_depth; opt.effort = first.flac_effort;
+        opt.flags = (first.flac_verify ? D2D_STREAMS_VERIFY : 0) | (first.flac_md5 ? D2D_STREAMS_MD5 : 0);
+        opt.chunk_bytes_per_channel = chunk; opt.cancel = &album_cancel;
+        opt.progress = [](void* u, float pct) { Progress* p = (Progress*)u; if (*p->s && pct < 100.0f) (*p->s)(ProgressUpdate{pct}); };      // (100 is sent once the files are closed)
+        opt.progress_user = &pg;
+        if (msg.empty() && d2d_convert_streams_flac(e, io.data(), n, &opt) != D2D_OK) msg = d2d_flac_error();
+        d2d_destroy(e);
+        for (uint32_t t = 0; t < n && msg.empty(); ++t) {
+            Impl& im = *tracks[t].p_;
+            sinks[t]->set_frame_stats(io[t].stats.samples_per_channel, io[t].stats.blocks, io[t].stats.min_frame_bytes, io[t].stats.max_frame_bytes);
+            samples[t] = io[t].stats.samples_per_channel;
+            if (first.flac_md5) sinks[t]->set_md5(io[t].md5);
+            if (!replaygain) continue;
+            if (d2d_loud_finish(own.m[t], &im.loud_result) != D2D_OK) { msg = d2d_flac_error(); break; }
+            if (true_peak) {                                            // (a stream without a frame has no rows: its sample peak, 0)
+                im.true_peak_value = im.loud_result.peak;
+                if (samples[t] && d2d_loud_true_peak(own.m[t], &im.true_peak_value) != D2D_OK) { msg = d2d_flac_error(); break; }
+                im.loud_result.peak = im.true_peak_value;
+            }
+            sinks[t]->set_loudness(im.loud_result);
+        }
+    } else {
+        // one after another on the existing path; progress as the share of the album's bytes
+        uint64_t before = 0;
+        for (uint32_t t = 0; t < n && msg.empty(); ++t) {
+            d2d_engine* e = nullptr;
+            if (d2d_create(&prm, 1, &e) != D2D_OK) throw std::runtime_error(d2d_create_error());
+            struct Progress { ProgressSender* s; uint64_t before, mine, total; } pg{&sender, before, srcs[t]->info().bytes_per_channel, total};
+            auto progress = [](void* u, float pct) {
+                Progress* p = (Progress*)u;
+                if (!*p->s || !p->total || pct >= 100.0f) return;
+                (*p->s)(ProgressUpdate{(float)(100.0 * ((double)p->before + (double)p->mine * pct / 100.0) / (double)p->total)});
+            };
+            if (d2d_convert_stream(e, read_cb, &ctx[t], write_cb, &ctx[t], &ctx[t].cancel_int, progress, &pg, srcs[t]->info().bytes_per_channel,
+                                   tracks[t].p_->chunk) != D2D_OK) msg = d2d_last_error(e);
+            d2d_destroy(e);
+            if (msg.empty()) msg = sinks[t]->end_stream();
+            before += srcs[t]->info().bytes_per_channel;
+        }
+    }
+    for (uint32_t t = 0; t < n; ++t) if (!ctx[t].io_error.empty()) msg = ctx[t].io_error;
+    // the album's loudness over every track's meter; its peak the largest sample peak, or the largest true peak
+    if (msg.empty() && replaygain) {
+        std::vector<const d2d_loud*> meters(n);
+        bool rows = true;
+        for (uint32_t t = 0; t < n; ++t) {
+            meters[t] = first.gpu_flac ? own.m[t] : sinks[t]->meter();
+            rows = rows && (first.gpu_flac ? samples[t] != 0 : sinks[t]->meter_has_true_peak_rows());
+        }
+        d2d_loud_result album{};
+        if (d2d_loud_finish_album(meters.data(), n, &album) != D2D_OK) msg = d2d_flac_error();
+        else if (true_peak) {
+            if (rows) { if (d2d_loud_true_peak_album(meters.data(), n, &album.peak) != D2D_OK) msg = d2d_flac_error(); }
+            else                                                        // a track without a frame has no true-peak rows: its sample peak, 0, stands in
+                for (uint32_t t = 0; t < n; ++t) {
+                    double v = 0.0;
+                    if ((first.gpu_flac ? samples[t] != 0 : sinks[t]->meter_has_true_peak_rows()) && d2d_loud_true_peak(meters[t], &v) == D2D_OK && v > album.peak) album.peak = v;
+                }
+        }
+        if (msg.empty()) for (uint32_t t = 0; t < n; ++t) sinks[t]->set_album_loudness(album);
+    }
+    const auto spent = std::chrono::steady_clock::now() - t0;
+    std::chrono::steady_clock::duration io_time{};
+    for (uint32_t t = 0; t < n; ++t) io_time += ctx[t].io_time;
+    for (uint32_t t = 0; t < n; ++t) {
+        const std::string ce = sinks[t]->close();
+        if (msg.empty() && !ce.empty()) msg = ce;
+    }
+    // per album on every track
+    double audio = 0.0;
+    for (uint32_t t = 0; t < n; ++t) audio += (double)srcs[t]->info().bytes_per_channel * 8.0 / (2822400.0 * prm.dsd_rate);
+    for (uint32_t t = 0; t < n; ++t) { tracks[t].p_->dsp_s = std::chrono::duration<double>(spent - io_time).count(); tracks[t].p_->audio_s = audio; }
+    if (!msg.empty()) throw std::runtime_error(msg);
+    if (sender) sender(ProgressUpdate{ONE_HUNDRED_PERCENT});
+}
 
 }  // namespace rdsd2pcm

@@ -1,6 +1,7 @@
 // d2d_loud_host.cpp -- the host half of the loudness calls (include/dsd2dxd_amd.h, "Loudness where the PCM is"): the K-weighting
 // coefficients, d2d_loud_measure_host, the CPU twin of the GPU call on loud_meter.h, and the integration behind both twins (gates,
-// ReplayGain); d2d_true_peak_measure_host, the CPU twin of the true-peak call on true_peak.h, and the meter's true-peak side.  No HIP:
+// ReplayGain; d2d_loud_finish_album: the same gates over the blocks of several meters); d2d_true_peak_measure_host, the CPU twin of the
+// true-peak call on true_peak.h, and the meter's true-peak side.  No HIP:
 // tools and tests build this file with g++ alone.
 #include <math.h>
 #include <string.h>
@@ -163,27 +164,71 @@ int d2d_loud_add(d2d_loud* h, const d2d_loud_cell* cells, size_t whole_subblocks
     return D2D_OK;
 }
 
-int d2d_loud_finish(const d2d_loud* h, d2d_loud_result* result) {
-    if (!h || !result) return fail(D2D_ERR_PARAM, "null meter or result");
+// the two gates over the blocks of `n` meters, in meter order then block order: what d2d_loud_finish (n = 1) and d2d_loud_finish_album share
+static d2d_loud_result integrate(const d2d_loud* const* meters, uint32_t n_meters) {
     d2d_loud_result r{};
-    r.peak = h->peak;
-    r.blocks_total = h->power.size();
+    for (uint32_t i = 0; i < n_meters; ++i) {
+        if (meters[i]->peak > r.peak) r.peak = meters[i]->peak;
+        r.blocks_total += meters[i]->power.size();
+    }
     auto lufs = [](double w) { return -0.691 + 10.0 * log10(w); };
     // the absolute gate
     double sum = 0.0; uint64_t n = 0;
-    for (double w : h->power)
-        if (w > 0.0 && lufs(w) > -70.0) { sum = sum + w; ++n; }
+    for (uint32_t i = 0; i < n_meters; ++i)
+        for (double w : meters[i]->power)
+            if (w > 0.0 && lufs(w) > -70.0) { sum = sum + w; ++n; }
     if (n) {
         const double relative = lufs(sum / (double)n) - 10.0;
         double kept = 0.0; uint64_t m = 0;
-        for (double w : h->power)
-            if (w > 0.0 && lufs(w) > -70.0 && lufs(w) > relative) { kept = kept + w; ++m; }
+        for (uint32_t i = 0; i < n_meters; ++i)
+            for (double w : meters[i]->power)
+                if (w > 0.0 && lufs(w) > -70.0 && lufs(w) > relative) { kept = kept + w; ++m; }
         r.valid = 1;                                               // (the loudest block lies above the mean less 10 LU: m > 0)
         r.lufs = lufs(kept / (double)m);
         r.gain_db = -18.0 - r.lufs;
         r.blocks_gated = r.blocks_total - m;
     } else r.blocks_gated = r.blocks_total;
-    *result = r;
+    return r;
+}
+
+int d2d_loud_finish(const d2d_loud* h, d2d_loud_result* result) {
+    if (!h || !result) return fail(D2D_ERR_PARAM, "null meter or result");
+    *result = integrate(&h, 1);
+    return D2D_OK;
+}
+
+// the meters of an album: at least one, none null, all of one channel count, rate and weights
+static int check_album(const d2d_loud* const* meters, uint32_t n) {
+    if (!meters || n == 0) return fail(D2D_ERR_PARAM, "an album has at least one meter");
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!meters[i]) return fail(D2D_ERR_PARAM, "null meter");
+        if (meters[i]->channels != meters[0]->channels || meters[i]->rate != meters[0]->rate ||
+            memcmp(meters[i]->weights, meters[0]->weights, sizeof(meters[0]->weights)))
+            return fail(D2D_ERR_PARAM, "meter " + std::to_string(i) + " differs from meter 0 in channels, rate or weights");
+    }
+    return D2D_OK;
+}
+
+int d2d_loud_finish_album(const d2d_loud* const* meters, uint32_t n, d2d_loud_result* result) {
+    if (!result) return fail(D2D_ERR_PARAM, "null meter or result");
+    const int rc = check_album(meters, n);
+    if (rc != D2D_OK) return rc;
+    *result = integrate(meters, n);
+    return D2D_OK;
+}
+
+int d2d_loud_true_peak_album(const d2d_loud* const* meters, uint32_t n, double* out) {
+    if (!out) return fail(D2D_ERR_PARAM, "null meter or result");
+    const int rc = check_album(meters, n);
+    if (rc != D2D_OK) return rc;
+    double largest = 0.0;
+    for (uint32_t i = 0; i < n; ++i) {
+        double v = 0.0;
+        const int prc = d2d_loud_true_peak(meters[i], &v);
+        if (prc != D2D_OK) return prc;
+        if (v > largest) largest = v;
+    }
+    *out = largest;
     return D2D_OK;
 }
 

@@ -32,7 +32,9 @@ extern "C" {
                              *     added under 11, nothing existing changed: the verify method, d2d_flac_verify_device_method / _host_method,
                              *     D2D_FLAC_VERIFY_*, d2d_flac_verify_stats; the d2d_flac_md5_* calls; the d2d_loud_* calls and
                              *     d2d_convert_stream_flac_loud; the d2d_true_peak_measure_* calls, d2d_tpeak_io and the meter's
-                             *     d2d_loud_set_true_peak / _add_true_peaks / _true_peak; D2D_DBG_NO_DITHER_TABLE and d2d_dither_table_calls */
+                             *     d2d_loud_set_true_peak / _add_true_peaks / _true_peak; D2D_DBG_NO_DITHER_TABLE and d2d_dither_table_calls;
+                             *     the d2d_segments_* calls, d2d_convert_streams_flac with d2d_stream_io / d2d_streams_options, and
+                             *     d2d_loud_finish_album / d2d_loud_true_peak_album */
 
 /* status codes */
 enum {
@@ -663,6 +665,92 @@ int d2d_convert_stream_flac_loud(d2d_engine* e, uint32_t bit_depth, uint32_t eff
                                  const volatile int* cancel, d2d_progress_fn progress, void* progress_user,
                                  uint64_t total_bytes_per_channel, size_t chunk_bytes_per_channel, d2d_flac_stream_stats* stats,
                                  d2d_flac_check* check /* NULL: not verified */, uint8_t md5[16] /* NULL: not hashed */, d2d_loud* loud);
+
+/* ---- Many streams per call: an album as one batch (added under ABI 11: no existing call or structure changed) ---- */
+
+/* A CHUNK'S BOOKKEEPING IN ONE LAUNCH.  A driver that carries PCM from chunk to chunk for many files has, per file and chunk, a handful
+ * of device-to-device copies and one download of a length that only the device knows.  These two calls do all of them at once.  Both
+ * follow d2d_loud_measure_device: the descriptors ride in the kernel arguments, a call larger than one launch takes (96 segments; 128
+ * pack sources) is cut into launches that run in order on `hip_stream` (NULL = the null stream), the call only enqueues, takes no
+ * engine, checks everything on the host before the first launch, and d2d_flac_error() has the message.
+ *
+ * d2d_segments_move_device copies seg[i].bytes bytes from seg[i].src to seg[i].dst for every i.  Both pointers are GPU-addressable
+ * (device or pinned host); any alignment and any length, 0 included (such a segment's pointers are not looked at).  No dst range may
+ * overlap a src range or another dst range of the same call (src ranges may overlap each other): checked on the host, D2D_ERR_PARAM,
+ * nothing written; so are a null pointer and a range that wraps the address space.  A successful call writes exactly the dst ranges and
+ * no other byte.  It reads the src ranges and, at most, the rest of the aligned 16-byte words that hold their first and last byte.
+ *
+ * d2d_segments_pack_device lays n variable-length segments back to back: segment k is *src[k].bytes bytes at src[k].base and lands at
+ * dst + offsets[k], offsets[0] = 0, offsets[k + 1] = offsets[k] + *src[k].bytes, no padding.  `bytes` is GPU-addressable and is read ON
+ * THE DEVICE when the launch runs (point it at d2d_flac_result::bytes_out: no synchronise lies between an encode and its download);
+ * max_bytes is what the host knows about it.  `offsets` holds n + 1 entries, GPU-addressable, 8-byte aligned; `dst` is normally pinned
+ * host memory, so one run of bytes for all files crosses the link, written by the kernel.  The host checks sum(max_bytes) <=
+ * dst_capacity, else D2D_ERR_CAPACITY; null or misaligned pointers -> D2D_ERR_PARAM; nothing launched.  `dst` and `offsets` must not
+ * overlap each other or a source (not checked: the lengths are not known).  If any *bytes_k > max_bytes_k on the device, nothing is
+ * copied and every offsets[k], k = 0 .. n, is UINT64_MAX.  A successful call writes exactly offsets[n] bytes of dst, the table, and
+ * nothing else.  n = 0 writes offsets[0] = 0.
+ *
+ * The _host twins do the same with memcpy on host memory (`bytes` read at the call): the same checks, the same bytes. */
+typedef struct d2d_segment { void* dst; const void* src; size_t bytes; } d2d_segment;
+typedef struct d2d_pack_src { const void* base; const uint64_t* bytes; size_t max_bytes; } d2d_pack_src;
+int d2d_segments_move_device(const d2d_segment* seg, uint32_t n, void* hip_stream);
+int d2d_segments_move_host(const d2d_segment* seg, uint32_t n);
+int d2d_segments_pack_device(const d2d_pack_src* src, uint32_t n, void* dst, size_t dst_capacity, uint64_t* offsets, void* hip_stream);
+int d2d_segments_pack_host(const d2d_pack_src* src, uint32_t n, void* dst, size_t dst_capacity, uint64_t* offsets);
+
+/* THE BATCH DRIVER.  d2d_convert_streams_flac converts n_files streams in lockstep through ONE engine created with n_files files:
+ * d2d_convert_stream_flac_loud for many streams.  Per chunk it reads each unfinished file's next piece into one pinned arena (one chunk
+ * ahead, so that `final` is known), then enqueues on the null stream, in this order: one upload, one d2d_translate_batch_device, one
+ * d2d_flac_md5_update_device (D2D_STREAMS_MD5), one d2d_segments_move_device (the carried PCM of encoder and meter and the new frames
+ * behind it; the buffers alternate so that no segment overlaps), one d2d_loud_measure_device and one d2d_true_peak_measure_device (files
+ * with a meter; with its true peak switched on), the encode, the verify (D2D_STREAMS_VERIFY), one d2d_segments_pack_device into pinned
+ * memory; then ONE hipStreamSynchronize, then each file's `write` in file order from the calling thread.  The number of these calls per
+ * chunk does not depend on n_files (*device_calls counts them and *chunks the chunks, where the pointers are given).  Files may have
+ * different lengths: a file that has ended takes part with 0 bytes / 0 frames, which every device call leaves alone; a file with no
+ * byte at all gets zero stats and no `write` call.  All files' meters, where given, are of the engine's channels and one rate.
+ *
+ * chunk_bytes_per_channel is per file; 0 = 512 KiB: with c the chunk, a 64-file stereo DSD64 -> 88.2 kHz 24-bit batch holds about
+ * 380 c of pinned memory (two input arenas, the frame bytes) and 850 c of device memory (input, new PCM, two carried buffers each for
+ * encoder and meter, frame bytes, workspace), 190 MiB and 425 MiB; DESIGN 4.6f has the sum.  For planar input a multiple of the block
+ * size, as for the single-stream calls.
+ *
+ * THE GUARANTEE.  For every file the concatenation of the bytes given to `write` equals, byte for byte, what
+ * d2d_convert_stream_flac_loud gives for that stream alone on an engine of one file with the same d2d_params, at any chunk size of
+ * either call; `stats`, `check` and `md5` are equal, and the meter, once finished, gives the same d2d_loud_result and the same true peak
+ * bit for bit.  It holds because a FIR output depends on its own file's bits only, the dither is keyed by (seed, channel, output index)
+ * and not by file, FLAC blocks and loudness sub-blocks are cut by stream position and not by chunk, and MD5 is a chain per file.
+ *
+ * ERRORS.  The whole call ends at the first failing callback (D2D_ERR_IO), block that does not verify (D2D_ERR_VERIFY; no file's bytes
+ * of that chunk reach `write`), raised cancel flag or device error; the message names the file index ("file 2: ...").  Parameter errors
+ * are found before any device call.  `progress` receives the percentage of the summed total_bytes_per_channel (only when every file
+ * states one) and exactly 100.0f last. */
+enum { D2D_STREAMS_VERIFY = 1, D2D_STREAMS_MD5 = 2 };
+typedef struct d2d_stream_io {
+    d2d_read_fn read;  void* read_user;
+    d2d_write_fn write; void* write_user;      /* write may be NULL */
+    uint64_t total_bytes_per_channel;          /* 0: unknown */
+    d2d_loud* loud;                            /* NULL: not measured; true peak as the meter says */
+    d2d_flac_stream_stats stats;               /* out */
+    d2d_flac_check check;                      /* out, when verifying */
+    uint8_t md5[16];                           /* out, when hashing */
+} d2d_stream_io;
+typedef struct d2d_streams_options {
+    uint32_t struct_size, bit_depth, effort, flags;   /* sizeof(d2d_streams_options); D2D_STREAMS_VERIFY | D2D_STREAMS_MD5 */
+    size_t chunk_bytes_per_channel;                   /* per file; 0: the default */
+    const volatile int* cancel;
+    d2d_progress_fn progress; void* progress_user;
+    uint64_t* device_calls;                           /* out, may be NULL: device calls the driver enqueued, synchronises included */
+    uint64_t* chunks;                                 /* out, may be NULL: chunks it ran */
+} d2d_streams_options;
+int d2d_convert_streams_flac(d2d_engine* e, d2d_stream_io* io, uint32_t n_files, const d2d_streams_options* opt);
+
+/* ALBUM LOUDNESS, host only.  d2d_loud_finish_album applies the two gates of d2d_loud_finish to the 400 ms blocks of all meters, taken
+ * in meter order then block order (blocks do not span tracks); `peak` is the largest sample peak, gain_db = -18 - lufs, `valid` as
+ * there.  Meters of different channels, rate or weights, a null meter or n = 0 -> D2D_ERR_PARAM.  With n = 1 it equals
+ * d2d_loud_finish bit for bit.  d2d_loud_true_peak_album gives the largest d2d_loud_true_peak, under that call's conditions for each
+ * meter. */
+int d2d_loud_finish_album(const d2d_loud* const* meters, uint32_t n, d2d_loud_result* result);
+int d2d_loud_true_peak_album(const d2d_loud* const* meters, uint32_t n, double* out);
 
 /* ---- shared tables (multi-GPU)------------------------------------------------------------ */
 

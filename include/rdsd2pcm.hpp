@@ -61,6 +61,16 @@ class Rdsd2Pcm {
 
     void do_conversion(const std::atomic<bool>& cancel, ProgressSender sender = nullptr);
     float check_level(const std::atomic<bool>& cancel, ProgressSender sender = nullptr);
+    // The tracks of one ALBUM (not a reference call; the C mirror does not have it): FLAC output; every track agrees with the first in
+    // every engine parameter and every FLAC switch, else it throws, naming the first track that differs and the field.  With
+    // set_gpu_flac all tracks go in lockstep through ONE engine of tracks.size() files (d2d_convert_streams_flac, include/dsd2dxd_amd.h);
+    // without it they run one after another on do_conversion's path.  Either way the sinks stay open until the album is measured, and
+    // with set_replaygain each file's VORBIS_COMMENT carries REPLAYGAIN_ALBUM_GAIN and REPLAYGAIN_ALBUM_PEAK behind the three track
+    // fields (d2d_loud_finish_album over all tracks' 400 ms blocks; the peak is the largest sample peak, with set_true_peak the largest
+    // true peak; the source's REPLAYGAIN_ALBUM_* fields are dropped).  Apart from those two fields every file is, byte for byte, what
+    // do_conversion writes for its track, and the files of the two paths are equal in every byte.  Progress is the share of the summed
+    // bytes; dsp_seconds() and audio_seconds() are the album's on every track afterwards.
+    static void convert_album(std::vector<Rdsd2Pcm>& tracks, const std::atomic<bool>& cancel, ProgressSender sender = nullptr);
     std::string file_name() const;
     std::string output_path() const;          // where do_conversion writes ("" for stdout)
     double dsp_seconds() const;               // time inside the engine during the last run (the "DSP speed" figure)
