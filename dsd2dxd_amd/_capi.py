@@ -126,6 +126,16 @@ class LoudResult(C.Structure):
                 ("blocks_total", C.c_uint64), ("blocks_gated", C.c_uint64)]
 
 
+class Mix(C.Structure):
+    """d2d_mix: out_channels rows x channels columns of Q15 coefficients (d2d_create_mix, d2d_mix_frames_host)"""
+    _fields_ = [("struct_size", C.c_uint32), ("out_channels", C.c_uint32), ("coef", C.POINTER(C.c_int32))]
+
+
+MIX_UNITY = 32768                                                       # a Q15 gain of 1.0
+# D2D_MIX_LAYOUT_*
+MIX_LAYOUT_AUTO, MIX_LAYOUT_STEREO, MIX_LAYOUT_LRC, MIX_LAYOUT_QUAD, MIX_LAYOUT_5_0, MIX_LAYOUT_5_1, MIX_LAYOUT_LRC_LFE = 0, 2, 3, 4, 5, 6, 7
+
+
 class Segment(C.Structure):
     """d2d_segment: `bytes` bytes from src to dst (d2d_segments_move_device / _host)"""
     _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p), ("bytes", C.c_size_t)]
@@ -187,7 +197,8 @@ EXPORTS = ["d2d_create", "d2d_create_error", "d2d_destroy", "d2d_reset", "d2d_la
            "d2d_true_peak_measure_device", "d2d_true_peak_measure_host", "d2d_loud_set_true_peak", "d2d_loud_add_true_peaks",
            "d2d_loud_true_peak", "d2d_dither_table_calls",
            "d2d_segments_move_device", "d2d_segments_move_host", "d2d_segments_pack_device", "d2d_segments_pack_host",
-           "d2d_convert_streams_flac", "d2d_loud_finish_album", "d2d_loud_true_peak_album"]
+           "d2d_convert_streams_flac", "d2d_loud_finish_album", "d2d_loud_true_peak_album",
+           "d2d_create_mix", "d2d_get_mix", "d2d_input_channels", "d2d_mix_preset", "d2d_mix_frames_host", "d2d_mix_error"]
 
 _lib = None
 
@@ -306,8 +317,51 @@ def lib():
         L.d2d_convert_streams_flac.argtypes = [C.c_void_p, C.POINTER(StreamIO), C.c_uint32, C.POINTER(StreamsOptions)]
         L.d2d_loud_finish_album.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(LoudResult)]
         L.d2d_loud_true_peak_album.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_double)]
+    if hasattr(L, "d2d_create_mix"):              # (as above: a D2D_AMD_LIB build of an older tree lacks the channel matrix)
+        L.d2d_create_mix.argtypes = [C.POINTER(Params), C.POINTER(Mix), C.c_uint32, C.POINTER(C.c_void_p)]
+        L.d2d_get_mix.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_size_t]
+        L.d2d_input_channels.argtypes = [C.c_void_p]
+        L.d2d_input_channels.restype = C.c_uint32
+        L.d2d_mix_preset.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
+        L.d2d_mix_frames_host.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_int32, C.POINTER(Mix), C.c_uint32, C.c_uint32,
+                                          C.c_double, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.d2d_mix_error.restype = C.c_char_p
     _lib = L
     return L
+
+
+def _mix_struct(coef, channels):
+    """(Mix, the int32 array it points at) of a rows x channels table of Q15 integers"""
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(coef, dtype=np.int64).reshape(-1, channels) if channels else np.zeros((0, 0)), dtype=np.int32)
+    return Mix(C.sizeof(Mix), a.shape[0], a.ctypes.data_as(C.POINTER(C.c_int32))), a
+
+
+def mix_preset(in_channels, target, layout=MIX_LAYOUT_AUTO):
+    """d2d_mix_preset: the fold-down rows of a layout as a list of rows of Q15 integers (target 2: Lo, Ro; 1: mono)"""
+    coef, rows = (C.c_int32 * (2 * max(in_channels, 1)))(), C.c_uint32()
+    rc = lib().d2d_mix_preset(in_channels, layout, target, coef, C.byref(rows))
+    if rc:
+        raise D2DError(rc, lib().d2d_mix_error().decode())
+    return [list(coef[r * in_channels:(r + 1) * in_channels]) for r in range(rows.value)]
+
+
+def mix_frames_host(sums, scale_bits, coef, bit_depth=24, dither="X", level_db=0.0, seed=0, first_index=0, capacity=None):
+    """d2d_mix_frames_host, the CPU twin of the mix pass: sums an int32 array (channels, frames) of exact FIR sums at scale 2^-scale_bits,
+    coef rows x channels Q15 integers.  Returns (frame bytes as a uint8 array, peaks per output channel).  No device."""
+    import numpy as np
+    x = np.ascontiguousarray(sums, dtype=np.int32)
+    channels, frames = x.shape
+    m, keep = _mix_struct(coef, channels)
+    fb = m.out_channels * (2 if bit_depth == 16 else 4 if bit_depth == 32 else 3)
+    cap = frames * fb if capacity is None else capacity
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    peaks = np.zeros(max(m.out_channels, 1), dtype=np.float64)
+    rc = lib().d2d_mix_frames_host(x.ctypes.data, frames, frames, channels, scale_bits, C.byref(m), bit_depth, ord(dither.upper()), level_db,
+                                   seed, first_index, out.ctypes.data, cap, peaks.ctypes.data)
+    if rc:
+        raise D2DError(rc, lib().d2d_mix_error().decode())
+    return out[:frames * fb], peaks[:m.out_channels]
 
 
 def _flac_check(rc):
@@ -590,17 +644,24 @@ class Engine:
     """One conversion context = one Rdsd2Pcm of the reference (src/main.rs:325-342), or a batch of
     `n_files` of them advanced together."""
 
-    def __init__(self, n_files=1, **kw):
+    def __init__(self, n_files=1, mix=None, **kw):
+        """mix: rows x channels Q15 integers (d2d_create_mix): the engine folds its channels into len(mix) output channels"""
         L = lib()
         self.params = make_params(**kw)
         h = C.c_void_p()
-        rc = L.d2d_create(C.byref(self.params), n_files, C.byref(h))
+        if mix is not None:
+            m, keep = _mix_struct(mix, self.params.channels)
+            rc = L.d2d_create_mix(C.byref(self.params), C.byref(m), n_files, C.byref(h))
+        else:
+            rc = L.d2d_create(C.byref(self.params), n_files, C.byref(h))
         if rc:
             raise D2DError(rc, L.d2d_create_error().decode())
         self._h = h
         self.n_files = n_files
         self.channels = self.params.channels                      # width of the INPUT
         self.out_channels = self.params.channel_count or (self.params.channels - self.params.channel_first)
+        if mix is not None:
+            self.out_channels = m.out_channels
         self.frame_bytes = L.d2d_frame_bytes(h)
 
     def close(self):
@@ -623,6 +684,16 @@ class Engine:
         self._check(lib().d2d_get_info(self._h, C.byref(i)))
         return dict(M=i.decimation, ntaps=i.ntaps, S=i.scale_bits, L=i.resamp_L, P=i.resamp_P,
                     kernel=i.kernel, filter=i.filter_name.decode())
+
+    def get_mix(self):
+        """d2d_get_mix: the engine's mix as a list of rows of Q15 integers, or None for an engine that does not mix"""
+        rows = C.c_uint32()
+        self._check(lib().d2d_get_mix(self._h, C.byref(rows), None, 0))
+        if not rows.value:
+            return None
+        coef = (C.c_int32 * (rows.value * self.channels))()
+        self._check(lib().d2d_get_mix(self._h, C.byref(rows), coef, len(coef)))
+        return [list(coef[r * self.channels:(r + 1) * self.channels]) for r in range(rows.value)]
 
     def kernel_name(self):
         return lib().d2d_kernel_name(self._h).decode()

@@ -29,7 +29,9 @@
 #include "d2d_mx.h"
 #include "d2d_px.h"
 #include "d2d_route.h"
+#include "d2d_sample.h"
 #include "d2d_tables.h"
+#include "mix/d2d_mix.h"
 
 using namespace d2d;
 
@@ -142,7 +144,16 @@ struct d2d_engine {
     int M = 0, Mb = 0, N = 0, Wb = 0, S = 0;
     uint32_t nstreams = 0;
     uint32_t Cin = 0;          // channels of the input layout
-    uint32_t C = 0, c0 = 0;    // channels converted (streams per file, width of the output frame) and the first of them
+    uint32_t C = 0, c0 = 0;    // channels converted (streams per file; the width of the output frame unless the engine mixes) and the first of them
+    // d2d_create_mix: Co rows x C columns of Q15 coefficients between the FIR sums and the requantiser (mix/d2d_mix.h).  The FIR pass is the 'N'
+    // dither's integer pass of the same shape (plan_p, plan_epi: what the route and the launches are planned with; the caller's own parameters
+    // on an unmixed engine), the mix pass makes the Co-wide frames (epi: its epilogue, channels = Co)
+    std::vector<int32_t> mix;
+    uint32_t Co = 0;           // width of the output frame: rows of the mix, or C
+    bool mixed() const { return !mix.empty(); }
+    d2d_params plan_p{};
+    Epilogue plan_epi{};
+    Buf<int32_t> d_mix;
     FirRoute route;            // which kernel, table layout and staging serve this engine (d2d_route.h: choose_route)
     MfmaLayout mfma{};
     mutable std::string kname; // d2d_kernel_name's answer before the first call
@@ -227,14 +238,6 @@ static uint64_t res_outputs_after(const d2d_engine* e, uint64_t nx) {
     return (nx * (uint64_t)e->fc.resamp->L - 1) / (uint64_t)e->fc.resamp->Mdn + 1;
 }
 
-// key of the counter-based dither generator for one channel (DESIGN.md "dither")
-static uint64_t rng_key64(uint64_t seed, uint32_t channel) {
-    uint64_t z = (seed ^ ((uint64_t)channel * 0xD1B54A32D192ED03ull)) + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 static int validate(const d2d_params& p, std::string& err) {
     if (p.channels < 1 || p.channels > 64) { err = "Invalid channel count"; return D2D_ERR_PARAM; }
     if (p.bit_depth != 16 && p.bit_depth != 20 && p.bit_depth != 24 && p.bit_depth != 32) {
@@ -251,6 +254,17 @@ static int validate(const d2d_params& p, std::string& err) {
     if (p.kernel > D2D_KERNEL_MFMA) { err = "Invalid kernel selector"; return D2D_ERR_PARAM; }
     if (!isfinite(p.level_db)) { err = "Invalid level"; return D2D_ERR_PARAM; }
     if (p.channel_first >= p.channels || p.channel_count > p.channels - p.channel_first) { err = "Invalid channel subset"; return D2D_ERR_PARAM; }
+    return D2D_OK;
+}
+
+// what d2d_create_mix refuses beyond d2d_create: the mix works on the exact int32 sums of whole files' channels
+static int validate_mix(const d2d_params& p, const std::vector<int32_t>& m, uint32_t rows, std::string& err) {
+    if (const char* why = mix_check(p.channels, rows, m.data())) { err = why; return D2D_ERR_PARAM; }
+    if (p.dither == 'N') { err = "a mix does not combine with the noise-shaped dither; use T, R, F or X"; return D2D_ERR_PARAM; }
+    if (p.tap_bits == 32) { err = "a mix does not combine with 32-bit taps"; return D2D_ERR_PARAM; }
+    if (p.channel_first != 0 || (p.channel_count != 0 && p.channel_count != p.channels)) {
+        err = "a mix does not combine with a channel subset: give the subset as rows of the mix"; return D2D_ERR_PARAM;
+    }
     return D2D_OK;
 }
 
@@ -290,14 +304,14 @@ static int clear_file_state(d2d_engine* e, uint32_t file) {
 // d2d_engine::launch, once the route is chosen and every table and the job table exist
 static void build_launch_state(d2d_engine* e) {
     LaunchState& l = e->launch;
-    l.fir = fir_launch(e->p, e->fc, e->epi, e->route, PASS_MAIN);
+    l.fir = fir_launch(e->plan_p, e->fc, e->plan_epi, e->route, PASS_MAIN);
     l.fir.bind(e->d_jobs, e->d_fir_tables);
     if (e->route.fine) {
-        l.fir_lo = fir_launch(e->p, e->fc, e->epi, e->route, PASS_LO, &e->lo_def);
+        l.fir_lo = fir_launch(e->plan_p, e->fc, e->plan_epi, e->route, PASS_LO, &e->lo_def);
         l.fir_lo.bind(e->d_jobs + e->nstreams, e->d_fir_tables_lo);
     }
     if (e->mono2_ok()) {
-        l.fir_m2 = fir_launch(e->p, e->fc, e->epi, e->route, PASS_MONO2);
+        l.fir_m2 = fir_launch(e->plan_p, e->fc, e->plan_epi, e->route, PASS_MONO2);
         l.fir_m2.bind(e->d_jobs + e->nstreams, e->d_fir_tables_m2);
     }
     l.rs.jobs = e->d_jobs; l.rs.tables = e->d_resamp;
@@ -315,14 +329,23 @@ static void build_launch_state(d2d_engine* e) {
 // d2d_create after the parameters are copied: every choice, table and buffer.  Errors go to e->err.
 static int init_engine(d2d_engine* e) {
     int rc = validate(e->p, e->err);
+    if (rc == D2D_OK && e->mixed()) rc = validate_mix(e->p, e->mix, e->Co, e->err);
     if (rc == D2D_OK) rc = choose_filters(e->p, e->fc, e->err);
-    if (rc == D2D_OK) rc = choose_route(e->p, e->fc, e->route, e->err);
+    // a mix reads exact int32 sums: a configuration whose filter choice has a stage B (DSD256 -> 96 kHz, DSD512 -> 48 kHz multiples, filter 'S')
+    // has 64-bit ones
+    if (rc == D2D_OK && e->mixed() && e->fc.resamp && !e->fc.poly)
+        return e->fail(D2D_ERR_FILTER, "a mix needs a single-pass filter: this configuration runs a second stage (DSD256 -> 96 kHz, DSD512 -> 48 kHz "
+                                       "multiples, filter S), whose sums are not 32-bit integers");
+    e->plan_p = e->mixed() ? mix_fir_params(e->p) : e->p;
+    if (rc == D2D_OK) rc = choose_route(e->plan_p, e->fc, e->route, e->err);
     if (rc != D2D_OK) return rc;
     const d2d_filter_def& f = *e->fc.fir;
     e->M = f.M; e->Mb = f.M / 8; e->N = f.ntaps; e->Wb = f.ntaps / 8; e->S = f.S;
     e->Cin = e->p.channels;
     e->epi = epilogue_of(e->p);
+    e->plan_epi = epilogue_of(e->plan_p);
     e->C = e->epi.channels;
+    if (e->mixed()) e->epi.channels = e->Co; else e->Co = e->C;
     e->c0 = e->p.channel_first;
     e->nstreams = e->n_files * e->C;
     e->files.resize(e->n_files);
@@ -376,7 +399,8 @@ static int init_engine(d2d_engine* e) {
         HIPCHK(e, e->d_resamp.upload(rt.data(), rt.size()));
         e->xs_hist = (uint32_t)e->fc.resamp->P;
     }
-    if (e->route.fine || e->cascade() || e->noise_shape)
+    if (e->mixed()) HIPCHK(e, e->d_mix.upload(e->mix.data(), e->mix.size() * sizeof(int32_t)));
+    if (e->route.fine || e->cascade() || e->noise_shape || e->mixed())
         HIPCHK(e, e->d_scratch.alloc(sizeof(int32_t) * ((size_t)e->xs_hist + 4096) * e->nstreams * (e->route.fine ? 2u : 1u)));
     if (e->noise_shape) {
         for (int i = 0; i < 2; ++i) HIPCHK(e, e->d_ns[i].alloc(sizeof(double) * 2 * e->nstreams));
@@ -398,9 +422,12 @@ extern "C" {
 
 const char* d2d_create_error(void) { return g_create_error.c_str(); }
 
-int d2d_create(const d2d_params* params, uint32_t n_files, d2d_engine** out) {
+int d2d_create(const d2d_params* params, uint32_t n_files, d2d_engine** out) { return d2d_create_mix(params, nullptr, n_files, out); }
+
+int d2d_create_mix(const d2d_params* params, const d2d_mix* mix, uint32_t n_files, d2d_engine** out) {
     if (out) *out = nullptr;
     if (!params || !out) { g_create_error = "null argument"; return D2D_ERR_PARAM; }
+    if (mix && mix->struct_size != sizeof(d2d_mix)) { g_create_error = "d2d_mix.struct_size mismatch"; return D2D_ERR_PARAM; }
     constexpr size_t legacy_size = offsetof(d2d_params, channel_first);           // ABI 1: no channel subset
     constexpr size_t abi3_size = offsetof(d2d_params, tap_bits);                  // ABI 2, 3: no tap grid (ABI 4 and 5 have today's size: reserved0 became debug_flags)
     if (params->struct_size != sizeof(d2d_params) && params->struct_size != legacy_size && params->struct_size != abi3_size) {
@@ -412,6 +439,13 @@ int d2d_create(const d2d_params* params, uint32_t n_files, d2d_engine** out) {
     memcpy(&e->p, params, params->struct_size);
     e->p.struct_size = sizeof(d2d_params);
     e->n_files = n_files;
+    if (mix) {
+        // (the bounds come first: nothing is read past what they admit; validate_mix repeats them with the other refusals, in d2d_create's order)
+        const char* why = mix_check(e->p.channels, mix->out_channels, mix->coef);
+        if (why) { g_create_error = why; return D2D_ERR_PARAM; }
+        e->Co = mix->out_channels;
+        e->mix.assign(mix->coef, mix->coef + (size_t)mix->out_channels * e->p.channels);
+    }
     const int rc = init_engine(e.get());
     if (rc != D2D_OK) { g_create_error = e->err; return rc; }
     *out = e.release();
@@ -434,7 +468,19 @@ int d2d_reset(d2d_engine* e) {
 
 const char* d2d_last_error(const d2d_engine* e) { return e ? e->err.c_str() : "null engine"; }
 
-size_t d2d_frame_bytes(const d2d_engine* e) { return e ? (size_t)e->epi.sample_bytes * e->C : 0; }
+size_t d2d_frame_bytes(const d2d_engine* e) { return e ? (size_t)e->epi.sample_bytes * e->Co : 0; }
+
+uint32_t d2d_input_channels(const d2d_engine* e) { return e ? e->Cin : 0u; }
+
+int d2d_get_mix(const d2d_engine* e, uint32_t* out_channels, int32_t* coef, size_t capacity) {
+    if (!e || !out_channels) return D2D_ERR_PARAM;
+    *out_channels = e->mixed() ? e->Co : 0u;
+    if (e->mixed() && coef) {
+        if (capacity < e->mix.size()) return D2D_ERR_CAPACITY;
+        std::copy(e->mix.begin(), e->mix.end(), coef);
+    }
+    return D2D_OK;
+}
 
 size_t d2d_next_frames(const d2d_engine* e, uint32_t file, size_t L) {
     if (!e || file >= e->n_files) return 0;
@@ -579,7 +625,7 @@ static uint32_t dither_table_stride(const d2d_engine* e, const CallPlan& pl) {
 // all start at the same index.  first_file: one of them, whose job rows hold the keys and the index.
 static bool dither_table_serves(const d2d_engine* e, const CallPlan& pl, const bool prime, uint32_t* first_file) {
     const FirLaunch& l = e->launch.fir;
-    if (prime || e->poly || pl.mono2 || !pl.run_fir || pl.max_nx == 0 || (e->p.debug_flags & D2D_DBG_NO_DITHER_TABLE)) return false;
+    if (prime || e->poly || e->mixed() || pl.mono2 || !pl.run_fir || pl.max_nx == 0 || (e->p.debug_flags & D2D_DBG_NO_DITHER_TABLE)) return false;
     if (l.family != FIR_MX || l.unit < 0 || e->C != 2 || l.m.f.coop || l.m.f.mono2) return false;
     const int MB = l.t[0], NT = l.t[1], KIND = l.t[3], SBY = l.t[4], NPR = l.t[5], ND = l.t[6];
     if (!mx_dither_table(MB, NT, KIND, SBY, NPR, ND)) return false;
@@ -600,7 +646,7 @@ static int reserve_call_buffers(d2d_engine* e, const CallPlan& pl, hipStream_t s
     uint32_t first_file = 0;
     if (dither_table_serves(e, pl, prime, &first_file))
         HIPCHK(e, e->d_dither.reserve(sizeof(uint32_t) * e->C * dither_table_stride(e, pl), wait_stream(s)));
-    if (e->cascade() || e->noise_shape || e->route.fine) {
+    if (e->cascade() || e->noise_shape || e->route.fine || e->mixed()) {
         int rc = grow_scratch(e, (size_t)e->xs_hist + (e->poly ? pl.max_frames : pl.max_nx), s);
         if (rc) return rc;
     }
@@ -649,7 +695,7 @@ static int enqueue_jobs(d2d_engine* e, const d2d_file_io* io, const CallPlan& pl
             j.m0 = st.nres;
             j.nres = e->fc.resamp && !prime ? (uint32_t)(pf.nres1 - st.nres) : 0;
             const uint64_t i0 = e->fc.resamp ? st.nres : st.nfir;     // index the dither counter runs on
-            const uint64_t k = rng_key64(e->p.seed, e->c0 + c);
+            const uint64_t k = dither_key64(e->p.seed, e->c0 + c);
             j.rng_kstep = (uint32_t)k | 1u;
             j.rng_key = (uint32_t)(k >> 32) + (uint32_t)(i0 >> 32) * j.rng_kstep;
             j.rng_lo0 = (uint32_t)i0;
@@ -738,6 +784,9 @@ static int launch_call(d2d_engine* e, const CallPlan& pl, hipStream_t s, const b
         HIPCHK(e, launch_noise_shape(ns, s));
         e->ns_cur ^= 1;
     }
+    // the mix pass: where the noise-shaping pass runs, and like it not on a prime
+    if (e->mixed() && !prime)
+        HIPCHK(e, launch_mix(e->d_jobs, e->d_mix, e->C, n_files, e->poly ? max_frames : max_nx, e->poly ? e->poly->S : e->S, e->epi, s));
     HIPCHK(e, launch_history(e->d_jobs, e->nstreams, e->Cin, e->route.B, e->route.keep, s));
     if (ps) HIPCHK(e, hipEventRecord(ps->second, s));
     return D2D_OK;
@@ -911,7 +960,7 @@ int d2d_translate_batch_host(d2d_engine* e, d2d_file_io* io, uint32_t n_files, s
         // of it at once (4 B per stage-A sample, 8 more per output where the two combine; two int32 halves with 32-bit taps) within half of
         // the free device memory -- otherwise the sliced pipeline below, which needs one slice of scratch
         bool direct = max_L < (1ull << 31);
-        if (direct && (e->cascade() || e->noise_shape || e->route.fine)) {
+        if (direct && (e->cascade() || e->noise_shape || e->route.fine || e->mixed())) {
             size_t free_b = 0, total_b = 0;
             HIPCHK(e, hipMemGetInfo(&free_b, &total_b));
             const double per_stream = (double)max_L / (double)e->Mb * (e->cascade() && e->noise_shape ? 12.0 : e->route.fine ? 8.0 : 4.0);
@@ -994,7 +1043,7 @@ int d2d_translate_batch_host(d2d_engine* e, d2d_file_io* io, uint32_t n_files, s
 
 int d2d_peak(d2d_engine* e, uint32_t file, uint32_t channel, double* peak_out) {
     if (!e || !peak_out) return D2D_ERR_PARAM;
-    if (file >= e->n_files || channel >= e->C) return e->fail(D2D_ERR_PARAM, "file/channel out of range");
+    if (file >= e->n_files || channel >= e->Co) return e->fail(D2D_ERR_PARAM, "file/channel out of range");
     HIPCHK(e, hipSetDevice(e->p.device));
     HIPCHK(e, hipStreamSynchronize(e->last_stream));
     HIPCHK(e, hipMemcpy(peak_out, e->d_peak + (size_t)file * e->C + channel, sizeof(double), hipMemcpyDeviceToHost));
@@ -1004,7 +1053,7 @@ int d2d_peak(d2d_engine* e, uint32_t file, uint32_t channel, double* peak_out) {
 int d2d_peak_dbfs(d2d_engine* e, uint32_t file, float* dbfs_out) {
     if (!e || !dbfs_out) return D2D_ERR_PARAM;
     double m = 0.0;
-    for (uint32_t c = 0; c < e->C; ++c) {
+    for (uint32_t c = 0; c < e->Co; ++c) {
         double v = 0.0;
         int rc = d2d_peak(e, file, c, &v);
         if (rc) return rc;
@@ -1194,7 +1243,7 @@ uint64_t d2d_dither_table_calls(const d2d_engine* e) { return e ? e->dither_tabl
 const char* d2d_kernel_name(const d2d_engine* e) {
     if (!e) return "";
     if (!e->launched.empty()) return e->launched.c_str();      // what the last call launched; before the first call: what the dispatch will choose
-    if (e->kname.empty()) e->kname = route_kernel_name(e->route, e->fc, e->epi);
+    if (e->kname.empty()) e->kname = route_kernel_name(e->route, e->fc, e->plan_epi);
     return e->kname.c_str();
 }
 

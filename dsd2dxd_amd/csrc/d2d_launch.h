@@ -100,6 +100,10 @@ hipError_t launch_noise_shape(const NoiseShapeArgs& a, hipStream_t s);
 // tap_bits = 32: frames from the two scratch halves, v = 256 v_hi + v_lo + lo_bias, y = v * 2^-sbits (d2d_kernels.hip)
 hipError_t launch_fine_combine(const StreamJob* jobs, uint32_t nstreams, uint32_t max_nout, size_t lo_off, int64_t lo_bias, int sbits,
                                const Epilogue& epi, hipStream_t s);
+// a mixed engine's frames from its files' scratch lines: `mix` holds epi.channels x in_channels Q15 coefficients on the device, the lines hold
+// y * 2^scale_bits (mix/d2d_mix.hip)
+hipError_t launch_mix(const StreamJob* jobs, const int32_t* mix, uint32_t in_channels, uint32_t nfiles, uint32_t max_nout, int scale_bits,
+                      const Epilogue& epi, hipStream_t s);
 hipError_t launch_history(const StreamJob* jobs, uint32_t nstreams, uint32_t C, uint32_t B, uint32_t keep, hipStream_t s);
 // table[c * stride + i] = the dither word of channel c (of `channels`), output n0 + i, i < max_nout, on the keys of the job rows from `job0` on
 hipError_t launch_dither_words(const StreamJob* jobs, uint32_t job0, uint32_t channels, uint32_t max_nout, uint32_t* table, uint32_t stride, hipStream_t s);

@@ -255,6 +255,13 @@ Epilogue epilogue_of(const d2d_params& p) {
     return epi;
 }
 
+d2d_params mix_fir_params(const d2d_params& p) {
+    d2d_params q = p;
+    q.dither = D2D_DITHER_NOISE_SHAPED;
+    if (q.bit_depth == 32) q.bit_depth = 24;
+    return q;
+}
+
 FirArgs fir_args_static(const d2d_params& p, const FilterChoice& fc, const Epilogue& epi, const FirRoute& r, const d2d_filter_def* lo) {
     const d2d_filter_def& f = *fc.fir;
     const d2d_filter_def& fd = lo ? *lo : f;

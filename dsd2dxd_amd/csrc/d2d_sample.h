@@ -34,6 +34,19 @@ D2D_HD uint32_t dither_word(uint32_t lo, uint32_t key, uint32_t kstep, uint32_t 
     return lowbias32(lo + key + (lo < lo0 ? kstep : 0u));
 }
 
+// The generator's 64-bit key of one channel (oracle: orc_rng_key): the engine splits it into StreamJob::rng_key / rng_kstep per call, the
+// host twins hash an absolute index on it directly (dither_word_at == orc_rng).
+D2D_HD uint64_t dither_key64(uint64_t seed, uint32_t channel) {
+    uint64_t z = (seed ^ ((uint64_t)channel * 0xD1B54A32D192ED03ull)) + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+D2D_HD uint32_t dither_word_at(uint64_t key64, uint64_t n) {
+    const uint32_t kstep = (uint32_t)key64 | 1u;
+    return lowbias32((uint32_t)n + (uint32_t)(key64 >> 32) + (uint32_t)(n >> 32) * kstep);
+}
+
 // The dither of the integer depths as an integer `term` of the hash word: triangular d = term * 2^-16 - 1 with term = lo16 + hi16 + 1,
 // rectangular d = term * 2^-17 - 1/2 with term = 2 hi16 + 1 (both symmetric about zero, never zero-width at the ends)
 template <int KIND>

@@ -81,6 +81,7 @@ static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effor
     const size_t fb = d2d_frame_bytes(e), sb = sample_bytes(bit_depth);
     if (fb == 0 || fb % sb || fb / sb > 8) return fail(D2D_ERR_PARAM, "the engine's frames do not hold 1 to 8 channels of this bit depth");
     const uint32_t ch = (uint32_t)(fb / sb);
+    const uint32_t in_ch = d2d_input_channels(e);      // the reads and uploads move whole INPUT frames: wider than the PCM's on a mixed or channel-subset engine
     if (chunk == 0) chunk = 1u << 22;
     // the engine's device becomes this thread's current device (d2d_peak selects it and waits for the engine's pending work)
     double peak0 = 0.0;
@@ -94,9 +95,9 @@ static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effor
     Stream st;
     PinBuf h_in[2], h_out, h_res, h_chk;
     DevBuf d_in, d_new, d_pcm, d_out, d_ws;
-    FLAC_HIP(h_in[0].alloc(chunk * ch), "hipHostMalloc"); FLAC_HIP(h_in[1].alloc(chunk * ch), "hipHostMalloc");
+    FLAC_HIP(h_in[0].alloc(chunk * in_ch), "hipHostMalloc"); FLAC_HIP(h_in[1].alloc(chunk * in_ch), "hipHostMalloc");
     FLAC_HIP(h_out.alloc(out_cap), "hipHostMalloc"); FLAC_HIP(h_res.alloc(sizeof(d2d_flac_result)), "hipHostMalloc");
-    FLAC_HIP(d_in.alloc(chunk * ch), "hipMalloc"); FLAC_HIP(d_new.alloc(chunk_frames * fb), "hipMalloc");
+    FLAC_HIP(d_in.alloc(chunk * in_ch), "hipMalloc"); FLAC_HIP(d_new.alloc(chunk_frames * fb), "hipMalloc");
     FLAC_HIP(d_pcm.alloc(cap_frames * fb), "hipMalloc"); FLAC_HIP(d_out.alloc(out_cap), "hipMalloc"); FLAC_HIP(d_ws.alloc(ws_cap), "hipMalloc");
     d2d_flac_result* res = (d2d_flac_result*)h_res.p;
     if (check) FLAC_HIP(h_chk.alloc(sizeof(d2d_flac_check)), "hipHostMalloc");
@@ -140,7 +141,7 @@ static int convert_stream_flac(d2d_engine* e, uint32_t bit_depth, uint32_t effor
         // has none) and is copied behind the carry on the same stream
         d2d_file_io tio{};
         tio.dsd = d_in.p; tio.bytes_per_channel = L; tio.pcm = d_new.p; tio.pcm_capacity_bytes = d_new.bytes;
-        FLAC_HIP(hipMemcpyAsync(d_in.p, h_in[cur].p, L * ch, hipMemcpyHostToDevice, st.s), "hipMemcpyAsync");
+        FLAC_HIP(hipMemcpyAsync(d_in.p, h_in[cur].p, L * in_ch, hipMemcpyHostToDevice, st.s), "hipMemcpyAsync");
         if (d2d_translate_batch_device(e, &tio, 1, st.s) != D2D_OK) return fail(D2D_ERR_DEVICE, d2d_last_error(e));
         const size_t nf = tio.frames_out;
         if (md5) {                                                    // the chunk's new frames, where the translate call left them

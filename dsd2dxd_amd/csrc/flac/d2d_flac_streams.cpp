@@ -66,6 +66,7 @@ extern "C" int d2d_convert_streams_flac(d2d_engine* e, d2d_stream_io* io, uint32
     const size_t fb = d2d_frame_bytes(e), sb = sample_bytes(bit_depth);
     if (fb == 0 || fb % sb || fb / sb > 8) return fail(D2D_ERR_PARAM, "the engine's frames do not hold 1 to 8 channels of this bit depth");
     const uint32_t ch = (uint32_t)(fb / sb);
+    const uint32_t in_ch = d2d_input_channels(e);      // the reads and uploads move whole INPUT frames: wider than the PCM's on a mixed or channel-subset engine
     const bool verify = (opt->flags & D2D_STREAMS_VERIFY) != 0, md5 = (opt->flags & D2D_STREAMS_MD5) != 0;
     uint32_t rate = 0;
     bool any_loud = false, any_tpeak = false, totals = true;
@@ -99,7 +100,7 @@ extern "C" int d2d_convert_streams_flac(d2d_engine* e, d2d_stream_io* io, uint32
     for (uint32_t f = 0; f < n; ++f) chunk_frames = std::max(chunk_frames, d2d_next_frames(e, f, chunk));
     chunk_frames += 64;
     const size_t cap_frames = chunk_frames + BS;
-    const size_t in_slot = align16(chunk * ch), new_slot = align16(chunk_frames * fb), pcm_slot = align16(cap_frames * fb);
+    const size_t in_slot = align16(chunk * in_ch), new_slot = align16(chunk_frames * fb), pcm_slot = align16(cap_frames * fb);
     const size_t out_slot = align16(d2d_flac_bound_bytes(ch, bit_depth, cap_frames, 1)), ws_slot = d2d_flac_workspace_bytes(ch, bit_depth, cap_frames, 1);
     const size_t S = rate / 10, l_cap = 3 * S + chunk_frames, l_rows = S ? l_cap / S + 2 : 0, loud_slot = align16(l_cap * fb);
     const size_t cells_slot = l_rows * ch * sizeof(d2d_loud_cell), peaks_slot = align16(l_rows * ch * sizeof(double));
@@ -155,7 +156,7 @@ extern "C" int d2d_convert_streams_flac(d2d_engine* e, d2d_stream_io* io, uint32
         for (uint32_t f = 0; f < n; ++f) {
             const size_t L = (size_t)run[f].got;
             if (L > chunk) return file_fail(D2D_ERR_IO, f, "read callback returned more than it was asked for");
-            if (L) in_bytes = f * in_slot + L * ch;
+            if (L) in_bytes = f * in_slot + L * in_ch;
             tio[f] = d2d_file_io{};
             tio[f].dsd = d_in.p + f * in_slot; tio[f].bytes_per_channel = L; tio[f].pcm = d_new.p + f * new_slot; tio[f].pcm_capacity_bytes = new_slot;
         }

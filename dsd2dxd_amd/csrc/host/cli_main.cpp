@@ -8,6 +8,9 @@
 //   verify <file.flac>... read back FLAC files the sinks here wrote: every frame is decoded (d2d_flac_decode_host) and the frame numbers,
 //                         the sample count, the smallest and largest frame and -- where STREAMINFO has one -- the MD5 are checked; one
 //                         line per file, a non-zero exit if any is bad (no GPU needed)
+//   --downmix stereo|mono (convert and levels) fold a multichannel stream down inside the engine with the preset of the container's layout
+//                         (raw input: by channel count, 4 = quad); --mix "g,g,..;g,g,.." an explicit matrix of decimal gains, a row per
+//                         output channel (Rdsd2Pcm::set_downmix / set_mix); `levels --downmix` reports the folded peak
 // It is not the reference's CLI (logging, progress bars, Rayon pool are out of scope).
 #include <stdio.h>
 #include <stdlib.h>
@@ -21,6 +24,7 @@
 #include "../../../include/dsd2dxd_amd.h"
 #include "../../../include/rdsd2pcm.hpp"
 #include "../flac/flac_parse.h"
+#include "../mix/d2d_mix_text.h"
 #include "dsd_reader.h"
 #include "id3_tag.h"
 #include "md5.h"
@@ -186,6 +190,7 @@ int main(int argc, char** argv) {
     size_t channels = 2, bit_depth = 24; char fmt = 'I', filt = 'E', endian = 'M', dither = 0, output = 'S';
     uint32_t block = 4096, rate = 352800, inrate = 1; double level = 0.0; bool append = false, recurse = false, quiet = false;
     int device = 0; unsigned long long seed = 0; uint32_t tap_bits = 0; bool gpu_flac = false, flac_verify = false, flac_md5 = false, replaygain = false, loudness = false, true_peak = false, album = false; int flac_effort = 0;
+    uint32_t downmix = 0; std::vector<int32_t> mix; uint32_t mix_rows = 0, mix_cols = 0;
     std::vector<std::string> files;
     for (; ai < argc; ++ai) {
         std::string a = argv[ai];
@@ -218,6 +223,14 @@ int main(int argc, char** argv) {
         else if (a == "--loudness") loudness = true;               // levels only: integrated loudness behind each file's peak (Rdsd2Pcm::set_loudness)
         else if (a == "--true-peak") true_peak = true;             // convert with --replaygain: REPLAYGAIN_TRACK_PEAK is the true peak; levels: each file's true peak in dBTP (Rdsd2Pcm::set_true_peak)
         else if (a == "--album") album = true;                     // convert -o f only: all inputs of the command are one album (Rdsd2Pcm::convert_album): with --gpu-flac one engine for all, with --replaygain the REPLAYGAIN_ALBUM_* fields
+        else if (a == "--downmix") {                               // fold down with the preset of the layout (Rdsd2Pcm::set_downmix)
+            const std::string t = val();
+            downmix = t == "stereo" ? 2u : t == "mono" ? 1u : 0u;
+            if (!downmix) { fprintf(stderr, "ERROR: --downmix takes stereo or mono\n"); return 2; }
+        } else if (a == "--mix") {                                 // an explicit matrix, decimal gains rounded to Q15 (Rdsd2Pcm::set_mix)
+            std::string err;
+            if (!d2d::parse_mix_text(val(), mix, mix_rows, mix_cols, err)) { fprintf(stderr, "ERROR: --mix: %s\n", err.c_str()); return 2; }
+        }
         else files.push_back(a);
     }
     if (album && (levels || tolower(output) != 'f')) {
@@ -242,6 +255,10 @@ int main(int argc, char** argv) {
     }
     if (flac_verify && !(gpu_flac && tolower(output) == 'f')) {
         fprintf(stderr, "ERROR: --flac-verify checks the frames --gpu-flac encodes: it needs --gpu-flac and -o f\n");
+        return 2;
+    }
+    if (downmix && mix_rows) {
+        fprintf(stderr, "ERROR: --downmix and --mix both set the engine's one matrix: give one of them\n");
         return 2;
     }
     if (files.empty()) files.push_back("-");
@@ -276,6 +293,8 @@ int main(int argc, char** argv) {
                 Rdsd2Pcm lib = Rdsd2Pcm::new_level_check(rate, ip, ft, en, channels, block, inrate,
                                                          fl == FilterType::EquirippleCascade ? fl : FilterType::Equiripple);
                 lib.set_device(device); lib.set_loudness(loudness); lib.set_true_peak(true_peak);
+                if (downmix) lib.set_downmix(downmix);
+                if (mix_rows) lib.set_mix(mix_rows, mix);
                 float db = lib.check_level(CANCEL_FLAG);
                 if (!loudness) printf("%s: %.4f dBFS", lib.file_name().c_str(), db);
                 else if (lib.loudness_valid()) printf("%s: %.4f dBFS, %.2f LUFS", lib.file_name().c_str(), db, lib.loudness_lufs());
@@ -289,6 +308,8 @@ int main(int argc, char** argv) {
                                ? Rdsd2Pcm::from_container(bit_depth, ot, level, rate, od, dt, fl, append, ".", path)
                                : Rdsd2Pcm::create(bit_depth, ot, level, rate, od, dt, ft, en, inrate, block, channels, fl, append, ".", ip);
             lib.set_device(device); lib.set_seed(seed); lib.set_tap_bits(tap_bits); lib.set_gpu_flac(gpu_flac); lib.set_flac_effort(flac_effort); lib.set_flac_verify(flac_verify); lib.set_flac_md5(flac_md5); lib.set_replaygain(replaygain); lib.set_true_peak(true_peak);
+            if (downmix) lib.set_downmix(downmix);
+            if (mix_rows) lib.set_mix(mix_rows, mix);
             if (album) { tracks.push_back(std::move(lib)); continue; }
             lib.do_conversion(CANCEL_FLAG);
             if (!quiet && !lib.warnings().empty()) fprintf(stderr, "WARNING: %s: %s\n", lib.file_name().c_str(), lib.warnings().c_str());

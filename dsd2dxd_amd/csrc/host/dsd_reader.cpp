@@ -48,6 +48,7 @@ static std::string probe_dsf(FILE* f, DsdInfo& o) {
     if (memcmp(m, "fmt ", 4) || le64(m + 4) != 52) return "DSF: bad 'fmt ' chunk";
     if (le32(m + 12) != 1) return "DSF: unsupported format version";
     if (le32(m + 16) != 0) return "DSF: unsupported format id (not raw DSD)";
+    o.dsf_channel_type = le32(m + 20);
     o.channels = le32(m + 24);
     o.sample_rate = le32(m + 28);
     const uint32_t bps = le32(m + 32);
@@ -114,6 +115,12 @@ static std::string probe_dff(FILE* f, DsdInfo& o) {
                 } else if (!memcmp(sc, "CHNL", 4)) {
                     uint8_t v[2];
                     if (fread(v, 1, 2, f) == 2) { o.channels = be16(v); have_ch = true; }
+                    o.dff_channel_ids.clear();
+                    for (uint64_t k = 0; k < o.channels && k < 64 && 2 + 4 * (k + 1) <= ssz; ++k) {
+                        char id[4];
+                        if (fread(id, 1, 4, f) != 4) break;
+                        o.dff_channel_ids.emplace_back(id, 4);
+                    }
                 } else if (!memcmp(sc, "CMPR", 4)) {
                     uint8_t v[4];
                     if (fread(v, 1, 4, f) == 4 && memcmp(v, "DSD ", 4)) return "DFF: compressed (DST) audio is not supported";

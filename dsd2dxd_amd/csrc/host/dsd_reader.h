@@ -37,6 +37,10 @@ struct DsdInfo {
     uint64_t metadata_offset = 0;     // DSF ID3 pointer / DFF 'ID3 ' chunk offset, 0 = none
     bool metadata_truncated = false;  // tag claims more bytes than the file holds
     std::string warning;
+    // the channel layout as the container states it: DSF's channel type (fmt chunk: 1 mono, 2 stereo, 3 L R C, 4 quad, 5 L R C LFE, 6 5.0,
+    // 7 5.1; 0 = not a DSF) and DFF's CHNL ids in order ("SLFT", "SRGT", "C   ", "LFE ", "LS  ", "RS  ", "MLFT", "MRGT", "C000"...)
+    uint32_t dsf_channel_type = 0;
+    std::vector<std::string> dff_channel_ids;
 };
 
 DsdFileFormat format_from_path(const std::string& path);     // by extension, like DsdFileFormat::from(&path)

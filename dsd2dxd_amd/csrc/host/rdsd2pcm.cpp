@@ -51,7 +51,18 @@ struct Rdsd2Pcm::Impl {
     double dsp_s = 0.0, audio_s = 0.0;
     std::string tag_warning;
     int artwork_copied = 0;
+    // set_downmix / set_mix: rows x prm.channels Q15 coefficients the engine folds the channels with (d2d_create_mix); empty: no mix
+    std::vector<int32_t> mix;
+    uint32_t mix_rows = 0;
+    uint32_t out_channels() const { return mix_rows ? mix_rows : prm.channels; }      // what sinks, tags and meters see
 };
+
+// the engine of a run: d2d_create, or d2d_create_mix where a mix is set
+static int create_engine(const Rdsd2Pcm::Impl& im, uint32_t n_files, d2d_engine** e) {
+    if (!im.mix_rows) return d2d_create(&im.prm, n_files, e);
+    const d2d_mix m{(uint32_t)sizeof(d2d_mix), im.mix_rows, im.mix.data()};
+    return d2d_create_mix(&im.prm, &m, n_files, e);
+}
 
 static uint32_t dither_code(DitherType d) { return d == DitherType::TPDF ? 'T' : d == DitherType::Rectangular ? 'R' : d == DitherType::FPD ? 'F' : d == DitherType::NoiseShaped ? 'N' : 'X'; }
 static uint32_t filter_code(FilterType f) {
@@ -159,6 +170,54 @@ bool Rdsd2Pcm::loudness_valid() const { return p_->loud_result.valid != 0; }
 double Rdsd2Pcm::loudness_lufs() const { return p_->loud_result.lufs; }
 void Rdsd2Pcm::set_true_peak(bool on) { p_->true_peak = on; }
 double Rdsd2Pcm::true_peak_dbtp() const { return 20.0 * log10(p_->true_peak_value); }
+// The container's layout as a D2D_MIX_LAYOUT_*; for raw input and stdin the channel count decides (4 channels: quad).  0xFFFFFFFF: a
+// container whose layout no preset serves.
+static uint32_t layout_of(const DsdInfo& info) {
+    const uint32_t none = 0xFFFFFFFFu;
+    if (info.format == d2dhost::DsdFileFormat::Dsf) {
+        static const uint32_t by_type[8] = {none, none, D2D_MIX_LAYOUT_STEREO, D2D_MIX_LAYOUT_LRC, D2D_MIX_LAYOUT_QUAD, D2D_MIX_LAYOUT_LRC_LFE,
+                                            D2D_MIX_LAYOUT_5_0, D2D_MIX_LAYOUT_5_1};
+        return info.dsf_channel_type < 8 ? by_type[info.dsf_channel_type] : none;
+    }
+    if (info.format == d2dhost::DsdFileFormat::Dff) {
+        std::string ids;
+        for (const std::string& id : info.dff_channel_ids) ids += id + "|";
+        if (ids == "SLFT|SRGT|") return D2D_MIX_LAYOUT_STEREO;
+        if (ids == "SLFT|SRGT|C   |") return D2D_MIX_LAYOUT_LRC;
+        if (ids == "SLFT|SRGT|LS  |RS  |") return D2D_MIX_LAYOUT_QUAD;
+        if (ids == "SLFT|SRGT|C   |LFE |") return D2D_MIX_LAYOUT_LRC_LFE;
+        if (ids == "MLFT|MRGT|C   |LS  |RS  |" || ids == "SLFT|SRGT|C   |LS  |RS  |") return D2D_MIX_LAYOUT_5_0;
+        if (ids == "MLFT|MRGT|C   |LFE |LS  |RS  |" || ids == "SLFT|SRGT|C   |LFE |LS  |RS  |") return D2D_MIX_LAYOUT_5_1;
+        return none;
+    }
+    return D2D_MIX_LAYOUT_AUTO;
+}
+
+void Rdsd2Pcm::set_downmix(uint32_t target) {
+    if (target == 0) { p_->mix.clear(); p_->mix_rows = 0; return; }
+    const uint32_t layout = layout_of(p_->info);
+    if (layout == 0xFFFFFFFFu) throw std::runtime_error("Invalid downmix: " + file_name() + " states a channel layout no preset serves (use an explicit mix)");
+    std::vector<int32_t> coef(2 * (size_t)std::max<uint32_t>(p_->prm.channels, 1));
+    uint32_t rows = 0;
+    if (d2d_mix_preset(p_->prm.channels, layout, target, coef.data(), &rows) != D2D_OK) throw std::runtime_error(d2d_mix_error());
+    coef.resize((size_t)rows * p_->prm.channels);
+    set_mix(rows, coef);
+}
+
+void Rdsd2Pcm::set_mix(uint32_t rows, const std::vector<int32_t>& coef) {
+    if (rows == 0) { p_->mix.clear(); p_->mix_rows = 0; return; }
+    if (coef.size() != (size_t)rows * p_->prm.channels) throw std::runtime_error("Invalid mix: it needs rows x channels coefficients, one column per channel of the stream");
+    Impl probe = *p_;
+    probe.mix = coef; probe.mix_rows = rows;
+    // a dry creation, as in validate_engine: the engine's own message for every refusal; a missing GPU is reported when the run starts
+    d2d_engine* e = nullptr;
+    const int rc = create_engine(probe, 1, &e);
+    if (rc == D2D_OK) d2d_destroy(e);
+    else if (rc != D2D_ERR_DEVICE) throw std::runtime_error(d2d_create_error());
+    p_->mix = coef; p_->mix_rows = rows;
+}
+uint32_t Rdsd2Pcm::output_channels() const { return p_->out_channels(); }
+
 void Rdsd2Pcm::set_flac_effort(int effort) {
     if (effort != D2D_FLAC_EFFORT_FIXED2 && effort != D2D_FLAC_EFFORT_SEARCH && effort != D2D_FLAC_EFFORT_LPC) throw std::runtime_error("Invalid FLAC effort; must be 0, 1 or 12");
     p_->flac_effort = (uint32_t)effort;
@@ -234,7 +293,7 @@ static PcmSink* open_output(Rdsd2Pcm::Impl& im, const DsdInfo& info, bool album)
         // -p: artwork next to the sources follows them into the output tree (README.md:115-119)
         if (im.out_dir) im.artwork_copied = d2dhost::copy_artwork(dirname_of(*im.in_path), dirname_of(im.out_path));
     }
-    err = open_sink((d2dhost::OutputType)(int)im.output, im.out_path, im.prm.channels, im.prm.output_rate, im.prm.bit_depth, &sink, &tag, im.replaygain, im.true_peak, album);
+    err = open_sink((d2dhost::OutputType)(int)im.output, im.out_path, im.out_channels(), im.prm.output_rate, im.prm.bit_depth, &sink, &tag, im.replaygain, im.true_peak, album);
     if (!err.empty()) throw std::runtime_error(err);
     sink->set_flac_effort(im.flac_effort);
     return sink;
@@ -256,11 +315,11 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
     if (!levels) sink = open_output(im, info, false);
     std::unique_ptr<PcmSink> sink_guard(sink);
     d2d_engine* e = nullptr;
-    if (d2d_create(&im.prm, 1, &e) != D2D_OK) throw std::runtime_error(d2d_create_error());
+    if (create_engine(im, 1, &e) != D2D_OK) throw std::runtime_error(d2d_create_error());
     RunCtx ctx; ctx.src = &src; ctx.sink = sink; ctx.cancel = &cancel; ctx.sender = &sender;
     std::unique_ptr<LoudFeed> feed;
     if (levels && (im.loudness || im.true_peak)) {
-        feed.reset(new LoudFeed(im.prm.channels, im.prm.bit_depth, im.prm.output_rate, im.true_peak));
+        feed.reset(new LoudFeed(im.out_channels(), im.prm.bit_depth, im.prm.output_rate, im.true_peak));
         if (!feed->error().empty()) { d2d_destroy(e); throw std::runtime_error(feed->error()); }
         ctx.feed = feed.get();
     }
@@ -277,7 +336,7 @@ static float run(Rdsd2Pcm::Impl& im, const std::atomic<bool>& cancel, ProgressSe
         d2d_flac_check check{};
         uint8_t digest[16];
         d2d_loud* meter = nullptr;
-        if (im.replaygain && d2d_loud_create(im.prm.channels, im.prm.output_rate, nullptr, &meter) != D2D_OK) rc = D2D_ERR_PARAM;
+        if (im.replaygain && d2d_loud_create(im.out_channels(), im.prm.output_rate, nullptr, &meter) != D2D_OK) rc = D2D_ERR_PARAM;
         else if (meter && im.true_peak && d2d_loud_set_true_peak(meter, 1) != D2D_OK) { rc = D2D_ERR_PARAM; d2d_loud_destroy(meter); }
         else if (meter) {
             // measured where the PCM is, on the stream that made it
@@ -356,6 +415,7 @@ static std::string album_difference(const Rdsd2Pcm::Impl& a, const Rdsd2Pcm::Imp
     ALBUM_SAME(a.flac_md5 == b.flac_md5, "FLAC MD5 switch");
     ALBUM_SAME(a.replaygain == b.replaygain, "ReplayGain switch");
     ALBUM_SAME(a.true_peak == b.true_peak, "true-peak switch");
+    ALBUM_SAME(a.mix_rows == b.mix_rows && a.mix == b.mix, "mix");
 #undef ALBUM_SAME
     return "";
 }
@@ -416,7 +476,7 @@ void Rdsd2Pcm::convert_album(std::vector<Rdsd2Pcm>& tracks, const std::atomic<bo
     std::vector<uint64_t> samples(n, 0);
     if (first.gpu_flac) {
         d2d_engine* e = nullptr;
-        if (d2d_create(&prm, n, &e) != D2D_OK) throw std::runtime_error(d2d_create_error());
+        if (create_engine(first, n, &e) != D2D_OK) throw std::runtime_error(d2d_create_error());
         size_t chunk = 0;                                               // the batch driver's default, in whole planar blocks (it is a multiple of 4096)
         const size_t B = prm.fmt == D2D_FMT_PLANAR ? prm.block_size : 1;
         if (B > 1 && ((size_t)1 << 19) % B) chunk = std::max(B, ((size_t)1 << 19) / B * B);
@@ -430,7 +490,7 @@ void Rdsd2Pcm::convert_album(std::vector<Rdsd2Pcm>& tracks, const std::atomic<bo
             io[t].total_bytes_per_channel = srcs[t]->info().bytes_per_channel;
             if (replaygain) {
                 d2d_loud* h = nullptr;
-                if (d2d_loud_create(prm.channels, prm.output_rate, nullptr, &h) != D2D_OK) { msg = d2d_flac_error(); break; }
+                if (d2d_loud_create(first.out_channels(), prm.output_rate, nullptr, &h) != D2D_OK) { msg = d2d_flac_error(); break; }
                 own.m.push_back(h);
                 if (true_peak && d2d_loud_set_true_peak(h, 1) != D2D_OK) { msg = d2d_flac_error(); break; }
                 io[t].loud = h;
@@ -464,7 +524,7 @@ void Rdsd2Pcm::convert_album(std::vector<Rdsd2Pcm>& tracks, const std::atomic<bo
         uint64_t before = 0;
         for (uint32_t t = 0; t < n && msg.empty(); ++t) {
             d2d_engine* e = nullptr;
-            if (d2d_create(&prm, 1, &e) != D2D_OK) throw std::runtime_error(d2d_create_error());
+            if (create_engine(first, 1, &e) != D2D_OK) throw std::runtime_error(d2d_create_error());
             struct Progress { ProgressSender* s; uint64_t before, mine, total; } pg{&sender, before, srcs[t]->info().bytes_per_channel, total};
             auto progress = [](void* u, float pct) {
                 Progress* p = (Progress*)u;

@@ -1,8 +1,10 @@
 // rdsd2pcm_c.cpp -- include/rdsd2pcm_c.h over include/rdsd2pcm.hpp: exceptions become codes + a thread-local message.
 #include "../../../include/rdsd2pcm_c.h"
+#include "../../../include/rdsd2pcm_mix_c.h"
 
 #include <atomic>
 #include <string>
+#include <vector>
 
 #include "../../../include/dsd2dxd_amd.h"
 #include "../../../include/rdsd2pcm.hpp"
@@ -97,6 +99,16 @@ int d2dh_new_level_check(uint32_t output_rate, const char* path, uint32_t fmt, u
 }
 
 void d2dh_free(d2dh_conv* c) { delete c; }
+
+// include/rdsd2pcm_mix_c.h
+int d2dh_set_downmix(d2dh_conv* c, uint32_t target) {
+    if (!c) { g_err = "null argument"; return D2D_ERR_PARAM; }
+    return guarded([&] { c->obj.set_downmix(target); });
+}
+int d2dh_set_mix(d2dh_conv* c, uint32_t rows, const int32_t* coef, size_t count) {
+    if (!c || (rows && !coef)) { g_err = "null argument"; return D2D_ERR_PARAM; }
+    return guarded([&] { c->obj.set_mix(rows, rows ? std::vector<int32_t>(coef, coef + count) : std::vector<int32_t>()); });
+}
 
 int d2dh_do_conversion(d2dh_conv* c, const volatile int* cancel, d2dh_progress_fn progress, void* user) {
     if (!c) { g_err = "null object"; return D2D_ERR_PARAM; }

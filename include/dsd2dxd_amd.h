@@ -34,7 +34,8 @@ extern "C" {
                              *     d2d_convert_stream_flac_loud; the d2d_true_peak_measure_* calls, d2d_tpeak_io and the meter's
                              *     d2d_loud_set_true_peak / _add_true_peaks / _true_peak; D2D_DBG_NO_DITHER_TABLE and d2d_dither_table_calls;
                              *     the d2d_segments_* calls, d2d_convert_streams_flac with d2d_stream_io / d2d_streams_options, and
-                             *     d2d_loud_finish_album / d2d_loud_true_peak_album */
+                             *     d2d_loud_finish_album / d2d_loud_true_peak_album; the channel matrix: d2d_mix, d2d_create_mix, d2d_get_mix,
+                             *     d2d_input_channels, d2d_mix_preset with D2D_MIX_LAYOUT_*, d2d_mix_frames_host, d2d_mix_error */
 
 /* status codes */
 enum {
@@ -246,6 +247,52 @@ int d2d_prime(d2d_engine* e, const uint8_t* dsd, size_t bytes_per_channel);
  * and `pcm_capacity_bytes` are ignored and may be NULL / 0; frames_out is set to 0.  A file with bytes_per_channel = 0
  * is left as it is.  Asynchronous on `hip_stream`. */
 int d2d_prime_batch_device(d2d_engine* e, d2d_file_io* io, uint32_t n_files, void* hip_stream);
+
+/* ---- the channel matrix: fold a multichannel stream down inside the engine (added under ABI 11) ---- */
+
+/* A mixed engine converts every one of params->channels input channels and emits frames of `out_channels` channels:
+ * output o of a frame is sum_c coef[o * channels + c] / 32768 * (channel c's filtered sample), formed on the exact integer
+ * FIR sums BEFORE level, dither and requantisation -- v_o = sum_c m[o][c] x_c is a 64-bit integer, y_o = v_o * 2^-(S+15)
+ * exactly, and from y_o on channel o gets the arithmetic of every other path, its dither word keyed by (seed, OUTPUT
+ * channel o, frame index).  DESIGN.md section 4.5b has the definition; 32768 times the identity gives the unmixed engine's
+ * bytes and peaks.  Bounds (D2D_ERR_PARAM): 1 <= out_channels <= channels, |m| <= 2^17, every row's sum of |m| <= 2^21;
+ * a row of zeros is allowed.  Refused with a message that names the reason: the noise-shaped dither, tap_bits = 32, a
+ * channel subset (D2D_ERR_PARAM), and every configuration whose filter runs a second stage -- DSD256 -> 96 kHz, DSD512 ->
+ * 48 kHz multiples, filter 'S' (D2D_ERR_FILTER).  d2d_frame_bytes, the capacity checks and d2d_peak (channel <
+ * out_channels) follow out_channels; seek, prime, tell, the batch entry points and the whole-stream drivers work as on
+ * any engine.  mix = NULL is d2d_create. */
+typedef struct d2d_mix {
+    uint32_t struct_size;      /* sizeof(d2d_mix) */
+    uint32_t out_channels;     /* rows */
+    const int32_t* coef;       /* out_channels x params->channels, row-major, Q15 */
+} d2d_mix;
+int d2d_create_mix(const d2d_params* params, const d2d_mix* mix, uint32_t n_files, d2d_engine** out);
+/* The engine's mix: *out_channels = its rows (0: the engine does not mix) and, when coef is not NULL, the rows x channels
+ * coefficients (capacity in int32; D2D_ERR_CAPACITY when they do not fit). */
+int d2d_get_mix(const d2d_engine* e, uint32_t* out_channels, int32_t* coef, size_t capacity);
+/* Channels of the engine's INPUT layout (params->channels): what a read callback fills per byte-per-channel, whatever the
+ * width of the PCM frames (a mix, a channel subset). */
+uint32_t d2d_input_channels(const d2d_engine* e);
+/* The fold-down presets.  Columns in container order; the LFE is dropped; every row sums to at most 32768, so the fold
+ * cannot clip where no single channel could.  target 2: rows Lo, Ro; target 1: one row, floor((Lo + Ro) / 2) per column.
+ *   D2D_MIX_LAYOUT_5_1 (FL FR C LFE BL BR)  Lo 13573 0 9597 0 9597 0   Ro 0 13573 9597 0 0 9597
+ *   D2D_MIX_LAYOUT_5_0 (FL FR C BL BR)      the same without the LFE column
+ *   D2D_MIX_LAYOUT_QUAD (FL FR BL BR)       Lo 19195 0 13573 0         Ro 0 19195 0 13573
+ *   D2D_MIX_LAYOUT_LRC (FL FR C), _LRC_LFE  Lo 19195 0 13573 (0)       Ro 0 19195 13573 (0)
+ *   D2D_MIX_LAYOUT_STEREO (FL FR)           target 1 only: 16384 16384
+ * D2D_MIX_LAYOUT_AUTO chooses by in_channels: 2 stereo, 3 L R C, 4 quad, 5 5.0, 6 5.1.  coef holds 2 * in_channels int32.
+ * D2D_ERR_PARAM (message: d2d_mix_error) for a layout that does not have in_channels channels, no preset, or a bad target. */
+enum { D2D_MIX_LAYOUT_AUTO = 0, D2D_MIX_LAYOUT_STEREO = 2, D2D_MIX_LAYOUT_LRC = 3, D2D_MIX_LAYOUT_QUAD = 4, D2D_MIX_LAYOUT_5_0 = 5,
+       D2D_MIX_LAYOUT_5_1 = 6, D2D_MIX_LAYOUT_LRC_LFE = 7 };
+int d2d_mix_preset(uint32_t in_channels, uint32_t layout, uint32_t target, int32_t* coef, uint32_t* out_channels);
+/* The CPU twin of the mix pass, compiled from the kernel's own header; no device.  sums: channel c's exact integer FIR sums
+ * of `frames` consecutive frames at sums[c * stride .. ], scale 2^-scale_bits; the first frame has index first_index (the
+ * dither counter).  Writes `frames` interleaved frames of mix->out_channels samples to pcm and raises peaks[o] (when not
+ * NULL; the caller zeroes them) to max |y_o * gain|.  bit_depth, dither (T / R / F / X), level_db and seed as in d2d_params. */
+int d2d_mix_frames_host(const int32_t* sums, size_t stride, size_t frames, uint32_t in_channels, int32_t scale_bits, const d2d_mix* mix,
+                        uint32_t bit_depth, uint32_t dither, double level_db, uint64_t seed, uint64_t first_index,
+                        void* pcm, size_t pcm_capacity_bytes, double* peaks);
+const char* d2d_mix_error(void);
 
 /* ---- whole-stream driver ------------------------------------------------------------------ */
 

@@ -119,6 +119,15 @@ class Rdsd2Pcm {
     // value afterwards (-inf for silence).
     void set_true_peak(bool on);
     double true_peak_dbtp() const;
+    // Fold the stream's channels down inside the engine, between the FIR sums and the requantiser (d2d_create_mix, include/dsd2dxd_amd.h;
+    // not a reference option).  set_downmix(2) / (1): the stereo / mono preset of the container's layout (DSF channel type, DFF CHNL ids; for
+    // raw input the channel count decides, 4 channels being quad); a container whose layout no preset serves throws.  set_mix: rows x
+    // channels Q15 coefficients, row-major -- swaps, polarity, mid/side.  Either throws the engine's own message for what d2d_create_mix
+    // refuses.  0 rows / target 0: no mix.  Sinks, tags, ReplayGain, set_gpu_flac, convert_album and check_level then see
+    // output_channels() channels; check_level returns the folded peak.  Without them nothing changes by a byte.
+    void set_downmix(uint32_t target);
+    void set_mix(uint32_t rows, const std::vector<int32_t>& coef);
+    uint32_t output_channels() const;
 
     struct Impl;                              // opaque state (public only so the .cpp's helpers can name it)
 

@@ -86,6 +86,9 @@ mod ffi {
         pub fn d2dh_set_device(c: *mut Conv, device: c_int);
         pub fn d2dh_find_dsd_files(paths: *const *const c_char, n: usize, recurse: c_int, each: Option<PathFn>, user: *mut c_void) -> c_int;
         pub fn d2dh_last_error() -> *const c_char;
+        // include/rdsd2pcm_mix_c.h
+        pub fn d2dh_set_downmix(c: *mut Conv, target: u32) -> c_int;
+        pub fn d2dh_set_mix(c: *mut Conv, rows: u32, coef: *const i32, count: usize) -> c_int;
     }
 }
 
@@ -192,4 +195,16 @@ impl Rdsd2Pcm {
 
     /// extension: pin this object's work to a GPU, e.g. `rayon::current_thread_index().unwrap_or(0) % n_gpus`
     pub fn set_device(&mut self, device: i32) { unsafe { ffi::d2dh_set_device(self.h, device as c_int) } }
+
+    /// extension: fold the channels down inside the engine with the preset of the container's layout; 2 = stereo, 1 = mono, 0 = no mix
+    pub fn set_downmix(&mut self, target: u32) -> Result<(), String> {
+        if unsafe { ffi::d2dh_set_downmix(self.h, target) } != 0 { return Err(last_error()); }
+        Ok(())
+    }
+
+    /// extension: an explicit matrix, `rows` x channels Q15 coefficients (32768 = 1.0), row-major
+    pub fn set_mix(&mut self, rows: u32, coef: &[i32]) -> Result<(), String> {
+        if unsafe { ffi::d2dh_set_mix(self.h, rows, coef.as_ptr(), coef.len()) } != 0 { return Err(last_error()); }
+        Ok(())
+    }
 }
