@@ -19,5 +19,6 @@ from ._capi import (D2DError, Engine, FileIO, Info, Params, lib, library_path, b
                     Segment, PackSrc, PACK_GAVE_UP, segments_move_host, segments_move_device, segments_pack_host, segments_pack_device,
                     StreamIO, StreamsOptions, STREAMS_VERIFY, STREAMS_MD5, loud_finish_album, loud_true_peak_album,
                     Mix, MIX_UNITY, mix_preset, mix_frames_host,
+                    HalfJob, half_taps, half_frames_host, half_frames_device,
                     MIX_LAYOUT_AUTO, MIX_LAYOUT_STEREO, MIX_LAYOUT_LRC, MIX_LAYOUT_QUAD, MIX_LAYOUT_5_0, MIX_LAYOUT_5_1, MIX_LAYOUT_LRC_LFE,
                     FLAC_BAD_NONE, FLAC_BAD_SIZE, FLAC_BAD_HEADER, FLAC_BAD_CRC8, FLAC_BAD_CRC16, FLAC_BAD_UNSUPPORTED, FLAC_BAD_SYNTAX, FLAC_BAD_LENGTH, FLAC_BAD_SAMPLES)

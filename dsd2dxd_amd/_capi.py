@@ -198,7 +198,8 @@ EXPORTS = ["d2d_create", "d2d_create_error", "d2d_destroy", "d2d_reset", "d2d_la
            "d2d_loud_true_peak", "d2d_dither_table_calls",
            "d2d_segments_move_device", "d2d_segments_move_host", "d2d_segments_pack_device", "d2d_segments_pack_host",
            "d2d_convert_streams_flac", "d2d_loud_finish_album", "d2d_loud_true_peak_album",
-           "d2d_create_mix", "d2d_get_mix", "d2d_input_channels", "d2d_mix_preset", "d2d_mix_frames_host", "d2d_mix_error"]
+           "d2d_create_mix", "d2d_get_mix", "d2d_input_channels", "d2d_mix_preset", "d2d_mix_frames_host", "d2d_mix_error",
+           "d2d_create_half", "d2d_half_factor", "d2d_half_taps", "d2d_half_frames_host", "d2d_half_frames_device", "d2d_half_error"]
 
 _lib = None
 
@@ -326,6 +327,14 @@ def lib():
         L.d2d_mix_frames_host.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_int32, C.POINTER(Mix), C.c_uint32, C.c_uint32,
                                           C.c_double, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]
         L.d2d_mix_error.restype = C.c_char_p
+    if hasattr(L, "d2d_create_half"):             # (as above: an older tree's build lacks the halved engine)
+        L.d2d_create_half.argtypes = [C.POINTER(Params), C.c_uint32, C.POINTER(C.c_void_p)]
+        L.d2d_half_factor.argtypes = [C.c_void_p]
+        L.d2d_half_factor.restype = C.c_uint32
+        L.d2d_half_taps.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_size_t]
+        L.d2d_half_frames_host.argtypes = [C.POINTER(HalfJob), C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64]
+        L.d2d_half_frames_device.argtypes = L.d2d_half_frames_host.argtypes + [C.c_void_p]
+        L.d2d_half_error.restype = C.c_char_p
     _lib = L
     return L
 
@@ -362,6 +371,61 @@ def mix_frames_host(sums, scale_bits, coef, bit_depth=24, dither="X", level_db=0
     if rc:
         raise D2DError(rc, lib().d2d_mix_error().decode())
     return out[:frames * fb], peaks[:m.out_channels]
+
+
+class HalfJob(C.Structure):
+    """d2d_half_job: one file of a call of the 2:1 decimator on its own (d2d_half_frames_host / _device)"""
+    _fields_ = [("sums", C.c_void_p), ("stride", C.c_size_t), ("n", C.c_size_t), ("first_index", C.c_uint64),
+                ("pcm", C.c_void_p), ("pcm_capacity_bytes", C.c_size_t), ("peaks", C.c_void_p), ("frames_out", C.c_size_t)]
+
+
+def half_taps():
+    """d2d_half_taps: (the decimator's taps as a list of integers, T): h[j] = q[j] * 2^-T"""
+    nt, t = C.c_uint32(), C.c_uint32()
+    rc = lib().d2d_half_taps(C.byref(nt), C.byref(t), None, 0)
+    if not rc:
+        taps = (C.c_int32 * nt.value)()
+        rc = lib().d2d_half_taps(C.byref(nt), C.byref(t), taps, nt.value)
+    if rc:
+        raise D2DError(rc, lib().d2d_half_error().decode())
+    return list(taps), t.value
+
+
+def _sample_bytes(bit_depth):
+    return 2 if bit_depth == 16 else 4 if bit_depth == 32 else 3
+
+
+def half_frames_host(lines, first_index, scale_bits, bit_depth=24, dither="X", level_db=0.0, seed=0, capacity=None):
+    """d2d_half_frames_host, the CPU twin of the half pass.  lines: one int32 array (channels, NT - 1 + n) per file -- the carried sums, then
+    the n new ones; first_index: one absolute index of the first new sum per file.  Returns [(frame bytes as a uint8 array, peaks per channel)]
+    per file.  capacity: bytes of every file's buffer (default: what its frames need).  No device."""
+    import numpy as np
+    nt = len(half_taps()[0])
+    xs = [np.ascontiguousarray(x, dtype=np.int32) for x in lines]
+    channels = xs[0].shape[0]
+    fb = channels * _sample_bytes(bit_depth)
+    jobs = (HalfJob * len(xs))()
+    outs, peaks = [], []
+    for j, x, first in zip(jobs, xs, first_index):
+        n = x.shape[1] - (nt - 1)
+        frames = ((first + n + 1) >> 1) - ((first + 1) >> 1)
+        cap = frames * fb if capacity is None else capacity
+        outs.append(np.zeros(max(cap, 1), dtype=np.uint8))
+        peaks.append(np.zeros(channels, dtype=np.float64))
+        j.sums, j.stride, j.n, j.first_index = x.ctypes.data, x.shape[1], n, first
+        j.pcm, j.pcm_capacity_bytes, j.peaks = outs[-1].ctypes.data, cap, peaks[-1].ctypes.data
+    rc = lib().d2d_half_frames_host(jobs, len(xs), channels, scale_bits, bit_depth, ord(dither.upper()), level_db, seed)
+    if rc:
+        raise D2DError(rc, lib().d2d_half_error().decode())
+    return [(o[:j.frames_out * fb], p) for o, p, j in zip(outs, peaks, jobs)]
+
+
+def half_frames_device(jobs, channels, scale_bits, bit_depth=24, dither="X", level_db=0.0, seed=0, stream=None):
+    """d2d_half_frames_device: jobs a ctypes array of HalfJob with GPU-addressable sums, pcm and peaks; one launch on `stream`
+    (hipStream_t int), returns once it has finished; every frames_out is filled."""
+    rc = lib().d2d_half_frames_device(jobs, len(jobs), channels, scale_bits, bit_depth, ord(dither.upper()), level_db, seed, C.c_void_p(stream or 0))
+    if rc:
+        raise D2DError(rc, lib().d2d_half_error().decode())
 
 
 def _flac_check(rc):
@@ -644,12 +708,17 @@ class Engine:
     """One conversion context = one Rdsd2Pcm of the reference (src/main.rs:325-342), or a batch of
     `n_files` of them advanced together."""
 
-    def __init__(self, n_files=1, mix=None, **kw):
-        """mix: rows x channels Q15 integers (d2d_create_mix): the engine folds its channels into len(mix) output channels"""
+    def __init__(self, n_files=1, mix=None, half=False, **kw):
+        """mix: rows x channels Q15 integers (d2d_create_mix): the engine folds its channels into len(mix) output channels.
+        half: d2d_create_half -- output_rate is 44100 or 48000, made by the exact 2:1 decimator behind the FIR of twice that rate"""
         L = lib()
         self.params = make_params(**kw)
         h = C.c_void_p()
-        if mix is not None:
+        if half:
+            if mix is not None:
+                raise D2DError(-1, "44100 / 48000 output does not combine with a mix")
+            rc = L.d2d_create_half(C.byref(self.params), n_files, C.byref(h))
+        elif mix is not None:
             m, keep = _mix_struct(mix, self.params.channels)
             rc = L.d2d_create_mix(C.byref(self.params), C.byref(m), n_files, C.byref(h))
         else:
@@ -684,6 +753,15 @@ class Engine:
         self._check(lib().d2d_get_info(self._h, C.byref(i)))
         return dict(M=i.decimation, ntaps=i.ntaps, S=i.scale_bits, L=i.resamp_L, P=i.resamp_P,
                     kernel=i.kernel, filter=i.filter_name.decode())
+
+    @classmethod
+    def create_half(cls, n_files=1, **kw):
+        """d2d_create_half: a halved engine (output_rate 44100 or 48000)"""
+        return cls(n_files=n_files, half=True, **kw)
+
+    def half_factor(self):
+        """2 for an engine of d2d_create_half, else 0"""
+        return lib().d2d_half_factor(self._h)
 
     def get_mix(self):
         """d2d_get_mix: the engine's mix as a list of rows of Q15 integers, or None for an engine that does not mix"""

@@ -32,6 +32,7 @@
 #include "d2d_sample.h"
 #include "d2d_tables.h"
 #include "mix/d2d_mix.h"
+#include "half/d2d_half.h"
 
 using namespace d2d;
 
@@ -154,6 +155,12 @@ struct d2d_engine {
     d2d_params plan_p{};
     Epilogue plan_epi{};
     Buf<int32_t> d_mix;
+    // d2d_create_half: p.output_rate is 44100 or 48000.  The FIR pass is the 'N' dither's integer pass of TWICE that rate (plan_p, fc, route: all
+    // of the doubled rate), its sums go to the scratch behind the HALF_HIST carried ones (xs_hist), and the half pass (half/d2d_half.hip) makes the
+    // frames: (n + 1) >> 1 of them after n sums
+    bool half = false;
+    uint64_t sums_at(uint64_t nfir, uint64_t nres) const { return fc.resamp ? nres : nfir; }          // the count the frames are numbered by ...
+    uint64_t frames_at(uint64_t nfir, uint64_t nres) const { return half ? half_frames_after(sums_at(nfir, nres)) : sums_at(nfir, nres); }   // ... and the frames
     FirRoute route;            // which kernel, table layout and staging serve this engine (d2d_route.h: choose_route)
     MfmaLayout mfma{};
     mutable std::string kname; // d2d_kernel_name's answer before the first call
@@ -268,6 +275,25 @@ static int validate_mix(const d2d_params& p, const std::vector<int32_t>& m, uint
     return D2D_OK;
 }
 
+// what d2d_create_half refuses beyond d2d_create, before the filter choice: the decimator reads exact int32 sums of whole files' channels and
+// its frames go straight to the requantiser
+static int validate_half(const d2d_params& p, std::string& err) {
+    if (p.output_rate != 44100 && p.output_rate != 48000) { err = "Invalid output rate; a halved engine makes 44100 or 48000"; return D2D_ERR_RATE; }
+    if (p.dsd_rate != 1 && p.dsd_rate != 2 && p.dsd_rate != 4 && p.dsd_rate != 8) { err = "Invalid DSD rate; must be 1, 2, 4 or 8"; return D2D_ERR_PARAM; }
+    if (p.dsd_rate == 8) { err = "44100 / 48000 output: DSD512 input has no 88200 / 96000 form to halve"; return D2D_ERR_RATE; }
+    if (p.dsd_rate == 4 && p.output_rate == 48000) {
+        err = "48000 output needs DSD64 or DSD128 input: DSD256 -> 96000 runs a second stage, whose sums are not 32-bit integers"; return D2D_ERR_RATE;
+    }
+    if (p.filter == 'S') { err = "44100 / 48000 output: the two-stage equiripple filter's sums are not 32-bit integers; use filter E"; return D2D_ERR_FILTER; }
+    if (p.filter == 'D') { err = "44100 / 48000 output: the dsd2pcm filter has no 88200 form to halve (DSD64 input and 352800 output only)"; return D2D_ERR_FILTER; }
+    if (p.dither == 'N') { err = "44100 / 48000 output does not combine with the noise-shaped dither; use T, R, F or X"; return D2D_ERR_PARAM; }
+    if (p.tap_bits == 32) { err = "44100 / 48000 output does not combine with 32-bit taps"; return D2D_ERR_PARAM; }
+    if (p.channel_first != 0 || (p.channel_count != 0 && p.channel_count != p.channels)) {
+        err = "44100 / 48000 output does not combine with a channel subset"; return D2D_ERR_PARAM;
+    }
+    return D2D_OK;
+}
+
 // what a stream that has not started yet holds as history
 static uint8_t idle_byte(const d2d_engine* e) { return e->p.endianness == D2D_MSB_FIRST ? IDLE_BYTE : (uint8_t)0x96; }  // 0x69 bit-reversed
 
@@ -330,13 +356,17 @@ static void build_launch_state(d2d_engine* e) {
 static int init_engine(d2d_engine* e) {
     int rc = validate(e->p, e->err);
     if (rc == D2D_OK && e->mixed()) rc = validate_mix(e->p, e->mix, e->Co, e->err);
-    if (rc == D2D_OK) rc = choose_filters(e->p, e->fc, e->err);
+    if (rc == D2D_OK && e->half) rc = validate_half(e->p, e->err);
+    if (rc != D2D_OK) return rc;
+    e->plan_p = e->half ? half_fir_params(e->p) : e->mixed() ? mix_fir_params(e->p) : e->p;
+    rc = choose_filters(e->plan_p, e->fc, e->err);        // (plan_p differs from p in the rate only for a halved engine: the doubled one)
     // a mix reads exact int32 sums: a configuration whose filter choice has a stage B (DSD256 -> 96 kHz, DSD512 -> 48 kHz multiples, filter 'S')
     // has 64-bit ones
     if (rc == D2D_OK && e->mixed() && e->fc.resamp && !e->fc.poly)
         return e->fail(D2D_ERR_FILTER, "a mix needs a single-pass filter: this configuration runs a second stage (DSD256 -> 96 kHz, DSD512 -> 48 kHz "
                                        "multiples, filter S), whose sums are not 32-bit integers");
-    e->plan_p = e->mixed() ? mix_fir_params(e->p) : e->p;
+    if (rc == D2D_OK && e->half && e->fc.resamp && !e->fc.poly)
+        return e->fail(D2D_ERR_RATE, "44100 / 48000 output needs a single-pass filter at the doubled rate: this one runs a second stage");
     if (rc == D2D_OK) rc = choose_route(e->plan_p, e->fc, e->route, e->err);
     if (rc != D2D_OK) return rc;
     const d2d_filter_def& f = *e->fc.fir;
@@ -400,7 +430,8 @@ static int init_engine(d2d_engine* e) {
         e->xs_hist = (uint32_t)e->fc.resamp->P;
     }
     if (e->mixed()) HIPCHK(e, e->d_mix.upload(e->mix.data(), e->mix.size() * sizeof(int32_t)));
-    if (e->route.fine || e->cascade() || e->noise_shape || e->mixed())
+    if (e->half) e->xs_hist = HALF_HIST;
+    if (e->route.fine || e->cascade() || e->noise_shape || e->mixed() || e->half)
         HIPCHK(e, e->d_scratch.alloc(sizeof(int32_t) * ((size_t)e->xs_hist + 4096) * e->nstreams * (e->route.fine ? 2u : 1u)));
     if (e->noise_shape) {
         for (int i = 0; i < 2; ++i) HIPCHK(e, e->d_ns[i].alloc(sizeof(double) * 2 * e->nstreams));
@@ -424,7 +455,12 @@ const char* d2d_create_error(void) { return g_create_error.c_str(); }
 
 int d2d_create(const d2d_params* params, uint32_t n_files, d2d_engine** out) { return d2d_create_mix(params, nullptr, n_files, out); }
 
-int d2d_create_mix(const d2d_params* params, const d2d_mix* mix, uint32_t n_files, d2d_engine** out) {
+static int create_engine(const d2d_params* params, const d2d_mix* mix, const bool half, uint32_t n_files, d2d_engine** out);
+int d2d_create_mix(const d2d_params* params, const d2d_mix* mix, uint32_t n_files, d2d_engine** out) { return create_engine(params, mix, false, n_files, out); }
+int d2d_create_half(const d2d_params* params, uint32_t n_files, d2d_engine** out) { return create_engine(params, nullptr, true, n_files, out); }
+uint32_t d2d_half_factor(const d2d_engine* e) { return e && e->half ? 2u : 0u; }
+
+static int create_engine(const d2d_params* params, const d2d_mix* mix, const bool half, uint32_t n_files, d2d_engine** out) {
     if (out) *out = nullptr;
     if (!params || !out) { g_create_error = "null argument"; return D2D_ERR_PARAM; }
     if (mix && mix->struct_size != sizeof(d2d_mix)) { g_create_error = "d2d_mix.struct_size mismatch"; return D2D_ERR_PARAM; }
@@ -439,6 +475,7 @@ int d2d_create_mix(const d2d_params* params, const d2d_mix* mix, uint32_t n_file
     memcpy(&e->p, params, params->struct_size);
     e->p.struct_size = sizeof(d2d_params);
     e->n_files = n_files;
+    e->half = half;
     if (mix) {
         // (the bounds come first: nothing is read past what they admit; validate_mix repeats them with the other refusals, in d2d_create's order)
         const char* why = mix_check(e->p.channels, mix->out_channels, mix->coef);
@@ -486,6 +523,7 @@ size_t d2d_next_frames(const d2d_engine* e, uint32_t file, size_t L) {
     if (!e || file >= e->n_files) return 0;
     const FileState& f = e->files[file];
     uint64_t nfir1 = (f.pos + L) / (uint64_t)e->Mb;
+    if (e->half) return (size_t)(e->frames_at(nfir1, res_outputs_after(e, nfir1)) - e->frames_at(f.nfir, f.nres));
     return e->fc.resamp ? (size_t)(res_outputs_after(e, nfir1) - f.nres) : (size_t)(nfir1 - f.nfir);
 }
 
@@ -525,7 +563,7 @@ int d2d_tell(const d2d_engine* e, uint32_t file, uint64_t* pos, uint64_t* next_f
     if (!e || file >= e->n_files) return D2D_ERR_PARAM;
     const FileState& st = e->files[file];
     if (pos) *pos = st.pos;
-    if (next_frame) *next_frame = e->fc.resamp ? st.nres : st.nfir;
+    if (next_frame) *next_frame = e->frames_at(st.nfir, st.nres);
     return D2D_OK;
 }
 
@@ -534,8 +572,12 @@ int d2d_tell(const d2d_engine* e, uint32_t file, uint64_t* pos, uint64_t* next_f
 //   composed polyphase: the carried history is sized for exactly this (d2d_create: keep);
 //   cascade: frame F(p) reads stage-A outputs no older than p / Mb - P - 1; the oldest of them ends no earlier than
 //   p - Mb - P Mb and its window reaches Wb further back: Wb + (P + 1) Mb.
+//   halved engine: frame F(p) reads the HALF_HIST sums in front of its newest one, each of which needs what the above says of an output:
+//   HALF_HIST more steps of Mb bytes (single filter), or of Mp / (8 Lp) bytes, rounded up (composed polyphase: Lp outputs per Mp bits).
 size_t d2d_preroll_bytes(const d2d_engine* e) {
     if (!e) return 0;
+    if (e->half && e->poly) return e->route.keep + ((size_t)HALF_HIST * (size_t)e->poly->Mp + 8u * (size_t)e->poly->Lp - 1u) / (8u * (size_t)e->poly->Lp) + 1u;
+    if (e->half) return (size_t)e->Wb + ((size_t)HALF_HIST + 1u) * (size_t)e->Mb;
     if (e->poly) return e->route.keep;
     if (e->cascade()) return (size_t)e->Wb + ((size_t)e->fc.resamp->P + 1) * (size_t)e->Mb;
     return (size_t)e->Wb + (size_t)e->Mb;
@@ -560,6 +602,7 @@ struct CallPlan {
     struct File { uint64_t nfir1, nres1, nframes; };     // FIR / stage-B outputs once the call is done, frames the call yields
     std::vector<File> files;
     uint32_t max_nx = 0, max_frames = 0, max_L = 0;      // the longest file's FIR outputs, frames and bytes per channel
+    uint32_t max_sums = 0;                               // halved engine: the longest file's new sums (a prime has them too, and no frames)
     bool run_fir = false;
     bool mono2 = false;                                  // the call goes through the mono pair
 };
@@ -572,7 +615,7 @@ static int plan_call(d2d_engine* e, d2d_file_io* io, const bool prime, CallPlan&
     const uint32_t n_files = e->n_files;
     // a prime runs a FIR only where its outputs carry over: stage A of the cascade.  Every other engine's prime plans no outputs at all (max_nx,
     // max_frames = 0), which is what keeps the FIR passes, the mono pair and the combining pass out of it.
-    pl.run_fir = !prime || e->cascade();
+    pl.run_fir = !prime || e->cascade() || e->half;
     pl.files.resize(n_files);
     // MONO2: every file's call splits into two equal halves of whole outputs and whole 16-byte chunks, long enough to hold the second half's history
     pl.mono2 = e->mono2_ok();
@@ -585,7 +628,8 @@ static int plan_call(d2d_engine* e, d2d_file_io* io, const bool prime, CallPlan&
         pf.nfir1 = (st.pos + L) / (uint64_t)e->Mb;
         pf.nres1 = res_outputs_after(e, pf.nfir1);
         const uint64_t nx = pl.run_fir ? pf.nfir1 - st.nfir : 0;
-        const uint64_t frames = prime ? 0 : e->fc.resamp ? pf.nres1 - st.nres : nx;
+        const uint64_t sums = e->sums_at(pf.nfir1, pf.nres1) - e->sums_at(st.nfir, st.nres);
+        const uint64_t frames = prime ? 0 : e->half ? e->frames_at(pf.nfir1, pf.nres1) - e->frames_at(st.nfir, st.nres) : e->fc.resamp ? pf.nres1 - st.nres : nx;
         pf.nframes = frames;
         if (frames * fb > io[f].pcm_capacity_bytes) return e->fail(D2D_ERR_CAPACITY, "pcm buffer too small");
         if (frames && (!io[f].pcm || ((uintptr_t)io[f].pcm & 15))) return e->fail(D2D_ERR_PARAM, "pcm device pointer must be non-null and 16-byte aligned");
@@ -594,6 +638,7 @@ static int plan_call(d2d_engine* e, d2d_file_io* io, const bool prime, CallPlan&
                                           "(cut the stream at multiples of d2d_slice_align_bytes)");
         pl.max_nx = std::max<uint32_t>(pl.max_nx, (uint32_t)nx);
         pl.max_frames = std::max<uint32_t>(pl.max_frames, (uint32_t)frames);
+        if (e->half) pl.max_sums = std::max<uint32_t>(pl.max_sums, (uint32_t)sums);
         pl.max_L = std::max<uint32_t>(pl.max_L, (uint32_t)L);
         if (pl.mono2) {     // (a mono engine: file f is stream f, and the job's nout is the FIR's)
             const uint64_t half = L / 2, nout = pf.nfir1 - st.nfir;
@@ -625,7 +670,7 @@ static uint32_t dither_table_stride(const d2d_engine* e, const CallPlan& pl) {
 // all start at the same index.  first_file: one of them, whose job rows hold the keys and the index.
 static bool dither_table_serves(const d2d_engine* e, const CallPlan& pl, const bool prime, uint32_t* first_file) {
     const FirLaunch& l = e->launch.fir;
-    if (prime || e->poly || e->mixed() || pl.mono2 || !pl.run_fir || pl.max_nx == 0 || (e->p.debug_flags & D2D_DBG_NO_DITHER_TABLE)) return false;
+    if (prime || e->poly || e->mixed() || e->half || pl.mono2 || !pl.run_fir || pl.max_nx == 0 || (e->p.debug_flags & D2D_DBG_NO_DITHER_TABLE)) return false;
     if (l.family != FIR_MX || l.unit < 0 || e->C != 2 || l.m.f.coop || l.m.f.mono2) return false;
     const int MB = l.t[0], NT = l.t[1], KIND = l.t[3], SBY = l.t[4], NPR = l.t[5], ND = l.t[6];
     if (!mx_dither_table(MB, NT, KIND, SBY, NPR, ND)) return false;
@@ -646,8 +691,8 @@ static int reserve_call_buffers(d2d_engine* e, const CallPlan& pl, hipStream_t s
     uint32_t first_file = 0;
     if (dither_table_serves(e, pl, prime, &first_file))
         HIPCHK(e, e->d_dither.reserve(sizeof(uint32_t) * e->C * dither_table_stride(e, pl), wait_stream(s)));
-    if (e->cascade() || e->noise_shape || e->route.fine || e->mixed()) {
-        int rc = grow_scratch(e, (size_t)e->xs_hist + (e->poly ? pl.max_frames : pl.max_nx), s);
+    if (e->cascade() || e->noise_shape || e->route.fine || e->mixed() || e->half) {
+        int rc = grow_scratch(e, (size_t)e->xs_hist + (e->half ? pl.max_sums : e->poly ? pl.max_frames : pl.max_nx), s);
         if (rc) return rc;
     }
     if (!prime && e->noise_shape && e->cascade()) {
@@ -694,7 +739,7 @@ static int enqueue_jobs(d2d_engine* e, const d2d_file_io* io, const CallPlan& pl
             j.och = c;
             j.m0 = st.nres;
             j.nres = e->fc.resamp && !prime ? (uint32_t)(pf.nres1 - st.nres) : 0;
-            const uint64_t i0 = e->fc.resamp ? st.nres : st.nfir;     // index the dither counter runs on
+            const uint64_t i0 = e->frames_at(st.nfir, st.nres);      // index the dither counter runs on
             const uint64_t k = dither_key64(e->p.seed, e->c0 + c);
             j.rng_kstep = (uint32_t)k | 1u;
             j.rng_key = (uint32_t)(k >> 32) + (uint32_t)(i0 >> 32) * j.rng_kstep;
@@ -732,6 +777,7 @@ static int launch_fir_pass(d2d_engine* e, const FirLaunch& p, uint32_t max_nout,
 static int launch_call(d2d_engine* e, const CallPlan& pl, hipStream_t s, const bool prime) {
     const LaunchState& l = e->launch;
     const uint32_t n_files = e->n_files, max_nx = pl.max_nx, max_frames = pl.max_frames;
+    const uint32_t px_nout = e->half ? pl.max_sums : max_frames;       // what the composed polyphase pass makes: frames, or a halved engine's sums
     EventPairs::Pair* ps = nullptr;
     if (e->profiling && (max_nx || (prime && pl.max_L))) HIPCHK(e, e->step.open(s, &ps));
     if (e->route.deinterleave) HIPCHK(e, launch_deinterleave(e->d_jobs, n_files, e->Cin, e->C, pl.max_L, s));
@@ -751,10 +797,10 @@ static int launch_call(d2d_engine* e, const CallPlan& pl, hipStream_t s, const b
             rc = launch_fir_pass(e, f, max_nx, s);
             if (!rc) ++e->dither_table_calls;
         } else
-            rc = e->poly ? launch_fir_pass(e, l.fir, max_frames, s) : pl.mono2 ? launch_fir_pass(e, l.fir_m2, max_nx / 2, s) : launch_fir_pass(e, l.fir, max_nx, s);
+            rc = e->poly ? launch_fir_pass(e, l.fir, px_nout, s) : pl.mono2 ? launch_fir_pass(e, l.fir_m2, max_nx / 2, s) : launch_fir_pass(e, l.fir, max_nx, s);
         if (rc) return rc;
     }
-    if ((e->poly ? max_frames : max_nx) && d2d_last_launched_kernel) e->launched = d2d_last_launched_kernel;
+    if ((e->poly ? px_nout : max_nx) && d2d_last_launched_kernel) e->launched = d2d_last_launched_kernel;
     if (e->route.fine && max_nx) {
         // second pass: the residual taps, into the second half of the scratch
         int rc = launch_fir_pass(e, l.fir_lo, max_nx, s);
@@ -787,6 +833,11 @@ static int launch_call(d2d_engine* e, const CallPlan& pl, hipStream_t s, const b
     // the mix pass: where the noise-shaping pass runs, and like it not on a prime
     if (e->mixed() && !prime)
         HIPCHK(e, launch_mix(e->d_jobs, e->d_mix, e->C, n_files, e->poly ? max_frames : max_nx, e->poly ? e->poly->S : e->S, e->epi, s));
+    // the half pass: where the mix pass runs, not on a prime; the sums it carries move to the front of their lines on every call that made some
+    if (e->half && pl.max_sums) {
+        if (!prime) HIPCHK(e, launch_half(e->d_jobs, e->C, n_files, pl.max_sums, e->poly ? e->poly->S : e->S, e->epi, s));
+        HIPCHK(e, launch_half_hist(e->d_jobs, e->nstreams, s));
+    }
     HIPCHK(e, launch_history(e->d_jobs, e->nstreams, e->Cin, e->route.B, e->route.keep, s));
     if (ps) HIPCHK(e, hipEventRecord(ps->second, s));
     return D2D_OK;
@@ -960,7 +1011,7 @@ int d2d_translate_batch_host(d2d_engine* e, d2d_file_io* io, uint32_t n_files, s
         // of it at once (4 B per stage-A sample, 8 more per output where the two combine; two int32 halves with 32-bit taps) within half of
         // the free device memory -- otherwise the sliced pipeline below, which needs one slice of scratch
         bool direct = max_L < (1ull << 31);
-        if (direct && (e->cascade() || e->noise_shape || e->route.fine || e->mixed())) {
+        if (direct && (e->cascade() || e->noise_shape || e->route.fine || e->mixed() || e->half)) {
             size_t free_b = 0, total_b = 0;
             HIPCHK(e, hipMemGetInfo(&free_b, &total_b));
             const double per_stream = (double)max_L / (double)e->Mb * (e->cascade() && e->noise_shape ? 12.0 : e->route.fine ? 8.0 : 4.0);

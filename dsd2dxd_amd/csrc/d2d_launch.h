@@ -108,5 +108,10 @@ hipError_t launch_history(const StreamJob* jobs, uint32_t nstreams, uint32_t C, 
 // table[c * stride + i] = the dither word of channel c (of `channels`), output n0 + i, i < max_nout, on the keys of the job rows from `job0` on
 hipError_t launch_dither_words(const StreamJob* jobs, uint32_t job0, uint32_t channels, uint32_t max_nout, uint32_t* table, uint32_t stride, hipStream_t s);
 hipError_t launch_xhist(const StreamJob* jobs, uint32_t nstreams, uint32_t P, hipStream_t s);
+// a halved engine's frames from its files' scratch lines (half/d2d_half.hip): job row f * channels + c holds channel c's line (xs: the new
+// sums, HALF_HIST carried ones in front), n0 / nout: the first new sum's index and their count, the dither keys of the first FRAME's index;
+// the lines hold y * 2^scale_bits.  launch_half_hist then moves every line's last HALF_HIST sums to its front, as launch_xhist does
+hipError_t launch_half(const StreamJob* jobs, uint32_t channels, uint32_t nfiles, uint32_t max_sums, int scale_bits, const Epilogue& epi, hipStream_t s);
+hipError_t launch_half_hist(const StreamJob* jobs, uint32_t nstreams, hipStream_t s);
 
 }  // namespace d2d

@@ -262,6 +262,14 @@ d2d_params mix_fir_params(const d2d_params& p) {
     return q;
 }
 
+// a halved engine's FIR pass: the 'N' dither's integer pass of twice the final rate (every kernel it reaches is one the unhalved engine of
+// that rate reaches)
+d2d_params half_fir_params(const d2d_params& p) {
+    d2d_params q = mix_fir_params(p);
+    q.output_rate = p.output_rate * 2u;
+    return q;
+}
+
 FirArgs fir_args_static(const d2d_params& p, const FilterChoice& fc, const Epilogue& epi, const FirRoute& r, const d2d_filter_def* lo) {
     const d2d_filter_def& f = *fc.fir;
     const d2d_filter_def& fd = lo ? *lo : f;

@@ -57,6 +57,7 @@ Epilogue epilogue_of(const d2d_params& p);
 // The parameters a MIXED engine's FIR pass is planned with (d2d_create_mix): the 'N' dither's integer pass of the same shape, so that every FIR
 // kernel a mix can reach is one the noise shaper already reaches.  Float output plans as 24 bits ('N' at 32 bits would be 'X': frames).
 d2d_params mix_fir_params(const d2d_params& p);
+d2d_params half_fir_params(const d2d_params& p);      // ... and of a halved engine (d2d_create_half): the same at twice the output rate
 // Every choice of d2d_create, in its order.  D2D_OK, or the error of a configuration nothing serves with its text in `err`.
 int choose_route(const d2d_params& p, const FilterChoice& fc, FirRoute& r, std::string& err);
 uint32_t route_table_variant(const FirRoute& r);

@@ -282,6 +282,7 @@ int main(int argc, char** argv) {
         for (auto& f : files) { if (f == "-") has_stdin = true; else paths.push_back(f); }
         std::vector<std::string> expanded = find_dsd_files(paths, recurse);
         if (has_stdin) expanded.insert(expanded.begin(), "-");
+        const bool half = rate == 44100 || rate == 48000;                  // extension: the halved rates, through the exact 2:1 decimator behind the FIR (Rdsd2Pcm::create_half)
         float overall = -INFINITY;
         std::vector<Rdsd2Pcm> tracks;                                      // --album: every input, converted together behind the loop
         for (auto& path : expanded) {
@@ -290,8 +291,9 @@ int main(int argc, char** argv) {
             std::optional<std::string> ip; if (!is_stdin) ip = path;
             if (levels) {
                 // (the reference's level check is always the equiripple filter, whatever -t says; -t S chooses which of its two definitions)
-                Rdsd2Pcm lib = Rdsd2Pcm::new_level_check(rate, ip, ft, en, channels, block, inrate,
-                                                         fl == FilterType::EquirippleCascade ? fl : FilterType::Equiripple);
+                const FilterType lf = fl == FilterType::EquirippleCascade ? fl : FilterType::Equiripple;
+                Rdsd2Pcm lib = half ? Rdsd2Pcm::new_level_check_half(rate, ip, ft, en, channels, block, inrate, lf)
+                                    : Rdsd2Pcm::new_level_check(rate, ip, ft, en, channels, block, inrate, lf);
                 lib.set_device(device); lib.set_loudness(loudness); lib.set_true_peak(true_peak);
                 if (downmix) lib.set_downmix(downmix);
                 if (mix_rows) lib.set_mix(mix_rows, mix);
@@ -304,9 +306,11 @@ int main(int argc, char** argv) {
                 if (!std::isnan(db) && db > overall) overall = db;          // dsd_levels/main.rs:184-202 skips NaN
                 continue;
             }
-            Rdsd2Pcm lib = (!is_stdin && DsdFileFormat::from(path).is_container())
-                               ? Rdsd2Pcm::from_container(bit_depth, ot, level, rate, od, dt, fl, append, ".", path)
-                               : Rdsd2Pcm::create(bit_depth, ot, level, rate, od, dt, ft, en, inrate, block, channels, fl, append, ".", ip);
+            const bool container = !is_stdin && DsdFileFormat::from(path).is_container();
+            Rdsd2Pcm lib = container ? (half ? Rdsd2Pcm::from_container_half(bit_depth, ot, level, rate, od, dt, fl, append, ".", path)
+                                             : Rdsd2Pcm::from_container(bit_depth, ot, level, rate, od, dt, fl, append, ".", path))
+                                     : (half ? Rdsd2Pcm::create_half(bit_depth, ot, level, rate, od, dt, ft, en, inrate, block, channels, fl, append, ".", ip)
+                                             : Rdsd2Pcm::create(bit_depth, ot, level, rate, od, dt, ft, en, inrate, block, channels, fl, append, ".", ip));
             lib.set_device(device); lib.set_seed(seed); lib.set_tap_bits(tap_bits); lib.set_gpu_flac(gpu_flac); lib.set_flac_effort(flac_effort); lib.set_flac_verify(flac_verify); lib.set_flac_md5(flac_md5); lib.set_replaygain(replaygain); lib.set_true_peak(true_peak);
             if (downmix) lib.set_downmix(downmix);
             if (mix_rows) lib.set_mix(mix_rows, mix);

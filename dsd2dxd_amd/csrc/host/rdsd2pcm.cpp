@@ -54,11 +54,14 @@ struct Rdsd2Pcm::Impl {
     // set_downmix / set_mix: rows x prm.channels Q15 coefficients the engine folds the channels with (d2d_create_mix); empty: no mix
     std::vector<int32_t> mix;
     uint32_t mix_rows = 0;
+    // create_half / from_container_half / new_level_check_half: prm.output_rate is 44100 or 48000 and the engine is d2d_create_half's
+    bool half = false;
     uint32_t out_channels() const { return mix_rows ? mix_rows : prm.channels; }      // what sinks, tags and meters see
 };
 
-// the engine of a run: d2d_create, or d2d_create_mix where a mix is set
+// the engine of a run: d2d_create, d2d_create_mix where a mix is set, d2d_create_half for a converter of the halved rates (set_mix keeps a mix away from it)
 static int create_engine(const Rdsd2Pcm::Impl& im, uint32_t n_files, d2d_engine** e) {
+    if (im.half) return d2d_create_half(&im.prm, n_files, e);
     if (!im.mix_rows) return d2d_create(&im.prm, n_files, e);
     const d2d_mix m{(uint32_t)sizeof(d2d_mix), im.mix_rows, im.mix.data()};
     return d2d_create_mix(&im.prm, &m, n_files, e);
@@ -89,11 +92,11 @@ static std::string rate_suffix(uint32_t rate) {
     return b;
 }
 
-static void validate_engine(const d2d_params& p) {
+static void validate_engine(const d2d_params& p, const bool half) {
     // a dry creation surfaces every parameter error with the engine's own message; a missing GPU is
     // reported later, when the conversion actually starts
     d2d_engine* e = nullptr;
-    int rc = d2d_create(&p, 1, &e);
+    int rc = half ? d2d_create_half(&p, 1, &e) : d2d_create(&p, 1, &e);
     if (rc == D2D_OK) { d2d_destroy(e); return; }
     if (rc == D2D_ERR_DEVICE) return;
     throw std::runtime_error(d2d_create_error());
@@ -108,7 +111,23 @@ Rdsd2Pcm Rdsd2Pcm::create(size_t bit_depth, OutputType output, double level_db, 
                           std::optional<std::string> out_dir, DitherType dither, FmtType fmt, Endianness endian,
                           uint32_t dsd_rate, uint32_t block_size, size_t channels, FilterType filter,
                           bool append_rate, std::string base_dir, std::optional<std::string> in_path) {
+    return make(false, bit_depth, output, level_db, output_rate, std::move(out_dir), dither, fmt, endian, dsd_rate, block_size, channels, filter, append_rate,
+                std::move(base_dir), std::move(in_path));
+}
+Rdsd2Pcm Rdsd2Pcm::create_half(size_t bit_depth, OutputType output, double level_db, uint32_t output_rate,
+                               std::optional<std::string> out_dir, DitherType dither, FmtType fmt, Endianness endian,
+                               uint32_t dsd_rate, uint32_t block_size, size_t channels, FilterType filter,
+                               bool append_rate, std::string base_dir, std::optional<std::string> in_path) {
+    return make(true, bit_depth, output, level_db, output_rate, std::move(out_dir), dither, fmt, endian, dsd_rate, block_size, channels, filter, append_rate,
+                std::move(base_dir), std::move(in_path));
+}
+
+Rdsd2Pcm Rdsd2Pcm::make(bool half, size_t bit_depth, OutputType output, double level_db, uint32_t output_rate,
+                        std::optional<std::string> out_dir, DitherType dither, FmtType fmt, Endianness endian,
+                        uint32_t dsd_rate, uint32_t block_size, size_t channels, FilterType filter,
+                        bool append_rate, std::string base_dir, std::optional<std::string> in_path) {
     auto im = std::make_unique<Impl>();
+    im->half = half;
     d2d_params& p = im->prm;
     p.struct_size = sizeof(p);
     p.dsd_rate = dsd_rate; p.output_rate = output_rate; p.channels = (uint32_t)channels;
@@ -122,18 +141,29 @@ Rdsd2Pcm Rdsd2Pcm::create(size_t bit_depth, OutputType output, double level_db, 
     if (im->in_path && im->info.format == d2dhost::DsdFileFormat::Unknown) im->info.format = d2dhost::DsdFileFormat::Raw;
     im->info.channels = p.channels; im->info.dsd_rate = dsd_rate; im->info.planar = p.fmt == D2D_FMT_PLANAR;
     im->info.msb_first = p.endianness == D2D_MSB_FIRST; im->info.block_size = block_size;
-    validate_engine(p);
+    validate_engine(p, half);
     return Rdsd2Pcm(std::move(im));
 }
 
 Rdsd2Pcm Rdsd2Pcm::from_container(size_t bit_depth, OutputType output, double level_db, uint32_t output_rate,
                                   std::optional<std::string> out_dir, DitherType dither, FilterType filter,
                                   bool append_rate, std::string base_dir, std::string path) {
+    return make_from_container(false, bit_depth, output, level_db, output_rate, std::move(out_dir), dither, filter, append_rate, std::move(base_dir), std::move(path));
+}
+Rdsd2Pcm Rdsd2Pcm::from_container_half(size_t bit_depth, OutputType output, double level_db, uint32_t output_rate,
+                                       std::optional<std::string> out_dir, DitherType dither, FilterType filter,
+                                       bool append_rate, std::string base_dir, std::string path) {
+    return make_from_container(true, bit_depth, output, level_db, output_rate, std::move(out_dir), dither, filter, append_rate, std::move(base_dir), std::move(path));
+}
+
+Rdsd2Pcm Rdsd2Pcm::make_from_container(bool half, size_t bit_depth, OutputType output, double level_db, uint32_t output_rate,
+                                       std::optional<std::string> out_dir, DitherType dither, FilterType filter,
+                                       bool append_rate, std::string base_dir, std::string path) {
     DsdInfo info;
     std::string err = probe(path, info);
     if (!err.empty()) throw std::runtime_error(err);
     // the container's own layout replaces the command-line flags (README.md:103-105)
-    Rdsd2Pcm r = create(bit_depth, output, level_db, output_rate, std::move(out_dir), dither,
+    Rdsd2Pcm r = make(half, bit_depth, output, level_db, output_rate, std::move(out_dir), dither,
                         info.planar ? FmtType::Planar : FmtType::Interleaved,
                         info.msb_first ? Endianness::MsbFirst : Endianness::LsbFirst, info.dsd_rate, info.block_size,
                         info.channels, filter, append_rate, std::move(base_dir), path);
@@ -143,11 +173,20 @@ Rdsd2Pcm Rdsd2Pcm::from_container(size_t bit_depth, OutputType output, double le
 
 Rdsd2Pcm Rdsd2Pcm::new_level_check(uint32_t output_rate, std::optional<std::string> path, FmtType fmt, Endianness endian,
                                    size_t channels, uint32_t block_size, uint32_t input_rate, FilterType filter) {
+    return make_level_check(false, output_rate, std::move(path), fmt, endian, channels, block_size, input_rate, filter);
+}
+Rdsd2Pcm Rdsd2Pcm::new_level_check_half(uint32_t output_rate, std::optional<std::string> path, FmtType fmt, Endianness endian,
+                                        size_t channels, uint32_t block_size, uint32_t input_rate, FilterType filter) {
+    return make_level_check(true, output_rate, std::move(path), fmt, endian, channels, block_size, input_rate, filter);
+}
+
+Rdsd2Pcm Rdsd2Pcm::make_level_check(bool half, uint32_t output_rate, std::optional<std::string> path, FmtType fmt, Endianness endian,
+                                    size_t channels, uint32_t block_size, uint32_t input_rate, FilterType filter) {
     Rdsd2Pcm r = (path && DsdFileFormat::from(*path).is_container())
-                     ? from_container(32, OutputType::Stdout, 0.0, output_rate, std::nullopt, DitherType::None,
-                                      filter, false, ".", *path)
-                     : create(32, OutputType::Stdout, 0.0, output_rate, std::nullopt, DitherType::None, fmt, endian,
-                              input_rate, block_size, channels, filter, false, ".", path);
+                     ? make_from_container(half, 32, OutputType::Stdout, 0.0, output_rate, std::nullopt, DitherType::None,
+                                           filter, false, ".", *path)
+                     : make(half, 32, OutputType::Stdout, 0.0, output_rate, std::nullopt, DitherType::None, fmt, endian,
+                            input_rate, block_size, channels, filter, false, ".", path);
     r.p_->level_only = true;
     return r;
 }
@@ -206,6 +245,7 @@ void Rdsd2Pcm::set_downmix(uint32_t target) {
 
 void Rdsd2Pcm::set_mix(uint32_t rows, const std::vector<int32_t>& coef) {
     if (rows == 0) { p_->mix.clear(); p_->mix_rows = 0; return; }
+    if (p_->half) throw std::runtime_error("Invalid mix: 44100 / 48000 output does not combine with a mix");
     if (coef.size() != (size_t)rows * p_->prm.channels) throw std::runtime_error("Invalid mix: it needs rows x channels coefficients, one column per channel of the stream");
     Impl probe = *p_;
     probe.mix = coef; probe.mix_rows = rows;
@@ -416,6 +456,7 @@ static std::string album_difference(const Rdsd2Pcm::Impl& a, const Rdsd2Pcm::Imp
     ALBUM_SAME(a.replaygain == b.replaygain, "ReplayGain switch");
     ALBUM_SAME(a.true_peak == b.true_peak, "true-peak switch");
     ALBUM_SAME(a.mix_rows == b.mix_rows && a.mix == b.mix, "mix");
+    ALBUM_SAME(a.half == b.half, "halved output rate");
 #undef ALBUM_SAME
     return "";
 }

@@ -1,6 +1,7 @@
 // rdsd2pcm_c.cpp -- include/rdsd2pcm_c.h over include/rdsd2pcm.hpp: exceptions become codes + a thread-local message.
 #include "../../../include/rdsd2pcm_c.h"
 #include "../../../include/rdsd2pcm_mix_c.h"
+#include "../../../include/rdsd2pcm_half_c.h"
 
 #include <atomic>
 #include <string>
@@ -95,6 +96,36 @@ int d2dh_new_level_check(uint32_t output_rate, const char* path, uint32_t fmt, u
     *out = nullptr;
     return guarded([&] {
         *out = new d2dh_conv(Rdsd2Pcm::new_level_check(output_rate, opt(path), fmt_of(fmt), endian_of(endian), channels, block_size, input_rate));
+    });
+}
+
+// include/rdsd2pcm_half_c.h
+int d2dh_new_half(uint32_t bit_depth, uint32_t output, double level_db, uint32_t output_rate, const char* out_dir, uint32_t dither,
+                  uint32_t fmt, uint32_t endian, uint32_t dsd_rate, uint32_t block_size, uint32_t channels, uint32_t filter,
+                  int append_rate, const char* base_dir, const char* in_path, d2dh_conv** out) {
+    if (!out) { g_err = "null argument"; return D2D_ERR_PARAM; }
+    *out = nullptr;
+    return guarded([&] {
+        *out = new d2dh_conv(Rdsd2Pcm::create_half(bit_depth, output_of(output), level_db, output_rate, opt(out_dir), dither_of(dither),
+                                                   fmt_of(fmt), endian_of(endian), dsd_rate, block_size, channels, filter_of(filter),
+                                                   append_rate != 0, base_dir ? base_dir : ".", opt(in_path)));
+    });
+}
+int d2dh_from_container_half(uint32_t bit_depth, uint32_t output, double level_db, uint32_t output_rate, const char* out_dir,
+                             uint32_t dither, uint32_t filter, int append_rate, const char* base_dir, const char* path, d2dh_conv** out) {
+    if (!out || !path) { g_err = "null argument"; return D2D_ERR_PARAM; }
+    *out = nullptr;
+    return guarded([&] {
+        *out = new d2dh_conv(Rdsd2Pcm::from_container_half(bit_depth, output_of(output), level_db, output_rate, opt(out_dir), dither_of(dither),
+                                                           filter_of(filter), append_rate != 0, base_dir ? base_dir : ".", path));
+    });
+}
+int d2dh_new_level_check_half(uint32_t output_rate, const char* path, uint32_t fmt, uint32_t endian, uint32_t channels,
+                              uint32_t block_size, uint32_t input_rate, d2dh_conv** out) {
+    if (!out) { g_err = "null argument"; return D2D_ERR_PARAM; }
+    *out = nullptr;
+    return guarded([&] {
+        *out = new d2dh_conv(Rdsd2Pcm::new_level_check_half(output_rate, opt(path), fmt_of(fmt), endian_of(endian), channels, block_size, input_rate));
     });
 }
 

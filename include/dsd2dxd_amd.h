@@ -35,7 +35,9 @@ extern "C" {
                              *     d2d_loud_set_true_peak / _add_true_peaks / _true_peak; D2D_DBG_NO_DITHER_TABLE and d2d_dither_table_calls;
                              *     the d2d_segments_* calls, d2d_convert_streams_flac with d2d_stream_io / d2d_streams_options, and
                              *     d2d_loud_finish_album / d2d_loud_true_peak_album; the channel matrix: d2d_mix, d2d_create_mix, d2d_get_mix,
-                             *     d2d_input_channels, d2d_mix_preset with D2D_MIX_LAYOUT_*, d2d_mix_frames_host, d2d_mix_error */
+                             *     d2d_input_channels, d2d_mix_preset with D2D_MIX_LAYOUT_*, d2d_mix_frames_host, d2d_mix_error; the halved engine
+                             *     (44.1 / 48 kHz): d2d_create_half, d2d_half_factor, d2d_half_taps, d2d_half_job, d2d_half_frames_host / _device,
+                             *     d2d_half_error */
 
 /* status codes */
 enum {
@@ -230,7 +232,8 @@ int d2d_seek(d2d_engine* e, uint32_t file, uint64_t bytes_per_channel);
 int d2d_tell(const d2d_engine* e, uint32_t file, uint64_t* bytes_per_channel, uint64_t* next_frame);
 /* The halo of the guarantee above, in bytes per channel, from the engine's tables: window plus one decimation step for a
  * single filter; the carried history of a composed polyphase filter; stage A's window plus P + 1 stage-A outputs for the
- * 48k cascade.  Below 1 KiB for every shipped table. */
+ * 48k cascade.  Below 1 KiB for every shipped table.  A halved engine (d2d_create_half) adds the input of the NT - 1 sums
+ * its decimator carries: about 1.5 to 6 KiB in all for its shapes. */
 size_t d2d_preroll_bytes(const d2d_engine* e);
 /* Noise-shaped dither ('N', integer depths) can only start where the shaper's state is known: at a frame index that is a
  * multiple of 8192.  This is the smallest A with F(k A) a multiple of 8192 for every k -- cut such streams at multiples
@@ -293,6 +296,58 @@ int d2d_mix_frames_host(const int32_t* sums, size_t stride, size_t frames, uint3
                         uint32_t bit_depth, uint32_t dither, double level_db, uint64_t seed, uint64_t first_index,
                         void* pcm, size_t pcm_capacity_bytes, double* peaks);
 const char* d2d_mix_error(void);
+
+/* ---- 44.1 and 48 kHz: an exact 2:1 decimator behind the FIR (added under ABI 11) ---- */
+
+/* A halved engine converts to twice params->output_rate exactly as the 'N' dither's integer pass of that shape does (the
+ * FIR kernels write every channel's exact integer sums x[i], scale 2^-S, into the scratch) and then low-pass filters and
+ * decimates them by two in integer arithmetic.  With the NT taps q[j] at 2^-T of d2d_half_taps (symmetric, sum q = 2^T,
+ * pass band to 0.22676 and stop band from 0.25 of the doubled rate) and x[i] = 0 for i < 0:
+ *     v[k] = sum_j q[j] x[2k - j]        exact, 64-bit
+ *     w[k] = (v[k] + 2^(T-1)) >> T       arithmetic shift: rounded to the scratch grid, ties towards +infinity
+ *     y[k] = w[k] * 2^-S                 exact; from y on the arithmetic of every other path: peak = max |y * gain|, level,
+ *                                        the dither word of (seed, channel, k), round half away from zero, clip, pack
+ * DESIGN.md section 4.5c has the definition.  Frame k exists as soon as x[2k] does: after n sums a file has produced
+ * (n + 1) >> 1 frames, and F(p) of the time-slice guarantee is that of the sums at p.  The filter's delay of (NT - 1) / 2
+ * sums (about 2.2 ms) is NOT compensated.  d2d_next_frames, d2d_tell, d2d_frame_bytes, the capacity checks, d2d_peak,
+ * d2d_reset, d2d_seek, d2d_prime*, d2d_translate*, the batch entry points and the whole-stream drivers follow the halved
+ * frame sequence; d2d_preroll_bytes grows by the input of NT - 1 sums; d2d_get_info describes the FIR at the doubled rate.
+ *
+ * params->output_rate is the final rate: 44100 (DSD64 / DSD128 / DSD256; filter E, and X / C where they offer 88200) or
+ * 48000 (DSD64 / DSD128, filter E); any other rate: D2D_ERR_RATE.  Refused with a message that names the reason: DSD512 and
+ * DSD256 -> 48000, whose 96 kHz form runs a second stage with 64-bit sums (D2D_ERR_RATE); filters S and D (D2D_ERR_FILTER);
+ * the noise-shaped dither, tap_bits = 32 and a channel subset (D2D_ERR_PARAM).  There is no mixed form.  d2d_create keeps
+ * refusing 44100 and 48000. */
+int d2d_create_half(const d2d_params* params, uint32_t n_files, d2d_engine** out);
+/* 2 for an engine of d2d_create_half, 0 for every other engine */
+uint32_t d2d_half_factor(const d2d_engine* e);
+/* The decimator's table: *nt taps at 2^-*t; taps (capacity in int32) may be NULL to ask for the sizes alone;
+ * D2D_ERR_CAPACITY when they do not fit. */
+int d2d_half_taps(uint32_t* nt, uint32_t* t, int32_t* taps, size_t capacity);
+/* The pass on its own.  One job is one file of a call: channel c's line at sums + c * stride holds the NT - 1 sums in front
+ * of the call (zeros at the start of a stream) followed by its n new ones (stride >= NT - 1 + n); first_index is the absolute
+ * index of the first new sum.  The frames k with first_index <= 2k < first_index + n are written to pcm, interleaved
+ * (frames_out: how many), and peaks[c] (when not NULL; the caller zeroes them) is raised to max |y * gain|.  Channel c's
+ * dither words are those of (seed, c, k).  bit_depth, dither (T / R / F / X), level_db and seed as in d2d_params;
+ * scale_bits is S.  A job with n = 0 does nothing.  Errors: d2d_half_error. */
+typedef struct d2d_half_job {
+    const int32_t* sums;
+    size_t stride;             /* int32 between the channels' lines */
+    size_t n;                  /* new sums per channel */
+    uint64_t first_index;
+    void* pcm;
+    size_t pcm_capacity_bytes;
+    double* peaks;             /* `channels` doubles, or NULL */
+    size_t frames_out;         /* written by the call */
+} d2d_half_job;
+/* the CPU twin of the kernel, compiled from the kernel's own header; no device */
+int d2d_half_frames_host(d2d_half_job* jobs, uint32_t n_jobs, uint32_t channels, int32_t scale_bits,
+                         uint32_t bit_depth, uint32_t dither, double level_db, uint64_t seed);
+/* The same call on the current device: sums, pcm (16-byte aligned) and peaks are GPU-addressable, every job goes into one
+ * launch on `hip_stream`, and the call returns once it has finished.  n below 2^31 per job. */
+int d2d_half_frames_device(d2d_half_job* jobs, uint32_t n_jobs, uint32_t channels, int32_t scale_bits,
+                           uint32_t bit_depth, uint32_t dither, double level_db, uint64_t seed, void* hip_stream);
+const char* d2d_half_error(void);
 
 /* ---- whole-stream driver ------------------------------------------------------------------ */
 

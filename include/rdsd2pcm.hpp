@@ -55,6 +55,21 @@ class Rdsd2Pcm {
     // filter: not a reference argument (its level check is always the equiripple filter); EquirippleCascade measures the two-stage definition
     static Rdsd2Pcm new_level_check(uint32_t output_rate, std::optional<std::string> path, FmtType fmt, Endianness endian,
                                     size_t channels, uint32_t block_size, uint32_t input_rate, FilterType filter = FilterType::Equiripple);
+    // The three constructors for 44100 and 48000 Hz output (not reference rates; include/dsd2dxd_amd.h, d2d_create_half): the engine converts
+    // to twice the rate and halves it with an exact 2:1 decimator behind the FIR.  Same arguments; output_rate is the final rate.  They throw
+    // the engine's own message for what d2d_create_half refuses (any other rate, DSD512, DSD256 -> 48000, filters S and D, the noise-shaped
+    // dither); set_tap_bits(32) fails when the run starts; set_mix / set_downmix throw.  Sinks, tags, the "-a" suffixes (_44_1K, _48K,
+    // " [44.1K]", " [48K]"), ReplayGain, set_true_peak, set_gpu_flac and its switches, convert_album and check_level see an ordinary converter at that rate.
+    // create, from_container and new_level_check keep refusing the two rates.
+    static Rdsd2Pcm create_half(size_t bit_depth, OutputType output, double level_db, uint32_t output_rate,
+                                std::optional<std::string> out_dir, DitherType dither, FmtType fmt, Endianness endian,
+                                uint32_t dsd_rate, uint32_t block_size, size_t channels, FilterType filter,
+                                bool append_rate, std::string base_dir, std::optional<std::string> in_path);
+    static Rdsd2Pcm from_container_half(size_t bit_depth, OutputType output, double level_db, uint32_t output_rate,
+                                        std::optional<std::string> out_dir, DitherType dither, FilterType filter,
+                                        bool append_rate, std::string base_dir, std::string path);
+    static Rdsd2Pcm new_level_check_half(uint32_t output_rate, std::optional<std::string> path, FmtType fmt, Endianness endian,
+                                         size_t channels, uint32_t block_size, uint32_t input_rate, FilterType filter = FilterType::Equiripple);
     Rdsd2Pcm(Rdsd2Pcm&&) noexcept;
     Rdsd2Pcm& operator=(Rdsd2Pcm&&) noexcept;
     ~Rdsd2Pcm();
@@ -134,6 +149,15 @@ class Rdsd2Pcm {
    private:
     std::unique_ptr<Impl> p_;
     explicit Rdsd2Pcm(std::unique_ptr<Impl> p);
+    static Rdsd2Pcm make(bool half, size_t bit_depth, OutputType output, double level_db, uint32_t output_rate,
+                         std::optional<std::string> out_dir, DitherType dither, FmtType fmt, Endianness endian,
+                         uint32_t dsd_rate, uint32_t block_size, size_t channels, FilterType filter,
+                         bool append_rate, std::string base_dir, std::optional<std::string> in_path);
+    static Rdsd2Pcm make_from_container(bool half, size_t bit_depth, OutputType output, double level_db, uint32_t output_rate,
+                                        std::optional<std::string> out_dir, DitherType dither, FilterType filter,
+                                        bool append_rate, std::string base_dir, std::string path);
+    static Rdsd2Pcm make_level_check(bool half, uint32_t output_rate, std::optional<std::string> path, FmtType fmt, Endianness endian,
+                                     size_t channels, uint32_t block_size, uint32_t input_rate, FilterType filter);
 };
 
 }  // namespace rdsd2pcm
